@@ -23,11 +23,15 @@ CPU tensors only; `nccl` = RCCL is accepted, the data path never touches it eith
 Rank 0 prints ONE JSON line (see README / DESIGN.md for the fields).  `value` is the HBM-resident rate (`residency`: "hbm":
 inputs in HBM, rows written to HBM, nothing crosses PCIe in the timed region); the rate a caller of output_a2m sees, with
 every row crossing the link into a host sink, is the separate `end_to_end` leg.  Besides the contract's fields the line
-carries `roofline` (the dominant kernel, splice_aligned_kernel; at N > 1 the SLOWEST rank's launches), `roofline_transpose`
-(the transpose of a source at the reference's own 64-bit padding into the library's path matrix, inside the timed region; the
-ABI's dense form, forward and inverse, and a 1024-bit-padded matrix measured after it), `unaligned` (a second, separately
-timed leg: the same rows without '-' padding), `end_to_end`, `parity` and -- at every N, timed on rank 0 after the timed
-region -- `cpu_baseline` (and `roofline_transpose.cpu_baseline`).
+carries `roofline` (the dominant kernel, splice_aligned_kernel; at N > 1 the SLOWEST rank's launches) and `roofline_transpose`
+(the transpose of a source at the reference's own 64-bit padding into the library's path matrix, inside the timed region).
+
+A plain run does only what the headline figure needs: set up, warm up, time --steps steps, write the last step's outputs
+(--dump-outputs DIR) and print the line.  Everything after the timed region moves behind --full: `parity` (rows checked
+against the CPU oracle), the ABI's dense transpose forward and inverse and a 1024-bit-padded matrix
+(`roofline_transpose.after_timing`), `unaligned` (a second, separately timed leg: the same rows without '-' padding),
+`end_to_end`, the memset yardstick of the roofline and -- at every N, timed on rank 0 -- `cpu_baseline` (and
+`roofline_transpose.cpu_baseline`).
 """
 
 import argparse
@@ -98,6 +102,38 @@ def _device_bytes(ptr, nbytes):
 	rc = rt.hipMemcpy(buf, ptr, nbytes, 2)   # hipMemcpyDeviceToHost
 	assert rc == 0, "hipMemcpy failed"
 	return buf.raw
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all arrays together
+DUMP_SEED = 20241015
+DUMP_WINDOWS, DUMP_WINDOW_BYTES = 256, 16384
+
+
+def sample_windows(n_rows, length, seed=DUMP_SEED, count=DUMP_WINDOWS, width=DUMP_WINDOW_BYTES):
+	"""A fixed, seeded choice of `count` windows of `width` bytes over `n_rows` rows of `length` bytes, as (row, byte offset) pairs: the first
+	row's first window, the last row's last window and the rest at random.  Depends on its arguments alone, so that two runs (or two builds)
+	with the same workload sample the same bytes.  Returns (pairs, width), width cut to the row length."""
+	width = max(0, min(width, length))
+	if n_rows <= 0 or width == 0:
+		return np.zeros((0, 2), dtype=np.int64), width
+	rng = np.random.default_rng(seed)
+	picks = np.stack([rng.integers(0, n_rows, count), rng.integers(0, length - width + 1, count)], axis=1)
+	picks[0] = (0, 0)
+	picks[-1] = (n_rows - 1, length - width)
+	return picks, width
+
+
+def write_outputs(directory, arrays):
+	"""--dump-outputs: DIR/<name>.npy for every array; float32 or float64 only, at most DUMP_LIMIT_BYTES in all."""
+	for name, a in arrays.items():
+		if a.dtype not in (np.float32, np.float64):
+			raise TypeError("%s: %s, expected float32 or float64" % (name, a.dtype))
+	total = sum(a.nbytes for a in arrays.values())
+	if total > DUMP_LIMIT_BYTES:
+		raise ValueError("outputs of %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+	os.makedirs(directory, exist_ok=True)
+	for name, a in arrays.items():
+		np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def device_binding(dev_index):
@@ -172,10 +208,24 @@ def build_checker_once():
 	subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s"], stdout=sys.stderr)
 
 
+def build_libraries():
+	"""build_native(): a no-op when the in-tree libraries are newer than their sources.  A checkout that build() made as another user may be
+	one this process cannot write, and a build_native() that takes its lock file even when nothing is stale fails there: the libraries build()
+	left are then used as they are, provided they exist."""
+	from vcf2multialign_amd import build as b
+	try:
+		b.build_native()
+	except PermissionError as e:
+		missing = [os.path.relpath(p, ROOT) for p in (b.LIB_PATH, b.SYNTH_LIB_PATH) if not os.path.exists(p)]
+		if missing:
+			sys.exit("[bench] %s missing and the checkout is not writable (%s): run build() first" % (" and ".join(missing), e))
+		log("[bench] the checkout is not writable (%s): using the libraries that build() left" % e)
+
+
 HUB_ENV = "V2M_BENCH_HUB"   # set for the children of `python bench.py --gpus N`: the parent serves barrier / gather over their pipes
 
 
-def launch_ranks(n, argv):
+def launch_ranks(n, argv, full=False):
 	"""`python bench.py --gpus N` typed as is (no WORLD_SIZE in the environment): this parent -- which has parsed its arguments
 	and nothing else, no torch import, no HIP call -- builds the libraries (in a child), starts the N ranks as fresh child
 	processes (RANK / LOCAL_RANK / WORLD_SIZE as under torch.distributed.run, plus V2M_BENCH_HUB) and is their hub: each rank's
@@ -187,10 +237,11 @@ def launch_ranks(n, argv):
 	import subprocess
 	import threading
 	if "--hub-selftest" not in argv:
-		rc = subprocess.call([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from vcf2multialign_amd import build; build.build_native()" % ROOT], stdout=sys.stderr)
+		rc = subprocess.call([sys.executable, "-c", "import sys; sys.path.insert(0, %r); import bench; bench.build_libraries()" % ROOT], stdout=sys.stderr)
 		if rc != 0:
 			sys.exit("[bench] building the native libraries failed (exit %d)" % rc)
-		build_checker_once()
+		if full:
+			build_checker_once()
 	procs = []
 	for r in range(n):
 		env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n))
@@ -349,13 +400,23 @@ def main():
 	ap.add_argument("--host-threads", type=int, default=0, help="threads per rank for the CPU oracle's row checks after timing; 0 = this rank's share of the job's CPU quota (sharding.host_threads_per_rank), at most 16")
 	ap.add_argument("--numa-bind", default="auto", choices=["auto", "on", "off"], help="keep this rank's threads (and with them the pinned slots they first touch) on its GPU's NUMA node: auto = at N > 1 only")
 	ap.add_argument("--hub-selftest", action="store_true", help="no GPU work: the ranks only exercise the barrier / gather plumbing of their launch form and rank 0 prints what it gathered (CPU test suite)")
+	ap.add_argument("--full", action="store_true", help="after the timed region, also run what the headline figure does not need: the row checks against the CPU oracle (--verify-rows), "
+		"the transpose extras (--transpose-extras, --cpu-transpose), the memset yardstick, the unaligned leg (--unaligned-rows), the CPU baseline (--cpu-baseline-rows) and the "
+		"end-to-end leg (--e2e-gb, --e2e-threads); without it those options have no effect")
+	ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after timing, write what the timed path computed in its last step to DIR/<name>.npy: the output buffer "
+		"holds the rows of the step's last batch; rows_sample = a fixed, seeded sample of %d windows of %d bytes of them (float32), row_checksums = every row's 64-bit "
+		"checksum (v2m_checksum_rows_device) as [high 32 bits, low 32 bits] (float64); at N > 1 every rank writes its own, suffixed _rank<r>" % (DUMP_WINDOWS, DUMP_WINDOW_BYTES))
 	args = ap.parse_args()
+	if not args.full:
+		# a plain run: set up, warm up, time the steps, dump, print the line -- none of the legs after the timed region
+		args.verify_rows = args.unaligned_rows = args.cpu_transpose = args.transpose_extras = args.cpu_baseline_rows = 0
+		args.e2e_gb = 0.0
 
 	rank = int(os.environ.get("RANK", "0"))
 	local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 	world = int(os.environ.get("WORLD_SIZE", "1"))
 	if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-		return launch_ranks(args.gpus, sys.argv[1:])
+		return launch_ranks(args.gpus, sys.argv[1:], full=args.full)
 	if world != args.gpus:
 		sys.exit("WORLD_SIZE (%d) != --gpus (%d)" % (world, args.gpus))
 	# Only the result line may appear on stdout: file descriptor 1 is pointed at stderr for everything else in this process
@@ -394,10 +455,11 @@ def main():
 	if not under_parent:            # (the parent of `python bench.py --gpus N` has built before it started the ranks)
 		if local_rank == 0:
 			try:
-				_build.build_native()   # no-op when the in-tree libraries are newer than their sources (hipcc cross-compiles gfx950)
+				build_libraries()       # no-op when the in-tree libraries are newer than their sources (hipcc cross-compiles gfx950)
 			except _build.StaleUnderProfiler as e:   # never a compiler launcher under a profiler's preload: build first, then profile
 				sys.exit("[bench] " + str(e))
-			build_checker_once()
+			if args.full:
+				build_checker_once()
 		hub.barrier()               # nobody loads the libraries before the (possible) rebuild is over
 	import vcf2multialign_amd as v2m
 	from vcf2multialign_amd import _native as N
@@ -483,6 +545,18 @@ def main():
 	elapsed = time.perf_counter() - t_begin
 	hub.barrier()
 	ctx.profile_enable(False)
+
+	# ---- what the timed path computed in its last step: the reused output buffer holds the rows of the step's last batch ----------
+	if args.dump_outputs:
+		n_last = batches[-1].n_rows if batches else 0
+		sums = ctx.checksum_rows_device(out_ptr, pitch, n_last, length=L) if n_last else np.zeros(0, dtype=np.uint64)
+		picks, width = sample_windows(n_last, L)
+		sample = np.zeros((len(picks), width), dtype=np.float32)
+		for i, (r, off) in enumerate(picks):
+			sample[i] = np.frombuffer(_device_bytes(out_ptr + int(r) * pitch + int(off), width), dtype=np.uint8)
+		suffix = "" if world == 1 else "_rank%d" % rank
+		write_outputs(args.dump_outputs, {"rows_sample" + suffix: sample, "row_checksums" + suffix: np.stack([sums >> np.uint64(32), sums & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)})
+		log("[bench] rank %d: the last step's outputs (%d rows of its last batch) written to %s" % (rank, n_last, args.dump_outputs))
 
 	# ---- this rank's kernel figures, from HIP events on the kernels' own stream ----------------------
 	launches, splice_ms = ctx.profile_get(N.KERNEL_SPLICE_ALIGNED)
@@ -644,16 +718,17 @@ def main():
 
 		# Context for the roofline number: what a plain device memset of the very same output buffer reaches in this
 		# process (the achievable write rate varies by +-10 % between processes / boxes).
-		ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-		fills = []
-		for _ in range(3):
-			ev0.record()
-			_hip_memset(torch, out_ptr, out_bytes)
-			ev1.record()
-			torch.cuda.synchronize()
-			fills.append(ev0.elapsed_time(ev1))
-		extras["memset_same_buffer_GBs"] = round(out_bytes / (min(fills) * 1e-3) / 1e9, 1)
-		extras["memset_same_buffer_rank"] = 0
+		if args.full:
+			ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+			fills = []
+			for _ in range(3):
+				ev0.record()
+				_hip_memset(torch, out_ptr, out_bytes)
+				ev1.record()
+				torch.cuda.synchronize()
+				fills.append(ev0.elapsed_time(ev1))
+			extras["memset_same_buffer_GBs"] = round(out_bytes / (min(fills) * 1e-3) / 1e9, 1)
+			extras["memset_same_buffer_rank"] = 0
 
 		# ---- second leg, timed on its own: --unaligned (sequence_writer.cc:80: no '-' padding) -----------------------------
 		# Measured on the SAME address footprint as the aligned leg (as many rows as the ~63-GB output buffer holds at the unaligned

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_has_the_contract_fields():
-	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "mini3", "--steps", "2", "--warmup", "1", "--output-candidates", "2", "--cpu-baseline-rows", "8"],
+	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "mini3", "--steps", "2", "--warmup", "1", "--output-candidates", "2", "--cpu-baseline-rows", "8"],
 		stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
 	assert r.returncode == 0, r.stderr.decode()[-2000:]
 	lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -60,11 +60,46 @@ def test_bench_line_has_the_contract_fields():
 	_check_end_to_end(d, n_ranks=1)
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+	"""Without --full the run sets up, warms up, times --steps steps, writes the last step's outputs and prints the line -- none of the legs after
+	the timed region.  --dump-outputs gives the same arrays from run to run, float32 / float64 within 64 MB, and the same ones as a --full run of the
+	same workload, whose parity check says the rows are the oracle's."""
+	import numpy as np
+	common = ["--config", "mini3", "--steps", "3", "--warmup", "1", "--output-candidates", "1", "--batch-rows", "40"]
+	dumps, lines = [], []
+	for k, extra in enumerate(([], [], ["--full", "--e2e-gb", "0", "--unaligned-rows", "0", "--cpu-transpose", "0", "--transpose-extras", "0", "--cpu-baseline-rows", "0"])):
+		out = tmp_path / ("out%d" % k)
+		r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra + ["--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
+		assert r.returncode == 0, r.stderr.decode()[-2000:]
+		got = [l for l in r.stdout.decode().splitlines() if l.strip()]
+		assert len(got) == 1, "exactly one line on stdout"
+		lines.append(json.loads(got[0]))
+		assert sorted(os.listdir(out)) == ["row_checksums.npy", "rows_sample.npy"]
+		arrays = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+		assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+		dumps.append(arrays)
+	plain, full = lines[0], lines[2]
+	for d in (plain, full):
+		assert d["metric"] == "aligned A2M Gbases/sec" and d["unit"] == "Gbases/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+		assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+		# --steps is the number of timed steps: every step launches the splice kernel once per batch
+		assert d["roofline"]["launches"] == 3 * d["config"]["per_rank"][0]["batches"]
+	for leg in ("parity", "cpu_baseline", "unaligned", "end_to_end"):
+		assert leg not in plain
+	assert "after_timing" not in plain["roofline_transpose"] and "memset_same_buffer_GBs" not in plain["roofline"]
+	assert full["parity"]["bit_exact"] is True and full["parity"]["all_rows"] is True
+	n_last = plain["config"]["rows_total"] - (plain["config"]["per_rank"][0]["batches"] - 1) * plain["config"]["batch_rows"]
+	assert dumps[0]["row_checksums.npy"].shape == (n_last, 2) and dumps[0]["rows_sample.npy"].shape[0] > 0
+	for other in dumps[1:]:
+		for name, a in dumps[0].items():
+			assert np.array_equal(a, other[name]), name
+
+
 def test_bench_unaligned_leg_on_the_dense_graph():
 	"""The dense variant mix of BASELINE config 5 (mini5: one ALT edge per ~40 bp, MNPs, multi-allelic sites), where the unaligned stream-out's
 	queue of short chunks is busiest: the leg is bit-exact against the oracle and carries its like-for-like yardstick (the aligned kernel on the
 	same rows, buffer and pitch), so the figure the documents quote for config 5 is one the driver's own suite exercises."""
-	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "mini5", "--steps", "1", "--warmup", "0", "--output-candidates", "1", "--cpu-baseline-rows", "4",
+	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "mini5", "--steps", "1", "--warmup", "0", "--output-candidates", "1", "--cpu-baseline-rows", "4",
 		"--e2e-gb", "0", "--cpu-transpose", "0", "--transpose-extras", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
 	assert r.returncode == 0, r.stderr.decode()[-2000:]
 	d = json.loads([l for l in r.stdout.decode().splitlines() if l.strip()][-1])
@@ -108,7 +143,7 @@ def test_bench_gpus_2_as_typed_starts_its_own_ranks():
 	"""`python bench.py --gpus 2` with no launcher around it: the parent starts both ranks as child processes (here both on device 0
 	over gloo, the one-GPU rehearsal of the N > 1 path), relays exactly one line on stdout and the ranks' chatter on stderr."""
 	env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--force-device", "0", "--config", "mini3",
+	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--force-device", "0", "--config", "mini3",
 		"--steps", "2", "--warmup", "1", "--output-candidates", "1", "--batch-rows", "40", "--cpu-baseline-rows", "8"],
 		stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT, env=env)
 	assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -154,7 +189,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
 		port = sock.getsockname()[1]
 	env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
 	r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-		os.path.join(ROOT, "bench.py"), "--gpus", "2", "--force-device", "0", "--config", "mini3",
+		os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--force-device", "0", "--config", "mini3",
 		"--steps", "2", "--warmup", "1", "--output-candidates", "1", "--batch-rows", "40", "--cpu-baseline-rows", "8"],
 		stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT, env=env)
 	assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -169,7 +204,7 @@ def test_bench_four_ranks_as_typed_uneven_shards():
 	"""Four ranks on one GPU (mini3: 200 copies -> blocks of 8 dealt 48 / 48 / 48 / 56, REF on rank 0): every rank binds only its own slice,
 	passes the same barriers (timed region, three end-to-end passes) and contributes its figures; the line adds up."""
 	env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--force-device", "0", "--config", "mini3",
+	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--force-device", "0", "--config", "mini3",
 		"--steps", "2", "--warmup", "1", "--output-candidates", "1", "--batch-rows", "20", "--cpu-baseline-rows", "8", "--e2e-threads", "4"],
 		stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT, env=env)
 	assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -188,7 +223,7 @@ def test_bench_four_ranks_as_typed_uneven_shards():
 
 # A GPU box allows at most 6 processes on its card at once, and the pytest process is one of them: five ranks is the most a test
 # started from here may put on the device.  The 8-rank plumbing of both launch forms runs without GPU work in tests/test_host_cpu.py.
-FIVE = ["--gpus", "5", "--force-device", "0", "--config", "mini3", "--steps", "2", "--warmup", "1", "--output-candidates", "1", "--batch-rows", "8", "--cpu-baseline-rows", "8"]
+FIVE = ["--full", "--gpus", "5", "--force-device", "0", "--config", "mini3", "--steps", "2", "--warmup", "1", "--output-candidates", "1", "--batch-rows", "8", "--cpu-baseline-rows", "8"]
 
 
 def _check_five_rank_line(d, rows, rank0_has_copies=True):

@@ -430,6 +430,68 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
 	assert r.returncode != 0 and b"WORLD_SIZE (3) != --gpus (2)" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_has_full_and_dump_outputs_options():
+	import subprocess
+	import sys
+	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120, env=_clean_env())
+	assert r.returncode == 0, r.stderr.decode()
+	assert b"--full" in r.stdout and b"--dump-outputs DIR" in r.stdout
+
+
+def test_bench_dump_sample_is_fixed_and_in_bounds():
+	"""--dump-outputs samples the same windows of the last batch's rows whenever the workload is the same, and never reads past a row."""
+	import bench
+	for n_rows, length in ((620, 100299831), (31, 2000003), (1, 5000), (3, 16384)):
+		picks, width = bench.sample_windows(n_rows, length)
+		again, _ = bench.sample_windows(n_rows, length)
+		assert np.array_equal(picks, again) and width == min(length, bench.DUMP_WINDOW_BYTES)
+		assert len(picks) == bench.DUMP_WINDOWS and (picks[:, 0] >= 0).all() and (picks[:, 0] < n_rows).all()
+		assert (picks[:, 1] >= 0).all() and (picks[:, 1] + width <= length).all()
+		assert tuple(picks[0]) == (0, 0) and tuple(picks[-1]) == (n_rows - 1, length - width)
+	assert len(bench.sample_windows(0, 1000)[0]) == 0 and len(bench.sample_windows(5, 0)[0]) == 0
+	assert bench.DUMP_WINDOWS * bench.DUMP_WINDOW_BYTES * 4 < bench.DUMP_LIMIT_BYTES      # the float32 sample alone leaves room
+
+
+def test_bench_write_outputs_takes_floats_within_the_limit(tmp_path):
+	import bench
+	bench.write_outputs(str(tmp_path / "d"), {"a": np.arange(6, dtype=np.float32).reshape(2, 3), "b": np.ones(4, dtype=np.float64)})
+	assert np.array_equal(np.load(tmp_path / "d" / "a.npy"), np.arange(6, dtype=np.float32).reshape(2, 3))
+	assert np.load(tmp_path / "d" / "b.npy").dtype == np.float64
+	with pytest.raises(TypeError):
+		bench.write_outputs(str(tmp_path / "e"), {"a": np.zeros(4, dtype=np.uint8)})
+	with pytest.raises(ValueError):
+		bench.write_outputs(str(tmp_path / "e"), {"a": np.zeros((64 << 20) // 8 + 1, dtype=np.float64)})
+	assert not (tmp_path / "e").exists()
+
+
+def test_build_native_writes_nothing_when_fresh(monkeypatch):
+	"""A checkout that build() made may be used by a user who cannot write it: with every library up to date, build_native() does not even
+	take its lock file."""
+	from vcf2multialign_amd import build
+	assert build.stale_targets() == []
+
+	def no_lock():
+		raise AssertionError("build_native() took its lock with nothing to build")
+	monkeypatch.setattr(build, "_build_lock", no_lock)
+	assert build.build_native() == build.LIB_PATH
+
+
+def test_bench_uses_the_libraries_of_a_checkout_it_cannot_write(monkeypatch, tmp_path):
+	"""bench.py's build step where the build lock cannot be taken (another user's checkout): the libraries build() left are used; without
+	them the run ends with a message."""
+	import bench
+	from vcf2multialign_amd import build
+
+	def refused(*a, **k):
+		raise PermissionError(13, "Permission denied", os.path.join(build.PKG_DIR, ".build.lock"))
+	monkeypatch.setattr(build, "build_native", refused)
+	bench.build_libraries()
+	monkeypatch.setattr(build, "LIB_PATH", str(tmp_path / "libv2m_hip.so"))
+	with pytest.raises(SystemExit) as e:
+		bench.build_libraries()
+	assert "run build() first" in str(e.value)
+
+
 def test_bench_as_typed_starts_child_ranks_and_relays_their_failure():
 	"""`python bench.py --gpus 2` without WORLD_SIZE starts two child ranks itself (no GPU here: both fail at the first HIP call);
 	the parent must relay the failure as a non-zero exit, print nothing on stdout and never exec over itself."""

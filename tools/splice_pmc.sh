@@ -8,7 +8,7 @@ for cfg in config3 config5; do
 	i=0
 	for counters in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU" "SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT" "SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY"; do
 		i=$((i+1))
-		timeout -k 10 300 rocprofv3 --pmc $counters --output-format csv -d $OUT/${cfg}_$i -o p -- python3 bench.py --config $cfg --steps 1 --warmup 0 --cpu-baseline-rows 0 --verify-rows 0 --output-candidates 1 > $OUT/${cfg}_$i.json 2> $OUT/${cfg}_$i.err || { tail -3 $OUT/${cfg}_$i.err; }
+		timeout -k 10 300 rocprofv3 --pmc $counters --output-format csv -d $OUT/${cfg}_$i -o p -- python3 bench.py --full --config $cfg --steps 1 --warmup 0 --cpu-baseline-rows 0 --verify-rows 0 --output-candidates 1 > $OUT/${cfg}_$i.json 2> $OUT/${cfg}_$i.err || { tail -3 $OUT/${cfg}_$i.err; }
 	done
 done
 python3 - <<'PY'

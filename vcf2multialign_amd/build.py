@@ -171,9 +171,19 @@ def _build(target, sources, dep_list, force, verbose, extra_flags=()):
 	return target
 
 
+def stale_targets():
+	"""The targets of build_native() that are missing or older than what they are built from (the same dependency lists it uses)."""
+	targets = [(SYNTH_LIB_PATH, deps("SYNTH_DEPS")), (LIB_PATH, deps("HIP_DEPS")), (TUNING_LIB_PATH, deps("HIP_DEPS")),
+		(HOST_LIB_PATH, deps("HOST_DEPS") + [LIB_PATH]), (CLI_PATH, deps("CLI_DEPS") + deps("HOST_DEPS") + [HOST_LIB_PATH])]
+	return [t for t, d in targets if _stale(t, d)]
+
+
 def build_native(force=False, verbose=False):
 	"""Compiles libv2m_hip.so (and the synthetic-input helper) for gfx950 if missing or older than the sources.  Raises
-	StaleUnderProfiler instead of compiling when a profiler's preload is in the environment (see under_profiler)."""
+	StaleUnderProfiler instead of compiling when a profiler's preload is in the environment (see under_profiler).  When everything is
+	up to date it writes nothing, not even the lock file: a checkout that build() made may be used by a user who cannot write it."""
+	if not force and not stale_targets():
+		return LIB_PATH
 	with _build_lock():
 		_build(SYNTH_LIB_PATH, SYNTH_SOURCES, deps("SYNTH_DEPS"), force, verbose)
 		_build(LIB_PATH, HIP_SOURCES, deps("HIP_DEPS"), force, verbose)
