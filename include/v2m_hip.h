@@ -33,7 +33,8 @@
  * V2M_ABI_VERSION: 1 = round 1 (transpose, graph, rows); 2 = + v2m_upload_path_slice, v2m_alloc_output / v2m_free_output,
  * v2m_profile_get_launches (v2m_bind_path_matrix_device followed without a step); 3 = + v2m_upload_path_blocks (and then
  * v2m_pbwt_cut_trials, v2m_pbwt_cut_records); 4 = + v2m_pbwt_cut_trials_streamed; 5 = + v2m_splice_rows_held / v2m_row_release (rows a
- * sink may keep until it says so).  Entries have only ever been added.
+ * sink may keep until it says so).  Entries have only ever been added.  V2M_SPLICE_BGZF, v2m_bgzf_compress, v2m_bgzf_bound and
+ * v2m_bgzf_frame_stored were added without a new version: a caller probes for them by symbol.
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -79,6 +80,10 @@ enum {
                                    * every byte value; the unaligned kernels use byte 0 as their padding marker, so a graph whose
                                    * ref_seq or label pool holds a NUL byte is refused in this mode (V2M_ERR_UNSUPPORTED) rather
                                    * than written without it. */
+#define V2M_SPLICE_BGZF 0x2u      /* v2m_splice_rows only (may be combined with V2M_SPLICE_UNALIGNED): the sink receives, per row and
+                                   * in batch order, the complete BGZF members of that row's body instead of the body (format below).
+                                   * v2m_splice_rows_held returns V2M_ERR_UNSUPPORTED with it, v2m_splice_rows_device
+                                   * V2M_ERR_INVALID_ARGUMENT. */
 
 typedef struct v2m_ctx v2m_ctx;
 
@@ -326,6 +331,31 @@ int v2m_pbwt_cut_records(v2m_ctx *ctx, uint64_t n_copies, uint64_t n_cuts, const
 	uint64_t pool_capacity, uint32_t *pool_lhs, uint32_t *pool_rhs, uint32_t *pool_size,
 	uint64_t *rec_pool_end, uint32_t *rec_distinct, uint32_t *rec_first_class, uint32_t *rec_first_is_ref, uint32_t *chunk_status);
 
+/* ---- BGZF output --------------------------------------------------------------------------------
+ *
+ * BGZF is the blocked gzip of the SAM/BAM specification, section 4.1; any gzip reader reads it, htslib indexes it.
+ *   - Output = a sequence of members.  Each member is a gzip member (RFC 1952) with FLG.FEXTRA set and one extra subfield 'B' 'C'
+ *     of SLEN 2 holding BSIZE = the member's total length - 1; a member is at most 65 536 bytes and holds at most 65 280
+ *     uncompressed bytes (0xff00).  The footer holds the CRC-32 (IEEE, reflected 0xEDB88320) and ISIZE.
+ *   - The deflate payload is one final block: dynamic Huffman (BTYPE 10) over zlib's Z_RLE tokens (literals and distance-1
+ *     matches), or stored (BTYPE 00) when that is not larger.  Compressed bytes need not match zlib's; decompressed ones do.
+ *   - A file ends with the 28-byte EOF member 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00.
+ *   - Row bodies: every row's body is cut into 65 280-byte pieces from its first byte, one member each (an empty body gives no
+ *     member).  So the decompressed bytes of a row's members are exactly its body, and an A2M file written with V2M_SPLICE_BGZF
+ *     is its plain bytes: the glue around the bodies ('>'id'\n' before, '\n' after) in stored members of
+ *     v2m_bgzf_frame_stored, then the EOF member. */
+
+/* Bytes that frame_stored or compress can write for n input bytes at most (n + 31 per 65 280-byte piece; 28 for n = 0). */
+uint64_t v2m_bgzf_bound(uint64_t n);
+
+/* Frames n host bytes as stored-block BGZF members (host only, no ctx or device); n = 0 writes exactly the EOF member.
+ * V2M_ERR_INVALID_ARGUMENT when cap is smaller than what the framing needs. */
+int v2m_bgzf_frame_stored(const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out);
+
+/* Compresses n host bytes to BGZF members on the GPU, through the kernels V2M_SPLICE_BGZF uses.  Synchronous; n = 0 writes nothing
+ * (no EOF member).  V2M_ERR_INVALID_ARGUMENT when the members do not fit into cap (v2m_bgzf_bound(n) always does). */
+int v2m_bgzf_compress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out);
+
 /* ---- verification helper ------------------------------------------------------------------ */
 
 /* 64-bit position-sensitive checksum of each of n_rows device rows (row i = d_rows + i*row_pitch,
@@ -345,7 +375,8 @@ enum {
 	V2M_KERNEL_SPLICE_UNALIGNED = 3, /* splice_unaligned_kernel (pass 2 of unaligned mode: build + compact the tiles) */
 	V2M_KERNEL_TEMPLATE = 4,        /* expand_reference_row_kernel (once per upload) */
 	V2M_KERNEL_UNALIGNED_COUNT = 5, /* count_unaligned_kernel + scan_tile_counts_kernel (pass 1 of unaligned mode) */
-	V2M_KERNEL_COUNT = 6
+	V2M_KERNEL_BGZF = 6,            /* bgzf_deflate_kernel + bgzf_scan_kernel + bgzf_compact_kernel (V2M_SPLICE_BGZF, v2m_bgzf_compress) */
+	V2M_KERNEL_COUNT = 7
 };
 
 /* When enabled, every launch of the kernels above is bracketed by HIP events on the ctx's

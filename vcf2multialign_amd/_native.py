@@ -20,9 +20,12 @@ V2M_ERR_INVALID_ARGUMENT, V2M_ERR_PRECONDITION, V2M_ERR_UNSUPPORTED, V2M_ERR_NO_
 V2M_ERR_HIP, V2M_ERR_OUT_OF_MEMORY, V2M_ERR_SINK, V2M_ERR_STATE = 5, 6, 7, 8
 V2M_PLOIDY_MAX = 0xFFFFFFFF
 V2M_SPLICE_UNALIGNED = 0x1
+V2M_SPLICE_BGZF = 0x2
 
 KERNEL_TRANSPOSE, KERNEL_RESOLVE, KERNEL_SPLICE_ALIGNED, KERNEL_SPLICE_UNALIGNED, KERNEL_TEMPLATE, KERNEL_UNALIGNED_COUNT = range(6)
-KERNEL_NAMES = ["transpose_bits_kernel", "resolve_effective_edges_kernel", "splice_aligned_kernel", "splice_unaligned_kernel", "expand_reference_row_kernel", "count_unaligned_kernel"]
+KERNEL_BGZF = 6
+KERNEL_NAMES = ["transpose_bits_kernel", "resolve_effective_edges_kernel", "splice_aligned_kernel", "splice_unaligned_kernel", "expand_reference_row_kernel", "count_unaligned_kernel",
+	"bgzf_deflate_kernel"]
 ABI_VERSION = 5
 
 
@@ -78,6 +81,9 @@ SIGNATURES = {
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_alloc_output": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
 	"v2m_free_output": (C.c_int, [C.c_void_p, C.c_void_p]),
+	"v2m_bgzf_bound": (C.c_uint64, [C.c_uint64]),
+	"v2m_bgzf_frame_stored": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
+	"v2m_bgzf_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
 	"v2m_checksum_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
 	"v2m_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
 	"v2m_profile_reset": (C.c_int, [C.c_void_p]),

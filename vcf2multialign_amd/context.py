@@ -156,9 +156,10 @@ class Context:
 		return self._lib.v2m_max_unaligned_length(self._h)
 
 	# ---- rows ----------------------------------------------------------------------------------
-	def splice_rows(self, rows, sink=None, unaligned=False):
+	def splice_rows(self, rows, sink=None, unaligned=False, bgzf=False):
 		"""v2m_splice_rows.  sink(row_index, body: bytes) is called per row in order; without a sink the
-		bodies are collected and returned as a list."""
+		bodies are collected and returned as a list.  bgzf=True: each row's body arrives as its BGZF members
+		(V2M_SPLICE_BGZF; gzip.decompress() of them is the body, b"" for an empty body)."""
 		if not isinstance(rows, RowBatch):
 			rows = RowBatch(rows)
 		collected = []
@@ -177,7 +178,8 @@ class Context:
 				return 1
 
 		cb = N.SINK_FN(_cb)
-		rc = self._lib.v2m_splice_rows(self._h, C.byref(rows.struct), N.V2M_SPLICE_UNALIGNED if unaligned else 0, cb, None)
+		flags = (N.V2M_SPLICE_UNALIGNED if unaligned else 0) | (N.V2M_SPLICE_BGZF if bgzf else 0)
+		rc = self._lib.v2m_splice_rows(self._h, C.byref(rows.struct), flags, cb, None)
 		if error:
 			raise error[0]
 		self._check(rc)
@@ -214,6 +216,15 @@ class Context:
 		self._check(self._lib.v2m_splice_rows_device(self._h, C.byref(rows.struct), N.V2M_SPLICE_UNALIGNED if unaligned else 0,
 			d_out, row_pitch, lengths.ctypes.data if want_lengths and rows.n_rows else None))
 		return lengths
+
+	def bgzf_compress(self, data):
+		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
+		src = bytes(data)
+		cap = bgzf_bound(len(src))
+		dst = C.create_string_buffer(cap)
+		n = C.c_uint64()
+		self._check(self._lib.v2m_bgzf_compress(self._h, src if src else None, len(src), dst, cap, C.byref(n)))
+		return dst.raw[:n.value]
 
 	def alloc_output(self, nbytes, candidates=3):
 		"""v2m_alloc_output: device memory for row output, picked among `candidates` allocations by measured write rate."""
@@ -254,6 +265,24 @@ def _profile_launches(self, kernel):
 
 
 Context.profile_launches = _profile_launches
+
+
+def bgzf_bound(n):
+	"""v2m_bgzf_bound: the most bytes bgzf_frame_stored / Context.bgzf_compress write for n input bytes."""
+	return int(N.load().v2m_bgzf_bound(n))
+
+
+def bgzf_frame_stored(data):
+	"""v2m_bgzf_frame_stored: `data` as stored-block BGZF members (host only); b"" gives exactly the 28-byte EOF member."""
+	lib = N.load()
+	src = bytes(data)
+	cap = bgzf_bound(len(src))
+	dst = C.create_string_buffer(cap)
+	n = C.c_uint64()
+	rc = lib.v2m_bgzf_frame_stored(src if src else None, len(src), dst, cap, C.byref(n))
+	if rc != N.V2M_OK:
+		raise V2MError(rc, "v2m_bgzf_frame_stored failed")
+	return dst.raw[:n.value]
 
 
 def checksum_rows_host(rows_bytes):

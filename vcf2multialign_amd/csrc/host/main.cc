@@ -45,6 +45,7 @@ struct options {
 	char const *pipe{}, *input_cut_positions{}, *output_cut_positions{};
 	bool output_sequences_separate{}, separate_plain{}, omit_reference{}, unaligned{}, verbose{}, graph_statistics{};
 	bool ref_mismatch_error{};
+	bool bgzf{};
 	std::vector<int> devices{0};
 };
 
@@ -70,6 +71,8 @@ void usage()
 		"  -x, --exclude-samples=file         TSV (chrom, sample, copy_idx) of copies to exclude\n"
 		"      --device=n[,m...]              HIP device(s) to run on (default 0); with several, the rows of an aligned\n"
 		"                                     A2M file are sharded over them (graph replicated, no collective)\n"
+		"      --bgzf                         Write the A2M file (-s) as BGZF, compressed on the GPU (gzip -d or any BGZF\n"
+		"                                     reader gives the plain A2M back; not with --pipe or --output-sequences-separate)\n"
 		"      --verbose\n"
 		"  -F, --founder-sequences=count      Produce founder sequences instead of haplotypes\n"
 		"  -d, --minimum-distance=distance    Minimum node distance (MSA co-ordinates) between cut positions\n"
@@ -166,7 +169,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -178,7 +181,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -221,6 +224,7 @@ int main(int argc, char **argv)
 			}
 			case o_verbose: opt.verbose = true; break;
 			case o_pipe: opt.pipe = optarg; break;
+			case o_bgzf: opt.bgzf = true; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -240,6 +244,10 @@ int main(int argc, char **argv)
 	if (opt.input_variants && !opt.chromosome) { std::cerr << "ERROR: --chromosome must be specified with --input-variants.\n"; return EXIT_FAILURE; }          // main.cc:589-593
 	if (opt.output_graph && !opt.input_variants) { std::cerr << "ERROR: --output-graph requires --input-variants.\n"; return EXIT_FAILURE; }                     // cmdline.ggo:40 (dependon)
 	if (opt.include_samples && opt.exclude_samples) { std::cerr << "ERROR: --include-samples and --exclude-samples are mutually exclusive.\n"; return EXIT_FAILURE; }
+	// --bgzf compresses the one A2M file; a pipe's command already is the user's compressor, one file per sequence is out of its scope
+	if (opt.bgzf && !opt.output_sequences_a2m) { std::cerr << "ERROR: --bgzf requires -s / --output-sequences-a2m.\n"; return EXIT_FAILURE; }
+	if (opt.bgzf && opt.pipe) { std::cerr << "ERROR: --bgzf cannot be combined with --pipe (the piped command compresses).\n"; return EXIT_FAILURE; }
+	if (opt.bgzf && opt.output_sequences_separate) { std::cerr << "ERROR: --bgzf cannot be combined with --output-sequences-separate.\n"; return EXIT_FAILURE; }
 
 	try {
 		// The GPU contexts come up on a second thread (HIP runtime start-up and stream creation: 0.2 s) while this one reads the
@@ -319,7 +327,7 @@ int main(int argc, char **argv)
 		std::vector<vh::gpu_context *> all_gpus;
 		for (auto &g : contexts) all_gpus.push_back(g.get());
 		bool const several(opt.haplotypes && all_gpus.size() > 1);
-		bool const sharded(several && opt.output_sequences_a2m && !opt.pipe && !opt.unaligned && !opt.output_sequences_separate);
+		bool const sharded(several && opt.output_sequences_a2m && !opt.pipe && !opt.unaligned && !opt.output_sequences_separate && !opt.bgzf);   // BGZF sizes are not known up front
 		bool const interleaved(several && !sharded);
 		vh::copy_interleave const deal{8, vh::u32(all_gpus.size())};
 		std::vector<vh::copy_shard> shards;
@@ -377,6 +385,7 @@ int main(int argc, char **argv)
 			for (std::size_t k(1); k < all_gpus.size(); ++k) output.add_gpu(*all_gpus[k]);
 			if (sharded) output.set_copy_shards(shards);
 			if (interleaved) output.set_copy_interleave(deal);
+			output.set_bgzf(opt.bgzf);
 			do_output(output);
 		} else {                                            // main.cc:487-550
 			vh::founder_sequence_greedy_output output(gpu, opt.pipe, opt.dst_chromosome, !opt.omit_reference, opt.unaligned, delegate);
@@ -422,6 +431,7 @@ int main(int argc, char **argv)
 			}
 			output.set_cut_positions(std::move(cuts));
 			output.set_assigned_samples(std::move(assigned), vh::u32(opt.founder_sequences));
+			output.set_bgzf(opt.bgzf);
 			founder_graph_uploaded.get();
 			if (first_sink_warm.valid()) first_sink_warm.get(); else vh::warm_up_sink(gpu, opt.unaligned);
 			do_output(output);

@@ -200,7 +200,7 @@ namespace {
 
 // splice() over several contexts that hold the chromosome copies dealt round-robin (set_copy_interleave): the sink sees the
 // rows in the batch's order, exactly as from one context.
-void output::splice_in_turns(row_set const &rows, v2m_sink_fn sink, void *user)
+void output::splice_in_turns(row_set const &rows, v2m_sink_fn sink, void *user, std::uint32_t extra_flags)
 {
 	if (rows.any_cuts) throw std::runtime_error("rows that switch copies need the whole path matrix on their GPU");
 	std::vector<gpu_context *> gpus{&m_gpu};
@@ -227,7 +227,7 @@ void output::splice_in_turns(row_set const &rows, v2m_sink_fn sink, void *user)
 				batch.n_rows = local_copy[k].size();
 				batch.copy_index = local_copy[k].data();
 				turn_state st{&gate, &global_row[k], sink, user};
-				gpus[k]->check(v2m_splice_rows(gpus[k]->get(), &batch, m_should_output_unaligned ? V2M_SPLICE_UNALIGNED : 0u, turn_sink, &st));
+				gpus[k]->check(v2m_splice_rows(gpus[k]->get(), &batch, (m_should_output_unaligned ? V2M_SPLICE_UNALIGNED : 0u) | extra_flags, turn_sink, &st));
 			} catch (...) {
 				errors[k] = std::current_exception();
 				{ std::lock_guard<std::mutex> const lock(gate.mutex); gate.failed = true; }   // nobody waits for this context's rows any longer
@@ -246,9 +246,9 @@ void output::splice_in_turns(row_set const &rows, v2m_sink_fn sink, void *user)
 }
 
 
-void output::splice(row_set const &rows, v2m_sink_fn sink, void *user)
+void output::splice(row_set const &rows, v2m_sink_fn sink, void *user, std::uint32_t extra_flags)
 {
-	if (m_interleaved && !m_more_gpus.empty()) { splice_in_turns(rows, sink, user); return; }
+	if (m_interleaved && !m_more_gpus.empty()) { splice_in_turns(rows, sink, user, extra_flags); return; }
 	v2m_row_batch batch{};
 	batch.n_rows = rows.copy_index.size();
 	batch.copy_index = rows.copy_index.data();
@@ -262,7 +262,7 @@ void output::splice(row_set const &rows, v2m_sink_fn sink, void *user)
 		batch.cut_nodes = rows.cut_nodes.data();
 		batch.cut_copies = rows.cut_copies.data();
 	}
-	m_gpu.check(v2m_splice_rows(m_gpu.get(), &batch, m_should_output_unaligned ? V2M_SPLICE_UNALIGNED : 0u, sink, user));
+	m_gpu.check(v2m_splice_rows(m_gpu.get(), &batch, (m_should_output_unaligned ? V2M_SPLICE_UNALIGNED : 0u) | extra_flags, sink, user));
 }
 
 
@@ -281,11 +281,30 @@ std::vector<std::uint32_t> output::rebased_copies(row_set const &rows, std::uint
 
 
 namespace {
-	struct a2m_state { std::ostream *stream; std::vector<std::string> const *ids; output_delegate *delegate; };
+	struct a2m_state { std::ostream *stream; std::vector<std::string> const *ids; output_delegate *delegate; bool bgzf; std::string text; std::vector<char> framed; };
+
+	// `n` bytes of text as stored BGZF members (v2m_bgzf_frame_stored; n = 0: the EOF member)
+	void write_bgzf_stored(std::ostream &os, char const *bytes, std::size_t n, std::vector<char> &buf)
+	{
+		buf.resize(v2m_bgzf_bound(n));
+		std::uint64_t written(0);
+		if (V2M_OK != v2m_bgzf_frame_stored(bytes, n, buf.data(), buf.size(), &written)) throw std::runtime_error("v2m_bgzf_frame_stored failed");
+		os.write(buf.data(), std::streamsize(written));
+	}
 
 	int a2m_sink(void *user, uint64_t row, char const *bytes, uint64_t length)
 	{
 		auto &st(*static_cast<a2m_state *>(user));
+		if (st.bgzf) {                                                     // bytes = the body's BGZF members
+			st.text.assign(1, '>');
+			st.text += (*st.ids)[row];
+			st.text += '\n';
+			write_bgzf_stored(*st.stream, st.text.data(), st.text.size(), st.framed);
+			st.stream->write(bytes, std::streamsize(length));
+			write_bgzf_stored(*st.stream, "\n", 1, st.framed);
+			st.delegate->handled_sequences(u32(1 + row));
+			return st.stream->good() ? 0 : 1;
+		}
 		*st.stream << '>' << (*st.ids)[row] << '\n';                       // sequence_writer.cc:35-36
 		st.stream->write(bytes, std::streamsize(length));
 		*st.stream << '\n';                                                // haplotype_output.cc:57,76
@@ -489,8 +508,9 @@ void output::splice_held(row_set const &rows, v2m_hold_sink_fn sink, void *user)
 
 void output::write_a2m(row_set const &rows, std::ostream &stream)
 {
-	a2m_state st{&stream, &rows.ids, m_delegate};
-	splice(rows, a2m_sink, &st);
+	a2m_state st{&stream, &rows.ids, m_delegate, m_bgzf, {}, {}};
+	splice(rows, a2m_sink, &st, m_bgzf ? V2M_SPLICE_BGZF : 0u);
+	if (m_bgzf) write_bgzf_stored(stream, nullptr, 0, st.framed);
 }
 
 
@@ -664,7 +684,7 @@ void output::output_a2m(variant_graph const &graph, char const *dst_name)       
 		if (!good) throw std::runtime_error(std::string("error while writing to the subprocess for ") + dst_name);
 		return;
 	}
-	if (!m_more_gpus.empty() && !m_should_output_unaligned && !m_interleaved) {
+	if (!m_more_gpus.empty() && !m_should_output_unaligned && !m_interleaved && !m_bgzf) {
 		write_a2m_sharded(a2m_rows(graph), dst_name);
 		return;
 	}

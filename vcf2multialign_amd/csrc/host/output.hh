@@ -57,6 +57,12 @@ public:
 	// row order straight from the contexts' pinned buffers (no copy, no queue: a turnstile on the row index).  While one
 	// context's rows are being written, the others' next blocks are crossing PCIe.
 	void set_copy_interleave(copy_interleave deal) { m_copy_interleave = deal; m_interleaved = true; }
+
+	// A2M output as BGZF (include/v2m_hip.h, "BGZF output"; the --bgzf extension): the rows' bodies compressed on the GPU
+	// (V2M_SPLICE_BGZF), the text around them in stored members, an EOF member at the end.  Decompressed, the file is the plain A2M.
+	// Only output_a2m() uses it; with several contexts the rows take the interleaved path (set_copy_interleave()), never the sharded
+	// one, whose file offsets are known up front.
+	void set_bgzf(bool bgzf) { m_bgzf = bgzf; }
 	virtual void output_a2m(variant_graph const &graph, std::ostream &stream) = 0;
 
 protected:
@@ -67,8 +73,9 @@ protected:
 		std::vector<std::uint32_t> cut_copies;
 		bool any_cuts{};
 	};
-	void splice(row_set const &rows, v2m_sink_fn sink, void *user);             // the sink sees the rows in batch order, one at a time
-	void splice_in_turns(row_set const &rows, v2m_sink_fn sink, void *user);
+	// the sink sees the rows in batch order, one at a time; extra_flags: V2M_SPLICE_BGZF or 0
+	void splice(row_set const &rows, v2m_sink_fn sink, void *user, std::uint32_t extra_flags = 0);
+	void splice_in_turns(row_set const &rows, v2m_sink_fn sink, void *user, std::uint32_t extra_flags = 0);
 	// rows that need no order and a sink that keeps them until it calls v2m_row_release (a pool of writers): v2m_splice_rows_held per context
 	void splice_held(row_set const &rows, v2m_hold_sink_fn sink, void *user);
 	static std::vector<std::uint32_t> rebased_copies(row_set const &rows, std::uint64_t first, std::uint64_t last, copy_shard shard);
@@ -88,6 +95,7 @@ protected:
 	output_delegate *m_delegate{};
 	bool m_should_output_reference{};
 	bool m_should_output_unaligned{};
+	bool m_bgzf{};
 };
 
 class haplotype_output final : public output {

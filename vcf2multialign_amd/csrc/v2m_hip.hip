@@ -27,6 +27,7 @@
 #include "../../include/v2m_hip.h"
 #include "kernels.hpp"
 #include "founder_kernels.hpp"
+#include "bgzf_kernels.hpp"
 
 using v2m::u32;
 using v2m::u64;
@@ -151,6 +152,10 @@ struct v2m_ctx {
 	held_ring_state held_state;
 	std::vector<std::unique_ptr<v2m_row_hold>> held_ring;
 	pinned_buf trials_stage[2];   // v2m_pbwt_cut_trials_streamed: the pairs' way back to the host
+	// BGZF (V2M_SPLICE_BGZF, v2m_bgzf_compress): one 64-KiB member slot per block of a slice, the members' sizes and scanned offsets,
+	// the dense members of a slice (two: one crossing the link while the next is compacted) and their row extents on the host
+	dev_buf d_bgzf_slots, d_bgzf_sizes, d_bgzf_offsets, d_bgzf_table, d_bgzf_dense[2], d_bgzf_in;
+	pinned_buf h_bgzf_table[2];
 	hipEvent_t ev_compute[2]{}, ev_copy[2]{};
 };
 
@@ -970,7 +975,7 @@ int check_batch(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags)
 {
 	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
 	if (!rows) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "rows is NULL");
-	if (flags & ~V2M_SPLICE_UNALIGNED) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+	if (flags & ~(V2M_SPLICE_UNALIGNED | V2M_SPLICE_BGZF)) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
 	if (!ctx->has_graph) return fail(ctx, V2M_ERR_STATE, "no graph uploaded");
 	if (rows->n_rows && !rows->copy_index && !rows->cut_offsets) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "rows->copy_index is NULL");
 	if (rows->cut_offsets && rows->cut_offsets[rows->n_rows] && (!rows->cut_nodes || !rows->cut_copies))
@@ -981,6 +986,140 @@ int check_batch(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags)
 	if ((flags & V2M_SPLICE_UNALIGNED) && ctx->has_nul_byte)
 		return fail(ctx, V2M_ERR_UNSUPPORTED, "the reference sequence or an ALT label holds a NUL byte, which the unaligned kernels use as their padding marker; aligned mode keeps such bytes");
 	return V2M_OK;
+}
+
+
+// ---- BGZF (bgzf_kernels.hpp) ------------------------------------------------------------------
+
+u64 bgzf_pieces(u64 n) { return (n + v2m::kBgzfBlockBytes - 1) / v2m::kBgzfBlockBytes; }
+
+// Queues the encoder for n_rows rows at d_rows (row r at d_rows + r * pitch; lengths on the device, or `length` for every row when
+// d_lengths is NULL) whose longest row has at most max_len bytes: the members densely into d_dense, and the row extents
+// (n_rows + 1 offsets into d_dense, the last one the total) into ctx->d_bgzf_table.  The grid is n_rows x the pieces of max_len;
+// the workgroups past a row's end write a member size of 0.
+int bgzf_encode_rows(v2m_ctx *ctx, char const *d_rows, u64 pitch, u64 const *d_lengths, u64 length, u64 max_len, u64 n_rows, char *d_dense)
+{
+	u64 const per_row(std::max<u64>(1, bgzf_pieces(max_len)));
+	u64 const n_blocks(n_rows * per_row);
+	if (n_blocks > 0x7FFFFFFFull || per_row > 0xFFFFFFFFull)
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "BGZF grid too large (%llu blocks); use smaller batches", (unsigned long long) n_blocks);
+	V2M_HIP_TRY(ctx, ctx->d_bgzf_slots.ensure(n_blocks * v2m::kBgzfSlotBytes));
+	V2M_HIP_TRY(ctx, ctx->d_bgzf_sizes.ensure(n_blocks * sizeof(u32)));
+	V2M_HIP_TRY(ctx, ctx->d_bgzf_offsets.ensure(n_blocks * sizeof(u64)));
+	V2M_HIP_TRY(ctx, ctx->d_bgzf_table.ensure((n_rows + 1) * sizeof(u64)));
+	{
+		timed_launch tl(ctx, V2M_KERNEL_BGZF);
+		hipLaunchKernelGGL(v2m::bgzf_deflate_kernel, dim3(unsigned(n_blocks)), dim3(v2m::kBgzfThreads), 0, ctx->stream,
+			d_rows, pitch, d_lengths, length, u32(per_row), ctx->d_bgzf_slots.as<char>(), ctx->d_bgzf_sizes.as<u32>());
+		hipLaunchKernelGGL(v2m::bgzf_scan_kernel, dim3(1), dim3(v2m::kBgzfScanThreads), 0, ctx->stream,
+			ctx->d_bgzf_sizes.as<u32>(), n_blocks, u32(per_row), n_rows, ctx->d_bgzf_offsets.as<u64>(), ctx->d_bgzf_table.as<u64>());
+		hipLaunchKernelGGL(v2m::bgzf_compact_kernel, dim3(unsigned(n_blocks)), dim3(256), 0, ctx->stream,
+			ctx->d_bgzf_slots.as<char>(), ctx->d_bgzf_sizes.as<u32>(), ctx->d_bgzf_offsets.as<u64>(), d_dense);
+	}
+	V2M_HIP_TRY(ctx, hipGetLastError());
+	return V2M_OK;
+}
+
+
+// v2m_splice_rows with V2M_SPLICE_BGZF.  The ring of v2m_splice_rows with the encoder after every slice's splice: slice s's members
+// are compacted into d_bgzf_dense[s & 1] and its row extents come back on the compute stream; the host reads the slice's total only
+// after slice s + 1 has been queued and then copies just the compressed bytes on the copy stream, so the link and the kernels still
+// overlap.  The dense buffers and pinned slots are sized by the worst case (v2m_bgzf_bound per row: tiny rows expand), and a slice
+// is cut so that its 64-KiB member slots stay within 1 GiB.
+int splice_rows_bgzf(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2m_sink_fn sink, void *user)
+{
+	u64 const L(ctx->aligned_len);
+	u64 const max_len(unaligned ? v2m_max_unaligned_length(ctx) : L);
+	u64 const pitch(unaligned ? ((max_len + 255) & ~u64(255)) : v2m_min_row_pitch(ctx));
+	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
+	u64 const slot_default(rows->n_rows * pitch < (u64(8) << 30) ? (u64(128) << 20) : (u64(512) << 20));
+	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : slot_default);
+	u64 const member_slots_per_row(std::max<u64>(1, bgzf_pieces(max_len)) * v2m::kBgzfSlotBytes);
+	u64 const rows_per_slice(std::max<u64>(1, std::min<u64>({rows->n_rows, slot_target / pitch, (u64(1) << 30) / member_slots_per_row})));
+	u64 const n_slices((rows->n_rows + rows_per_slice - 1) / rows_per_slice);
+	u64 const dense_bytes(rows_per_slice * v2m_bgzf_bound(max_len));
+	for (int i(0); i < (n_slices > 1 ? 2 : 1); ++i) {
+		V2M_HIP_TRY(ctx, ctx->ring[i].ensure(rows_per_slice * pitch));
+		V2M_HIP_TRY(ctx, ctx->d_bgzf_dense[i].ensure(dense_bytes));
+		V2M_HIP_TRY(ctx, ctx->host_ring[i].ensure(dense_bytes));
+		V2M_HIP_TRY(ctx, ctx->h_bgzf_table[i].ensure((rows_per_slice + 1) * sizeof(u64)));
+	}
+	std::vector<u64> extents[2];
+	auto const slice_rows([&](u64 s, u64 &r0, u64 &r1) { r0 = s * rows_per_slice; r1 = std::min(rows->n_rows, r0 + rows_per_slice); });
+
+	auto const launch([&](u64 s) -> int {
+		int const b(int(s & 1));
+		u64 r0, r1;
+		slice_rows(s, r0, r1);
+		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_copy[b], 0));   // d_bgzf_dense[b] has crossed the link
+		if (int const rc = unaligned
+				? splice_unaligned_slice(ctx, rows, r0, r1, ctx->ring[b].as<char>(), pitch)
+				: splice_aligned_slice(ctx, rows, r0, r1, ctx->ring[b].as<char>(), pitch))
+			return rc;
+		if (int const rc = bgzf_encode_rows(ctx, ctx->ring[b].as<char>(), pitch, unaligned ? ctx->d_row_lengths.as<u64>() : nullptr, L, max_len, r1 - r0, ctx->d_bgzf_dense[b].as<char>()))
+			return rc;
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_bgzf_table[b].p, ctx->d_bgzf_table.p, (r1 - r0 + 1) * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
+		return V2M_OK;
+	});
+	auto const issue_copy([&](u64 s) -> int {
+		int const b(int(s & 1));
+		u64 r0, r1;
+		slice_rows(s, r0, r1);
+		V2M_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_compute[b]));
+		u64 const *const table(ctx->h_bgzf_table[b].as<u64>());
+		extents[b].assign(table, table + (r1 - r0 + 1));
+		if (extents[b].back() > ctx->host_ring[b].bytes)
+			return fail(ctx, V2M_ERR_HIP, "BGZF members of rows %llu.. exceed their bound", (unsigned long long) r0);
+		if (extents[b].back())
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->host_ring[b].p, ctx->d_bgzf_dense[b].p, extents[b].back(), hipMemcpyDeviceToHost, ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_copy[b], ctx->copy_stream));
+		return V2M_OK;
+	});
+	auto const drain([&](u64 s) -> int {
+		int const b(int(s & 1));
+		u64 r0, r1;
+		slice_rows(s, r0, r1);
+		V2M_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_copy[b]));
+		char const *const base(ctx->host_ring[b].as<char>());
+		for (u64 r(r0); r < r1; ++r) {
+			u64 const begin(extents[b][r - r0]), end(extents[b][r - r0 + 1]);
+			if (sink(user, r, base + begin, end - begin)) return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
+		}
+		return V2M_OK;
+	});
+
+	int rc(V2M_OK);
+	u64 launched(0), copied(0), drained(0);
+	for (u64 s(0); s < n_slices && V2M_OK == rc; ++s) {
+		if (V2M_OK != (rc = launch(s))) break;
+		launched = s + 1;
+		if (s >= 1) { if (V2M_OK != (rc = issue_copy(s - 1))) break; copied = s; }
+		if (s >= 2) { if (V2M_OK != (rc = drain(s - 2))) break; drained = s - 1; }
+	}
+	while (V2M_OK == rc && copied < launched) { rc = issue_copy(copied); if (V2M_OK == rc) ++copied; }
+	while (V2M_OK == rc && drained < copied) { rc = drain(drained); if (V2M_OK == rc) ++drained; }
+	(void) hipStreamSynchronize(ctx->stream);
+	(void) hipStreamSynchronize(ctx->copy_stream);
+	return rc;
+}
+
+
+// CRC-32 (IEEE, reflected 0xEDB88320) of n host bytes.
+uint32_t crc32_host(unsigned char const *p, u64 n)
+{
+	static uint32_t const *const table([] {
+		static uint32_t t[256];
+		for (uint32_t i(0); i < 256; ++i) {
+			uint32_t c(i);
+			for (int k(0); k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+			t[i] = c;
+		}
+		return t;
+	}());
+	uint32_t c(0xFFFFFFFFu);
+	for (u64 i(0); i < n; ++i) c = table[(c ^ p[i]) & 255] ^ (c >> 8);
+	return ~c;
 }
 
 } // namespace
@@ -1721,6 +1860,7 @@ int v2m_pbwt_cut_records(v2m_ctx *ctx, uint64_t n_copies, uint64_t n_cuts, const
 int v2m_splice_rows_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, void *d_out, uint64_t row_pitch, uint64_t *row_lengths_out)
 {
 	if (int const rc = check_batch(ctx, rows, flags)) return rc;
+	if (flags & V2M_SPLICE_BGZF) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "V2M_SPLICE_BGZF needs a sink (v2m_splice_rows): device rows are not compressed");
 	if (0 == rows->n_rows) return V2M_OK;
 	bool const unaligned(flags & V2M_SPLICE_UNALIGNED);
 	if (!d_out || ((uintptr_t) d_out & 15)) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_out must be a 16-byte aligned device pointer");
@@ -1756,6 +1896,7 @@ int v2m_splice_rows(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m
 			if (sink(user, r, "", 0)) return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
 		return V2M_OK;
 	}
+	if (flags & V2M_SPLICE_BGZF) return splice_rows_bgzf(ctx, rows, unaligned, sink, user);
 
 	// Slices of the batch alternate between two device buffers and two pinned host buffers:
 	// the D2H copy of slice s runs on copy_stream while the kernels of slice s+1 run on stream.
@@ -1839,6 +1980,7 @@ int v2m_splice_rows_held(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags
 {
 	if (int const rc = check_batch(ctx, rows, flags)) return rc;
 	if (!sink) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "sink is NULL");
+	if (flags & V2M_SPLICE_BGZF) return fail(ctx, V2M_ERR_UNSUPPORTED, "V2M_SPLICE_BGZF is not supported by v2m_splice_rows_held");
 	if (n_slots < 2 || n_slots > 64) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "n_slots must be between 2 and 64 (got %u)", n_slots);
 	if (0 == rows->n_rows) return V2M_OK;
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2032,6 +2174,75 @@ int v2m_free_output(v2m_ctx *ctx, void *d_ptr)
 	if (!d_ptr) return V2M_OK;
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 	V2M_HIP_TRY(ctx, hipFree(d_ptr));
+	return V2M_OK;
+}
+
+
+
+// ---- BGZF ------------------------------------------------------------------------------------------
+
+uint64_t v2m_bgzf_bound(uint64_t n)
+{
+	return 0 == n ? 28 : n + v2m::kBgzfStoredOverhead * bgzf_pieces(n);
+}
+
+int v2m_bgzf_frame_stored(const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out)
+{
+	static unsigned char const eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	if ((n && !src) || !n_out || (!dst && cap)) return V2M_ERR_INVALID_ARGUMENT;
+	*n_out = 0;
+	u64 const need(v2m_bgzf_bound(n));
+	if (cap < need) return V2M_ERR_INVALID_ARGUMENT;
+	unsigned char *out(static_cast<unsigned char *>(dst));
+	if (0 == n) { std::memcpy(out, eof, sizeof(eof)); *n_out = sizeof(eof); return V2M_OK; }
+	unsigned char const *in(static_cast<unsigned char const *>(src));
+	auto const le16([](unsigned char *p, u32 v) { p[0] = v & 255; p[1] = (v >> 8) & 255; });
+	auto const le32([&](unsigned char *p, u32 v) { le16(p, v); le16(p + 2, v >> 16); });
+	for (u64 done(0); done < n;) {
+		u32 const piece(u32(std::min<u64>(n - done, v2m::kBgzfBlockBytes)));
+		std::memcpy(out, eof, 16);                                   // the header up to BSIZE
+		le16(out + 16, piece + v2m::kBgzfStoredOverhead - 1);
+		out[18] = 1;                                                 // BFINAL, BTYPE 00
+		le16(out + 19, piece);
+		le16(out + 21, ~piece & 0xffffu);
+		std::memcpy(out + 23, in + done, piece);
+		le32(out + 23 + piece, crc32_host(in + done, piece));
+		le32(out + 27 + piece, piece);
+		out += piece + v2m::kBgzfStoredOverhead;
+		done += piece;
+	}
+	*n_out = need;
+	return V2M_OK;
+}
+
+int v2m_bgzf_compress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if ((n && !src) || !n_out) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "src or n_out is NULL");
+	*n_out = 0;
+	if (0 == n) return V2M_OK;
+	if (!dst) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "dst is NULL");
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	u64 const chunk_max(u64(v2m::kBgzfBlockBytes) * 4096);   // 267 MB of input per pass
+	u64 const first(std::min(n, chunk_max));
+	V2M_HIP_TRY(ctx, ctx->d_bgzf_in.ensure((first + 15) & ~u64(15)));
+	V2M_HIP_TRY(ctx, ctx->d_bgzf_dense[0].ensure(v2m_bgzf_bound(first)));
+	u64 written(0);
+	for (u64 done(0); done < n;) {
+		u64 const chunk(std::min(n - done, chunk_max));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bgzf_in.p, static_cast<char const *>(src) + done, chunk, hipMemcpyHostToDevice, ctx->stream));
+		if (int const rc = bgzf_encode_rows(ctx, ctx->d_bgzf_in.as<char>(), 0, nullptr, chunk, chunk, 1, ctx->d_bgzf_dense[0].as<char>())) return rc;
+		u64 extent[2];
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(extent, ctx->d_bgzf_table.p, sizeof(extent), hipMemcpyDeviceToHost, ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		if (extent[1] > cap - written)
+			return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "dst holds %llu bytes; the members need more (v2m_bgzf_bound(n) = %llu)", (unsigned long long) cap, (unsigned long long) v2m_bgzf_bound(n));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(static_cast<char *>(dst) + written, ctx->d_bgzf_dense[0].p, extent[1], hipMemcpyDeviceToHost, ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		written += extent[1];
+		done += chunk;
+	}
+	*n_out = written;
 	return V2M_OK;
 }
 

@@ -2,15 +2,19 @@
 the row order, FASTA identifiers and '\\n' placement of haplotype_output::output_a2m
 (libvcf2multialign/haplotype_output.cc:38-82) and founder_sequence_greedy_output::output_a2m
 (libvcf2multialign/founder_sequence_greedy_output.cc:515-550), with every row body produced by the
-GPU through v2m_splice_rows instead of output_sequence()."""
+GPU through v2m_splice_rows instead of output_sequence().
 
-from .context import RowBatch
+With bgzf=True the stream receives a BGZF file (include/v2m_hip.h, "BGZF output") whose decompressed bytes are the plain A2M:
+the '>'id'\n' and '\n' around every body in stored members, the bodies as the GPU's members, then the EOF member."""
+
+from .context import RowBatch, bgzf_frame_stored
 from .variant_graph import PLOIDY_MAX
 
 
 class Output:
-	def __init__(self, ctx, chromosome_id=None, should_output_reference=True, should_output_unaligned=False):
+	def __init__(self, ctx, chromosome_id=None, should_output_reference=True, should_output_unaligned=False, bgzf=False):
 		self.ctx = ctx
+		self.bgzf = bgzf
 		self.chromosome_id = chromosome_id
 		self.should_output_reference = should_output_reference
 		self.should_output_unaligned = should_output_unaligned
@@ -19,11 +23,19 @@ class Output:
 		return ((self.chromosome_id + "\t") if self.chromosome_id else "") + name
 
 	def _write_rows(self, stream, ids, rows):
-		def sink(i, body):
-			stream.write(b">" + ids[i].encode() + b"\n")
-			stream.write(body)
-			stream.write(b"\n")
-		self.ctx.splice_rows(RowBatch(rows), sink=sink, unaligned=self.should_output_unaligned)
+		if self.bgzf:
+			def sink(i, members):
+				stream.write(bgzf_frame_stored(b">" + ids[i].encode() + b"\n"))
+				stream.write(members)
+				stream.write(bgzf_frame_stored(b"\n"))
+		else:
+			def sink(i, body):
+				stream.write(b">" + ids[i].encode() + b"\n")
+				stream.write(body)
+				stream.write(b"\n")
+		self.ctx.splice_rows(RowBatch(rows), sink=sink, unaligned=self.should_output_unaligned, bgzf=self.bgzf)
+		if self.bgzf:
+			stream.write(bgzf_frame_stored(b""))
 
 
 class HaplotypeOutput(Output):
