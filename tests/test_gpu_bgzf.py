@@ -1,16 +1,20 @@
 """The GPU BGZF encoder (V2M_SPLICE_BGZF, v2m_bgzf_compress, --bgzf): every output decompresses, with Python's zlib as the
-independent decoder, to exactly the bytes the same call writes without compression."""
+independent decoder, to exactly the bytes the same call writes without compression; and every member is byte for byte the one the CPU
+reference encoder (tests/deflate_ref.py) writes for its piece, at the edge inputs of tests/test_bgzf_model.py."""
 
 import gzip
 import os
 import random
+import shutil
 import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import deflate_ref
 import synth
+import test_bgzf_model as edges
 from test_bgzf_host import EOF_MEMBER, bgzf_members
 
 pytestmark = pytest.mark.gpu
@@ -123,7 +127,8 @@ def test_a2m_like_ratio(v2m, ctx):
 
 
 def test_fibonacci_frequencies_force_the_length_limit(v2m, ctx):
-	"""Symbol frequencies 1, 1, 2, 3, 5, 8, ... over 22 symbols: an unlimited Huffman code would need 21-bit codes."""
+	"""Symbol frequencies 1, 1, 2, 3, 5, 8, ... over 22 symbols.  (The builder's tie-break balances plain Fibonacci frequencies into
+	12-bit codes; test_exact_limiters has a piece that does need the 15-bit limit.)"""
 	fib = [1, 1]
 	while len(fib) < 22:
 		fib.append(fib[-1] + fib[-2])
@@ -164,6 +169,7 @@ def _rows_match(v2m, ctx, rows, unaligned):
 			continue
 		assert len(bgzf_members(members)) == -(-len(body) // PIECE)
 		assert gzip.decompress(members) == body, "row %d" % i
+		assert members == deflate_ref.encode(body), "row %d: the members are not the reference encoder's" % i
 
 
 def test_fixture_rows(v2m, ctx):
@@ -288,3 +294,178 @@ def test_config3_full_size(v2m):
 		assert packed == plain
 		bases = sum(n for n, _ in plain.values())
 		assert n_bytes[0] / bases <= 0.29, n_bytes[0] / bases
+
+
+# ---- byte for byte against the CPU reference encoder (tests/deflate_ref.py) ---------------------------------
+
+def _first_difference(got, want):
+	"""Where two members first differ, and the first token where their blocks differ (when the kernel's member decodes)."""
+	i = next((k for k, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+	where = "%d vs %d bytes, first difference at byte %d" % (len(got), len(want), i)
+	try:
+		g = deflate_ref.inflate_tokens(deflate_ref.member_payload(got))
+		w = deflate_ref.inflate_tokens(deflate_ref.member_payload(want))
+	except deflate_ref.DeflateError as e:
+		return where + " (the kernel's member does not inflate: %s)" % e
+	if [b["btype"] for b in g] != [b["btype"] for b in w]:
+		return where + "; BTYPE %s vs %s" % ([b["btype"] for b in g], [b["btype"] for b in w])
+	tg, tw = deflate_ref.tokens_of(g), deflate_ref.tokens_of(w)
+	j = next((k for k, (a, b) in enumerate(zip(tg, tw)) if a != b), min(len(tg), len(tw)))
+	if j < max(len(tg), len(tw)):
+		pos = sum(1 if t[0] == "lit" else t[1] for t in tw[:j])
+		return where + "; token %d (input byte %d): %s vs %s" % (j, pos, tg[j:j + 3], tw[j:j + 3])
+	for key in ("hlit", "hclen", "cl_lengths", "lit_lengths"):
+		if g[0].get(key) != w[0].get(key):
+			return where + "; same tokens, %s differ: %s vs %s" % (key, g[0].get(key), w[0].get(key))
+	return where
+
+
+def _exact(ctx, cases):
+	"""ctx.bgzf_compress(data) == deflate_ref.encode(data) for every (name, data); one call per case."""
+	bad = []
+	for name, data in cases:
+		got, want = ctx.bgzf_compress(data), deflate_ref.encode(data)
+		if got != want:
+			try:
+				gm = bgzf_members(got)
+			except Exception:   # (the kernel's output is not even valid BGZF)
+				gm = []
+			if b"".join(p for _, p in gm) != data:
+				gm = []
+			wm = bgzf_members(want)
+			k = next((k for k, (a, b) in enumerate(zip(gm, wm)) if a[0] != b[0]), 0)
+			bad.append("%s, member %d: %s" % (name, k, _first_difference(gm[k][0], wm[k][0]) if gm else "does not decompress to the input"))
+	assert not bad, "%d of %d cases differ from the reference encoder:\n" % (len(bad), len(cases)) + "\n".join(bad[:20])
+
+
+def test_exact_piece_sizes(ctx):
+	_exact(ctx, edges.size_pieces())
+
+
+def test_exact_runs_at_segment_edges(ctx):
+	_exact(ctx, [(name, data) for name, data, _ in edges.segment_edge_pieces()])
+
+
+def test_exact_byte_values(ctx):
+	_exact(ctx, edges.byte_value_pieces())
+
+
+def test_exact_limiters(ctx):
+	"""The literal/length code folded into 15 bits, and the code-length code into 7 (the model's tests show both need it)."""
+	_exact(ctx, [("15-bit limit", edges.fibonacci_piece()), ("7-bit code-length limit", edges.cl_limit_piece())])
+
+
+def test_exact_stored_dynamic_tie(ctx):
+	"""Through stored_bytes == dynamic_bytes: at the tie the stored block is the one (stored iff it is not larger)."""
+	sweep = edges.tie_sweep()
+	diffs = [d for _, _, d in sweep]
+	assert 0 in diffs and min(diffs) < 0 < max(diffs)
+	_exact(ctx, [("run of %d, stored - dynamic = %d" % (r, d), piece) for r, piece, d in sweep])
+	for r, piece, d in sweep:
+		if d == 0:
+			assert ctx.bgzf_compress(piece)[18] & 7 == 1, "the tie takes the stored block"
+
+
+def test_exact_random_pieces(ctx):
+	_exact(ctx, edges.random_pieces(64))
+
+
+def test_exact_in_one_call(ctx):
+	"""The same pieces as the members of one multi-piece call (every piece a full one, so the pieces are the cases)."""
+	cases = [d for _, d, _ in edges.segment_edge_pieces()] + [d for _, d in edges.random_pieces(64) if len(d) == PIECE]
+	data = b"".join(cases)
+	assert ctx.bgzf_compress(data) == b"".join(deflate_ref.encode_member(d) for d in cases)
+
+
+def _distinct_pieces(n_bytes, seed):
+	"""n_bytes of A2M-like pieces, each made distinct by its index in its first 8 bytes."""
+	n = -(-n_bytes // PIECE)
+	base = np.frombuffer(edges.a2m_like(seed, PIECE), np.uint8)
+	a = np.tile(base, n)
+	a.reshape(n, PIECE)[:, :8] = np.arange(n, dtype="<u8").view(np.uint8).reshape(n, 8)
+	return a[:n_bytes].tobytes()
+
+
+def _check_pieces(out, data):
+	members = bgzf_members(out)
+	assert len(members) == -(-len(data) // PIECE)
+	for k, (_, p) in enumerate(members):
+		assert p == data[k * PIECE:(k + 1) * PIECE], "member %d" % k
+	return members
+
+
+@pytest.mark.parametrize("n_pieces", [1023, 1024, 1025, 2049])
+def test_many_blocks_in_one_pass(ctx, n_pieces):
+	"""The member-size scan runs in rounds of 1024 blocks: every member in its place, and the members at the rounds' edges exact."""
+	data = _distinct_pieces(n_pieces * PIECE - 1000, n_pieces)
+	members = _check_pieces(ctx.bgzf_compress(data), data)
+	for k in sorted({0, 1, 1022, 1023, 1024, 1025, 2047, 2048, n_pieces - 2, n_pieces - 1} & set(range(n_pieces))):
+		assert members[k][0] == deflate_ref.encode_member(data[k * PIECE:(k + 1) * PIECE]), "member %d" % k
+
+
+def test_multi_pass_compress(ctx):
+	"""v2m_bgzf_compress takes 4096 pieces per pass: an input of two passes, the members either side of the boundary exact, and the
+	whole output that of one call per pass."""
+	chunk = 4096 * PIECE
+	data = _distinct_pieces(chunk + 2 * PIECE + 77, 3)
+	out = ctx.bgzf_compress(data)
+	members = _check_pieces(out, data)
+	assert len(members) == 4096 + 3
+	for k in (4094, 4095, 4096, 4097, 4098):
+		assert members[k][0] == deflate_ref.encode_member(data[k * PIECE:(k + 1) * PIECE]), "member %d" % k
+	assert out == ctx.bgzf_compress(data[:chunk]) + ctx.bgzf_compress(data[chunk:])
+
+
+# ---- the same file whichever way it is written -----------------------------------------------------------
+
+def _run_env(args, **env):
+	e = dict(os.environ)
+	e.update(env)
+	return subprocess.run([CLI] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=e)
+
+
+def test_cli_files_are_reproducible(v2m, tmp_path):
+	"""--bgzf files are byte-identical across one context and --device=0,0, across ring slice sizes, and to what the Python
+	HaplotypeOutput writes, aligned and --unaligned; -F likewise across contexts and slice sizes."""
+	g = synth.build_case(tmp_path, 36, 90000, 1500, 8, long_every=40)
+	fa, vcf = str(tmp_path / "synth.fa"), str(tmp_path / "synth.vcf")
+	files = {}
+	for mode in (["-H"], ["-H", "--unaligned"], ["-F", "7"]):
+		outs = []
+		for extra, env in [([], {}), (["--device=0,0"], {}), ([], {"V2M_RING_SLOT_BYTES": "300000"}), (["--device=0,0"], {"V2M_RING_SLOT_BYTES": "1000000"})]:
+			out = tmp_path / ("out%d.a2m.gz" % len(outs))
+			r = _run_env(["-r", fa, "-a", vcf, "-c", "1", "-s", str(out), "--bgzf"] + mode + extra, **env)
+			assert r.returncode == 0, r.stderr.decode()
+			outs.append(out.read_bytes())
+		assert all(o == outs[0] for o in outs), (mode, [len(o) for o in outs])
+		files[" ".join(mode)] = outs[0]
+	import io
+	vg = v2m.VariantGraph.from_object(g)
+	with v2m.Context(0) as c:
+		c.upload_graph(vg, g.ref)
+		for unaligned, key in ((False, "-H"), (True, "-H --unaligned")):
+			buf = io.BytesIO()
+			v2m.HaplotypeOutput(c, bgzf=True, should_output_unaligned=unaligned).output_a2m(vg, buf)
+			assert buf.getvalue() == files[key], key
+	gz = shutil.which("gzip")
+	if gz:
+		for key, data in files.items():
+			r = subprocess.run([gz, "-dc"], input=data, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+			assert r.returncode == 0 and r.stdout == gzip.decompress(data), (key, r.stderr)
+
+
+def test_cli_fixture_file_is_the_python_one(v2m, ctx, tmp_path):
+	import io
+	import oracle
+	for unaligned in (False, True):
+		out = tmp_path / "out.a2m.gz"
+		args = ["--haplotypes", "--input-reference=" + os.path.join(FIX, "test-4.fa"), "--input-variants=" + os.path.join(FIX, "test-4.vcf"),
+			"--chromosome=1", "--bgzf", "-s", str(out)] + (["--unaligned"] if unaligned else [])
+		r = _run(args)
+		assert r.returncode == 0, r.stderr.decode()
+		g = oracle.build_variant_graph(os.path.join(FIX, "test-4.fa"), os.path.join(FIX, "test-4.vcf"), "1")
+		vg = v2m.VariantGraph.from_object(g)
+		ctx.upload_graph(vg, g.ref)
+		buf = io.BytesIO()
+		v2m.HaplotypeOutput(ctx, bgzf=True, should_output_unaligned=unaligned).output_a2m(vg, buf)
+		assert buf.getvalue() == out.read_bytes()

@@ -9,7 +9,8 @@
 //   the bit cost of every thread's tokens -> a block prefix sum gives each thread its bit offset -> one final dynamic block
 //   (BTYPE 10) packed into an LDS staging slot with ds_or, or a stored block when that is not larger.
 //   CRC-32: every thread a table CRC of its segment in the raw register form (init 0, no final xor), moved to the block's end
-//   by multiplying with x^(8 L) mod P (powers x^(8 2^k) precomputed), xor-reduced; the init and final xor are applied once.
+//   by multiplying with x^(8 L) mod P (powers x^(2^k) precomputed, from k = 3 on for whole bytes), xor-reduced; the init and final xor
+//   are applied once.
 // bgzf_scan_kernel: exclusive scan of the member sizes of a slice (one workgroup), row extents + slice total into a small table.
 // bgzf_compact_kernel: copies the members densely to their scanned offsets.
 #pragma once
@@ -18,7 +19,7 @@
 #include <stdint.h>
 
 // Tables in constant memory, outside namespace v2m: tests/test_kernel_isa.py reads every _ZN3v2m label of the ISA as a kernel.
-// x^(8 * 2^k) mod P in the reflected representation (CRC-32, P = 0xEDB88320)
+// x^(2^k) mod P in the reflected representation (CRC-32, P = 0xEDB88320); crc_shift by n bytes starts at k = 3 (x^8: one byte)
 __constant__ static uint32_t const kBgzfCrcX2n[32] = {
 	0x40000000, 0x20000000, 0x08000000, 0x00800000, 0x00008000, 0xedb88320, 0xb1e6b092, 0xa06a2517, 0xed627dae, 0x88d14467, 0xd7bbfe6a,
 	0xec447f11, 0x8e7ea170, 0x6427800e, 0x4d47bae0, 0x09fe548f, 0x83852d0f, 0x30362f1a, 0x7b5a9cc3, 0x31fec169, 0x9fec022a, 0x6c8dedc4,
