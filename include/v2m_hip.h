@@ -34,7 +34,8 @@
  * v2m_profile_get_launches (v2m_bind_path_matrix_device followed without a step); 3 = + v2m_upload_path_blocks (and then
  * v2m_pbwt_cut_trials, v2m_pbwt_cut_records); 4 = + v2m_pbwt_cut_trials_streamed; 5 = + v2m_splice_rows_held / v2m_row_release (rows a
  * sink may keep until it says so).  Entries have only ever been added.  V2M_SPLICE_BGZF, v2m_bgzf_compress, v2m_bgzf_bound and
- * v2m_bgzf_frame_stored were added without a new version: a caller probes for them by symbol.
+ * v2m_bgzf_frame_stored were added without a new version, and so were v2m_set_column_window and v2m_window_length: a caller
+ * probes for them by symbol.
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -188,10 +189,11 @@ int v2m_upload_path_blocks(v2m_ctx *ctx, const uint64_t *paths_by_edge_and_chrom
  * has finished (v2m_ctx_synchronize()). */
 int v2m_bind_path_matrix_device(v2m_ctx *ctx, const void *d_paths_by_edge_and_chrom_copy, uint64_t n_rows, uint64_t n_cols);
 
-/* aligned_positions.back(): the length of every aligned row. 0 before an upload. */
+/* aligned_positions.back(): the length of every aligned row. 0 before an upload.  (A column window does not change it.) */
 uint64_t v2m_aligned_length(const v2m_ctx *ctx);
 /* The row pitch the library itself uses in aligned mode (aligned length rounded up to 256: rows then start on
- * 256-B boundaries).  v2m_splice_rows_device accepts any multiple of 16 that is >= the aligned length rounded up to 16. */
+ * 256-B boundaries).  v2m_splice_rows_device accepts any multiple of 16 that is >= the aligned length rounded up to 16.
+ * With a column window (v2m_set_column_window) both rules take the window's length instead of the aligned length. */
 uint64_t v2m_min_row_pitch(const v2m_ctx *ctx);
 
 /* ---- rows -------------------------------------------------------------------------------- */
@@ -264,8 +266,29 @@ int v2m_splice_rows_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t fla
 int v2m_alloc_output(v2m_ctx *ctx, uint64_t bytes, int candidates, void **d_out);
 int v2m_free_output(v2m_ctx *ctx, void *d_ptr);
 
-/* Upper bound of any unaligned row's length for the uploaded graph. */
+/* Upper bound of any unaligned row's length for the uploaded graph (with a column window: the window's length). */
 uint64_t v2m_max_unaligned_length(const v2m_ctx *ctx);
+
+/* ---- column windows ---------------------------------------------------------------------------
+ *
+ * A column window [col_begin, col_end), 0 <= col_begin < col_end <= L = v2m_aligned_length(), makes every following
+ * v2m_splice_rows, v2m_splice_rows_held and v2m_splice_rows_device call produce window bodies instead of whole rows:
+ *   - aligned mode: bytes [col_begin, col_end) of the whole aligned row, exactly;
+ *   - unaligned mode: every byte the walk emits sits in its own column (a reference segment or label never exceeds its aligned span,
+ *     the padding fills the rest); the body is the emitted bytes whose column lies in the window, in order.  The walk's padding is
+ *     left out, a '-' that is part of the reference or of a label is kept, so the body is never longer than col_end - col_begin;
+ *   - V2M_SPLICE_BGZF: the members cover the window body, cut into 65 280-byte pieces from its first byte.
+ * A window equal to the whole row gives exactly the bytes of no window.  Row order, cut semantics and everything else are unchanged;
+ * v2m_aligned_length() stays L, while v2m_min_row_pitch(), v2m_max_unaligned_length() and the row_pitch rules of
+ * v2m_splice_rows_device describe the window's rows.  The work of a row call scales with the window: its tiles and the edge words
+ * that reach into it (plus the look-back of their restart points).
+ * v2m_upload_graph resets the window to the whole row, and so does v2m_set_column_window(ctx, 0, L).  Returns V2M_ERR_STATE
+ * before an upload and V2M_ERR_INVALID_ARGUMENT for an empty or out-of-range window.  Synchronous.
+ * A reference range [s, e) (0-based, half-open) is the window [col(s), col(e)) with col(p) = aligned_positions[n] +
+ * (p - reference_positions[n]) for the last node n with reference_positions[n] <= p, and col(reference length) = L. */
+int v2m_set_column_window(v2m_ctx *ctx, uint64_t col_begin, uint64_t col_end);
+/* col_end - col_begin of the window; L without one (0 before an upload). */
+uint64_t v2m_window_length(const v2m_ctx *ctx);
 
 /* ---- founder search: the chunk walks ---------------------------------- */
 

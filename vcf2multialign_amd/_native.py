@@ -69,6 +69,8 @@ SIGNATURES = {
 	"v2m_aligned_length": (C.c_uint64, [C.c_void_p]),
 	"v2m_min_row_pitch": (C.c_uint64, [C.c_void_p]),
 	"v2m_max_unaligned_length": (C.c_uint64, [C.c_void_p]),
+	"v2m_set_column_window": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+	"v2m_window_length": (C.c_uint64, [C.c_void_p]),
 	"v2m_splice_rows": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, SINK_FN, C.c_void_p]),
 	"v2m_splice_rows_held": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint32, HOLD_SINK_FN, C.c_void_p]),
 	"v2m_row_release": (None, [C.c_void_p]),

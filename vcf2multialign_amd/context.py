@@ -155,6 +155,16 @@ class Context:
 	def max_unaligned_length(self):
 		return self._lib.v2m_max_unaligned_length(self._h)
 
+	def set_column_window(self, col_begin, col_end):
+		"""v2m_set_column_window: every following row call produces columns [col_begin, col_end) of the rows (aligned: exactly those
+		bytes; unaligned: the emitted bytes whose column lies there).  (0, aligned_length) is the whole row again, as is a new upload."""
+		self._check(self._lib.v2m_set_column_window(self._h, int(col_begin), int(col_end)))
+
+	@property
+	def window_length(self):
+		"""v2m_window_length: col_end - col_begin of the column window, the aligned length without one."""
+		return self._lib.v2m_window_length(self._h)
+
 	# ---- rows ----------------------------------------------------------------------------------
 	def splice_rows(self, rows, sink=None, unaligned=False, bgzf=False):
 		"""v2m_splice_rows.  sink(row_index, body: bytes) is called per row in order; without a sink the

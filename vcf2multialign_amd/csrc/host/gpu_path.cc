@@ -2,6 +2,8 @@
 
 #include <cstdlib>
 #include <exception>
+#include <stdexcept>
+#include <string>
 
 #include <algorithm>
 
@@ -33,6 +35,21 @@ bit_matrix transpose_matrix(gpu_context &gpu, bit_matrix const &mat)
 void transpose_paths(gpu_context &gpu, variant_graph &graph)
 {
 	graph.paths_by_chrom_copy_and_edge = transpose_matrix(gpu, graph.paths_by_edge_and_chrom_copy);
+}
+
+
+column_window columns_of_reference_range(variant_graph const &graph, u64 ref_len, u64 s, u64 e)
+{
+	auto const &rp(graph.reference_positions);
+	auto const &ap(graph.aligned_positions);
+	if (!(s < e && e <= ref_len) || rp.empty())
+		throw std::invalid_argument("reference range [" + std::to_string(s) + ", " + std::to_string(e) + ") is empty or not within the reference (" + std::to_string(ref_len) + ")");
+	auto const col([&](u64 p) -> u64 {
+		if (p >= ref_len) return ap.back();
+		u64 const n(u64(std::upper_bound(rp.begin(), rp.end(), p) - rp.begin()) - 1);   // rp[0] = 0 <= p
+		return ap[n] + (p - rp[n]);
+	});
+	return {col(s), col(e)};
 }
 
 

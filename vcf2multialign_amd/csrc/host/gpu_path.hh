@@ -41,6 +41,12 @@ void transpose_paths(gpu_context &gpu, variant_graph &graph);
 // comes from upload_path_slice()).
 void upload_graph(gpu_context &gpu, sequence_type const &ref_seq, variant_graph const &graph, bool with_paths = true);
 
+// The column window of the 0-based half-open reference range [s, e) (0 <= s < e <= ref_len): [col(s), col(e)) with
+// col(p) = aligned_positions[n] + (p - reference_positions[n]) for the last node n with reference_positions[n] <= p and
+// col(ref_len) = the aligned length -- what v2m_set_column_window() takes.  Throws std::invalid_argument for a range outside that.
+struct column_window { u64 begin{}, end{}; };
+column_window columns_of_reference_range(variant_graph const &graph, u64 ref_len, u64 s, u64 e);
+
 // Pays the sink path's one-off costs ahead of time (a gigabyte of pinned host memory: 0.15 s of hipHostMalloc, the device
 // slots, the templates) by splicing a few REF rows into a sink that drops them.  For callers that have something else
 // to do before the first real row (the founder search); needs an uploaded graph.

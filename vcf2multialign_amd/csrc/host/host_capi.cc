@@ -122,6 +122,18 @@ void *v2mh_read_graph(char const *path, char *err, size_t errlen)
 
 #define HG(h) (*static_cast<host_graph *>(h))
 uint64_t v2mh_node_count(void *h) { return HG(h).graph.node_count(); }
+// The column window of the reference range [s, e) (gpu_path.hh: columns_of_reference_range); -1 for a range outside the reference.
+int v2mh_columns_of_reference_range(void *h, uint64_t s, uint64_t e, uint64_t *col_begin, uint64_t *col_end)
+{
+	try {
+		auto const w(vh::columns_of_reference_range(HG(h).graph, HG(h).ref.size(), s, e));
+		*col_begin = w.begin;
+		*col_end = w.end;
+		return 0;
+	} catch (std::invalid_argument const &) {
+		return -1;
+	}
+}
 uint64_t v2mh_edge_count(void *h) { return HG(h).graph.edge_count(); }
 uint64_t v2mh_sample_count(void *h) { return HG(h).graph.sample_names.size(); }
 uint64_t v2mh_ref_length(void *h) { return HG(h).ref.size(); }

@@ -46,6 +46,8 @@ struct options {
 	bool output_sequences_separate{}, separate_plain{}, omit_reference{}, unaligned{}, verbose{}, graph_statistics{};
 	bool ref_mismatch_error{};
 	bool bgzf{};
+	char const *region{};                 // --region=START-END: 1-based inclusive positions on the reference sequence
+	std::uint64_t region_start{}, region_end{};
 	std::vector<int> devices{0};
 };
 
@@ -73,6 +75,8 @@ void usage()
 		"                                     A2M file are sharded over them (graph replicated, no collective)\n"
 		"      --bgzf                         Write the A2M file (-s) as BGZF, compressed on the GPU (gzip -d or any BGZF\n"
 		"                                     reader gives the plain A2M back; not with --pipe or --output-sequences-separate)\n"
+		"      --region=START-END             Output only the alignment columns of reference positions START..END (1-based,\n"
+		"                                     inclusive, as in samtools/bcftools), with the insertions anchored there\n"
 		"      --verbose\n"
 		"  -F, --founder-sequences=count      Produce founder sequences instead of haplotypes\n"
 		"  -d, --minimum-distance=distance    Minimum node distance (MSA co-ordinates) between cut positions\n"
@@ -156,6 +160,20 @@ struct progress_delegate final : vh::output_delegate {
 	}
 };
 
+// --region's value: START-END, decimal, 1 <= START <= END (the reference length is checked once the reference is read).
+bool parse_region(char const *text, std::uint64_t &start, std::uint64_t &end)
+{
+	std::string const s(text);
+	auto const dash(s.find('-'));
+	if (std::string::npos == dash) return false;
+	auto const number([](std::string const &t, std::uint64_t &out) {
+		if (t.empty() || t.size() > 18 || std::string::npos != t.find_first_not_of("0123456789")) return false;
+		out = std::stoull(t);
+		return true;
+	});
+	return number(s.substr(0, dash), start) && number(s.substr(dash + 1), end) && 1 <= start && start <= end;
+}
+
 } // namespace
 
 
@@ -169,7 +187,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -181,7 +199,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -225,6 +243,7 @@ int main(int argc, char **argv)
 			case o_verbose: opt.verbose = true; break;
 			case o_pipe: opt.pipe = optarg; break;
 			case o_bgzf: opt.bgzf = true; break;
+			case o_region: opt.region = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -248,6 +267,10 @@ int main(int argc, char **argv)
 	if (opt.bgzf && !opt.output_sequences_a2m) { std::cerr << "ERROR: --bgzf requires -s / --output-sequences-a2m.\n"; return EXIT_FAILURE; }
 	if (opt.bgzf && opt.pipe) { std::cerr << "ERROR: --bgzf cannot be combined with --pipe (the piped command compresses).\n"; return EXIT_FAILURE; }
 	if (opt.bgzf && opt.output_sequences_separate) { std::cerr << "ERROR: --bgzf cannot be combined with --output-sequences-separate.\n"; return EXIT_FAILURE; }
+	if (opt.region && !parse_region(opt.region, opt.region_start, opt.region_end)) {
+		std::cerr << "ERROR: --region must be START-END with 1 <= START <= END (1-based, inclusive), got \"" << opt.region << "\".\n";
+		return EXIT_FAILURE;
+	}
 
 	try {
 		// The GPU contexts come up on a second thread (HIP runtime start-up and stream creation: 0.2 s) while this one reads the
@@ -270,6 +293,10 @@ int main(int argc, char **argv)
 			return EXIT_FAILURE;
 		}
 		std::cerr << " Done. Reference length is " << ref_seq.size() << ".\n";
+		if (opt.region && opt.region_end > ref_seq.size()) {
+			std::cerr << "ERROR: --region end " << opt.region_end << " is past the end of the reference sequence (" << ref_seq.size() << ").\n";
+			return EXIT_FAILURE;
+		}
 		// A missing or unusable GPU, or a bad --device, should end the run here, before the variants are parsed, not minutes later.
 		// HIP's start-up takes 0.2 s whether it ends in a context or in an error, so after a reference of any size (100 Mb: 0.07 s
 		// + 30 ms of grace here; a genome: seconds) the outcome is usually in; when it is not, waiting for it would only take the
@@ -367,6 +394,14 @@ int main(int argc, char **argv)
 		}
 		progress_delegate delegate;
 		delegate.verbose = opt.verbose;
+		// --region: every context produces the window of columns of reference range [START - 1, END) (include/v2m_hip.h, column windows);
+		// the founder search above has run over the whole chromosome.  Set after the uploads, which reset it.
+		auto const apply_region([&] {
+			if (!opt.region) return;
+			auto const w(vh::columns_of_reference_range(graph, ref_seq.size(), opt.region_start - 1, opt.region_end));
+			if (opt.verbose) std::cerr << "Region " << opt.region_start << '-' << opt.region_end << ": alignment columns [" << w.begin << ", " << w.end << ") of " << graph.aligned_length() << ".\n";
+			for (auto *g : all_gpus) g->check(v2m_set_column_window(g->get(), w.begin, w.end));
+		});
 		auto const do_output([&](vh::output &output) {   // main.cc:456-473
 			if (opt.output_sequences_a2m) {
 				std::cerr << "Outputting sequences as A2M...\n";
@@ -386,6 +421,7 @@ int main(int argc, char **argv)
 			if (sharded) output.set_copy_shards(shards);
 			if (interleaved) output.set_copy_interleave(deal);
 			output.set_bgzf(opt.bgzf);
+			apply_region();
 			do_output(output);
 		} else {                                            // main.cc:487-550
 			vh::founder_sequence_greedy_output output(gpu, opt.pipe, opt.dst_chromosome, !opt.omit_reference, opt.unaligned, delegate);
@@ -434,6 +470,7 @@ int main(int argc, char **argv)
 			output.set_bgzf(opt.bgzf);
 			founder_graph_uploaded.get();
 			if (first_sink_warm.valid()) first_sink_warm.get(); else vh::warm_up_sink(gpu, opt.unaligned);
+			apply_region();
 			do_output(output);
 		}
 	} catch (vh::gpu_error const &e) {

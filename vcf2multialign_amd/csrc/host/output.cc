@@ -598,7 +598,7 @@ void output::write_a2m_sharded(row_set const &rows, char const *dst_name)
 {
 	std::vector<gpu_context *> gpus{&m_gpu};
 	gpus.insert(gpus.end(), m_more_gpus.begin(), m_more_gpus.end());
-	std::uint64_t const n(rows.copy_index.size()), L(v2m_aligned_length(m_gpu.get()));
+	std::uint64_t const n(rows.copy_index.size()), L(v2m_window_length(m_gpu.get()));   // the column window's length when one is set (every context has the same)
 	std::vector<std::uint64_t> offsets(n + 1, 0);
 	for (std::uint64_t i(0); i < n; ++i) offsets[i + 1] = offsets[i] + 1 + rows.ids[i].size() + 1 + L + 1;   // '>' id '\n' body '\n'
 

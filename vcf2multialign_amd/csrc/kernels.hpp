@@ -901,11 +901,11 @@ __global__ __launch_bounds__(64 * kWaves) void transpose_bits_rot_kernel(
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void expand_reference_row_kernel(
 	char const *__restrict__ ref, u32 const *__restrict__ ref_pos, u32 const *__restrict__ aln_pos,
-	u32 n_nodes, u32 L, u64 n_chunks, uint4 *__restrict__ out, char gap)
+	u32 n_nodes, u32 L, u64 n_chunks, uint4 *__restrict__ out, char gap, u32 col_base = 0)
 {
 	u64 const c = (u64) blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= n_chunks) return;
-	u64 const p0 = c * 16;
+	u64 const p0 = col_base + c * 16;   // a column window's template starts at its first column (L is then the window's end)
 	unsigned char bytes[16];
 	if (p0 >= L) {
 		out[c] = make_uint4(0, 0, 0, 0);
@@ -1001,14 +1001,14 @@ __device__ __forceinline__ u64 load_row_word(
 // contiguous piece of the row's (sorted) segment table, found once; the lanes then take one segment each, so the
 // table is read coalesced and all the scattered path-word loads of the piece are in flight together.
 __global__ __launch_bounds__(256) void assemble_row_bits_kernel(
-	u64 const *__restrict__ paths, u64 words_per_copy, row_segments rs, u64 *__restrict__ assembled, u32 n_words, u32 row_base)
+	u64 const *__restrict__ paths, u64 words_per_copy, row_segments rs, u64 *__restrict__ assembled, u32 n_words, u32 row_base, u32 word_base)
 {
 	__shared__ unsigned long long acc[256];
 	u32 const row = blockIdx.y + row_base;
 	u32 const s_begin = rs.seg_offsets[row], s_end = rs.seg_offsets[row + 1];
 	if (s_end - s_begin <= 1) return;                        // whole workgroup: the row is read straight from its copy
 	u32 const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	u32 const w0 = (blockIdx.x * 4 + wave) * 64;              // this wave's first word
+	u32 const w0 = word_base + (blockIdx.x * 4 + wave) * 64;  // this wave's first word (words [word_base, n_words) are assembled)
 	acc[threadIdx.x] = 0;
 	__syncthreads();
 	if (w0 < n_words) {
@@ -1120,7 +1120,7 @@ __global__ __launch_bounds__(256) void resolve_effective_edges_kernel(
 	u64 const *__restrict__ paths, u64 words_per_copy, u32 n_edges,
 	row_segments rs, edge_span const *__restrict__ spans, u64 const *__restrict__ overlappable,
 	u32 const *__restrict__ ovl_rank, u64 const *__restrict__ blocker_masks,
-	u64 *__restrict__ eff, u32 n_words, u32 eff_words_per_row, u32 row_base, u32 piece_base,
+	u64 *__restrict__ eff, u32 n_words, u32 eff_words_per_row, u32 row_base, u32 word_base,
 	u32 *__restrict__ queue, u32 *__restrict__ queue_counts /* [kResolveQueueShards] */, u32 shard_capacity, u32 *__restrict__ needs_serial, u32 max_back_words)
 {
 	u32 const row = blockIdx.x + row_base;
@@ -1135,7 +1135,7 @@ __global__ __launch_bounds__(256) void resolve_effective_edges_kernel(
 	} else {
 		row_words = rs.assembled + (u64) row * rs.assembled_words;
 	}
-	u32 const w_first = (blockIdx.y + piece_base) * kResolveWordsPerThread * blockDim.x + threadIdx.x;
+	u32 const w_first = word_base + blockIdx.y * kResolveWordsPerThread * blockDim.x + threadIdx.x;   // words [word_base, n_words)
 	u64 w_all[kResolveWordsPerThread], ovl_all[kResolveWordsPerThread], mask_a[kResolveWordsPerThread], mask_b[kResolveWordsPerThread];
 	u32 rank_all[kResolveWordsPerThread];
 #pragma unroll
@@ -1145,7 +1145,7 @@ __global__ __launch_bounds__(256) void resolve_effective_edges_kernel(
 		w_all[piece] = row_words ? row_words[wc] : 0;
 		ovl_all[piece] = overlappable[wc];
 		rank_all[piece] = ovl_rank[wc];
-		if (wi == n_words - 1) w_all[piece] &= tail_mask;
+		if (wi == (n_edges - 1) >> 6) w_all[piece] &= tail_mask;
 	}
 #pragma unroll
 	for (int piece = 0; piece < kResolveWordsPerThread; ++piece) {
@@ -1193,7 +1193,7 @@ __global__ __launch_bounds__(256) void resolve_queued_words_kernel(
 		u32 const row = row_base + entry / n_words, wi = entry % n_words;
 		u32 const s_begin = rs.seg_offsets[row], s_end = rs.seg_offsets[row + 1];
 		u64 w = load_row_word(paths, words_per_copy, rs, row, s_begin, s_end, wi);
-		if (wi == n_words - 1) w &= tail_mask;
+		if (wi == (n_edges - 1) >> 6) w &= tail_mask;
 		eff[(u64) row * eff_words_per_row + wi] = resolve_word_exact(paths, words_per_copy, rs, row, s_begin, s_end, spans, overlappable, wi, w, overlappable[wi], needs_serial, max_back_words);
 	}
 }
@@ -1203,7 +1203,8 @@ __global__ __launch_bounds__(256) void resolve_queued_words_kernel(
 __global__ __launch_bounds__(256) void resolve_rows_serial_kernel(
 	u64 const *__restrict__ paths, u64 words_per_copy, u32 n_edges,
 	row_segments rs, edge_span const *__restrict__ spans,
-	u64 *__restrict__ eff, u64 eff_words_per_row, u32 n_rows, u32 const *__restrict__ needs_serial)
+	u64 *__restrict__ eff, u64 eff_words_per_row, u32 n_rows, u32 const *__restrict__ needs_serial,
+	u32 word_begin /* a restart point: edge word_begin * 64 is not overlappable */, u32 word_end)
 {
 	int const lane = threadIdx.x & 63;
 	u32 const row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -1215,10 +1216,10 @@ __global__ __launch_bounds__(256) void resolve_rows_serial_kernel(
 	u64 *const eff_row = eff + (u64) row * eff_words_per_row;
 	u32 cur = 0;   // current node of the walk at the start of this chunk (wave-uniform)
 
-	for (u32 base = 0; base < n_words; base += 64) {
+	for (u32 base = word_begin; base < word_end; base += 64) {
 		u32 const wi = base + lane;
 		u64 w = 0;
-		if (wi < n_words) {
+		if (wi < word_end) {
 			w = load_row_word(paths, words_per_copy, rs, row, s_begin, s_end, wi);
 			if (wi == n_words - 1 && (n_edges & 63))
 				w &= (1ULL << (n_edges & 63)) - 1;       // padding bits are zero by contract; do not trust them
@@ -1277,11 +1278,11 @@ __global__ __launch_bounds__(256) void resolve_rows_serial_kernel(
 		} else {
 			cur = chunk_max > cur ? chunk_max : cur;
 		}
-		if (wi < eff_words_per_row)
+		if (wi < word_end)
 			eff_row[wi] = out;
 	}
-	// words between n_words and eff_words_per_row (when the scratch row is wider) stay untouched:
-	// the splice kernel never reads bits >= n_edges.
+	// words from word_end on (when the scratch row is wider) stay untouched:
+	// the splice kernel never reads bits >= n_edges, nor, in a column window, past the window's edges.
 }
 
 
@@ -1349,7 +1350,8 @@ struct patch_cache {
 };
 
 struct tile_job {
-	u32 tile_base, cross_begin, n_cross, range_begin, n_range;
+	u32 tile_base, tile_end;   // the tile's aligned columns [tile_base, tile_end); tile_end < tile_base + kTileBytes only at a window's end
+	u32 cross_begin, n_cross, range_begin, n_range;
 	u32 n_lds;          // candidates of the range cached in LDS
 	u32 w0;             // first effective-bit word cached
 };
@@ -1365,11 +1367,15 @@ __device__ __forceinline__ void load_eff_cache(
 		pc.eff[i / nw][i % nw] = eff[(u64) (first_row + i / nw) * eff_words_per_row + job.w0 + i % nw];
 }
 
+// kWindow: the tiles are those of the column window [col_base, col_end) (tile t = columns col_base + t * kTileBytes on, clipped to
+// col_end); without it tile t is columns t * kTileBytes on and col_base / col_end are not read.
+template <bool kWindow = false>
 __device__ __forceinline__ void load_patch_cache(
 	patch_cache &pc, tile_job &job, tile_tables const &tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
-	u64 const *__restrict__ eff, u64 eff_words_per_row, u32 tile, u32 row_begin, u32 n_group_rows, int t)
+	u64 const *__restrict__ eff, u64 eff_words_per_row, u32 tile, u32 row_begin, u32 n_group_rows, int t, u32 col_base = 0, u32 col_end = 0)
 {
-	job.tile_base = tile * (u32) kTileBytes;
+	job.tile_base = (kWindow ? col_base : 0u) + tile * (u32) kTileBytes;
+	job.tile_end = (kWindow && col_end - job.tile_base < (u32) kTileBytes) ? col_end : job.tile_base + kTileBytes;
 	job.cross_begin = tt.cross_offsets[tile];
 	job.n_cross = tt.cross_offsets[tile + 1] - job.cross_begin;
 	job.range_begin = tt.edge_begin[tile];
@@ -1424,10 +1430,11 @@ __device__ __forceinline__ bool candidate_in_lds(tile_job const &job, u32 i)
 }
 
 // The part of candidate i's span that falls into the tile, from the cached descriptor when it is representable there.
+template <bool kWindow = false>
 __device__ __forceinline__ tile_patch candidate_patch(
 	patch_cache const &pc, tile_job const &job, edge_patch const *__restrict__ patches, u32 i, u32 e, bool cached)
 {
-	u32 const tile_end = job.tile_base + kTileBytes;
+	u32 const tile_end = kWindow ? job.tile_end : job.tile_base + kTileBytes;
 	cached_patch c{};
 	if (cached) {
 		c = pc.patch[i - job.n_cross];
@@ -1467,7 +1474,7 @@ __device__ __forceinline__ bool candidate_effective(
 	return (eff_row[e >> 6] >> (e & 63)) & 1;
 }
 
-template <typename F>
+template <bool kWindow, typename F>
 __device__ __forceinline__ void for_each_effective_candidate(
 	patch_cache const &pc, tile_job const &job, tile_tables const &tt, edge_patch const *__restrict__ patches,
 	u64 const *__restrict__ eff_row, u32 local_row, int t, F &&f)
@@ -1477,19 +1484,20 @@ __device__ __forceinline__ void for_each_effective_candidate(
 		u32 e;
 		bool cached;
 		if (!candidate_effective(pc, job, tt, eff_row, local_row, i, e, cached)) continue;
-		f(candidate_patch(pc, job, patches, i, e, cached));
+		f(candidate_patch<kWindow>(pc, job, patches, i, e, cached));
 	}
 }
 
 // Overwrites, in the LDS tile `buf`, the spans of the row's effective edges.  Contains the barriers that separate
 // it from the tile's readers; must be called by all threads of the workgroup.
+template <bool kWindow = false>
 __device__ __forceinline__ void patch_row_tile(
 	unsigned char *buf, patch_cache &pc, tile_job const &job, tile_tables const &tt,
 	edge_patch const *__restrict__ patches, char const *__restrict__ labels,
 	u64 const *__restrict__ eff_row, u32 local_row, int t, char gap)
 {
-	u32 const tile_end = job.tile_base + kTileBytes;
-	for_each_effective_candidate(pc, job, tt, patches, eff_row, local_row, t, [&](tile_patch const &tp) {
+	u32 const tile_end = kWindow ? job.tile_end : job.tile_base + kTileBytes;
+	for_each_effective_candidate<kWindow>(pc, job, tt, patches, eff_row, local_row, t, [&](tile_patch const &tp) {
 		if (tp.to - tp.from > kLongPatch) {
 			u32 const slot = atomicAdd(&pc.long_count, 1u);
 			if (slot < (u32) kLongQueueLds) { pc.long_queue[slot] = tp.edge; return; }
@@ -1532,12 +1540,12 @@ __device__ __forceinline__ void map_block(u32 b, u32 n_groups, u32 n_tiles, u32 
 	tile = t0 + within % run;
 }
 
-template <bool kNonTemporal>
-__global__ __launch_bounds__(kSpliceThreads) void splice_aligned_kernel(
+template <bool kNonTemporal, bool kWindow>
+__device__ __forceinline__ void splice_aligned_tiles(
 	vec4u const *__restrict__ tmpl, u64 const *__restrict__ eff, u64 eff_words_per_row,
 	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
 	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 n_tiles, u32 tile_run,
-	u64 store_limit /* aligned length rounded up to 16 */, char gap)
+	u64 store_limit, char gap, u32 col_base, u32 col_end)
 {
 	__shared__ vec4u lds[2][kTileChunks];
 	__shared__ patch_cache pc;
@@ -1554,7 +1562,7 @@ __global__ __launch_bounds__(kSpliceThreads) void splice_aligned_kernel(
 		pristine[k] = tmpl[(u64) tile * kTileChunks + t + kSpliceThreads * k];
 
 	tile_job job;
-	load_patch_cache(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t);
+	load_patch_cache<kWindow>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end);
 	u32 const tile_base = job.tile_base;
 
 	for (u32 row = row_begin; row < row_end; ++row) {
@@ -1570,13 +1578,13 @@ __global__ __launch_bounds__(kSpliceThreads) void splice_aligned_kernel(
 			buf[t + kSpliceThreads * k] = pristine[k];
 		__syncthreads();
 
-		patch_row_tile((unsigned char *) buf, pc, job, tt, patches, labels, eff + (u64) row * eff_words_per_row, cached_row, t, gap);
+		patch_row_tile<kWindow>((unsigned char *) buf, pc, job, tt, patches, labels, eff + (u64) row * eff_words_per_row, cached_row, t, gap);
 
 		char *const dst = out + (u64) row * row_pitch + (u64) tile * kTileBytes;
 #pragma unroll
 		for (int k = 0; k < kChunksPerThread; ++k) {
 			int const c = t + kSpliceThreads * k;
-			if ((u64) tile_base + (u64) c * 16 < store_limit) {
+			if ((kWindow ? (u64) tile * kTileBytes : (u64) tile_base) + (u64) c * 16 < store_limit) {
 				vec4u const nv = buf[c];
 				if (kNonTemporal)
 					__builtin_nontemporal_store(nv, (vec4u *) (dst + c * 16));
@@ -1585,6 +1593,33 @@ __global__ __launch_bounds__(kSpliceThreads) void splice_aligned_kernel(
 			}
 		}
 	}
+}
+
+template <bool kNonTemporal>
+__global__ __launch_bounds__(kSpliceThreads) void splice_aligned_kernel(
+	vec4u const *__restrict__ tmpl, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 n_tiles, u32 tile_run,
+	u64 store_limit /* aligned length rounded up to 16 */, char gap)
+{
+	splice_aligned_tiles<kNonTemporal, false>(tmpl, eff, eff_words_per_row, tt, patches, labels, out, row_pitch, n_rows, rows_per_group, n_groups,
+		n_tiles, tile_run, store_limit, gap, 0u, 0u);
+}
+
+// The same for the column window [col_base, col_end) (v2m_set_column_window): row bodies are columns [col_base, col_end) of the aligned
+// rows.  tmpl is the REF row's window, tiled from col_base; tt are the window's tile tables (tile t = columns col_base + t * kTileBytes
+// on: its edges begin there, its crossing edges begin before and reach into it, the first tile's include every edge that begins before
+// col_base and reaches into the window); edge indices, `patches` and the effective-edge words stay those of the whole graph; n_tiles and
+// store_limit (the window length rounded up to 16) are the window's.  Spans are clipped to col_end.
+template <bool kNonTemporal>
+__global__ __launch_bounds__(kSpliceThreads) void splice_aligned_window_kernel(
+	vec4u const *__restrict__ tmpl, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 n_tiles, u32 tile_run,
+	u64 store_limit, char gap, u32 col_base, u32 col_end)
+{
+	splice_aligned_tiles<kNonTemporal, true>(tmpl, eff, eff_words_per_row, tt, patches, labels, out, row_pitch, n_rows, rows_per_group, n_groups,
+		n_tiles, tile_run, store_limit, gap, col_base, col_end);
 }
 
 
@@ -1661,11 +1696,12 @@ __device__ __forceinline__ u32 count_nonzero_bytes(unsigned char const *tile, u3
 constexpr int kCountRowsMax = 256;   // rows per group the count kernel can hold (host clamps rows_per_group)
 constexpr int kCandDeltaLds = 1024;  // candidates per tile whose (row-independent) count change is kept in LDS
 
-__global__ __launch_bounds__(kSpliceThreads) void count_unaligned_kernel(
+template <bool kWindow>
+__device__ __forceinline__ void count_unaligned_tiles(
 	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
 	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
 	u32 *__restrict__ tile_counts /* [n_rows][n_tiles] */, u32 n_tiles,
-	u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
+	u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end)
 {
 	__shared__ vec4u lds[kTileChunks];        // the pristine template tile, shared by all rows of the group
 	__shared__ patch_cache pc;
@@ -1694,7 +1730,7 @@ __global__ __launch_bounds__(kSpliceThreads) void count_unaligned_kernel(
 	for (u32 r = t; r < (u32) kCountRowsMax; r += kSpliceThreads) row_delta[r] = 0;
 
 	tile_job job;
-	load_patch_cache(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t);
+	load_patch_cache<kWindow>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end);
 	__syncthreads();
 	u32 tile_count = 0;
 #pragma unroll
@@ -1711,7 +1747,7 @@ __global__ __launch_bounds__(kSpliceThreads) void count_unaligned_kernel(
 	};
 	u32 const n_cand = job.n_cross + job.n_range;
 	for (u32 i = t; i < n_cand && i < (u32) kCandDeltaLds; i += kSpliceThreads)
-		cand_delta[i] = patch_delta(candidate_patch(pc, job, patches, i, candidate_edge(job, tt, i), candidate_in_lds(job, i)));
+		cand_delta[i] = patch_delta(candidate_patch<kWindow>(pc, job, patches, i, candidate_edge(job, tt, i), candidate_in_lds(job, i)));
 	__syncthreads();
 	// The group may hold more rows than the LDS cache of effective-edge words (kGroupRowsLds): the template tile, its count
 	// and the per-candidate changes are set up once per group, the cached words are reloaded every kGroupRowsLds rows.
@@ -1739,7 +1775,7 @@ __global__ __launch_bounds__(kSpliceThreads) void count_unaligned_kernel(
 			for (; bits; bits &= bits - 1) {
 				u32 const e = first + (u32) __builtin_ctzll(bits);
 				u32 const i = job.n_cross + (e - job.range_begin);
-				delta += i < (u32) kCandDeltaLds ? cand_delta[i] : patch_delta(candidate_patch(pc, job, patches, i, e, true));
+				delta += i < (u32) kCandDeltaLds ? cand_delta[i] : patch_delta(candidate_patch<kWindow>(pc, job, patches, i, e, true));
 			}
 			if (delta) atomicAdd(&row_delta[sub - row_begin + r], delta);
 		}
@@ -1750,13 +1786,32 @@ __global__ __launch_bounds__(kSpliceThreads) void count_unaligned_kernel(
 			u32 const i = j < job.n_cross ? j : j + job.n_lds;
 			u32 const e = candidate_edge(job, tt, i);
 			if (!((eff[(u64) (sub + r) * eff_words_per_row + (e >> 6)] >> (e & 63)) & 1)) continue;
-			int const delta = i < (u32) kCandDeltaLds ? cand_delta[i] : patch_delta(candidate_patch(pc, job, patches, i, e, false));
+			int const delta = i < (u32) kCandDeltaLds ? cand_delta[i] : patch_delta(candidate_patch<kWindow>(pc, job, patches, i, e, false));
 			if (delta) atomicAdd(&row_delta[sub - row_begin + r], delta);
 		}
 	}
 	__syncthreads();
 	for (u32 r = t; r < row_end - row_begin; r += kSpliceThreads)
 		tile_counts[(u64) (row_begin + r) * n_tiles + tile] = (u32) ((int) tile_count + row_delta[r]);
+}
+
+__global__ __launch_bounds__(kSpliceThreads) void count_unaligned_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 *__restrict__ tile_counts /* [n_rows][n_tiles] */, u32 n_tiles,
+	u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
+{
+	count_unaligned_tiles<false>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_counts, n_tiles, n_rows, rows_per_group, n_groups, tile_run, 0u, 0u);
+}
+
+// The same over the tiles of a column window (as splice_aligned_window_kernel; tmpl0 = the window of the REF row with 0 as padding).
+__global__ __launch_bounds__(kSpliceThreads) void count_unaligned_window_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 *__restrict__ tile_counts /* [n_rows][n_tiles] */, u32 n_tiles,
+	u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end)
+{
+	count_unaligned_tiles<true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_counts, n_tiles, n_rows, rows_per_group, n_groups, tile_run, col_base, col_end);
 }
 
 // v_perm_b32 selector that moves the bytes of a dword named by the 4-bit mask `keep` to its low end, in order (0x0c = a
@@ -1983,12 +2038,12 @@ __device__ __forceinline__ void pack_chunk_and_store_exact(vec4u const x, u32 co
 // chunks no longer fit the queue (tiles inside long insertions) are packed where they are by their own wave.
 // Measured (profiles/r05/unaligned_shared_pack.txt): config 5 11.5 -> 10.95 ms per 244 rows (aligned kernel, same rows: 9.03), VALU 308 -> 256, SALU 213 -> ~156
 // per wave and row tile (the scans in lockstep took the rest); config 3 within what two boxes differ by.
-template <bool kNonTemporal, u32 kQueue = 128>
-__global__ __launch_bounds__(kSpliceThreads) void splice_unaligned_kernel(
+template <bool kNonTemporal, u32 kQueue, bool kWindow>
+__device__ __forceinline__ void splice_unaligned_tiles(
 	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
 	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
 	u32 const *__restrict__ tile_offsets /* [n_rows][n_tiles]: where each tile's bytes start in its row */, u32 n_tiles,
-	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
+	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end)
 {
 	constexpr int kWaves = kSpliceThreads / 64, kSlots = kChunksPerThread * kWaves;
 	// kQueue: short chunks of a row tile that wait for the packing wave(s)
@@ -2020,7 +2075,7 @@ __global__ __launch_bounds__(kSpliceThreads) void splice_unaligned_kernel(
 		pristine[k] = tmpl0[(u64) tile * kTileChunks + t + kSpliceThreads * k];
 
 	tile_job job;
-	load_patch_cache(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t);
+	load_patch_cache<kWindow>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end);
 
 	char *dst_prev = out;
 	for (u32 row = row_begin; ; ++row) {                                      // (one round more than there are rows: the last one only packs the last row's queue)
@@ -2050,7 +2105,7 @@ __global__ __launch_bounds__(kSpliceThreads) void splice_unaligned_kernel(
 		}
 		if (past_end) break;
 
-		patch_row_tile((unsigned char *) lds, pc, job, tt, patches, labels, eff + (u64) row * eff_words_per_row, (row - row_begin) % (u32) kGroupRowsLds, t, 0);
+		patch_row_tile<kWindow>((unsigned char *) lds, pc, job, tt, patches, labels, eff + (u64) row * eff_words_per_row, (row - row_begin) % (u32) kGroupRowsLds, t, 0);
 
 		// Thread t owns the 16-B chunks t, t + 256, ...  Scanned word: surviving bytes in the low half, "short chunk" (1 ... 15 of them) in the high half.
 		vec4u v[kChunksPerThread];
@@ -2117,6 +2172,30 @@ __global__ __launch_bounds__(kSpliceThreads) void splice_unaligned_kernel(
 		dst_prev = dst;
 		// wave_sums is rewritten only after the next row's barriers
 	}
+}
+
+template <bool kNonTemporal, u32 kQueue = 128>
+__global__ __launch_bounds__(kSpliceThreads) void splice_unaligned_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 const *__restrict__ tile_offsets /* [n_rows][n_tiles]: where each tile's bytes start in its row */, u32 n_tiles,
+	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
+{
+	splice_unaligned_tiles<kNonTemporal, kQueue, false>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_offsets, n_tiles, out, row_pitch,
+		n_rows, rows_per_group, n_groups, tile_run, 0u, 0u);
+}
+
+// The same over the tiles of a column window (as splice_aligned_window_kernel): the bytes of a window tile are the emitted bytes whose
+// column lies in it, so the row is the window's unaligned body.
+template <bool kNonTemporal>
+__global__ __launch_bounds__(kSpliceThreads) void splice_unaligned_window_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 const *__restrict__ tile_offsets, u32 n_tiles,
+	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end)
+{
+	splice_unaligned_tiles<kNonTemporal, 128, true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_offsets, n_tiles, out, row_pitch,
+		n_rows, rows_per_group, n_groups, tile_run, col_base, col_end);
 }
 
 // Exclusive prefix sum of the per-tile byte counts of each row (in place) and the row lengths.

@@ -117,6 +117,23 @@ struct v2m_ctx {
 	dev_buf d_template0;   // the REF row with 0 as padding byte (unaligned mode), built on first use
 	bool has_template0{};
 	dev_buf d_tile_edge_begin, d_cross_offsets, d_cross_edges;
+	// host copies of what v2m_set_column_window derives a window's tables from
+	std::vector<u32> h_aln_pos, h_tile_edge_begin, h_cross_offsets, h_cross_edges;
+	std::vector<v2m::edge_patch> h_patches;
+	std::vector<u64> h_overlappable;
+
+	// v2m_set_column_window: the columns [begin, end) every row call produces, with the tables of its tiles (tile t = columns
+	// begin + t * kTileBytes on) and the edge words resolve has to decide for it: [word_lo, word_hi), with the look-back that
+	// those words' restart points need reaching no further than word_restart (edge word_restart * 64 is not overlappable).
+	// Inactive = whole rows, which take the whole-row tables and kernels.
+	struct column_window {
+		bool active{};
+		u64 begin{}, end{};
+		u32 n_tiles{};
+		u32 word_restart{}, word_lo{}, word_hi{};
+		dev_buf d_template, d_template0, d_edge_begin, d_cross_offsets, d_cross_edges;
+		bool has_template0{};
+	} win;
 
 	// paths_by_chrom_copy_and_edge
 	u64 const *d_paths{};
@@ -712,15 +729,31 @@ u32 rows_per_group_for(u64 n_rows)
 // that every row starts line-aligned.
 u64 eff_row_words(v2m_ctx const *ctx) { return (((ctx->n_edges + 63) / 64) + 15) & ~u64(15); }
 
-// Effective-edge bits of rows [row_begin, row_end) of the batch into ctx->d_eff.
+// Bytes of every aligned row the row calls produce: the column window's length, or the aligned length.
+u64 row_length(v2m_ctx const *ctx) { return ctx->win.active ? ctx->win.end - ctx->win.begin : ctx->aligned_len; }
+u32 row_tiles(v2m_ctx const *ctx) { return ctx->win.active ? ctx->win.n_tiles : ctx->n_tiles; }
+
+// The effective-edge words a row call resolves, [lo, hi), and the scratch layout: a row holds words [restart, restart + stride) (the
+// look-back of the words' restart points stays within them), so word w of row r is at d_eff + r * stride + (w - restart).
+struct word_range { u64 restart, lo, hi, stride; };
+word_range row_words(v2m_ctx const *ctx)
+{
+	if (!ctx->win.active) return {0, 0, (ctx->n_edges + 63) / 64, eff_row_words(ctx)};
+	auto const &w(ctx->win);
+	return {w.word_restart, w.word_lo, w.word_hi, (u64(w.word_hi - w.word_restart) + 15) & ~u64(15)};
+}
+
+// Effective-edge bits of rows [row_begin, row_end) of the batch into ctx->d_eff (words row_words(ctx), laid out as that says).
 int resolve_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row_end)
 {
 	u64 const n_rows(row_end - row_begin);
-	u64 const eff_words(eff_row_words(ctx)), n_words((ctx->n_edges + 63) / 64);
+	word_range const wr(row_words(ctx));
+	u64 const eff_words(wr.stride), n_words(wr.hi);   // words [wr.lo, n_words) are resolved
 	if (0 == ctx->n_edges) return V2M_OK;
 
 	prepared_rows pr;
 	if (int const rc = prepare_rows(ctx, rows, row_begin, row_end, pr)) return rc;
+	if (wr.lo >= wr.hi) return V2M_OK;   // a column window that no edge reaches into
 	auto const upload([&](dev_buf &dst, u32 const *src, u64 count) -> int {
 		V2M_HIP_TRY(ctx, dst.ensure(std::max<size_t>(count * sizeof(u32), 16)));
 		if (count) V2M_HIP_TRY(ctx, hipMemcpyAsync(dst.p, src, count * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
@@ -746,41 +779,44 @@ int resolve_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 ro
 	bool const any_switching_row(pr.any_switching_row);
 	if (any_switching_row) V2M_HIP_TRY(ctx, ctx->d_row_bits.ensure(n_rows * eff_words * sizeof(u64)));
 
-	v2m::row_segments rs{ctx->d_seg_offsets.as<u32>(), ctx->d_seg_edge_begin.as<u32>(), ctx->d_seg_copy.as<u32>(),
-		any_switching_row ? ctx->d_row_bits.as<u64>() : nullptr, u32(eff_words)};
+	// (the scratch pointers are offset so that the kernels index them with edge words of the whole graph)
+	u64 *const d_eff(ctx->d_eff.as<u64>() - wr.restart);
+	u64 *const d_row_bits(any_switching_row ? ctx->d_row_bits.as<u64>() - wr.restart : nullptr);
+	v2m::row_segments rs{ctx->d_seg_offsets.as<u32>(), ctx->d_seg_edge_begin.as<u32>(), ctx->d_seg_copy.as<u32>(), d_row_bits, u32(eff_words)};
 	char const *const back_env(std::getenv("V2M_MAX_BACK_WORDS"));   // test knob: 0 forces the serial kernel for every cross-word restart
 	u32 const max_back_words((back_env && *back_env) ? u32(std::strtoul(back_env, nullptr, 10)) : v2m::kMaxBackWords);
 	{
 		timed_launch tl(ctx, V2M_KERNEL_RESOLVE);
 		// rows per launch: queue entries are 32-bit (row, word) indices
 		u64 const rows_per_launch(std::max<u64>(1, std::min<u64>(65535, 0xFFFFFFFFull / std::max<u64>(1, n_words))));
+		u64 const assembled_words(n_words - wr.restart), resolved_words(n_words - wr.lo);
 		for (u64 r0(0); r0 < n_rows; r0 += rows_per_launch) {
 			u64 const nr(std::min<u64>(rows_per_launch, n_rows - r0));
 			if (any_switching_row)
 				for (u64 y0(0); y0 < nr; y0 += 65535)   // grid.y limit
-					hipLaunchKernelGGL(v2m::assemble_row_bits_kernel, dim3(unsigned((n_words + 255) / 256), unsigned(std::min<u64>(65535, nr - y0))), dim3(256), 0, ctx->stream,
-						ctx->d_paths, ctx->path_pitch, rs, ctx->d_row_bits.as<u64>(), u32(n_words), u32(r0 + y0));
+					hipLaunchKernelGGL(v2m::assemble_row_bits_kernel, dim3(unsigned((assembled_words + 255) / 256), unsigned(std::min<u64>(65535, nr - y0))), dim3(256), 0, ctx->stream,
+						ctx->d_paths, ctx->path_pitch, rs, d_row_bits, u32(n_words), u32(r0 + y0), u32(wr.restart));
 			// the queue's segments hold every word of the launch if they have to (iid random bits do that), up to 1 GiB in all;
 			// a workgroup whose segment is full decides its overflow itself
-			u64 const shard_capacity(std::max<u64>(256, std::min<u64>(nr * n_words, u64(1) << 28) / v2m::kResolveQueueShards));
+			u64 const shard_capacity(std::max<u64>(256, std::min<u64>(nr * resolved_words, u64(1) << 28) / v2m::kResolveQueueShards));
 			V2M_HIP_TRY(ctx, ctx->d_resolve_queue.ensure(shard_capacity * v2m::kResolveQueueShards * sizeof(u32)));
 			V2M_HIP_TRY(ctx, ctx->d_resolve_count.ensure(v2m::kResolveQueueShards * sizeof(u32)));
 			V2M_HIP_TRY(ctx, hipMemsetAsync(ctx->d_resolve_count.p, 0, v2m::kResolveQueueShards * sizeof(u32), ctx->stream));
-			for (u64 piece0(0), pieces((n_words + 256 * v2m::kResolveWordsPerThread - 1) / (256 * v2m::kResolveWordsPerThread)); piece0 < pieces; piece0 += 65535)   // grid.y limit; rows run fastest
+			for (u64 piece0(0), pieces((resolved_words + 256 * v2m::kResolveWordsPerThread - 1) / (256 * v2m::kResolveWordsPerThread)); piece0 < pieces; piece0 += 65535)   // grid.y limit; rows run fastest
 				hipLaunchKernelGGL(v2m::resolve_effective_edges_kernel, dim3(unsigned(nr), unsigned(std::min<u64>(65535, pieces - piece0))), dim3(256), 0, ctx->stream,
 					ctx->d_paths, ctx->path_pitch, u32(ctx->n_edges), rs, ctx->d_spans.as<v2m::edge_span>(), ctx->d_overlappable.as<u64>(),
 					ctx->d_ovl_rank.as<u32>(), ctx->d_blocker_masks.as<u64>(),
-					ctx->d_eff.as<u64>(), u32(n_words), u32(eff_words), u32(r0), u32(piece0),
+					d_eff, u32(n_words), u32(eff_words), u32(r0), u32(wr.lo + piece0 * 256 * v2m::kResolveWordsPerThread),
 					ctx->d_resolve_queue.as<u32>(), ctx->d_resolve_count.as<u32>(), u32(shard_capacity), ctx->d_needs_serial.as<u32>(), max_back_words);
 			hipLaunchKernelGGL(v2m::resolve_queued_words_kernel, dim3(2 * v2m::kResolveQueueShards), dim3(256), 0, ctx->stream,
 				ctx->d_paths, ctx->path_pitch, u32(ctx->n_edges), rs, ctx->d_spans.as<v2m::edge_span>(), ctx->d_overlappable.as<u64>(),
-				ctx->d_eff.as<u64>(), u32(n_words), u32(eff_words), u32(r0),
+				d_eff, u32(n_words), u32(eff_words), u32(r0),
 				ctx->d_resolve_queue.as<u32>(), ctx->d_resolve_count.as<u32>(), u32(shard_capacity), ctx->d_needs_serial.as<u32>(), max_back_words);
 		}
 		// rows whose restart point is too far back for the per-word kernel (chromosome-scale deletions)
 		hipLaunchKernelGGL(v2m::resolve_rows_serial_kernel, dim3(unsigned((n_rows + 3) / 4)), dim3(256), 0, ctx->stream,
 			ctx->d_paths, ctx->path_pitch, u32(ctx->n_edges), rs, ctx->d_spans.as<v2m::edge_span>(),
-			ctx->d_eff.as<u64>(), eff_words, u32(n_rows), ctx->d_needs_serial.as<u32>());
+			d_eff, eff_words, u32(n_rows), ctx->d_needs_serial.as<u32>(), u32(wr.restart), u32(n_words));
 	}
 	V2M_HIP_TRY(ctx, hipGetLastError());
 	return V2M_OK;
@@ -804,8 +840,8 @@ int make_grid(v2m_ctx *ctx, u64 n_rows, splice_grid &g)
 {
 	g.rows_per_group = rows_per_group_for(n_rows);
 	g.n_groups = u32((n_rows + g.rows_per_group - 1) / g.rows_per_group);
-	g.n_blocks = u64(ctx->n_tiles) * g.n_groups;
-	g.tile_run = tile_run_for(ctx->n_tiles);
+	g.n_blocks = u64(row_tiles(ctx)) * g.n_groups;
+	g.tile_run = tile_run_for(row_tiles(ctx));
 	if (g.n_blocks > 0x7FFFFFFFull)
 		return fail(ctx, V2M_ERR_UNSUPPORTED, "splice grid too large (%llu workgroups); use smaller batches", (unsigned long long) g.n_blocks);
 	return V2M_OK;
@@ -823,8 +859,22 @@ int splice_aligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin,
 	splice_grid g;
 	if (int const rc = make_grid(ctx, n_rows, g)) return rc;
 	v2m::tile_tables tt{ctx->d_tile_edge_begin.as<u32>(), ctx->d_cross_offsets.as<u32>(), ctx->d_cross_edges.as<u32>()};
-	u64 const store_limit((ctx->aligned_len + 15) & ~u64(15));
+	u64 const store_limit((row_length(ctx) + 15) & ~u64(15));
+	auto const &w(ctx->win);
 	auto launch = [&](bool nt) {
+		if (w.active) {
+			// a column window: its own template and tile tables, the effective-edge words of row_words(ctx)
+			word_range const wr(row_words(ctx));
+			v2m::tile_tables const wt{w.d_edge_begin.as<u32>(), w.d_cross_offsets.as<u32>(), w.d_cross_edges.as<u32>()};
+			auto const go([&](auto kernel) {
+				hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+					w.d_template.as<v2m::vec4u>(), ctx->d_eff.as<u64>() - wr.restart, wr.stride, wt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+					d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, w.n_tiles, g.tile_run, store_limit, '-', u32(w.begin), u32(w.end));
+			});
+			if (nt) go(v2m::splice_aligned_window_kernel<true>);
+			else go(v2m::splice_aligned_window_kernel<false>);
+			return;
+		}
 		if (nt)
 			hipLaunchKernelGGL(v2m::splice_aligned_kernel<true>, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
 				ctx->d_template.as<v2m::vec4u>(), ctx->d_eff.as<u64>(), eff_words, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
@@ -844,7 +894,7 @@ int splice_aligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin,
 	// faster one is kept.
 	int mode(forced_store_mode());
 	if (mode < 0) mode = ctx->store_mode;
-	if (mode < 0 && n_rows * ctx->aligned_len >= (u64(1) << 30)) {
+	if (mode < 0 && n_rows * row_length(ctx) >= (u64(1) << 30)) {
 		scoped_events ev;
 		V2M_HIP_TRY(ctx, ev.create(5));
 		V2M_HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
@@ -885,13 +935,25 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 		V2M_HIP_TRY(ctx, hipMemsetAsync(ctx->d_row_lengths.p, 0, n_rows * sizeof(u64), ctx->stream));
 		return V2M_OK;
 	}
+	auto &w(ctx->win);
+	if (w.active && !w.has_template0) {   // the window of the REF row with 0 as padding, built on first use
+		u64 const n_chunks(u64(w.n_tiles) * v2m::kTileChunks);
+		V2M_HIP_TRY(ctx, w.d_template0.ensure(n_chunks * 16));
+		{
+			timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
+			hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
+				ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), u32(w.end), n_chunks, w.d_template0.as<uint4>(), char(0), u32(w.begin));
+		}
+		V2M_HIP_TRY(ctx, hipGetLastError());
+		w.has_template0 = true;
+	}
 	u64 const n_chunks(u64(ctx->n_tiles) * v2m::kTileChunks);
-	if (!ctx->has_template0) {
+	if (!w.active && !ctx->has_template0) {
 		V2M_HIP_TRY(ctx, ctx->d_template0.ensure(n_chunks * 16));
 		{
 			timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
 			hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
-				ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), u32(ctx->aligned_len), n_chunks, ctx->d_template0.as<uint4>(), char(0));
+				ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), u32(ctx->aligned_len), n_chunks, ctx->d_template0.as<uint4>(), char(0), 0u);
 		}
 		V2M_HIP_TRY(ctx, hipGetLastError());
 		ctx->has_template0 = true;
@@ -901,8 +963,13 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 	u64 const eff_words(eff_row_words(ctx));
 	splice_grid g;
 	if (int const rc = make_grid(ctx, n_rows, g)) return rc;
-	V2M_HIP_TRY(ctx, ctx->d_tile_counts.ensure(n_rows * ctx->n_tiles * sizeof(u32)));
+	u32 const n_tiles(row_tiles(ctx));
+	V2M_HIP_TRY(ctx, ctx->d_tile_counts.ensure(n_rows * n_tiles * sizeof(u32)));
 	v2m::tile_tables tt{ctx->d_tile_edge_begin.as<u32>(), ctx->d_cross_offsets.as<u32>(), ctx->d_cross_edges.as<u32>()};
+	// a column window: its own template and tile tables, the effective-edge words of row_words(ctx)
+	word_range const wr(row_words(ctx));
+	v2m::tile_tables const wt{w.d_edge_begin.as<u32>(), w.d_cross_offsets.as<u32>(), w.d_cross_edges.as<u32>()};
+	u64 const *const d_eff_win(ctx->d_eff.as<u64>() - wr.restart);
 	{
 		// pass 1 builds no row, so it takes more rows per workgroup than pass 2 (the template tile, its byte count and the candidates' changes
 		// are set up once per group): as many as the kernel holds (kCountRowsMax = 256; measured per 620 / 244 rows of config 3 / 5: 32 rows
@@ -911,13 +978,28 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 		u32 const count_rows(u32(std::min<u64>(std::max<u64>(1, n_rows), (ce && *ce && std::atoi(ce) > 0) ? u64(std::min(std::atoi(ce), int(v2m::kCountRowsMax))) : u64(v2m::kCountRowsMax))));
 		u32 const count_groups(u32((n_rows + count_rows - 1) / count_rows));
 		timed_launch tl(ctx, V2M_KERNEL_UNALIGNED_COUNT);
-		hipLaunchKernelGGL(v2m::count_unaligned_kernel, dim3(unsigned(u64(ctx->n_tiles) * count_groups)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
-			ctx->d_template0.as<v2m::vec4u>(), ctx->d_eff.as<u64>(), eff_words, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
-			ctx->d_tile_counts.as<u32>(), ctx->n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run);
+		if (w.active)
+			hipLaunchKernelGGL(v2m::count_unaligned_window_kernel, dim3(unsigned(u64(n_tiles) * count_groups)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+				w.d_template0.as<v2m::vec4u>(), d_eff_win, wr.stride, wt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+				ctx->d_tile_counts.as<u32>(), n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run, u32(w.begin), u32(w.end));
+		else
+			hipLaunchKernelGGL(v2m::count_unaligned_kernel, dim3(unsigned(u64(ctx->n_tiles) * count_groups)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+				ctx->d_template0.as<v2m::vec4u>(), ctx->d_eff.as<u64>(), eff_words, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+				ctx->d_tile_counts.as<u32>(), ctx->n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run);
 		hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(unsigned(n_rows)), dim3(256), 0, ctx->stream,
-			ctx->d_tile_counts.as<u32>(), ctx->n_tiles, ctx->d_row_lengths.as<u64>());
+			ctx->d_tile_counts.as<u32>(), n_tiles, ctx->d_row_lengths.as<u64>());
 	}
 	auto const launch([&](bool nt) {
+		if (w.active) {
+			auto const go_window([&](auto kernel) {
+				hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+					w.d_template0.as<v2m::vec4u>(), d_eff_win, wr.stride, wt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+					ctx->d_tile_counts.as<u32>(), n_tiles, d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run, u32(w.begin), u32(w.end));
+			});
+			if (nt) go_window(v2m::splice_unaligned_window_kernel<true>);
+			else go_window(v2m::splice_unaligned_window_kernel<false>);
+			return;
+		}
 		auto const go([&](auto kernel) {
 			hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
 				ctx->d_template0.as<v2m::vec4u>(), ctx->d_eff.as<u64>(), eff_words, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
@@ -940,7 +1022,7 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 		if (0 == std::strcmp(mode_env, "plain")) mode = 0;
 		else if (0 == std::strcmp(mode_env, "nt")) mode = 1;
 	}
-	if (mode < 0 && n_rows * ctx->ref_len >= (u64(1) << 30)) {
+	if (mode < 0 && n_rows * (w.active ? row_length(ctx) : ctx->ref_len) >= (u64(1) << 30)) {
 		scoped_events ev;
 		V2M_HIP_TRY(ctx, ev.create(5));
 		V2M_HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
@@ -1028,7 +1110,7 @@ int bgzf_encode_rows(v2m_ctx *ctx, char const *d_rows, u64 pitch, u64 const *d_l
 // is cut so that its 64-KiB member slots stay within 1 GiB.
 int splice_rows_bgzf(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2m_sink_fn sink, void *user)
 {
-	u64 const L(ctx->aligned_len);
+	u64 const L(row_length(ctx));
 	u64 const max_len(unaligned ? v2m_max_unaligned_length(ctx) : L);
 	u64 const pitch(unaligned ? ((max_len + 255) & ~u64(255)) : v2m_min_row_pitch(ctx));
 	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
@@ -1396,6 +1478,7 @@ int v2m_upload_graph(v2m_ctx *ctx, const v2m_graph_view *g, const char *ref_seq,
 	// --- upload ------------------------------------------------------------------------------
 	ctx->has_graph = false;
 	ctx->has_template0 = false;
+	ctx->win.active = false;            // a new graph: whole rows again
 	V2M_HIP_TRY(ctx, ctx->d_ref.ensure(std::max<u64>(ref_len, 16)));
 	if (ref_len) V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref.p, ref_seq, ref_len, hipMemcpyHostToDevice, ctx->stream));
 	V2M_HIP_TRY(ctx, ctx->d_labels.ensure(std::max<u64>(label_total, 16)));
@@ -1416,7 +1499,7 @@ int v2m_upload_graph(v2m_ctx *ctx, const v2m_graph_view *g, const char *ref_seq,
 	{
 		timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
 		hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
-			ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(N), u32(L), n_chunks, ctx->d_template.as<uint4>(), '-');
+			ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(N), u32(L), n_chunks, ctx->d_template.as<uint4>(), '-', 0u);
 	}
 	V2M_HIP_TRY(ctx, hipGetLastError());
 
@@ -1441,6 +1524,12 @@ int v2m_upload_graph(v2m_ctx *ctx, const v2m_graph_view *g, const char *ref_seq,
 	ctx->n_tiles = n_tiles;
 	ctx->h_csum = std::move(csum);
 	ctx->h_tgt_prefix_max = std::move(tgt_prefix_max);
+	ctx->h_aln_pos = std::move(aln_pos);
+	ctx->h_patches = std::move(patches);
+	ctx->h_overlappable = std::move(overlappable);
+	ctx->h_tile_edge_begin = std::move(tile_edge_begin);
+	ctx->h_cross_offsets = std::move(cross_offsets);
+	ctx->h_cross_edges = std::move(cross_edges);
 	ctx->has_graph = true;
 	return V2M_OK;
 }
@@ -1588,8 +1677,83 @@ int v2m_upload_path_blocks(v2m_ctx *ctx, const uint64_t *src_words, uint64_t n_r
 }
 
 uint64_t v2m_aligned_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ctx->aligned_len : 0; }
-uint64_t v2m_min_row_pitch(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ((ctx->aligned_len + 255) & ~u64(255)) : 0; }
-uint64_t v2m_max_unaligned_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ctx->ref_len + ctx->label_bytes : 0; }
+uint64_t v2m_min_row_pitch(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ((row_length(ctx) + 255) & ~u64(255)) : 0; }
+uint64_t v2m_max_unaligned_length(const v2m_ctx *ctx)
+{
+	if (!(ctx && ctx->has_graph)) return 0;
+	return ctx->win.active ? row_length(ctx) : ctx->ref_len + ctx->label_bytes;   // a window's unaligned body never exceeds its columns
+}
+uint64_t v2m_window_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? row_length(ctx) : 0; }
+
+int v2m_set_column_window(v2m_ctx *ctx, uint64_t col_begin, uint64_t col_end)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!ctx->has_graph) return fail(ctx, V2M_ERR_STATE, "no graph uploaded");
+	u64 const L(ctx->aligned_len);
+	if (!(col_begin < col_end && col_end <= L))
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "column window [%llu, %llu) is empty or not within the aligned length %llu",
+			(unsigned long long) col_begin, (unsigned long long) col_end, (unsigned long long) L);
+	auto &w(ctx->win);
+	w.active = false;
+	if (0 == col_begin && L == col_end) return V2M_OK;   // the whole row: today's tables and kernels
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+	// Tile t of the window is columns [B_t, B_t + kTileBytes) clipped to col_end, B_t = col_begin + t * kTileBytes.  Its range: the edges
+	// that begin in it (edges are ordered by aligned begin).  Its crossing edges (aln_begin < B_t < aln_end): those of the whole-row tile
+	// T = B_t / kTileBytes that still reach past B_t, then those that begin in [T * kTileBytes, B_t) and reach past it -- ascending.
+	auto const &patches(ctx->h_patches);
+	u64 const W(col_end - col_begin);
+	u32 const n_tiles(u32((W + v2m::kTileBytes - 1) / v2m::kTileBytes));
+	auto const first_beginning_at([&](u64 col) -> u32 {   // first edge with aln_begin >= col
+		return u32(std::partition_point(patches.begin(), patches.end(), [&](v2m::edge_patch const &p) { return p.aln_begin < col; }) - patches.begin());
+	});
+	std::vector<u32> edge_begin(n_tiles + 1), cross_offsets(n_tiles + 1, 0), cross_edges;
+	for (u32 t(0); t <= n_tiles; ++t) edge_begin[t] = first_beginning_at(std::min<u64>(col_begin + u64(t) * v2m::kTileBytes, col_end));
+	for (u32 t(0); t < n_tiles; ++t) {
+		u64 const B(col_begin + u64(t) * v2m::kTileBytes), T(B / v2m::kTileBytes);
+		for (u32 i(ctx->h_cross_offsets[T]); i < ctx->h_cross_offsets[T + 1]; ++i)
+			if (patches[ctx->h_cross_edges[i]].aln_end > B) cross_edges.push_back(ctx->h_cross_edges[i]);
+		for (u32 e(ctx->h_tile_edge_begin[T]); e < edge_begin[t]; ++e)
+			if (patches[e].aln_end > B) cross_edges.push_back(e);
+		cross_offsets[t + 1] = u32(cross_edges.size());
+	}
+
+	// The edge words resolve decides: from the first edge whose span reaches past col_begin (the running maximum of the edges' targets
+	// is ordered, and so are the targets' aligned positions) to the last one that begins before col_end.  Their restart points (the
+	// nearest earlier edge that is not overlappable, kernels.hpp) lie at or after the last word whose first edge is not overlappable.
+	u32 const e_hi(edge_begin[n_tiles]);
+	u64 e_lo(0), hi(e_hi);
+	while (e_lo < hi) {
+		u64 const mid((e_lo + hi) / 2);
+		if (ctx->h_aln_pos[ctx->h_tgt_prefix_max[mid + 1]] > col_begin) hi = mid; else e_lo = mid + 1;
+	}
+	w.word_restart = w.word_lo = w.word_hi = 0;   // no edge reaches into the window: nothing to resolve
+	if (e_lo < e_hi) {
+		w.word_lo = u32(e_lo / 64);
+		w.word_hi = u32((u64(e_hi) + 63) / 64);
+		w.word_restart = w.word_lo;
+		while (w.word_restart > 0 && (ctx->h_overlappable[w.word_restart] & 1)) --w.word_restart;
+	}
+
+	if (int const rc = upload_vec(ctx, w.d_edge_begin, edge_begin)) return rc;
+	if (int const rc = upload_vec(ctx, w.d_cross_offsets, cross_offsets)) return rc;
+	if (int const rc = upload_vec(ctx, w.d_cross_edges, cross_edges)) return rc;
+	u64 const n_chunks(u64(n_tiles) * v2m::kTileChunks);
+	V2M_HIP_TRY(ctx, w.d_template.ensure(n_chunks * 16));
+	{
+		timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
+		hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
+			ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), u32(col_end), n_chunks, w.d_template.as<uint4>(), '-', u32(col_begin));
+	}
+	V2M_HIP_TRY(ctx, hipGetLastError());
+	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	w.begin = col_begin;
+	w.end = col_end;
+	w.n_tiles = n_tiles;
+	w.has_template0 = false;
+	w.active = true;
+	return V2M_OK;
+}
 
 
 // ---- founder search: chunk walks ------------------------------------------------------------------
@@ -1864,14 +2028,14 @@ int v2m_splice_rows_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t fla
 	if (0 == rows->n_rows) return V2M_OK;
 	bool const unaligned(flags & V2M_SPLICE_UNALIGNED);
 	if (!d_out || ((uintptr_t) d_out & 15)) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_out must be a 16-byte aligned device pointer");
-	u64 const need(unaligned ? v2m_max_unaligned_length(ctx) : ctx->aligned_len);
+	u64 const need(unaligned ? v2m_max_unaligned_length(ctx) : row_length(ctx));
 	if (row_pitch % 16 || row_pitch < ((need + 15) & ~u64(15)))
 		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "row_pitch must be a multiple of 16 and at least %llu rounded up to 16", (unsigned long long) need);
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 	if (!unaligned) {
 		if (int const rc = splice_aligned_slice(ctx, rows, 0, rows->n_rows, static_cast<char *>(d_out), row_pitch)) return rc;
 		if (row_lengths_out)
-			for (u64 r(0); r < rows->n_rows; ++r) row_lengths_out[r] = ctx->aligned_len;
+			for (u64 r(0); r < rows->n_rows; ++r) row_lengths_out[r] = row_length(ctx);
 		return V2M_OK;
 	}
 	if (int const rc = splice_unaligned_slice(ctx, rows, 0, rows->n_rows, static_cast<char *>(d_out), row_pitch)) return rc;
@@ -1890,7 +2054,7 @@ int v2m_splice_rows(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 	bool const unaligned(flags & V2M_SPLICE_UNALIGNED);
 
-	u64 const L(ctx->aligned_len);
+	u64 const L(row_length(ctx));
 	if (0 == L) {
 		for (u64 r(0); r < rows->n_rows; ++r)
 			if (sink(user, r, "", 0)) return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
@@ -1985,7 +2149,7 @@ int v2m_splice_rows_held(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags
 	if (0 == rows->n_rows) return V2M_OK;
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 	bool const unaligned(flags & V2M_SPLICE_UNALIGNED);
-	u64 const L(ctx->aligned_len);
+	u64 const L(row_length(ctx));
 
 	auto &state(ctx->held_state);
 	auto const wait_released([&](v2m_row_hold &slot) {

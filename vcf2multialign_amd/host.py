@@ -51,6 +51,8 @@ def _load():
 		L.v2mh_find_founders_mt.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint]
 		L.v2mh_set_paths_by_chrom_copy_and_edge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
 		L.v2mh_overlap_get.argtypes = [C.c_void_p, C.c_uint64, _u64p, _u64p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+		L.v2mh_columns_of_reference_range.restype = C.c_int
+		L.v2mh_columns_of_reference_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, _u64p, _u64p]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -134,6 +136,14 @@ class HostGraph:
 				ln, rp, vid, smp, ci, gt = C.c_uint64(), C.c_uint64(), C.c_char_p(), C.c_char_p(), C.c_uint32(), C.c_uint32()
 				L.v2mh_overlap_get(h, i, C.byref(ln), C.byref(rp), C.byref(vid), C.byref(smp), C.byref(ci), C.byref(gt))
 				self.overlaps.append({"lineno": ln.value, "ref_pos": rp.value, "var_id": vid.value.decode(), "sample": smp.value.decode(), "chrom_copy_idx": ci.value, "gt": gt.value})
+
+	def columns_of_reference_range(self, s, e):
+		"""The column window of the 0-based half-open reference range [s, e), computed by the C++ host
+		(v2mh_columns_of_reference_range; VariantGraph.columns_of_reference_range is the same rule in Python)."""
+		b, en = C.c_uint64(), C.c_uint64()
+		if _load().v2mh_columns_of_reference_range(self._h, int(s), int(e), C.byref(b), C.byref(en)):
+			raise ValueError("reference range [%d, %d) is empty or not within the reference (%d)" % (int(s), int(e), len(self.ref)))
+		return b.value, en.value
 
 	def __del__(self):
 		try:

@@ -5,15 +5,19 @@ the row order, FASTA identifiers and '\\n' placement of haplotype_output::output
 GPU through v2m_splice_rows instead of output_sequence().
 
 With bgzf=True the stream receives a BGZF file (include/v2m_hip.h, "BGZF output") whose decompressed bytes are the plain A2M:
-the '>'id'\n' and '\n' around every body in stored members, the bodies as the GPU's members, then the EOF member."""
+the '>'id'\n' and '\n' around every body in stored members, the bodies as the GPU's members, then the EOF member.
+
+With region=(s, e) every body is the column window of the 0-based half-open reference range [s, e) (include/v2m_hip.h, "column
+windows"); ids and row order stay as they are."""
 
 from .context import RowBatch, bgzf_frame_stored
-from .variant_graph import PLOIDY_MAX
+from .variant_graph import PLOIDY_MAX, columns_of_reference_range
 
 
 class Output:
-	def __init__(self, ctx, chromosome_id=None, should_output_reference=True, should_output_unaligned=False, bgzf=False):
+	def __init__(self, ctx, chromosome_id=None, should_output_reference=True, should_output_unaligned=False, bgzf=False, region=None):
 		self.ctx = ctx
+		self.region = region   # (s, e): only the columns of the 0-based half-open reference range [s, e) (v2m_set_column_window)
 		self.bgzf = bgzf
 		self.chromosome_id = chromosome_id
 		self.should_output_reference = should_output_reference
@@ -22,7 +26,16 @@ class Output:
 	def _fasta_id(self, name):
 		return ((self.chromosome_id + "\t") if self.chromosome_id else "") + name
 
-	def _write_rows(self, stream, ids, rows):
+	def _write_rows(self, stream, ids, rows, graph):
+		if self.region is None:
+			return self._write_bodies(stream, ids, rows)
+		self.ctx.set_column_window(*columns_of_reference_range(graph.reference_positions, graph.aligned_positions, *self.region))
+		try:
+			return self._write_bodies(stream, ids, rows)
+		finally:
+			self.ctx.set_column_window(0, self.ctx.aligned_length)
+
+	def _write_bodies(self, stream, ids, rows):
 		if self.bgzf:
 			def sink(i, members):
 				stream.write(bgzf_frame_stored(b">" + ids[i].encode() + b"\n"))
@@ -50,7 +63,7 @@ class HaplotypeOutput(Output):
 			for chr_copy_idx in range(graph.sample_ploidy(sample_idx)):   # :65
 				ids.append(self._fasta_id("%s-%d" % (sample, 1 + chr_copy_idx)))     # :69-72
 				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)     # :28-31
-		self._write_rows(stream, ids, rows)
+		self._write_rows(stream, ids, rows, graph)
 		return len(rows)
 
 
@@ -69,5 +82,5 @@ class FounderSequenceGreedyOutput(Output):
 			ids.append(self._fasta_id(str(1 + col_idx)))
 			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
 			rows.append(list(zip(cut_positions[:-1], col)))               # delegate: switch copy at each cut node (:106-114)
-		self._write_rows(stream, ids, rows)
+		self._write_rows(stream, ids, rows, graph)
 		return len(rows)

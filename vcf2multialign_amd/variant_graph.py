@@ -44,9 +44,31 @@ class VariantGraph:
 	def aligned_length(self):
 		return int(self.aligned_positions[-1]) if self.node_count else 0
 
+	def columns_of_reference_range(self, s, e):
+		"""The column window [col(s), col(e)) of the 0-based half-open reference range [s, e) (see columns_of_reference_range)."""
+		return columns_of_reference_range(self.reference_positions, self.aligned_positions, s, e)
+
 	# variant_graph.hh:73-74
 	def sample_ploidy(self, sample_idx):
 		return int(self.ploidy_csum[sample_idx + 1]) - int(self.ploidy_csum[sample_idx])
 
 	def total_chromosome_copies(self):
 		return int(self.ploidy_csum[-1])
+
+
+def columns_of_reference_range(reference_positions, aligned_positions, s, e):
+	"""The column window of the 0-based half-open reference range [s, e), 0 <= s < e <= R (R = the sink node's reference position, the
+	reference length): [col(s), col(e)) with col(p) = aligned_positions[n] + (p - reference_positions[n]) for the last node n with
+	reference_positions[n] <= p, and col(R) = the aligned length.  The window holds the range's columns, the insertion columns anchored
+	inside it and the padding after its last base; v2m_set_column_window takes it as is."""
+	s, e = int(s), int(e)
+	R = int(reference_positions[-1]) if len(reference_positions) else 0
+	if not 0 <= s < e <= R:
+		raise ValueError("reference range [%d, %d) is empty or not within the reference (%d)" % (s, e, R))
+
+	def col(p):
+		if p >= R:
+			return int(aligned_positions[-1])
+		n = int(np.searchsorted(reference_positions, np.uint64(p), side="right")) - 1
+		return int(aligned_positions[n]) + (p - int(reference_positions[n]))
+	return col(s), col(e)
