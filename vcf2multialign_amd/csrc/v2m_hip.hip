@@ -78,8 +78,9 @@ struct event_pair { hipEvent_t begin{}, end{}; };
 } // namespace
 
 
-// One pinned slot of v2m_splice_rows_held: the rows of one slice, and how many of them the sink still holds.  A row's hold IS its
-// slot (include/v2m_hip.h: v2m_row_hold), so that a release is one decrement under the ring's mutex from whatever thread.
+// One pinned slot of the context's ring: the rows of one slice, and how many of them a v2m_splice_rows_held sink still holds.  A
+// row's hold IS its slot (include/v2m_hip.h: v2m_row_hold), so that a release is one decrement under the ring's mutex from whatever
+// thread.
 struct held_ring_state {
 	std::mutex mutex;
 	std::condition_variable released;
@@ -90,6 +91,25 @@ struct v2m_row_hold {
 	hipEvent_t copied{};                // the slice's D2H copy has landed in `host`
 	uint64_t outstanding{};             // delivered rows not yet released (under ring->mutex)
 	held_ring_state *ring{};
+};
+
+
+// The edge words a row call resolves, [lo, hi), and the scratch layout: a row holds words [restart, restart + stride) (the look-back
+// of the words' restart points stays within them), so word w of row r is at d_eff + r * stride + (w - restart).
+struct word_range { u64 restart, lo, hi, stride; };
+
+// The columns [begin, end) every row call produces, with what the splice kernels take for them: the REF row with '-' as padding and
+// the one with 0 (unaligned mode, built on first use), the tables of the view's tiles (tile t = columns begin + t * kTileBytes on),
+// and the edge words resolve decides.
+struct row_view {
+	u64 begin{}, end{};
+	u64 max_unaligned{};                // the longest unaligned body a row of the view can have
+	u32 n_tiles{};
+	dev_buf d_template, d_template0;
+	bool has_template0{};
+	dev_buf d_edge_begin, d_cross_offsets, d_cross_edges;
+	word_range words{};
+	u64 length() const { return end - begin; }
 };
 
 
@@ -109,31 +129,21 @@ struct v2m_ctx {
 	bool has_graph{};
 	u64 n_nodes{}, n_edges{}, ref_len{}, aligned_len{}, label_bytes{};
 	bool has_nul_byte{};                // ref_seq or a label holds a 0 byte: the unaligned kernels' padding marker (kernels.hpp), so --unaligned refuses
-	u32 n_tiles{};
 	std::vector<u32> h_csum;            // alt_edge_count_csum narrowed, [N + 1]
 	std::vector<u32> h_tgt_prefix_max;  // [E + 1]: max target over edges < e (cut validation)
-	dev_buf d_ref, d_ref_pos, d_aln_pos, d_spans, d_patches, d_labels, d_template, d_overlappable;
+	dev_buf d_ref, d_ref_pos, d_aln_pos, d_spans, d_patches, d_labels, d_overlappable;
 	dev_buf d_ovl_rank, d_blocker_masks;   // per word: overlappable edges before it; per overlappable edge: who can block it
-	dev_buf d_template0;   // the REF row with 0 as padding byte (unaligned mode), built on first use
-	bool has_template0{};
-	dev_buf d_tile_edge_begin, d_cross_offsets, d_cross_edges;
 	// host copies of what v2m_set_column_window derives a window's tables from
 	std::vector<u32> h_aln_pos, h_tile_edge_begin, h_cross_offsets, h_cross_edges;
 	std::vector<v2m::edge_patch> h_patches;
 	std::vector<u64> h_overlappable;
 
-	// v2m_set_column_window: the columns [begin, end) every row call produces, with the tables of its tiles (tile t = columns
-	// begin + t * kTileBytes on) and the edge words resolve has to decide for it: [word_lo, word_hi), with the look-back that
-	// those words' restart points need reaching no further than word_restart (edge word_restart * 64 is not overlappable).
-	// Inactive = whole rows, which take the whole-row tables and kernels.
-	struct column_window {
-		bool active{};
-		u64 begin{}, end{};
-		u32 n_tiles{};
-		u32 word_restart{}, word_lo{}, word_hi{};
-		dev_buf d_template, d_template0, d_edge_begin, d_cross_offsets, d_cross_edges;
-		bool has_template0{};
-	} win;
+	// whole rows (v2m_upload_graph) and the column window of v2m_set_column_window; row calls produce the columns of the view in force,
+	// and the window's is in force only while `windowed`, which also picks the window instances of the splice kernels
+	row_view whole, window;
+	bool windowed{};
+	row_view &view() { return windowed ? window : whole; }
+	row_view const &view() const { return windowed ? window : whole; }
 
 	// paths_by_chrom_copy_and_edge
 	u64 const *d_paths{};
@@ -164,16 +174,16 @@ struct v2m_ctx {
 	dev_buf d_resolve_queue, d_resolve_count;   // (row, word) pairs the streaming resolve pass leaves to the dense one
 	dev_buf d_eff, d_row_bits, d_seg_offsets, d_seg_edge_begin, d_seg_copy, d_sums, d_lengths, d_needs_serial, d_tile_counts, d_row_lengths;
 	dev_buf ring[2];
-	pinned_buf host_ring[2];
-	// v2m_splice_rows_held: more pinned slots than the two above, each kept until the sink has released its rows
+	// pinned slots: the rows of v2m_splice_rows[_held] (a slot is kept until the sink has released its rows); slots 0 and 1 also stage
+	// the BGZF members and v2m_upload_path_blocks' columns
 	held_ring_state held_state;
-	std::vector<std::unique_ptr<v2m_row_hold>> held_ring;
+	std::vector<std::unique_ptr<v2m_row_hold>> host_slots;
 	pinned_buf trials_stage[2];   // v2m_pbwt_cut_trials_streamed: the pairs' way back to the host
 	// BGZF (V2M_SPLICE_BGZF, v2m_bgzf_compress): one 64-KiB member slot per block of a slice, the members' sizes and scanned offsets,
 	// the dense members of a slice (two: one crossing the link while the next is compacted) and their row extents on the host
 	dev_buf d_bgzf_slots, d_bgzf_sizes, d_bgzf_offsets, d_bgzf_table, d_bgzf_dense[2], d_bgzf_in;
 	pinned_buf h_bgzf_table[2];
-	hipEvent_t ev_compute[2]{}, ev_copy[2]{};
+	hipEvent_t ev_compute[2]{};
 };
 
 
@@ -704,9 +714,16 @@ int prepare_rows(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row
 
 
 // Tuning knobs (read per call so that one process can A/B them).
-// V2M_NT_STORES=0/1 forces plain / nontemporal output stores; unset = calibrate once per context (below).
-int forced_store_mode()
+// V2M_NT_STORES=0/1 (aligned) and V2M_UNALIGNED_STORE=plain|nt (unaligned) force plain / nontemporal output stores; unset = calibrate
+// once per context (store_flavour_launch).  -1 = not forced.
+int forced_store_mode(bool unaligned)
 {
+	if (unaligned) {
+		char const *const e = std::getenv("V2M_UNALIGNED_STORE");
+		if (e && 0 == std::strcmp(e, "plain")) return 0;
+		if (e && 0 == std::strcmp(e, "nt")) return 1;
+		return -1;
+	}
 	char const *e = std::getenv("V2M_NT_STORES");
 	if (!(e && *e)) return -1;
 	return std::atoi(e) != 0 ? 1 : 0;
@@ -725,29 +742,26 @@ u32 rows_per_group_for(u64 n_rows)
 }
 
 
-// Words per row of the effective-edge scratch: the edge count in 64-bit words, rounded up to a whole 128-B line so
-// that every row starts line-aligned.
-u64 eff_row_words(v2m_ctx const *ctx) { return (((ctx->n_edges + 63) / 64) + 15) & ~u64(15); }
-
-// Bytes of every aligned row the row calls produce: the column window's length, or the aligned length.
-u64 row_length(v2m_ctx const *ctx) { return ctx->win.active ? ctx->win.end - ctx->win.begin : ctx->aligned_len; }
-u32 row_tiles(v2m_ctx const *ctx) { return ctx->win.active ? ctx->win.n_tiles : ctx->n_tiles; }
-
-// The effective-edge words a row call resolves, [lo, hi), and the scratch layout: a row holds words [restart, restart + stride) (the
-// look-back of the words' restart points stays within them), so word w of row r is at d_eff + r * stride + (w - restart).
-struct word_range { u64 restart, lo, hi, stride; };
-word_range row_words(v2m_ctx const *ctx)
+// The REF row of a view with `gap` as padding ('-', or 0 for the unaligned kernels) into dst: chunk c holds columns view.begin + 16 c on.
+int expand_reference(v2m_ctx *ctx, row_view const &v, dev_buf &dst, char gap)
 {
-	if (!ctx->win.active) return {0, 0, (ctx->n_edges + 63) / 64, eff_row_words(ctx)};
-	auto const &w(ctx->win);
-	return {w.word_restart, w.word_lo, w.word_hi, (u64(w.word_hi - w.word_restart) + 15) & ~u64(15)};
+	u64 const n_chunks(u64(v.n_tiles) * v2m::kTileChunks);
+	V2M_HIP_TRY(ctx, dst.ensure(n_chunks * 16));
+	{
+		timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
+		hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
+			ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), u32(v.end), n_chunks, dst.as<uint4>(), gap, u32(v.begin));
+	}
+	V2M_HIP_TRY(ctx, hipGetLastError());
+	return V2M_OK;
 }
 
-// Effective-edge bits of rows [row_begin, row_end) of the batch into ctx->d_eff (words row_words(ctx), laid out as that says).
+
+// Effective-edge bits of rows [row_begin, row_end) of the batch into ctx->d_eff (the words of the view in force, laid out as its word_range says).
 int resolve_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row_end)
 {
 	u64 const n_rows(row_end - row_begin);
-	word_range const wr(row_words(ctx));
+	word_range const wr(ctx->view().words);
 	u64 const eff_words(wr.stride), n_words(wr.hi);   // words [wr.lo, n_words) are resolved
 	if (0 == ctx->n_edges) return V2M_OK;
 
@@ -840,61 +854,29 @@ int make_grid(v2m_ctx *ctx, u64 n_rows, splice_grid &g)
 {
 	g.rows_per_group = rows_per_group_for(n_rows);
 	g.n_groups = u32((n_rows + g.rows_per_group - 1) / g.rows_per_group);
-	g.n_blocks = u64(row_tiles(ctx)) * g.n_groups;
-	g.tile_run = tile_run_for(row_tiles(ctx));
+	g.n_blocks = u64(ctx->view().n_tiles) * g.n_groups;
+	g.tile_run = tile_run_for(ctx->view().n_tiles);
 	if (g.n_blocks > 0x7FFFFFFFull)
 		return fail(ctx, V2M_ERR_UNSUPPORTED, "splice grid too large (%llu workgroups); use smaller batches", (unsigned long long) g.n_blocks);
 	return V2M_OK;
 }
 
 
-// Resolve + aligned splice of rows [row_begin, row_end) of the batch into d_out.
-int splice_aligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row_end, char *d_out, u64 row_pitch)
+// Issues launch(nt) once more with the store flavour of the splice kind (ctx->store_mode, or ctx->unaligned_store_mode for the unaligned
+// splice) and times it as that kind's kernel.  Output rows are written once and never re-read by the GPU, so nontemporal stores (which
+// keep the rows from displacing the template and edge tables in L2 / Infinity Cache) usually win: 7.2-7.6 ms against 8.1-8.5 ms per
+// 51-GB aligned launch at config 3.  But on some boxes / memory layouts they are stuck in a slower mode for the whole life of a process
+// (9.1-9.3 ms, tools/probe_nt*.py), while plain stores stay put; the unaligned splice differs by box and buffer too (7.2 vs 5.4 ms per 256
+// config-3 rows on one box, 5.6 vs 6.0 ms on another).  The flavour is therefore calibrated once per context and kind, on the first
+// launch that writes >= 1 GiB (`bytes`): that launch is issued twice per flavour (the output is the same every time) and the faster one
+// is kept.
+template <typename F>
+int store_flavour_launch(v2m_ctx *ctx, bool unaligned, u64 n_rows, u64 bytes, F const &launch)
 {
-	u64 const n_rows(row_end - row_begin);
-	if (0 == n_rows || 0 == ctx->aligned_len) return V2M_OK;
-	if (int const rc = resolve_slice(ctx, rows, row_begin, row_end)) return rc;
-
-	u64 const eff_words(eff_row_words(ctx));
-	splice_grid g;
-	if (int const rc = make_grid(ctx, n_rows, g)) return rc;
-	v2m::tile_tables tt{ctx->d_tile_edge_begin.as<u32>(), ctx->d_cross_offsets.as<u32>(), ctx->d_cross_edges.as<u32>()};
-	u64 const store_limit((row_length(ctx) + 15) & ~u64(15));
-	auto const &w(ctx->win);
-	auto launch = [&](bool nt) {
-		if (w.active) {
-			// a column window: its own template and tile tables, the effective-edge words of row_words(ctx)
-			word_range const wr(row_words(ctx));
-			v2m::tile_tables const wt{w.d_edge_begin.as<u32>(), w.d_cross_offsets.as<u32>(), w.d_cross_edges.as<u32>()};
-			auto const go([&](auto kernel) {
-				hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
-					w.d_template.as<v2m::vec4u>(), ctx->d_eff.as<u64>() - wr.restart, wr.stride, wt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
-					d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, w.n_tiles, g.tile_run, store_limit, '-', u32(w.begin), u32(w.end));
-			});
-			if (nt) go(v2m::splice_aligned_window_kernel<true>);
-			else go(v2m::splice_aligned_window_kernel<false>);
-			return;
-		}
-		if (nt)
-			hipLaunchKernelGGL(v2m::splice_aligned_kernel<true>, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
-				ctx->d_template.as<v2m::vec4u>(), ctx->d_eff.as<u64>(), eff_words, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
-				d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, ctx->n_tiles, g.tile_run, store_limit, '-');
-		else
-			hipLaunchKernelGGL(v2m::splice_aligned_kernel<false>, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
-				ctx->d_template.as<v2m::vec4u>(), ctx->d_eff.as<u64>(), eff_words, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
-				d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, ctx->n_tiles, g.tile_run, store_limit, '-');
-	};
-
-	// Output rows are written once and never re-read by the GPU, so nontemporal stores (which keep the
-	// rows from displacing the template and edge tables in L2 / Infinity Cache) usually win: 7.2-7.6 ms
-	// against 8.1-8.5 ms per 51-GB launch at config 3.  But on some boxes / memory layouts they are stuck
-	// in a slower mode for the whole life of a process (9.1-9.3 ms, tools/probe_nt*.py), while plain stores
-	// stay put.  The flavour is therefore calibrated once per context, on the first launch that writes
-	// >= 1 GiB: that launch is issued twice per flavour (the output is the same every time) and the
-	// faster one is kept.
-	int mode(forced_store_mode());
-	if (mode < 0) mode = ctx->store_mode;
-	if (mode < 0 && n_rows * row_length(ctx) >= (u64(1) << 30)) {
+	int &slot(unaligned ? ctx->unaligned_store_mode : ctx->store_mode);
+	int mode(forced_store_mode(unaligned));
+	if (mode < 0) mode = slot;
+	if (mode < 0 && bytes >= (u64(1) << 30)) {
 		scoped_events ev;
 		V2M_HIP_TRY(ctx, ev.create(5));
 		V2M_HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
@@ -906,21 +888,51 @@ int splice_aligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin,
 		float t[4];
 		for (int i(0); i < 4; ++i) V2M_HIP_TRY(ctx, hipEventElapsedTime(&t[i], ev[i], ev[i + 1]));
 		float const nt_ms(std::min(t[0], t[2])), plain_ms(std::min(t[1], t[3]));
-		ctx->store_mode = nt_ms <= plain_ms ? 1 : 0;
+		slot = nt_ms <= plain_ms ? 1 : 0;
 		char buf[160];
-		std::snprintf(buf, sizeof(buf), "aligned splice stores: %s (calibrated on %llu rows: nontemporal %.3f ms, plain %.3f ms)",
-			ctx->store_mode ? "nontemporal" : "plain", (unsigned long long) n_rows, nt_ms, plain_ms);
+		std::snprintf(buf, sizeof(buf), "%s splice stores: %s (calibrated on %llu rows: nontemporal %.3f ms, plain %.3f ms)",
+			unaligned ? "unaligned" : "aligned", slot ? "nontemporal" : "plain", (unsigned long long) n_rows, nt_ms, plain_ms);
+		if (unaligned && ctx->info.size() > 2000) ctx->info.clear();
 		if (!ctx->info.empty()) ctx->info += "; ";
 		ctx->info += buf;
-		mode = ctx->store_mode;
+		mode = slot;
 	}
 	if (mode < 0) mode = 1;   // small launches before any calibration
 	{
-		timed_launch tl(ctx, V2M_KERNEL_SPLICE_ALIGNED);
+		timed_launch tl(ctx, unaligned ? V2M_KERNEL_SPLICE_UNALIGNED : V2M_KERNEL_SPLICE_ALIGNED);
 		launch(0 != mode);
 	}
 	V2M_HIP_TRY(ctx, hipGetLastError());
 	return V2M_OK;
+}
+
+
+// Resolve + aligned splice of rows [row_begin, row_end) of the batch into d_out.
+int splice_aligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row_end, char *d_out, u64 row_pitch)
+{
+	u64 const n_rows(row_end - row_begin);
+	if (0 == n_rows || 0 == ctx->aligned_len) return V2M_OK;
+	if (int const rc = resolve_slice(ctx, rows, row_begin, row_end)) return rc;
+
+	row_view const &v(ctx->view());
+	splice_grid g;
+	if (int const rc = make_grid(ctx, n_rows, g)) return rc;
+	v2m::tile_tables const tt{v.d_edge_begin.as<u32>(), v.d_cross_offsets.as<u32>(), v.d_cross_edges.as<u32>()};
+	u64 const store_limit((v.length() + 15) & ~u64(15));
+	auto const launch([&](bool nt) {
+		auto const go([&](auto kernel, auto... window) {
+			hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+				v.d_template.as<v2m::vec4u>(), ctx->d_eff.as<u64>() - v.words.restart, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+				d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, v.n_tiles, g.tile_run, store_limit, '-', window...);
+		});
+		if (ctx->windowed) {
+			if (nt) go(v2m::splice_aligned_window_kernel<true>, u32(v.begin), u32(v.end));
+			else go(v2m::splice_aligned_window_kernel<false>, u32(v.begin), u32(v.end));
+		}
+		else if (nt) go(v2m::splice_aligned_kernel<true>);
+		else go(v2m::splice_aligned_kernel<false>);
+	});
+	return store_flavour_launch(ctx, false, n_rows, n_rows * v.length(), launch);
 }
 
 
@@ -935,41 +947,19 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 		V2M_HIP_TRY(ctx, hipMemsetAsync(ctx->d_row_lengths.p, 0, n_rows * sizeof(u64), ctx->stream));
 		return V2M_OK;
 	}
-	auto &w(ctx->win);
-	if (w.active && !w.has_template0) {   // the window of the REF row with 0 as padding, built on first use
-		u64 const n_chunks(u64(w.n_tiles) * v2m::kTileChunks);
-		V2M_HIP_TRY(ctx, w.d_template0.ensure(n_chunks * 16));
-		{
-			timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
-			hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
-				ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), u32(w.end), n_chunks, w.d_template0.as<uint4>(), char(0), u32(w.begin));
-		}
-		V2M_HIP_TRY(ctx, hipGetLastError());
-		w.has_template0 = true;
-	}
-	u64 const n_chunks(u64(ctx->n_tiles) * v2m::kTileChunks);
-	if (!w.active && !ctx->has_template0) {
-		V2M_HIP_TRY(ctx, ctx->d_template0.ensure(n_chunks * 16));
-		{
-			timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
-			hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
-				ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), u32(ctx->aligned_len), n_chunks, ctx->d_template0.as<uint4>(), char(0), 0u);
-		}
-		V2M_HIP_TRY(ctx, hipGetLastError());
-		ctx->has_template0 = true;
+	row_view &v(ctx->view());
+	if (!v.has_template0) {   // the REF row with 0 as padding, built on first use
+		if (int const rc = expand_reference(ctx, v, v.d_template0, 0)) return rc;
+		v.has_template0 = true;
 	}
 	if (int const rc = resolve_slice(ctx, rows, row_begin, row_end)) return rc;
 
-	u64 const eff_words(eff_row_words(ctx));
 	splice_grid g;
 	if (int const rc = make_grid(ctx, n_rows, g)) return rc;
-	u32 const n_tiles(row_tiles(ctx));
-	V2M_HIP_TRY(ctx, ctx->d_tile_counts.ensure(n_rows * n_tiles * sizeof(u32)));
-	v2m::tile_tables tt{ctx->d_tile_edge_begin.as<u32>(), ctx->d_cross_offsets.as<u32>(), ctx->d_cross_edges.as<u32>()};
-	// a column window: its own template and tile tables, the effective-edge words of row_words(ctx)
-	word_range const wr(row_words(ctx));
-	v2m::tile_tables const wt{w.d_edge_begin.as<u32>(), w.d_cross_offsets.as<u32>(), w.d_cross_edges.as<u32>()};
-	u64 const *const d_eff_win(ctx->d_eff.as<u64>() - wr.restart);
+	V2M_HIP_TRY(ctx, ctx->d_tile_counts.ensure(n_rows * v.n_tiles * sizeof(u32)));
+	bool const windowed(ctx->windowed);
+	v2m::tile_tables const tt{v.d_edge_begin.as<u32>(), v.d_cross_offsets.as<u32>(), v.d_cross_edges.as<u32>()};
+	u64 const *const d_eff(ctx->d_eff.as<u64>() - v.words.restart);
 	{
 		// pass 1 builds no row, so it takes more rows per workgroup than pass 2 (the template tile, its byte count and the candidates' changes
 		// are set up once per group): as many as the kernel holds (kCountRowsMax = 256; measured per 620 / 244 rows of config 3 / 5: 32 rows
@@ -978,33 +968,27 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 		u32 const count_rows(u32(std::min<u64>(std::max<u64>(1, n_rows), (ce && *ce && std::atoi(ce) > 0) ? u64(std::min(std::atoi(ce), int(v2m::kCountRowsMax))) : u64(v2m::kCountRowsMax))));
 		u32 const count_groups(u32((n_rows + count_rows - 1) / count_rows));
 		timed_launch tl(ctx, V2M_KERNEL_UNALIGNED_COUNT);
-		if (w.active)
-			hipLaunchKernelGGL(v2m::count_unaligned_window_kernel, dim3(unsigned(u64(n_tiles) * count_groups)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
-				w.d_template0.as<v2m::vec4u>(), d_eff_win, wr.stride, wt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
-				ctx->d_tile_counts.as<u32>(), n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run, u32(w.begin), u32(w.end));
-		else
-			hipLaunchKernelGGL(v2m::count_unaligned_kernel, dim3(unsigned(u64(ctx->n_tiles) * count_groups)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
-				ctx->d_template0.as<v2m::vec4u>(), ctx->d_eff.as<u64>(), eff_words, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
-				ctx->d_tile_counts.as<u32>(), ctx->n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run);
+		auto const count([&](auto kernel, auto... window) {
+			hipLaunchKernelGGL(kernel, dim3(unsigned(u64(v.n_tiles) * count_groups)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+				v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+				ctx->d_tile_counts.as<u32>(), v.n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run, window...);
+		});
+		if (windowed) count(v2m::count_unaligned_window_kernel, u32(v.begin), u32(v.end));
+		else count(v2m::count_unaligned_kernel);
 		hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(unsigned(n_rows)), dim3(256), 0, ctx->stream,
-			ctx->d_tile_counts.as<u32>(), n_tiles, ctx->d_row_lengths.as<u64>());
+			ctx->d_tile_counts.as<u32>(), v.n_tiles, ctx->d_row_lengths.as<u64>());
 	}
 	auto const launch([&](bool nt) {
-		if (w.active) {
-			auto const go_window([&](auto kernel) {
-				hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
-					w.d_template0.as<v2m::vec4u>(), d_eff_win, wr.stride, wt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
-					ctx->d_tile_counts.as<u32>(), n_tiles, d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run, u32(w.begin), u32(w.end));
-			});
-			if (nt) go_window(v2m::splice_unaligned_window_kernel<true>);
-			else go_window(v2m::splice_unaligned_window_kernel<false>);
+		auto const go([&](auto kernel, auto... window) {
+			hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+				v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+				ctx->d_tile_counts.as<u32>(), v.n_tiles, d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run, window...);
+		});
+		if (windowed) {
+			if (nt) go(v2m::splice_unaligned_window_kernel<true>, u32(v.begin), u32(v.end));
+			else go(v2m::splice_unaligned_window_kernel<false>, u32(v.begin), u32(v.end));
 			return;
 		}
-		auto const go([&](auto kernel) {
-			hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
-				ctx->d_template0.as<v2m::vec4u>(), ctx->d_eff.as<u64>(), eff_words, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
-				ctx->d_tile_counts.as<u32>(), ctx->n_tiles, d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run);
-		});
 #ifdef V2M_TUNING_BUILD
 		// V2M_UNALIGNED_KERNEL=wave | shared64: the stream-out whose every wave packs its own short chunks / the product's with a queue of 64 (tools/unaligned_ab.sh)
 		static int const flavour([] { char const *const e(std::getenv("V2M_UNALIGNED_KERNEL")); return !e ? 0 : 0 == std::strcmp(e, "wave") ? 1 : 0 == std::strcmp(e, "shared64") ? 2 : 0; }());
@@ -1014,42 +998,7 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 		if (nt) go(v2m::splice_unaligned_kernel<true>);
 		else go(v2m::splice_unaligned_kernel<false>);
 	});
-	// Store flavour: as for the aligned splice, which of nontemporal and plain stores is faster depends on the box and the
-	// buffer (7.2 vs 5.4 ms per 256 config-3 rows on one box, 5.6 vs 6.0 ms on another), so the first launch that writes
-	// >= 1 GiB is issued twice per flavour (same output every time) and the faster one is kept.  V2M_UNALIGNED_STORE=plain|nt forces.
-	int mode(ctx->unaligned_store_mode);
-	if (char const *const mode_env = std::getenv("V2M_UNALIGNED_STORE")) {
-		if (0 == std::strcmp(mode_env, "plain")) mode = 0;
-		else if (0 == std::strcmp(mode_env, "nt")) mode = 1;
-	}
-	if (mode < 0 && n_rows * (w.active ? row_length(ctx) : ctx->ref_len) >= (u64(1) << 30)) {
-		scoped_events ev;
-		V2M_HIP_TRY(ctx, ev.create(5));
-		V2M_HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
-		for (int i(0); i < 4; ++i) {
-			launch(0 == (i & 1));   // nt, plain, nt, plain
-			V2M_HIP_TRY(ctx, hipEventRecord(ev[i + 1], ctx->stream));
-		}
-		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		float t[4];
-		for (int i(0); i < 4; ++i) V2M_HIP_TRY(ctx, hipEventElapsedTime(&t[i], ev[i], ev[i + 1]));
-		float const nt_ms(std::min(t[0], t[2])), plain_ms(std::min(t[1], t[3]));
-		ctx->unaligned_store_mode = nt_ms <= plain_ms ? 1 : 0;
-		char buf[160];
-		std::snprintf(buf, sizeof(buf), "unaligned splice stores: %s (calibrated on %llu rows: nontemporal %.3f ms, plain %.3f ms)",
-			ctx->unaligned_store_mode ? "nontemporal" : "plain", (unsigned long long) n_rows, nt_ms, plain_ms);
-		if (ctx->info.size() > 2000) ctx->info.clear();
-		if (!ctx->info.empty()) ctx->info += "; ";
-		ctx->info += buf;
-		mode = ctx->unaligned_store_mode;
-	}
-	if (mode < 0) mode = 1;   // small launches before any calibration
-	{
-		timed_launch tl(ctx, V2M_KERNEL_SPLICE_UNALIGNED);
-		launch(0 != mode);
-	}
-	V2M_HIP_TRY(ctx, hipGetLastError());
-	return V2M_OK;
+	return store_flavour_launch(ctx, true, n_rows, n_rows * (windowed ? v.length() : ctx->ref_len), launch);
 }
 
 
@@ -1068,6 +1017,45 @@ int check_batch(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags)
 	if ((flags & V2M_SPLICE_UNALIGNED) && ctx->has_nul_byte)
 		return fail(ctx, V2M_ERR_UNSUPPORTED, "the reference sequence or an ALT label holds a NUL byte, which the unaligned kernels use as their padding marker; aligned mode keeps such bytes");
 	return V2M_OK;
+}
+
+
+// How a row call cuts its batch into slices: row pitch, rows per slice, slice count and the bytes of a slice's rows.  Slices of
+// 512 MB; of 128 MB for batches of less than 8 GB (a founder run's 26 rows): a gigabyte of pinned memory takes 0.15 s to set up and as
+// long to give back, which a run of a second notices (config 4 end to end: 1.39 -> 1.22 s).  max_rows_per_slice: a limit of the
+// caller's (BGZF's member slots).
+struct slice_plan { u64 pitch, rows_per_slice, n_slices, slot_bytes; };
+
+slice_plan plan_slices(v2m_ctx const *ctx, u64 n_rows, bool unaligned, u64 max_rows_per_slice = ~u64(0))
+{
+	slice_plan p;
+	p.pitch = unaligned ? ((v2m_max_unaligned_length(ctx) + 255) & ~u64(255)) : v2m_min_row_pitch(ctx);
+	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
+	u64 const slot_default(n_rows * p.pitch < (u64(8) << 30) ? (u64(128) << 20) : (u64(512) << 20));
+	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : slot_default);
+	p.rows_per_slice = std::max<u64>(1, std::min<u64>({n_rows, slot_target / p.pitch, max_rows_per_slice}));
+	p.n_slices = (n_rows + p.rows_per_slice - 1) / p.rows_per_slice;
+	p.slot_bytes = p.rows_per_slice * p.pitch;
+	return p;
+}
+
+// The first n of the context's pinned slots, each of at least `bytes`.  No row of theirs may be held (wait_released).
+int ensure_host_slots(v2m_ctx *ctx, u64 n, u64 bytes)
+{
+	while (ctx->host_slots.size() < n) {
+		std::unique_ptr<v2m_row_hold> slot(new v2m_row_hold);
+		slot->ring = &ctx->held_state;
+		V2M_HIP_TRY(ctx, hipEventCreateWithFlags(&slot->copied, hipEventDisableTiming));
+		ctx->host_slots.push_back(std::move(slot));
+	}
+	for (u64 i(0); i < n; ++i) V2M_HIP_TRY(ctx, ctx->host_slots[i]->host.ensure(bytes));
+	return V2M_OK;
+}
+
+void wait_released(v2m_ctx *ctx, v2m_row_hold &slot)
+{
+	std::unique_lock<std::mutex> lock(ctx->held_state.mutex);
+	ctx->held_state.released.wait(lock, [&] { return 0 == slot.outstanding; });
 }
 
 
@@ -1103,29 +1091,26 @@ int bgzf_encode_rows(v2m_ctx *ctx, char const *d_rows, u64 pitch, u64 const *d_l
 }
 
 
-// v2m_splice_rows with V2M_SPLICE_BGZF.  The ring of v2m_splice_rows with the encoder after every slice's splice: slice s's members
+// v2m_splice_rows with V2M_SPLICE_BGZF.  The slices of v2m_splice_rows with the encoder after every slice's splice: slice s's members
 // are compacted into d_bgzf_dense[s & 1] and its row extents come back on the compute stream; the host reads the slice's total only
-// after slice s + 1 has been queued and then copies just the compressed bytes on the copy stream, so the link and the kernels still
-// overlap.  The dense buffers and pinned slots are sized by the worst case (v2m_bgzf_bound per row: tiny rows expand), and a slice
-// is cut so that its 64-KiB member slots stay within 1 GiB.
+// after slice s + 1 has been queued and then copies just the compressed bytes into pinned slot s & 1 on the copy stream, so the link
+// and the kernels still overlap.  The dense buffers and pinned slots are sized by the worst case (v2m_bgzf_bound per row: tiny rows
+// expand), and a slice is cut so that its 64-KiB member slots stay within 1 GiB.
 int splice_rows_bgzf(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2m_sink_fn sink, void *user)
 {
-	u64 const L(row_length(ctx));
+	u64 const L(ctx->view().length());
 	u64 const max_len(unaligned ? v2m_max_unaligned_length(ctx) : L);
-	u64 const pitch(unaligned ? ((max_len + 255) & ~u64(255)) : v2m_min_row_pitch(ctx));
-	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
-	u64 const slot_default(rows->n_rows * pitch < (u64(8) << 30) ? (u64(128) << 20) : (u64(512) << 20));
-	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : slot_default);
 	u64 const member_slots_per_row(std::max<u64>(1, bgzf_pieces(max_len)) * v2m::kBgzfSlotBytes);
-	u64 const rows_per_slice(std::max<u64>(1, std::min<u64>({rows->n_rows, slot_target / pitch, (u64(1) << 30) / member_slots_per_row})));
-	u64 const n_slices((rows->n_rows + rows_per_slice - 1) / rows_per_slice);
+	slice_plan const p(plan_slices(ctx, rows->n_rows, unaligned, (u64(1) << 30) / member_slots_per_row));
+	u64 const pitch(p.pitch), rows_per_slice(p.rows_per_slice), n_slices(p.n_slices);
 	u64 const dense_bytes(rows_per_slice * v2m_bgzf_bound(max_len));
-	for (int i(0); i < (n_slices > 1 ? 2 : 1); ++i) {
-		V2M_HIP_TRY(ctx, ctx->ring[i].ensure(rows_per_slice * pitch));
+	int const n_buffers(n_slices > 1 ? 2 : 1);
+	for (int i(0); i < n_buffers; ++i) {
+		V2M_HIP_TRY(ctx, ctx->ring[i].ensure(p.slot_bytes));
 		V2M_HIP_TRY(ctx, ctx->d_bgzf_dense[i].ensure(dense_bytes));
-		V2M_HIP_TRY(ctx, ctx->host_ring[i].ensure(dense_bytes));
 		V2M_HIP_TRY(ctx, ctx->h_bgzf_table[i].ensure((rows_per_slice + 1) * sizeof(u64)));
 	}
+	if (int const rc = ensure_host_slots(ctx, n_buffers, dense_bytes)) return rc;
 	std::vector<u64> extents[2];
 	auto const slice_rows([&](u64 s, u64 &r0, u64 &r1) { r0 = s * rows_per_slice; r1 = std::min(rows->n_rows, r0 + rows_per_slice); });
 
@@ -1133,7 +1118,7 @@ int splice_rows_bgzf(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2
 		int const b(int(s & 1));
 		u64 r0, r1;
 		slice_rows(s, r0, r1);
-		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_copy[b], 0));   // d_bgzf_dense[b] has crossed the link
+		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->host_slots[b]->copied, 0));   // d_bgzf_dense[b] has crossed the link
 		if (int const rc = unaligned
 				? splice_unaligned_slice(ctx, rows, r0, r1, ctx->ring[b].as<char>(), pitch)
 				: splice_aligned_slice(ctx, rows, r0, r1, ctx->ring[b].as<char>(), pitch))
@@ -1151,19 +1136,20 @@ int splice_rows_bgzf(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2
 		V2M_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_compute[b]));
 		u64 const *const table(ctx->h_bgzf_table[b].as<u64>());
 		extents[b].assign(table, table + (r1 - r0 + 1));
-		if (extents[b].back() > ctx->host_ring[b].bytes)
+		pinned_buf &host(ctx->host_slots[b]->host);
+		if (extents[b].back() > host.bytes)
 			return fail(ctx, V2M_ERR_HIP, "BGZF members of rows %llu.. exceed their bound", (unsigned long long) r0);
 		if (extents[b].back())
-			V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->host_ring[b].p, ctx->d_bgzf_dense[b].p, extents[b].back(), hipMemcpyDeviceToHost, ctx->copy_stream));
-		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_copy[b], ctx->copy_stream));
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(host.p, ctx->d_bgzf_dense[b].p, extents[b].back(), hipMemcpyDeviceToHost, ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->host_slots[b]->copied, ctx->copy_stream));
 		return V2M_OK;
 	});
 	auto const drain([&](u64 s) -> int {
 		int const b(int(s & 1));
 		u64 r0, r1;
 		slice_rows(s, r0, r1);
-		V2M_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_copy[b]));
-		char const *const base(ctx->host_ring[b].as<char>());
+		V2M_HIP_TRY(ctx, hipEventSynchronize(ctx->host_slots[b]->copied));
+		char const *const base(ctx->host_slots[b]->host.as<char>());
 		for (u64 r(r0); r < r1; ++r) {
 			u64 const begin(extents[b][r - r0]), end(extents[b][r - r0 + 1]);
 			if (sink(user, r, base + begin, end - begin)) return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
@@ -1183,6 +1169,98 @@ int splice_rows_bgzf(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2
 	while (V2M_OK == rc && drained < copied) { rc = drain(drained); if (V2M_OK == rc) ++drained; }
 	(void) hipStreamSynchronize(ctx->stream);
 	(void) hipStreamSynchronize(ctx->copy_stream);
+	return rc;
+}
+
+
+// Rows [r0, r1) of a slice in a pinned slot: row r at base + (r - r0) * pitch, with lengths[r - r0] bytes (unaligned) or `length`.
+struct slot_rows {
+	u64 r0, r1;
+	char const *base;
+	u64 pitch, length;
+	u64 const *lengths;
+	char const *row(u64 r) const { return base + (r - r0) * pitch; }
+	u64 bytes(u64 r) const { return lengths ? lengths[r - r0] : length; }
+};
+
+// v2m_splice_rows and v2m_splice_rows_held.  Slices of the batch alternate between two device slots and go round the first n_slots
+// pinned slots: the D2H copy of slice s runs on copy_stream while the kernels of slice s + 1 run on stream, and then
+// deliver(slot, slot_rows) hands slice s to the sink.  A slot is copied into again only when its rows are all released (a deliver
+// that holds none leaves nothing to wait for), and when the call returns, both streams are idle and no row is held.  `name` labels
+// the V2M_SPLICE_TIMING line.
+template <typename F>
+int splice_rows_pipeline(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, u64 n_slots, char const *name, F const &deliver)
+{
+	u64 const L(ctx->view().length());
+	if (0 == L) {   // rows without a byte: nothing to copy, nothing to hold on to
+		if (int const rc = ensure_host_slots(ctx, 1, 0)) return rc;
+		int const rc(deliver(*ctx->host_slots[0], slot_rows{0, rows->n_rows, "", 0, 0, nullptr}));
+		wait_released(ctx, *ctx->host_slots[0]);
+		return rc;
+	}
+	slice_plan const p(plan_slices(ctx, rows->n_rows, unaligned));
+	u64 const lengths_bytes(p.rows_per_slice * sizeof(u64));   // unaligned: row lengths ride at the end of the pinned slot
+	u64 const slots_used(std::min(n_slots, p.n_slices));
+	for (int i(0); i < (p.n_slices > 1 ? 2 : 1); ++i) V2M_HIP_TRY(ctx, ctx->ring[i].ensure(p.slot_bytes));
+	if (int const rc = ensure_host_slots(ctx, slots_used, p.slot_bytes + lengths_bytes)) return rc;
+	auto const slot_of([&](u64 s) -> v2m_row_hold & { return *ctx->host_slots[s % n_slots]; });
+	auto const first_row([&](u64 s) { return s * p.rows_per_slice; });
+	auto const end_row([&](u64 s) { return std::min(rows->n_rows, (s + 1) * p.rows_per_slice); });
+
+	auto const issue([&](u64 s) -> int {
+		v2m_row_hold &slot(slot_of(s));
+		int const d(int(s & 1));
+		u64 const r0(first_row(s)), r1(end_row(s));
+		wait_released(ctx, slot);                                             // the slice that was here n_slots slices ago
+		// the device slot is written again only when the copy that reads it (slice s - 2) is over
+		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, slot_of(s - 2).copied, 0));
+		if (int const rc = unaligned
+				? splice_unaligned_slice(ctx, rows, r0, r1, ctx->ring[d].as<char>(), p.pitch)
+				: splice_aligned_slice(ctx, rows, r0, r1, ctx->ring[d].as<char>(), p.pitch))
+			return rc;
+		if (unaligned)   // d_row_lengths is reused by the next slice: take the copy on the compute stream
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.as<char>() + p.slot_bytes, ctx->d_row_lengths.p, (r1 - r0) * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[d], ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[d], 0));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, ctx->ring[d].p, (r1 - r0) * p.pitch, hipMemcpyDeviceToHost, ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
+		return V2M_OK;
+	});
+	auto const hand_over([&](u64 s) -> int {
+		v2m_row_hold &slot(slot_of(s));
+		V2M_HIP_TRY(ctx, hipEventSynchronize(slot.copied));
+		char const *const base(slot.host.as<char>());
+		return deliver(slot, slot_rows{first_row(s), end_row(s), base, p.pitch, L, unaligned ? reinterpret_cast<u64 const *>(base + p.slot_bytes) : nullptr});
+	});
+
+	// V2M_SPLICE_TIMING=1: where the host's time of this call went (row tables + launches / waiting for copies + the sink), to stderr
+	bool const timing(nullptr != std::getenv("V2M_SPLICE_TIMING"));
+	double t_issue(0), t_drain(0);
+	auto const now([] { return std::chrono::steady_clock::now(); });
+	auto const since([&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(now() - t).count(); });
+	auto const t_call(now());
+
+	int rc(V2M_OK);
+	u64 launched(0);
+	for (u64 s(0); s < p.n_slices && V2M_OK == rc; ++s) {
+		auto const t_slice(now());
+		rc = issue(s);
+		t_issue += since(t_slice);
+		if (V2M_OK != rc) break;
+		launched = s + 1;
+		auto const t_d(now());
+		if (s >= 1) rc = hand_over(s - 1);                                   // its copy ran under this slice's kernels
+		t_drain += since(t_d);
+	}
+	auto const t_d(now());
+	if (V2M_OK == rc && launched) rc = hand_over(launched - 1);
+	t_drain += since(t_d);
+	// leave both streams idle and every slot released whatever happened (the slots are the library's)
+	(void) hipStreamSynchronize(ctx->stream);
+	(void) hipStreamSynchronize(ctx->copy_stream);
+	for (u64 i(0); i < slots_used; ++i) wait_released(ctx, *ctx->host_slots[i]);
+	if (timing) std::fprintf(stderr, "[%s] %llu rows in %llu slices: %.3f s in all, %.3f s preparing and launching, %.3f s waiting for copies and in the sink\n",
+		name, (unsigned long long) rows->n_rows, (unsigned long long) p.n_slices, since(t_call), t_issue, t_drain);
 	return rc;
 }
 
@@ -1272,7 +1350,6 @@ int v2m_ctx_create(int device_id, v2m_ctx **ctx_out)
 	}
 	for (int i(0); i < 2 && hipSuccess == st; ++i) {
 		st = hipEventCreateWithFlags(&ctx->ev_compute[i], hipEventDisableTiming);
-		if (hipSuccess == st) st = hipEventCreateWithFlags(&ctx->ev_copy[i], hipEventDisableTiming);
 		if (hipSuccess == st) st = hipEventCreateWithFlags(&ctx->ev_row_stage[i], hipEventDisableTiming);
 	}
 	if (hipSuccess != st) {
@@ -1294,10 +1371,9 @@ void v2m_ctx_destroy(v2m_ctx *ctx)
 	for (auto &e : ctx->free_events) { (void) hipEventDestroy(e.begin); (void) hipEventDestroy(e.end); }
 	for (int i(0); i < 2; ++i) {
 		if (ctx->ev_compute[i]) (void) hipEventDestroy(ctx->ev_compute[i]);
-		if (ctx->ev_copy[i]) (void) hipEventDestroy(ctx->ev_copy[i]);
 		if (ctx->ev_row_stage[i]) (void) hipEventDestroy(ctx->ev_row_stage[i]);
 	}
-	for (auto &slot : ctx->held_ring) if (slot && slot->copied) (void) hipEventDestroy(slot->copied);
+	for (auto &slot : ctx->host_slots) if (slot && slot->copied) (void) hipEventDestroy(slot->copied);
 	(void) hipStreamDestroy(ctx->stream);
 	(void) hipStreamDestroy(ctx->copy_stream);
 	delete ctx;
@@ -1477,8 +1553,8 @@ int v2m_upload_graph(v2m_ctx *ctx, const v2m_graph_view *g, const char *ref_seq,
 
 	// --- upload ------------------------------------------------------------------------------
 	ctx->has_graph = false;
-	ctx->has_template0 = false;
-	ctx->win.active = false;            // a new graph: whole rows again
+	ctx->windowed = false;              // a new graph: whole rows again
+	ctx->n_nodes = N; ctx->n_edges = E; ctx->ref_len = ref_len; ctx->aligned_len = L; ctx->label_bytes = label_total;
 	V2M_HIP_TRY(ctx, ctx->d_ref.ensure(std::max<u64>(ref_len, 16)));
 	if (ref_len) V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref.p, ref_seq, ref_len, hipMemcpyHostToDevice, ctx->stream));
 	V2M_HIP_TRY(ctx, ctx->d_labels.ensure(std::max<u64>(label_total, 16)));
@@ -1490,18 +1566,20 @@ int v2m_upload_graph(v2m_ctx *ctx, const v2m_graph_view *g, const char *ref_seq,
 	if (int const rc = upload_vec(ctx, ctx->d_overlappable, overlappable)) return rc;
 	if (int const rc = upload_vec(ctx, ctx->d_ovl_rank, ovl_rank)) return rc;
 	if (int const rc = upload_vec(ctx, ctx->d_blocker_masks, blocker_masks)) return rc;
-	if (int const rc = upload_vec(ctx, ctx->d_tile_edge_begin, tile_edge_begin)) return rc;
-	if (int const rc = upload_vec(ctx, ctx->d_cross_offsets, cross_offsets)) return rc;
-	if (int const rc = upload_vec(ctx, ctx->d_cross_edges, cross_edges)) return rc;
 
-	u64 const n_chunks(u64(n_tiles) * v2m::kTileChunks);
-	V2M_HIP_TRY(ctx, ctx->d_template.ensure(n_chunks * 16));
-	{
-		timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
-		hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
-			ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(N), u32(L), n_chunks, ctx->d_template.as<uint4>(), '-', 0u);
-	}
-	V2M_HIP_TRY(ctx, hipGetLastError());
+	// whole rows: every edge word resolved, rows of the effective-edge scratch the edge count in 64-bit words rounded up to a whole
+	// 128-B line so that every row starts line-aligned
+	row_view &v(ctx->whole);
+	v.begin = 0;
+	v.end = L;
+	v.max_unaligned = ref_len + label_total;
+	v.n_tiles = n_tiles;
+	v.has_template0 = false;
+	v.words = {0, 0, (E + 63) / 64, (((E + 63) / 64) + 15) & ~u64(15)};
+	if (int const rc = upload_vec(ctx, v.d_edge_begin, tile_edge_begin)) return rc;
+	if (int const rc = upload_vec(ctx, v.d_cross_offsets, cross_offsets)) return rc;
+	if (int const rc = upload_vec(ctx, v.d_cross_edges, cross_edges)) return rc;
+	if (int const rc = expand_reference(ctx, v, v.d_template, '-')) return rc;
 
 	ctx->d_paths = nullptr;
 	ctx->by_edge_valid = false;
@@ -1517,11 +1595,9 @@ int v2m_upload_graph(v2m_ctx *ctx, const v2m_graph_view *g, const char *ref_seq,
 	}
 	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 
-	ctx->n_nodes = N; ctx->n_edges = E; ctx->ref_len = ref_len; ctx->aligned_len = L; ctx->label_bytes = label_total;
 	// The reference streams whatever bytes the FASTA / VCF held (sequence_writer.cc:73-74).  Aligned mode does the same here; the
 	// unaligned kernels mark padding with byte 0, so a graph that holds one is refused there (check_batch) instead of losing it.
 	ctx->has_nul_byte = (ref_len && std::memchr(ref_seq, 0, ref_len)) || (label_total && std::memchr(g->alt_edge_label_bytes, 0, label_total));
-	ctx->n_tiles = n_tiles;
 	ctx->h_csum = std::move(csum);
 	ctx->h_tgt_prefix_max = std::move(tgt_prefix_max);
 	ctx->h_aln_pos = std::move(aln_pos);
@@ -1636,7 +1712,7 @@ int v2m_upload_path_blocks(v2m_ctx *ctx, const uint64_t *src_words, uint64_t n_r
 		// host threads and sent slot by slot
 		unsigned char const tail_mask((n_copies % 8) ? (unsigned char) ((1u << (n_copies % 8)) - 1) : (unsigned char) 0xFF);
 		size_t const slot_cols(std::max<size_t>(1, std::min<size_t>(n_cols, (size_t(64) << 20) / col_bytes)));
-		for (int i(0); i < 2; ++i) V2M_HIP_TRY(ctx, ctx->host_ring[i].ensure(slot_cols * col_bytes));
+		if (int const rc = ensure_host_slots(ctx, 2, slot_cols * col_bytes)) return rc;
 		scoped_events sent;
 		V2M_HIP_TRY(ctx, sent.create(2));
 		size_t slot_index(0);
@@ -1644,7 +1720,7 @@ int v2m_upload_path_blocks(v2m_ctx *ctx, const uint64_t *src_words, uint64_t n_r
 			size_t const nc(std::min(slot_cols, size_t(n_cols) - c0));
 			int const b(int(slot_index & 1));
 			if (slot_index >= 2) V2M_HIP_TRY(ctx, hipEventSynchronize(sent[b]));   // the slot's previous upload has left the host buffer
-			char *const stage(static_cast<char *>(ctx->host_ring[b].p));
+			char *const stage(ctx->host_slots[b]->host.as<char>());
 			auto const pack([&](size_t lo, size_t hi) {
 				for (size_t c(lo); c < hi; ++c) {
 					char *const d(stage + c * col_bytes);
@@ -1677,13 +1753,9 @@ int v2m_upload_path_blocks(v2m_ctx *ctx, const uint64_t *src_words, uint64_t n_r
 }
 
 uint64_t v2m_aligned_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ctx->aligned_len : 0; }
-uint64_t v2m_min_row_pitch(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ((row_length(ctx) + 255) & ~u64(255)) : 0; }
-uint64_t v2m_max_unaligned_length(const v2m_ctx *ctx)
-{
-	if (!(ctx && ctx->has_graph)) return 0;
-	return ctx->win.active ? row_length(ctx) : ctx->ref_len + ctx->label_bytes;   // a window's unaligned body never exceeds its columns
-}
-uint64_t v2m_window_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? row_length(ctx) : 0; }
+uint64_t v2m_min_row_pitch(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ((ctx->view().length() + 255) & ~u64(255)) : 0; }
+uint64_t v2m_max_unaligned_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ctx->view().max_unaligned : 0; }
+uint64_t v2m_window_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ctx->view().length() : 0; }
 
 int v2m_set_column_window(v2m_ctx *ctx, uint64_t col_begin, uint64_t col_end)
 {
@@ -1693,9 +1765,8 @@ int v2m_set_column_window(v2m_ctx *ctx, uint64_t col_begin, uint64_t col_end)
 	if (!(col_begin < col_end && col_end <= L))
 		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "column window [%llu, %llu) is empty or not within the aligned length %llu",
 			(unsigned long long) col_begin, (unsigned long long) col_end, (unsigned long long) L);
-	auto &w(ctx->win);
-	w.active = false;
-	if (0 == col_begin && L == col_end) return V2M_OK;   // the whole row: today's tables and kernels
+	ctx->windowed = false;
+	if (0 == col_begin && L == col_end) return V2M_OK;   // the whole row: the whole-row view and kernels
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 
 	// Tile t of the window is columns [B_t, B_t + kTileBytes) clipped to col_end, B_t = col_begin + t * kTileBytes.  Its range: the edges
@@ -1727,31 +1798,26 @@ int v2m_set_column_window(v2m_ctx *ctx, uint64_t col_begin, uint64_t col_end)
 		u64 const mid((e_lo + hi) / 2);
 		if (ctx->h_aln_pos[ctx->h_tgt_prefix_max[mid + 1]] > col_begin) hi = mid; else e_lo = mid + 1;
 	}
-	w.word_restart = w.word_lo = w.word_hi = 0;   // no edge reaches into the window: nothing to resolve
+	row_view &w(ctx->window);
+	u64 restart(0), lo(0), word_hi(0);   // no edge reaches into the window: nothing to resolve
 	if (e_lo < e_hi) {
-		w.word_lo = u32(e_lo / 64);
-		w.word_hi = u32((u64(e_hi) + 63) / 64);
-		w.word_restart = w.word_lo;
-		while (w.word_restart > 0 && (ctx->h_overlappable[w.word_restart] & 1)) --w.word_restart;
+		lo = e_lo / 64;
+		word_hi = (u64(e_hi) + 63) / 64;
+		restart = lo;
+		while (restart > 0 && (ctx->h_overlappable[restart] & 1)) --restart;
 	}
-
+	w.words = {restart, lo, word_hi, (word_hi - restart + 15) & ~u64(15)};
+	w.begin = col_begin;
+	w.end = col_end;
+	w.max_unaligned = W;                 // a window's unaligned body never exceeds its columns
+	w.n_tiles = n_tiles;
+	w.has_template0 = false;
 	if (int const rc = upload_vec(ctx, w.d_edge_begin, edge_begin)) return rc;
 	if (int const rc = upload_vec(ctx, w.d_cross_offsets, cross_offsets)) return rc;
 	if (int const rc = upload_vec(ctx, w.d_cross_edges, cross_edges)) return rc;
-	u64 const n_chunks(u64(n_tiles) * v2m::kTileChunks);
-	V2M_HIP_TRY(ctx, w.d_template.ensure(n_chunks * 16));
-	{
-		timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
-		hipLaunchKernelGGL(v2m::expand_reference_row_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
-			ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), u32(col_end), n_chunks, w.d_template.as<uint4>(), '-', u32(col_begin));
-	}
-	V2M_HIP_TRY(ctx, hipGetLastError());
+	if (int const rc = expand_reference(ctx, w, w.d_template, '-')) return rc;
 	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	w.begin = col_begin;
-	w.end = col_end;
-	w.n_tiles = n_tiles;
-	w.has_template0 = false;
-	w.active = true;
+	ctx->windowed = true;
 	return V2M_OK;
 }
 
@@ -2028,14 +2094,14 @@ int v2m_splice_rows_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t fla
 	if (0 == rows->n_rows) return V2M_OK;
 	bool const unaligned(flags & V2M_SPLICE_UNALIGNED);
 	if (!d_out || ((uintptr_t) d_out & 15)) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_out must be a 16-byte aligned device pointer");
-	u64 const need(unaligned ? v2m_max_unaligned_length(ctx) : row_length(ctx));
+	u64 const need(unaligned ? v2m_max_unaligned_length(ctx) : ctx->view().length());
 	if (row_pitch % 16 || row_pitch < ((need + 15) & ~u64(15)))
 		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "row_pitch must be a multiple of 16 and at least %llu rounded up to 16", (unsigned long long) need);
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 	if (!unaligned) {
 		if (int const rc = splice_aligned_slice(ctx, rows, 0, rows->n_rows, static_cast<char *>(d_out), row_pitch)) return rc;
 		if (row_lengths_out)
-			for (u64 r(0); r < rows->n_rows; ++r) row_lengths_out[r] = row_length(ctx);
+			for (u64 r(0); r < rows->n_rows; ++r) row_lengths_out[r] = ctx->view().length();
 		return V2M_OK;
 	}
 	if (int const rc = splice_unaligned_slice(ctx, rows, 0, rows->n_rows, static_cast<char *>(d_out), row_pitch)) return rc;
@@ -2053,83 +2119,13 @@ int v2m_splice_rows(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m
 	if (0 == rows->n_rows) return V2M_OK;
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 	bool const unaligned(flags & V2M_SPLICE_UNALIGNED);
-
-	u64 const L(row_length(ctx));
-	if (0 == L) {
-		for (u64 r(0); r < rows->n_rows; ++r)
-			if (sink(user, r, "", 0)) return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
+	if ((flags & V2M_SPLICE_BGZF) && 0 != ctx->view().length()) return splice_rows_bgzf(ctx, rows, unaligned, sink, user);
+	// a row is the sink's for the duration of its call only
+	return splice_rows_pipeline(ctx, rows, unaligned, 2, "v2m_splice_rows", [&](v2m_row_hold &, slot_rows const &sl) -> int {
+		for (u64 r(sl.r0); r < sl.r1; ++r)
+			if (sink(user, r, sl.row(r), sl.bytes(r))) return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
 		return V2M_OK;
-	}
-	if (flags & V2M_SPLICE_BGZF) return splice_rows_bgzf(ctx, rows, unaligned, sink, user);
-
-	// Slices of the batch alternate between two device buffers and two pinned host buffers:
-	// the D2H copy of slice s runs on copy_stream while the kernels of slice s+1 run on stream.
-	u64 const pitch(unaligned ? ((v2m_max_unaligned_length(ctx) + 255) & ~u64(255)) : v2m_min_row_pitch(ctx));
-	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
-	// 512-MB slots; 128-MB ones for batches of less than 8 GB (a founder run's 26 rows): a gigabyte of pinned memory takes 0.15 s
-	// to set up and as long to give back, which a run of a second notices (config 4 end to end: 1.39 -> 1.22 s)
-	u64 const slot_default(rows->n_rows * pitch < (u64(8) << 30) ? (u64(128) << 20) : (u64(512) << 20));
-	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : slot_default);
-	u64 const rows_per_slice(std::max<u64>(1, std::min<u64>(rows->n_rows, slot_target / pitch)));
-	u64 const n_slices((rows->n_rows + rows_per_slice - 1) / rows_per_slice);
-	u64 const slot_bytes(rows_per_slice * pitch);
-	u64 const lengths_bytes(rows_per_slice * sizeof(u64));   // unaligned: row lengths ride at the end of the pinned slot
-	for (int i(0); i < (n_slices > 1 ? 2 : 1); ++i) {
-		V2M_HIP_TRY(ctx, ctx->ring[i].ensure(slot_bytes));
-		V2M_HIP_TRY(ctx, ctx->host_ring[i].ensure(slot_bytes + lengths_bytes));
-	}
-
-	auto drain = [&](u64 s) -> int {
-		int const b(int(s & 1));
-		V2M_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_copy[b]));
-		u64 const r0(s * rows_per_slice), r1(std::min(rows->n_rows, r0 + rows_per_slice));
-		char const *base(static_cast<char const *>(ctx->host_ring[b].p));
-		u64 const *lengths(reinterpret_cast<u64 const *>(base + slot_bytes));
-		for (u64 r(r0); r < r1; ++r)
-			if (sink(user, r, base + (r - r0) * pitch, unaligned ? lengths[r - r0] : L)) return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
-		return V2M_OK;
-	};
-
-	// V2M_SPLICE_TIMING=1: where the host's time of this call went (row tables + launches / waiting for copies + the sink), to stderr
-	bool const timing(nullptr != std::getenv("V2M_SPLICE_TIMING"));
-	double t_issue(0), t_drain(0);
-	auto const now([] { return std::chrono::steady_clock::now(); });
-	auto const since([&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(now() - t).count(); });
-	auto const t_call(now());
-
-	int rc(V2M_OK);
-	u64 launched(0);
-	for (u64 s(0); s < n_slices && V2M_OK == rc; ++s) {
-		int const b(int(s & 1));
-		u64 const r0(s * rows_per_slice), r1(std::min(rows->n_rows, r0 + rows_per_slice));
-		auto const t_slice(now());
-		rc = unaligned
-			? splice_unaligned_slice(ctx, rows, r0, r1, ctx->ring[b].as<char>(), pitch)
-			: splice_aligned_slice(ctx, rows, r0, r1, ctx->ring[b].as<char>(), pitch);
-		t_issue += since(t_slice);
-		if (V2M_OK != rc) break;
-		hipError_t st(hipSuccess);
-		if (unaligned)   // d_row_lengths is reused by the next slice: take the copy on the compute stream
-			st = hipMemcpyAsync(static_cast<char *>(ctx->host_ring[b].p) + slot_bytes, ctx->d_row_lengths.p, (r1 - r0) * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream);
-		if (hipSuccess == st) st = hipEventRecord(ctx->ev_compute[b], ctx->stream);
-		if (hipSuccess == st) st = hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0);
-		if (hipSuccess == st) st = hipMemcpyAsync(ctx->host_ring[b].p, ctx->ring[b].p, (r1 - r0) * pitch, hipMemcpyDeviceToHost, ctx->copy_stream);
-		if (hipSuccess == st) st = hipEventRecord(ctx->ev_copy[b], ctx->copy_stream);
-		if (hipSuccess != st) { rc = fail(ctx, V2M_ERR_HIP, "D2H pipeline: %s", hipGetErrorString(st)); break; }
-		launched = s + 1;
-		auto const t_d(now());
-		if (s >= 1) rc = drain(s - 1);
-		t_drain += since(t_d);
-	}
-	auto const t_d(now());
-	if (V2M_OK == rc && launched) rc = drain(launched - 1);
-	t_drain += since(t_d);
-	// leave both streams idle whatever happened
-	(void) hipStreamSynchronize(ctx->stream);
-	(void) hipStreamSynchronize(ctx->copy_stream);
-	if (timing) std::fprintf(stderr, "[v2m_splice_rows] %llu rows in %llu slices: %.3f s in all, %.3f s preparing and launching, %.3f s waiting for copies and in the sink\n",
-		(unsigned long long) rows->n_rows, (unsigned long long) n_slices, since(t_call), t_issue, t_drain);
-	return rc;
+	});
 }
 
 
@@ -2148,96 +2144,17 @@ int v2m_splice_rows_held(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags
 	if (n_slots < 2 || n_slots > 64) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "n_slots must be between 2 and 64 (got %u)", n_slots);
 	if (0 == rows->n_rows) return V2M_OK;
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
-	bool const unaligned(flags & V2M_SPLICE_UNALIGNED);
-	u64 const L(row_length(ctx));
-
 	auto &state(ctx->held_state);
-	auto const wait_released([&](v2m_row_hold &slot) {
-		std::unique_lock<std::mutex> lock(state.mutex);
-		state.released.wait(lock, [&] { return 0 == slot.outstanding; });
-	});
-	// hands rows [r0, r1) of a slot to the sink; returns V2M_ERR_SINK when the sink refuses one (that row and the rows after it count
-	// as never delivered)
-	auto const deliver([&](v2m_row_hold &slot, u64 r0, u64 r1, u64 pitch, u64 slot_bytes) -> int {
-		char const *const base(slot.host.as<char>());
-		u64 const *const lengths(reinterpret_cast<u64 const *>(base + slot_bytes));
-		{ std::lock_guard<std::mutex> const lock(state.mutex); slot.outstanding = r1 - r0; }
-		for (u64 r(r0); r < r1; ++r) {
-			if (0 == sink(user, r, L ? base + (r - r0) * pitch : "", (unaligned && L) ? lengths[r - r0] : L, &slot)) continue;
-			{ std::lock_guard<std::mutex> const lock(state.mutex); slot.outstanding -= r1 - r; }   // (the only waiter is this thread)
+	// every row of the slice is held until released; when the sink refuses a row, that row and the rows after it count as never delivered
+	return splice_rows_pipeline(ctx, rows, flags & V2M_SPLICE_UNALIGNED, n_slots, "v2m_splice_rows_held", [&](v2m_row_hold &slot, slot_rows const &sl) -> int {
+		{ std::lock_guard<std::mutex> const lock(state.mutex); slot.outstanding = sl.r1 - sl.r0; }
+		for (u64 r(sl.r0); r < sl.r1; ++r) {
+			if (0 == sink(user, r, sl.row(r), sl.bytes(r), &slot)) continue;
+			{ std::lock_guard<std::mutex> const lock(state.mutex); slot.outstanding -= sl.r1 - r; }   // (the only waiter is this thread)
 			return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
 		}
 		return V2M_OK;
 	});
-
-	while (ctx->held_ring.size() < n_slots) {
-		std::unique_ptr<v2m_row_hold> slot(new v2m_row_hold);
-		slot->ring = &state;
-		V2M_HIP_TRY(ctx, hipEventCreateWithFlags(&slot->copied, hipEventDisableTiming));
-		ctx->held_ring.push_back(std::move(slot));
-	}
-
-	if (0 == L) {   // rows without a byte: nothing to copy, nothing to hold on to
-		auto &slot(*ctx->held_ring[0]);
-		int const rc(deliver(slot, 0, rows->n_rows, 0, 0));
-		wait_released(slot);
-		return rc;
-	}
-
-	u64 const pitch(unaligned ? ((v2m_max_unaligned_length(ctx) + 255) & ~u64(255)) : v2m_min_row_pitch(ctx));
-	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
-	u64 const slot_default(rows->n_rows * pitch < (u64(8) << 30) ? (u64(128) << 20) : (u64(512) << 20));
-	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : slot_default);
-	u64 const rows_per_slice(std::max<u64>(1, std::min<u64>(rows->n_rows, slot_target / pitch)));
-	u64 const n_slices((rows->n_rows + rows_per_slice - 1) / rows_per_slice);
-	u64 const slot_bytes(rows_per_slice * pitch);
-	u64 const lengths_bytes(rows_per_slice * sizeof(u64));
-	int rc(V2M_OK);
-	auto const hip_step([&](hipError_t st, char const *what) {
-		if (hipSuccess != st && V2M_OK == rc) rc = fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "%s: %s", what, hipGetErrorString(st));
-		return hipSuccess == st;
-	});
-	for (int i(0); i < (n_slices > 1 ? 2 : 1) && V2M_OK == rc; ++i) hip_step(ctx->ring[i].ensure(slot_bytes), "device slot");
-	u64 const slots_used(std::min<u64>(n_slots, n_slices));
-
-	u64 launched(0), delivered(0);
-	for (u64 s(0); s < n_slices && V2M_OK == rc; ++s) {
-		auto &slot(*ctx->held_ring[s % n_slots]);
-		int const d(int(s & 1));
-		u64 const r0(s * rows_per_slice), r1(std::min(rows->n_rows, r0 + rows_per_slice));
-		wait_released(slot);                                              // the slice that was here n_slots slices ago
-		if (!hip_step(slot.host.ensure(slot_bytes + lengths_bytes), "pinned slot")) break;
-		// the device slot is written again only when the copy that reads it (slice s - 2) is over
-		if (s >= 2 && !hip_step(hipStreamWaitEvent(ctx->stream, ctx->held_ring[(s - 2) % n_slots]->copied, 0), "device slot reuse")) break;
-		rc = unaligned
-			? splice_unaligned_slice(ctx, rows, r0, r1, ctx->ring[d].as<char>(), pitch)
-			: splice_aligned_slice(ctx, rows, r0, r1, ctx->ring[d].as<char>(), pitch);
-		if (V2M_OK != rc) break;
-		bool ok(true);
-		if (unaligned) ok = hip_step(hipMemcpyAsync(slot.host.as<char>() + slot_bytes, ctx->d_row_lengths.p, (r1 - r0) * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream), "row lengths");
-		ok = ok && hip_step(hipEventRecord(ctx->ev_compute[d], ctx->stream), "event");
-		ok = ok && hip_step(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[d], 0), "event");
-		ok = ok && hip_step(hipMemcpyAsync(slot.host.p, ctx->ring[d].p, (r1 - r0) * pitch, hipMemcpyDeviceToHost, ctx->copy_stream), "D2H copy");
-		ok = ok && hip_step(hipEventRecord(slot.copied, ctx->copy_stream), "event");
-		if (!ok) break;
-		launched = s + 1;
-		if (s >= 1) {                                                     // the slice before this one: its copy ran under this one's kernels
-			auto &prev(*ctx->held_ring[(s - 1) % n_slots]);
-			if (!hip_step(hipEventSynchronize(prev.copied), "D2H copy")) break;
-			rc = deliver(prev, r0 - rows_per_slice, r0, pitch, slot_bytes);
-			delivered = s;
-		}
-	}
-	if (V2M_OK == rc && launched > delivered) {
-		auto &last(*ctx->held_ring[(launched - 1) % n_slots]);
-		if (hip_step(hipEventSynchronize(last.copied), "D2H copy"))
-			rc = deliver(last, (launched - 1) * rows_per_slice, std::min(rows->n_rows, launched * rows_per_slice), pitch, slot_bytes);
-	}
-	// whatever happened: both streams idle, and no row still in a writer's hands when the call returns (the slots are the library's)
-	(void) hipStreamSynchronize(ctx->stream);
-	(void) hipStreamSynchronize(ctx->copy_stream);
-	for (u64 i(0); i < std::max<u64>(slots_used, 1); ++i) wait_released(*ctx->held_ring[i]);
-	return rc;
 }
 
 void v2m_row_release(v2m_row_hold *hold)
