@@ -100,3 +100,31 @@ def with_random_paths(g, seed, density):
 		g.label_offsets, g.label_bytes, words, ep, hp, g.sample_names, g.ploidy_csum)
 	g2.ref = g.ref
 	return g2
+
+
+def extreme_spans_case(tmpdir, dense_tile=False):
+	"""Spans and labels beyond what a splice workgroup's LDS cache can describe: a 150 kb deletion (span >= 64 KiB) with 30 SNVs under it,
+	a 70 kb insertion, 40 insertions of 200 bp inside one 16-KiB tile (more long patches than the long-span queue holds) and a multi-allelic
+	site; 3 diploid samples.  dense_tile adds 2100 SNVs on every other base of 4200 (so that more than 1024 edges begin in one tile) and a
+	1500-bp insertion (a label longer than the 1-KiB cached slice)."""
+	rng = np.random.default_rng(77)
+	ref = random_reference(rng, 400000)
+	recs = []
+
+	def rec(pos, ref_len, alts, gts):
+		recs.append((pos, ref[pos:pos + ref_len], alts, np.array(gts)))
+	rec(1000, 150000, [ref[1000:1001]], [[1, 0], [0, 0], [1, 1]])                        # 150 kb deletion (span >= 64 KiB)
+	for k in range(30):                                                                 # variants under it: skipped by copies 0, 4, 5
+		rec(2000 + 500 * k, 1, [_alt_base(rng, ref[2000 + 500 * k])], [[1, 1], [1, 0], [0, 1]])
+	rec(160000, 1, [ref[160000:160001] + random_reference(rng, 70000)], [[0, 1], [1, 0], [0, 0]])   # 70 kb insertion
+	for k in range(40):                                                                 # 40 insertions of 200 bp inside one 16-KiB tile, all carried by copy 1
+		p = 250000 + 150 * k
+		rec(p, 1, [ref[p:p + 1] + random_reference(rng, 200)], [[0, 1], [0, 0], [1, 0]])
+	rec(300000, 5, [ref[300000:300001], ref[300000:300001] + b"ACGTACGTACGT"], [[1, 2], [2, 1], [0, 2]])
+	if dense_tile:
+		for k in range(2100):
+			p = 320000 + 2 * k
+			rec(p, 1, [_alt_base(rng, ref[p])], rng.integers(0, 2, size=(3, 2)).tolist())
+		rec(330000, 1, [ref[330000:330001] + random_reference(rng, 1500)], [[1, 0], [0, 1], [1, 1]])
+	fa, vcf = write_inputs(str(tmpdir), ref, recs, 3)
+	return oracle.build_variant_graph(fa, vcf, "1")

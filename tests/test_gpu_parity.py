@@ -224,22 +224,7 @@ def test_extreme_spans_and_cache_limits(v2m, ctx, tmp_path, monkeypatch):
 	"""Spans and labels beyond what the workgroup's LDS cache can describe (>= 64 KiB spans, labels past the cached
 	2 KiB slice), more long patches in one tile-row than the long-span queue holds, and row groups larger than the
 	cached effective-bit rows: all must fall back to the global-memory path without changing a byte."""
-	rng = np.random.default_rng(77)
-	ref = synth.random_reference(rng, 400000)
-	recs = []
-	def rec(pos, ref_len, alts, gts):
-		recs.append((pos, ref[pos:pos + ref_len], alts, np.array(gts)))
-	n = 3   # samples, diploid
-	rec(1000, 150000, [ref[1000:1001]], [[1, 0], [0, 0], [1, 1]])                        # 150 kb deletion (span >= 64 KiB)
-	for k in range(30):                                                                 # variants under it: skipped by copies 0, 4, 5
-		rec(2000 + 500 * k, 1, [synth._alt_base(rng, ref[2000 + 500 * k])], [[1, 1], [1, 0], [0, 1]])
-	rec(160000, 1, [ref[160000:160001] + synth.random_reference(rng, 70000)], [[0, 1], [1, 0], [0, 0]])   # 70 kb insertion
-	for k in range(40):                                                                 # 40 insertions of 200 bp inside one 16-KiB tile, all carried by copy 1
-		p = 250000 + 150 * k
-		rec(p, 1, [ref[p:p + 1] + synth.random_reference(rng, 200)], [[0, 1], [0, 0], [1, 0]])
-	rec(300000, 5, [ref[300000:300001], ref[300000:300001] + b"ACGTACGTACGT"], [[1, 2], [2, 1], [0, 2]])
-	fa, vcf = synth.write_inputs(str(tmp_path), ref, recs, n)
-	g = oracle.build_variant_graph(fa, vcf, "1")
+	g = synth.extreme_spans_case(tmp_path)
 	assert g.aligned_length > 470000
 	_upload(v2m, ctx, g)
 	rows = [v2m.PLOIDY_MAX] + list(range(6)) + [[(0, 0), (g.node_count - 3, 3)]]
@@ -809,3 +794,28 @@ def test_held_rows_refusals_and_errors(ctx, v2m, tmp_path, monkeypatch):
 	ctx.splice_rows_held(rows, keep, n_slots=2)
 	assert [out[r] for r in range(len(rows))] == _oracle_rows(g, rows)
 	ctx.splice_rows_held([], keep, n_slots=2)                                            # no row: nothing happens
+
+
+@pytest.mark.parametrize("capacity", ["0", "3", None])
+def test_resolve_queue_capacity(v2m, ctx, tmp_path, monkeypatch, capacity):
+	"""V2M_RESOLVE_QUEUE_CAPACITY (test knob) sets the entries of each queue shard of the streaming resolve pass without its floor of 256: at 0
+	every hard word is decided inside resolve_effective_edges_kernel (the branch a full shard takes), at 3 the shards fill part of the way and
+	the rest overflows there; unset, the default.  Dense iid path bits (most words are hard) and founder rows."""
+	if capacity is not None:
+		monkeypatch.setenv("V2M_RESOLVE_QUEUE_CAPACITY", capacity)
+	g = synth.with_random_paths(synth.build_case(tmp_path, 11, 60000, 5000, 4, multi_allelic=0.2, long_every=97), 5, 0.9)
+	_upload(v2m, ctx, g)
+	rng = np.random.default_rng(12)
+	reach, bridges = 0, []
+	for n in range(g.node_count - 1):
+		if n >= reach and n > 0:
+			bridges.append(n)
+		for e in range(int(g.alt_edge_count_csum[n]), int(g.alt_edge_count_csum[n + 1])):
+			reach = max(reach, int(g.alt_edge_targets[e]))
+	H = g.total_chromosome_copies
+	rows = [v2m.PLOIDY_MAX] + list(range(H))
+	for k in (3, 30, min(300, len(bridges))):
+		cuts = [0] + sorted(int(x) for x in rng.choice(bridges, size=k, replace=False))
+		rows.append(list(zip(cuts, (int(x) for x in rng.integers(0, H, size=len(cuts))))))
+	assert ctx.splice_rows(rows) == _oracle_rows(g, rows)
+	assert ctx.splice_rows(rows, unaligned=True) == _oracle_rows(g, rows, unaligned=True)

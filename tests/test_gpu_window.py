@@ -457,3 +457,96 @@ def test_cli_region_founders(tmp_path):
 	r = _run(common + ["-s", str(win), "--region=%d-%d" % (S, E)])
 	assert r.returncode == 0, r.stderr.decode()
 	assert [(h, x[b:e]) for h, x in _records(full.read_bytes())] == _records(win.read_bytes())
+
+
+# ---- paths the small windows above do not reach ---------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nt,unaligned_store", [("0", "plain"), ("1", "nt")])
+def test_window_store_flavours_forced(v2m, ctx, tmp_path, monkeypatch, nt, unaligned_store):
+	"""Both store flavours of the window kernels (splice_aligned_window_kernel<false / true>, splice_unaligned_window_kernel<false / true>):
+	small launches default to nontemporal stores and only launches of 1 GiB and more calibrate, so the plain ones run only when forced."""
+	monkeypatch.setenv("V2M_NT_STORES", nt)
+	monkeypatch.setenv("V2M_UNALIGNED_STORE", unaligned_store)
+	g = synth.with_random_paths(synth.build_case(tmp_path, 41, 60000, 1500, 3, multi_allelic=0.2, long_every=30, max_indel=64), 6, 0.3)
+	rows = [PLOIDY_MAX] + list(range(g.total_chromosome_copies))
+	check_windows(v2m, ctx, g, rows, window_classes(g, np.random.default_rng(41)), forms=("rows", "device"))
+
+
+@pytest.mark.parametrize("rows_per_group,count_rows", [("1", "7"), ("17", None), ("256", "1")])
+def test_batches_of_many_rows(v2m, ctx, tmp_path, monkeypatch, rows_per_group, count_rows):
+	"""More than 300 rows in one call (copies cycled, REF and founder rows among them), whole and windowed: several count groups of
+	count_unaligned[_window]_kernel, the effective-edge cache reloaded every 16 rows of a splice group, V2M_ROWS_PER_GROUP at 1, 17 and 256
+	and V2M_COUNT_ROWS_PER_GROUP at 1, 7 and the default."""
+	monkeypatch.setenv("V2M_ROWS_PER_GROUP", rows_per_group)
+	if count_rows is not None:
+		monkeypatch.setenv("V2M_COUNT_ROWS_PER_GROUP", count_rows)
+	g = synth.with_random_paths(synth.build_case(tmp_path, 43, 40000, 1200, 4, multi_allelic=0.2, long_every=25), 7, 0.3)
+	H = g.total_chromosome_copies
+	rng = np.random.default_rng(43)
+	bridges = _bridges(g)
+	kinds = [PLOIDY_MAX] + list(range(H))
+	for k in (4, 40):
+		cuts = [0] + sorted(int(x) for x in rng.choice(bridges, size=k, replace=False))
+		kinds.append(list(zip(cuts, (int(x) for x in rng.integers(0, H, size=len(cuts))))))
+	rows = [kinds[i % len(kinds)] for i in range(311)]
+	vg = v2m.VariantGraph.from_object(g)
+	ctx.upload_graph(vg, g.ref)
+	for unaligned in (False, True):
+		want = [oracle_row(g, r, unaligned) for r in kinds]
+		assert ctx.splice_rows(rows, unaligned=unaligned) == [want[i % len(kinds)] for i in range(len(rows))], "whole rows, unaligned=%s" % unaligned
+	walked = walk_rows(g, kinds)
+	L = int(g.aligned_positions[-1])
+	for b, e in ((0, L), (TILE - 100, 2 * TILE + 7), (L // 3, L // 3 + 5000), (L - 3 * TILE - 1, L - 1)):
+		ctx.set_column_window(b, e)
+		bodies = [window_bodies(w, b, e) for w in walked]
+		for unaligned in (False, True):
+			got = ctx.splice_rows(rows, unaligned=unaligned)
+			assert len(got) == len(rows)
+			for i, a in enumerate(got):
+				assert a == bodies[i % len(kinds)][1 if unaligned else 0], "[%d, %d) unaligned=%s row %d" % (b, e, unaligned, i)
+	ctx.set_column_window(0, L)
+
+
+def test_cache_limits_under_windows(v2m, ctx, tmp_path, monkeypatch):
+	"""test_extreme_spans_and_cache_limits' graph plus a tile with more than 1024 edges beginning in it and a label longer than 1 KiB, under
+	windows that start or end inside the 150-kb deletion, inside the 70-kb insertion's label and inside the dense tile: every LDS-cache
+	fallback of the window kernels (candidates past kCandLds and kCandDeltaLds, labels past kLabelLds, spans >= 64 KiB, a full long-span
+	queue), also with row groups larger than the cached effective-edge rows."""
+	g = synth.extreme_spans_case(tmp_path, dense_tile=True)
+	ap = np.asarray(g.aligned_positions, dtype=np.int64)
+	csum = np.asarray(g.alt_edge_count_csum, dtype=np.int64)
+	src = np.repeat(np.arange(len(ap) - 1), np.diff(csum)[:len(ap) - 1])
+	begin, end = ap[src], ap[np.asarray(g.alt_edge_targets, dtype=np.int64)]
+	llen = np.diff(np.asarray(g.label_offsets, dtype=np.int64))
+	per_tile = np.bincount(begin // TILE)
+	dense = int(np.argmax(per_tile))
+	assert per_tile[dense] > 1024 and llen.max() >= 70000 and ((llen > 1024) & (llen < 2000)).any()
+	d = int(np.argmax(end - begin))                                   # the 150-kb deletion
+	i = int(np.argmax(llen))                                          # the 70-kb insertion
+	j = int(np.nonzero((llen > 1024) & (llen < 2000))[0][0])          # the 1500-bp insertion
+	L = int(ap[-1])
+	db, de, ib, jb = int(begin[d]), int(end[d]), int(begin[i]), int(begin[j])
+	windows = [("starts_in_deletion", db + 5000, db + 90000), ("ends_in_deletion", db - 100, db + 20000), ("inside_deletion", db + 70000, de - 70000),
+		("starts_in_insertion", ib + 1000, ib + int(llen[i]) + 500), ("ends_in_insertion", ib - 50, ib + 40000),
+		("starts_in_dense_tile", dense * TILE + 100, min(L, (dense + 2) * TILE + 9)), ("ends_in_dense_tile", dense * TILE - 3000, dense * TILE + 9000),
+		("in_long_label", jb + 10, jb + 1400), ("whole", 0, L)]
+	rows = [PLOIDY_MAX] + list(range(6)) + [[(0, 0), (g.node_count - 3, 3)]]
+	check_windows(v2m, ctx, g, rows, windows)
+	monkeypatch.setenv("V2M_ROWS_PER_GROUP", "40")                  # 48 rows in one group of 40: rows 16.. use the uncached path
+	check_windows(v2m, ctx, g, rows * 6, windows[:1] + windows[5:7])
+
+
+@pytest.mark.parametrize("capacity", ["0", "3", None])
+def test_resolve_queue_capacity_windowed(v2m, ctx, tmp_path, monkeypatch, capacity):
+	"""test_gpu_parity.py::test_resolve_queue_capacity under column windows: the streaming resolve pass's overflow branch on a window's words."""
+	if capacity is not None:
+		monkeypatch.setenv("V2M_RESOLVE_QUEUE_CAPACITY", capacity)
+	g = synth.with_random_paths(synth.build_case(tmp_path, 11, 60000, 5000, 4, multi_allelic=0.2, long_every=97), 5, 0.9)
+	rng = np.random.default_rng(13)
+	bridges = _bridges(g)
+	H = g.total_chromosome_copies
+	rows = [PLOIDY_MAX] + list(range(H))
+	for k in (3, 30):
+		cuts = [0] + sorted(int(x) for x in rng.choice(bridges, size=k, replace=False))
+		rows.append(list(zip(cuts, (int(x) for x in rng.integers(0, H, size=len(cuts))))))
+	check_windows(v2m, ctx, g, rows, window_classes(g, rng, n_random=3))

@@ -15,15 +15,19 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module", params=["product", "tuning"])
+BUILD_FLAGS = {"product": [], "tuning": ["-DV2M_TUNING_BUILD"], "checked": ["-DV2M_CHECKED_BUILD"]}
+
+
+@pytest.fixture(scope="module", params=["product", "tuning", "checked"])
 def isa(request, tmp_path_factory):
-	"""The emitted ISA of the product build and of the tuning build (-DV2M_TUNING_BUILD: every transpose variant that can be timed)."""
+	"""The emitted ISA of the product build, of the tuning build (-DV2M_TUNING_BUILD: every transpose variant that can be timed) and of
+	the checked build (-DV2M_CHECKED_BUILD: LDS poisoned before use, tests only)."""
 	from vcf2multialign_amd import build
 	hipcc = build.find_hipcc()
 	if hipcc is None:
 		pytest.skip("hipcc not found")
 	out = tmp_path_factory.mktemp("isa") / "v2m_hip.s"
-	extra = ["-DV2M_TUNING_BUILD"] if request.param == "tuning" else []
+	extra = BUILD_FLAGS[request.param]
 	subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only"] + extra + ["-o", str(out), build.HIP_SOURCES[0]], cwd=ROOT)
 	kernels, name, cur = {}, None, []
 	for line in out.read_text().split("\n"):
@@ -89,3 +93,72 @@ def test_no_kernel_touches_m0(isa):
 			continue
 		uses = [l.strip() for l in lines if re.search(r"\bm0\b", l.split(";")[0])]
 		assert not uses, (name, uses[:3])
+
+
+def test_poison_only_in_the_checked_build(isa, request):
+	"""The checked build's LDS and scratch poison (kernels.hpp: V2M_POISON_LDS, v2m_lds_poison_seed, poison_fill_kernel) leaves no trace in
+	the product's or the tuning build's device code; the checked build has it."""
+	text = isa["__text__"]
+	if request.node.callspec.params["isa"] == "checked":
+		assert "v2m_lds_poison_seed" in text and "poison_fill_kernel" in text
+	else:
+		assert "poison" not in text.lower()
+
+
+def _strip_comments(text):
+	text = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), text, flags=re.S)
+	return re.sub(r"//[^\n]*", "", text)
+
+
+def _drop_tuning_only(text):
+	"""The text outside `#ifdef V2M_TUNING_BUILD ... #endif` (nested conditionals counted)."""
+	out, depth, skip = [], 0, None
+	for line in text.split("\n"):
+		s = line.strip()
+		if s.startswith("#if"):
+			depth += 1
+			if skip is None and re.match(r"#\s*ifdef\s+V2M_TUNING_BUILD\b", s):
+				skip = depth
+		elif s.startswith("#endif"):
+			if skip == depth:
+				skip = None
+				depth -= 1
+				continue
+			depth -= 1
+		out.append("" if skip is not None else line)
+	return "\n".join(out)
+
+
+def _functions(text):
+	"""The text cut at every line that begins a function or kernel at column 0 (`template`, `__global__`, `__device__`): each piece holds
+	one function's head and body (and whatever follows it up to the next one)."""
+	return re.split(r"\n(?=template\b|__global__|__device__)", text)
+
+
+def _shared_names(decl):
+	"""The object names a `__shared__ ... ;` declaration declares."""
+	decl = re.sub(r"__attribute__\s*\(\(.*?\)\)", " ", decl)
+	decl = re.sub(r"\[[^\]]*\]", "[]", decl.replace("__shared__", " "))
+	parts = [p.strip() for p in decl.split(",")]
+	names = [re.findall(r"(\w+)\s*(?:\[\]\s*)*;?$", parts[0])[0]]
+	names += [re.match(r"(\w+)", p).group(1) for p in parts[1:]]
+	return names
+
+
+def test_every_lds_object_is_poisoned_in_the_checked_build():
+	"""Lint: every __shared__ object in csrc/*.hpp, outside tuning-only code, is passed to V2M_POISON_LDS in the same function (so that the
+	checked build fills it with garbage before the kernel's first LDS access)."""
+	import glob
+	csrc = os.path.join(ROOT, "vcf2multialign_amd", "csrc")
+	seen, missing = 0, []
+	for path in sorted(glob.glob(os.path.join(csrc, "*.hpp"))):
+		with open(path) as f:
+			text = _drop_tuning_only(_strip_comments(f.read()))
+		for body in _functions(text):
+			for decl in re.findall(r"__shared__[^;]*;", body):
+				for name in _shared_names(decl):
+					seen += 1
+					if not re.search(r"V2M_POISON_LDS\(\s*%s\s*\)" % re.escape(name), body):
+						missing.append("%s: %s" % (os.path.basename(path), name))
+	assert seen >= 40, seen
+	assert not missing, "LDS objects never passed to V2M_POISON_LDS: " + ", ".join(missing)

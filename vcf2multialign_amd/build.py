@@ -4,6 +4,10 @@
   libv2m_hip_tuning.so   -- the same sources with -DV2M_TUNING_BUILD: every transpose shape / flavour that was measured on
                             the way to the three the product ships.  Loaded only by tools/tune_transpose.py and
                             tests/test_gpu_tuning_build.py (V2M_HIP_LIBRARY); nothing in the product path uses it.
+  libv2m_hip_checked.so  -- the same sources with -DV2M_CHECKED_BUILD: every kernel fills its LDS with a seeded pattern before use,
+                            device scratch and pinned staging are filled likewise before each call or slice takes them
+                            (kernels.hpp, v2m_hip.hip).  libv2m_host_checked.so is the C++ host library linked against it.  Loaded
+                            only by tests/test_gpu_checked_build.py (V2M_HIP_LIBRARY, V2M_HOST_LIBRARY, in a child process).
 
 hipcc cross-compiles for gfx950 without a GPU present.
 """
@@ -56,6 +60,7 @@ def include_closure(sources, strict=False):
 HIP_SOURCES = [os.path.join(CSRC, "v2m_hip.hip")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra"]
 TUNING_LIB_PATH = os.path.join(PKG_DIR, "libv2m_hip_tuning.so")
+CHECKED_LIB_PATH = os.path.join(PKG_DIR, "libv2m_hip_checked.so")
 
 # synthetic-input generator (bench + scale tests): host generator + the HIP kernel filling genotype bits
 SYNTH_LIB_PATH = os.path.join(PKG_DIR, "libv2m_synth.so")
@@ -63,6 +68,7 @@ SYNTH_SOURCES = [os.path.join(CSRC, "synth", "synth_capi.hip"), os.path.join(CSR
 
 # C++ host: graph builder, readers, output classes (libv2m_host.so) and the command-line driver
 HOST_LIB_PATH = os.path.join(PKG_DIR, "libv2m_host.so")
+CHECKED_HOST_LIB_PATH = os.path.join(PKG_DIR, "libv2m_host_checked.so")
 HOST_DIR = os.path.join(CSRC, "host")
 HOST_SOURCES = [os.path.join(HOST_DIR, f) for f in ("graph_builder.cc", "readers.cc", "gpu_path.cc", "output.cc", "founder.cc", "graph_file.cc", "host_capi.cc")]
 CLI_PATH = os.path.join(PKG_DIR, "bin", "vcf2multialign")
@@ -154,6 +160,9 @@ def _build_host(force, verbose):
 	if force or _stale(HOST_LIB_PATH, deps("HOST_DEPS") + [LIB_PATH]):
 		refuse_to_compile_under_profiler(HOST_LIB_PATH)
 		_link([cxx] + CXX_FLAGS + ["-fPIC", "-shared"], HOST_LIB_PATH, HOST_SOURCES + ["-L" + PKG_DIR, "-lv2m_hip", "-Wl,-rpath,$ORIGIN"], verbose)
+	if force or _stale(CHECKED_HOST_LIB_PATH, deps("HOST_DEPS") + [CHECKED_LIB_PATH]):
+		refuse_to_compile_under_profiler(CHECKED_HOST_LIB_PATH)
+		_link([cxx] + CXX_FLAGS + ["-fPIC", "-shared"], CHECKED_HOST_LIB_PATH, HOST_SOURCES + ["-L" + PKG_DIR, "-lv2m_hip_checked", "-Wl,-rpath,$ORIGIN"], verbose)
 	if force or _stale(CLI_PATH, deps("CLI_DEPS") + deps("HOST_DEPS") + [HOST_LIB_PATH]):
 		refuse_to_compile_under_profiler(CLI_PATH)
 		os.makedirs(os.path.dirname(CLI_PATH), exist_ok=True)
@@ -173,8 +182,9 @@ def _build(target, sources, dep_list, force, verbose, extra_flags=()):
 
 def stale_targets():
 	"""The targets of build_native() that are missing or older than what they are built from (the same dependency lists it uses)."""
-	targets = [(SYNTH_LIB_PATH, deps("SYNTH_DEPS")), (LIB_PATH, deps("HIP_DEPS")), (TUNING_LIB_PATH, deps("HIP_DEPS")),
-		(HOST_LIB_PATH, deps("HOST_DEPS") + [LIB_PATH]), (CLI_PATH, deps("CLI_DEPS") + deps("HOST_DEPS") + [HOST_LIB_PATH])]
+	targets = [(SYNTH_LIB_PATH, deps("SYNTH_DEPS")), (LIB_PATH, deps("HIP_DEPS")), (TUNING_LIB_PATH, deps("HIP_DEPS")), (CHECKED_LIB_PATH, deps("HIP_DEPS")),
+		(HOST_LIB_PATH, deps("HOST_DEPS") + [LIB_PATH]), (CHECKED_HOST_LIB_PATH, deps("HOST_DEPS") + [CHECKED_LIB_PATH]),
+		(CLI_PATH, deps("CLI_DEPS") + deps("HOST_DEPS") + [HOST_LIB_PATH])]
 	return [t for t, d in targets if _stale(t, d)]
 
 
@@ -188,5 +198,6 @@ def build_native(force=False, verbose=False):
 		_build(SYNTH_LIB_PATH, SYNTH_SOURCES, deps("SYNTH_DEPS"), force, verbose)
 		_build(LIB_PATH, HIP_SOURCES, deps("HIP_DEPS"), force, verbose)
 		_build(TUNING_LIB_PATH, HIP_SOURCES, deps("HIP_DEPS"), force, verbose, ["-DV2M_TUNING_BUILD"])
+		_build(CHECKED_LIB_PATH, HIP_SOURCES, deps("HIP_DEPS"), force, verbose, ["-DV2M_CHECKED_BUILD"])
 		_build_host(force, verbose)
 	return LIB_PATH

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels.hpp"   // V2M_POISON_LDS
+
 // Tables in constant memory, outside namespace v2m: tests/test_kernel_isa.py reads every _ZN3v2m label of the ISA as a kernel.
 // x^(2^k) mod P in the reflected representation (CRC-32, P = 0xEDB88320); crc_shift by n bytes starts at k = 3 (x^8: one byte)
 __constant__ static uint32_t const kBgzfCrcX2n[32] = {
@@ -317,6 +319,7 @@ __global__ void __launch_bounds__(kBgzfThreads) bgzf_deflate_kernel(char const *
 	u64 const k(blockIdx.x), row(k / blocks_per_row), j(k % blocks_per_row);
 	u64 const row_len(lengths ? lengths[row] : length);
 	if (j * kBgzfBlockBytes >= row_len) { if (0 == t) sizes[k] = 0; return; }
+	V2M_POISON_LDS(s);
 	u32 const nb(u32(row_len - j * kBgzfBlockBytes < kBgzfBlockBytes ? row_len - j * kBgzfBlockBytes : kBgzfBlockBytes));
 	char const *const src(rows + row * pitch + j * kBgzfBlockBytes);
 
@@ -493,6 +496,8 @@ __global__ void __launch_bounds__(kBgzfScanThreads) bgzf_scan_kernel(u32 const *
 {
 	__shared__ u64 wave_sums[kBgzfScanThreads / 64];
 	__shared__ u64 carry_in;
+	V2M_POISON_LDS(wave_sums);
+	V2M_POISON_LDS(carry_in);
 	u32 const t(threadIdx.x), lane(t & 63), wave(t >> 6);
 	if (0 == t) carry_in = 0;
 	for (u64 base(0); base < n_blocks; base += kBgzfScanThreads) {

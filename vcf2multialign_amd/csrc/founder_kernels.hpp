@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels.hpp"   // V2M_POISON_LDS
+
 namespace v2m {
 
 constexpr int kPbwtThreads = 1024;                    // (512 / 256 threads with twice / four times the copies each: 40.5 + 22.0 ms / 71.7 + 39.9 ms at config 4 against 30.5 + 17.3)
@@ -331,6 +333,22 @@ __global__ __launch_bounds__(kPbwtThreads) void pbwt_cut_trials_kernel(
 	uint32_t const my_begin = (uint32_t) t * per < n_copies ? (uint32_t) t * per : n_copies;
 	uint32_t const my_end = my_begin + per < n_copies ? my_begin + per : n_copies;
 	uint32_t const my_count = my_end - my_begin;
+	V2M_POISON_LDS(order);
+	V2M_POISON_LDS(divergence);
+	V2M_POISON_LDS(column);
+	V2M_POISON_LDS(wave_items);
+	V2M_POISON_LDS(hash_key);
+	V2M_POISON_LDS(hash_count);
+	V2M_POISON_LDS(bin_slot);
+	V2M_POISON_LDS(bin_key);
+	V2M_POISON_LDS(bin_packed);
+	V2M_POISON_LDS(bin_sum);
+	V2M_POISON_LDS(n_bins_s);
+	V2M_POISON_LDS(reduce_max);
+	V2M_POISON_LDS(reduce_cnt);
+	V2M_POISON_LDS(failed_s);
+	V2M_POISON_LDS(emitted_s);
+	V2M_POISON_LDS(smallest_s);
 
 	for (uint32_t i = t; i < n_copies; i += kPbwtThreads) {
 		order[i] = (unsigned short) start_order[(uint64_t) chunk * n_copies + i];
@@ -573,6 +591,13 @@ __global__ __launch_bounds__(kPbwtThreads) void pbwt_cut_records_kernel(
 	uint32_t const chunk = blockIdx.x;
 	uint64_t const cut_begin = chunk_first_cut[chunk], cut_end = chunk_first_cut[chunk + 1];
 	if (cut_begin >= cut_end) { if (t == 0) chunk_status[chunk] = 0u; return; }
+	V2M_POISON_LDS(order);
+	V2M_POISON_LDS(divergence);
+	V2M_POISON_LDS(column);
+	V2M_POISON_LDS(wave_items);
+	V2M_POISON_LDS(class_items);
+	V2M_POISON_LDS(copy_class_lds);
+	V2M_POISON_LDS(span_start_index_lds);
 	constexpr uint32_t per = kPer;
 	uint32_t const my_begin = (uint32_t) t * per < n_copies ? (uint32_t) t * per : n_copies;
 	uint32_t const my_end = my_begin + per < n_copies ? my_begin + per : n_copies;

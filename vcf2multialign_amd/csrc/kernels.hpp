@@ -15,6 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#ifdef V2M_CHECKED_BUILD
+__device__ uint32_t v2m_lds_poison_seed;   // set by v2m_ctx_create from V2M_POISON_SEED (checked build only)
+#endif
+
 namespace v2m {
 
 typedef uint32_t u32;
@@ -23,6 +27,65 @@ typedef uint64_t u64;
 constexpr int kWave = 64;
 typedef u32 vec4u __attribute__((ext_vector_type(4)));   // native 16-B vector (nontemporal builtins need it)
 typedef vec4u vec4u_unaligned8 __attribute__((aligned(8)));   // a 16-B access at an 8-byte aligned address (legal on gfx950: unaligned access mode)
+
+// ---------------------------------------------------------------------------------------------
+// Checked build (-DV2M_CHECKED_BUILD: libv2m_hip_checked.so, loaded by tests only).  A workgroup's LDS starts out holding
+// whatever the previous workgroup on the CU left there -- usually the same kernel's data, of the right shape -- so a read
+// of LDS the kernel never wrote rarely changes an output byte.  In the checked build every kernel fills each of its
+// __shared__ objects with a pattern first (a hash of the context's seed, the workgroup index and the word offset: no two
+// workgroups see the same garbage) and passes a barrier; V2M_POISON_LDS_RANGE refills the dead part of a buffer that a
+// loop reuses.  In the product and tuning builds both macros are empty.
+// ---------------------------------------------------------------------------------------------
+#ifdef V2M_CHECKED_BUILD
+__device__ __forceinline__ u32 poison_hash(u32 seed, u32 wg, u32 i)
+{
+	u32 h = seed ^ (wg * 0x9E3779B1u) ^ (i * 0x85EBCA77u);
+	h ^= h >> 15; h *= 0x2C1B3C6Du;
+	h ^= h >> 12; h *= 0x297A2D39u;
+	h ^= h >> 15;
+	return h;
+}
+
+__device__ __forceinline__ u32 poison_workgroup()
+{
+	return blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+}
+
+// Elements [begin, end) of the array `a` of W, by every thread of the workgroup (no barrier).
+template <typename W>
+__device__ __forceinline__ void poison_lds_words(W *a, u32 begin, u32 end)
+{
+	u32 const seed = v2m_lds_poison_seed, wg = poison_workgroup();
+	u32 const threads = blockDim.x * blockDim.y * blockDim.z;
+	u32 const t = threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z);
+	for (u32 i = begin + t; i < end; i += threads) a[i] = (W) poison_hash(seed, wg, i);
+}
+
+// All of `obj`, in the widest unit its alignment allows.
+template <typename T>
+__device__ __forceinline__ void poison_lds_object(T &obj)
+{
+	if constexpr (alignof(T) >= 4 && 0 == sizeof(T) % 4) poison_lds_words(reinterpret_cast<u32 *>(&obj), 0u, (u32) (sizeof(T) / 4));
+	else if constexpr (alignof(T) >= 2 && 0 == sizeof(T) % 2) poison_lds_words(reinterpret_cast<unsigned short *>(&obj), 0u, (u32) (sizeof(T) / 2));
+	else poison_lds_words(reinterpret_cast<unsigned char *>(&obj), 0u, (u32) sizeof(T));
+}
+
+// Fills dev_buf allocations and per-call scratch (v2m_hip.hip): byte i of the buffer gets byte i % 4 of poison_hash(seed, salt, i / 4).
+__global__ __launch_bounds__(256) void poison_fill_kernel(unsigned char *__restrict__ p, u64 n_bytes, u32 seed, u32 salt)
+{
+	u64 const n_words = n_bytes / 4;
+	for (u64 i = (u64) blockIdx.x * 256 + threadIdx.x; i < n_words; i += (u64) gridDim.x * 256)
+		reinterpret_cast<u32 *>(p)[i] = poison_hash(seed, salt, (u32) i);
+	if (0 == blockIdx.x && threadIdx.x < (n_bytes & 3))
+		p[4 * n_words + threadIdx.x] = (unsigned char) (poison_hash(seed, salt, (u32) n_words) >> (8 * threadIdx.x));
+}
+
+#define V2M_POISON_LDS(obj) do { ::v2m::poison_lds_object(obj); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
+#define V2M_POISON_LDS_RANGE(array, begin, end) ::v2m::poison_lds_words(&(array)[0], (begin), (end))
+#else
+#define V2M_POISON_LDS(obj) ((void) 0)
+#define V2M_POISON_LDS_RANGE(array, begin, end) ((void) 0)
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Geometry of the aligned splice.
@@ -215,6 +278,7 @@ __global__ __launch_bounds__(kTrThreads) void transpose_bits_kernel(
 	int const wave = t >> 6;
 	u64 item;
 	if (!xcd_chunked_item(blockIdx.x, (u64) n_row_panels * n_col_panels, items_per_xcd, item)) return;   // whole workgroup
+	V2M_POISON_LDS(panel);
 	// rows_fastest: vertically adjacent panels (which share source lines) are consecutive items; otherwise horizontally
 	// adjacent ones (which share destination lines).  The host picks per shape.
 	u64 const rw0 = (rows_fastest ? item % n_row_panels : item / n_col_panels) * kR;    // first source row-word
@@ -291,6 +355,8 @@ __global__ __launch_bounds__(64 * kWaves) void transpose_bits_stream_kernel(
 	int const wave = t >> 6;
 	u64 item;
 	if (!xcd_chunked_item(blockIdx.x, (u64) n_row_panels * n_col_panels, items_per_xcd, item)) return;   // whole workgroup
+	V2M_POISON_LDS(in);
+	V2M_POISON_LDS(slab);
 	u64 const rw0 = (rows_fastest ? item % n_row_panels : item / n_col_panels) * kTsR;
 	u64 const cg0 = (rows_fastest ? item / n_row_panels : item % n_col_panels) * kTsC;
 	u64 const n_cols = DW * 64;
@@ -402,6 +468,8 @@ __global__ __launch_bounds__(64 * kW) void transpose_bits_ring_kernel(
 
 	u64 item;
 	if (!xcd_chunked_item(blockIdx.x, (u64) n_panels * n_spans, items_per_xcd, item)) return;   // whole workgroup
+	V2M_POISON_LDS(stage);
+	V2M_POISON_LDS(ring);
 	u32 const panel = panel_fastest ? (u32) (item % n_panels) : (u32) (item / n_spans);
 	u32 const span = panel_fastest ? (u32) (item / n_panels) : (u32) (item % n_spans);
 
@@ -544,6 +612,8 @@ __global__ __launch_bounds__(64 * kWaves) void transpose_bits_lines_kernel(
 
 	u64 item64;
 	if (!xcd_chunked_item(blockIdx.x, (u64) n_panels * n_spans, items_per_xcd, item64)) return;   // whole workgroup
+	V2M_POISON_LDS(in);
+	V2M_POISON_LDS(slab);
 	u32 const item = (u32) item64;                                 // (a grid has fewer than 2^31 workgroups)
 	u32 const panel = panel_fastest ? item % n_panels : item / n_spans;
 	u32 const span = panel_fastest ? item / n_panels : item % n_spans;
@@ -739,6 +809,9 @@ __global__ __launch_bounds__(64 * kWaves) void transpose_bits_rot_kernel(
 
 	u64 item64;
 	if (!xcd_chunked_item(blockIdx.x, (u64) n_panels * n_spans, items_per_xcd, item64)) return;   // whole workgroup
+	V2M_POISON_LDS(in);
+	V2M_POISON_LDS(slab);
+	V2M_POISON_LDS(slab_lane);
 	u32 const item = (u32) item64;
 	u32 const panel = panel_fastest ? item % n_panels : item / n_spans;
 	u32 const span = panel_fastest ? item / n_panels : item % n_spans;
@@ -1007,6 +1080,7 @@ __global__ __launch_bounds__(256) void assemble_row_bits_kernel(
 	u32 const row = blockIdx.y + row_base;
 	u32 const s_begin = rs.seg_offsets[row], s_end = rs.seg_offsets[row + 1];
 	if (s_end - s_begin <= 1) return;                        // whole workgroup: the row is read straight from its copy
+	V2M_POISON_LDS(acc);
 	u32 const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	u32 const w0 = word_base + (blockIdx.x * 4 + wave) * 64;  // this wave's first word (words [word_base, n_words) are assembled)
 	acc[threadIdx.x] = 0;
@@ -1521,6 +1595,8 @@ __device__ __forceinline__ void patch_row_tile(
 		__syncthreads();
 		if (t == 0) pc.long_count = 0;   // next read is after the next row's first barrier
 	}
+	// (checked build: the whole long-span queue is dead from here until the next row writes it, after the next barrier)
+	V2M_POISON_LDS_RANGE(pc.long_queue, 0u, (u32) kLongQueueLds);
 }
 
 // Workgroup -> (tile, row group).  The grid is cut into super-blocks of `tile_run` consecutive tiles x all row
@@ -1555,6 +1631,8 @@ __device__ __forceinline__ void splice_aligned_tiles(
 	map_block(blockIdx.x, n_groups, n_tiles, tile_run, tile, group);
 	u32 const row_begin = group * rows_per_group;
 	u32 const row_end = (row_begin + rows_per_group < n_rows) ? row_begin + rows_per_group : n_rows;
+	V2M_POISON_LDS(lds);
+	V2M_POISON_LDS(pc);
 
 	vec4u pristine[kChunksPerThread];
 #pragma unroll
@@ -1714,6 +1792,11 @@ __device__ __forceinline__ void count_unaligned_tiles(
 	map_block(blockIdx.x, n_groups, n_tiles, tile_run, tile, group);
 	u32 const row_begin = group * rows_per_group;
 	u32 const row_end = (row_begin + rows_per_group < n_rows) ? row_begin + rows_per_group : n_rows;
+	V2M_POISON_LDS(lds);
+	V2M_POISON_LDS(pc);
+	V2M_POISON_LDS(row_delta);
+	V2M_POISON_LDS(cand_delta);
+	V2M_POISON_LDS(wave_sums);
 
 	u32 mine = 0;
 #pragma unroll
@@ -2055,6 +2138,13 @@ __device__ __forceinline__ void splice_unaligned_tiles(
 	__shared__ u32 queue_desc[kQueue];
 	__shared__ u32 queue_count;
 
+	V2M_POISON_LDS(lds);
+	V2M_POISON_LDS(pc);
+	V2M_POISON_LDS(wave_sums);
+	V2M_POISON_LDS(compact_sel);
+	V2M_POISON_LDS(queue_data);
+	V2M_POISON_LDS(queue_desc);
+	V2M_POISON_LDS(queue_count);
 	int const t = threadIdx.x;
 	int const lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
 	if (t < 16) compact_sel[t] = compaction_selector((u32) t);   // first read follows the row loop's barriers
@@ -2094,6 +2184,9 @@ __device__ __forceinline__ void splice_unaligned_tiles(
 		if (row != row_begin) {
 			// the queue of the row before: packed by wave (row + pass) % 4, 64 entries a pass
 			u32 const n = (u32) __builtin_amdgcn_readfirstlane((int) queue_count);
+			// (checked build: the entries past the row's queue are read by nobody until this row's queue is written after the next barrier)
+			V2M_POISON_LDS_RANGE(queue_desc, n < kQueue ? n : kQueue, kQueue);
+			V2M_POISON_LDS_RANGE(queue_data, n < kQueue ? n : kQueue, kQueue);
 			for (u32 pass = 0; 64 * pass < n; ++pass) {
 				if (((row + pass) & (u32) (kWaves - 1)) != (u32) wave) continue;
 				u32 const idx = 64 * pass + (u32) lane;
@@ -2204,6 +2297,8 @@ __global__ __launch_bounds__(256) void scan_tile_counts_kernel(u32 *__restrict__
 	__shared__ u32 wave_sums[4];
 	__shared__ u32 carry_s;
 	u32 *const row = tile_counts + (u64) blockIdx.x * n_tiles;
+	V2M_POISON_LDS(wave_sums);
+	V2M_POISON_LDS(carry_s);
 	int const t = threadIdx.x, lane = t & 63, wave = t >> 6;
 	if (t == 0) carry_s = 0;
 	__syncthreads();

@@ -36,6 +36,45 @@ namespace {
 
 thread_local std::string g_create_error;
 
+#ifdef V2M_CHECKED_BUILD
+// Checked build (kernels.hpp): device memory and pinned staging are filled with a pattern derived from V2M_POISON_SEED before use, so
+// that a kernel or a copy that reads what nobody wrote in this call sees garbage instead of the previous call's (usually right) bytes.
+std::atomic<u32> g_poison_seed{0x9E3779B9u};
+std::atomic<u32> g_poison_salt{1};
+
+u32 poison_mix(u32 h)
+{
+	h ^= h >> 16; h *= 0x7FEB352Du;
+	h ^= h >> 15; h *= 0x846CA68Bu;
+	return h ^ (h >> 16);
+}
+
+// After a device-wide synchronize (nothing in flight is overwritten), and synchronized again.
+hipError_t poison_device(void *p, size_t n)
+{
+	if (!p || !n) return hipSuccess;
+	hipError_t st(hipDeviceSynchronize());
+	if (hipSuccess != st) return st;
+	u64 const words(n / 4);
+	unsigned const blocks(unsigned(std::min<u64>(4096, words / 256 + 1)));
+	hipLaunchKernelGGL(v2m::poison_fill_kernel, dim3(blocks), dim3(256), 0, 0, static_cast<unsigned char *>(p), u64(n), g_poison_seed.load(), poison_mix(g_poison_salt++));
+	if (hipSuccess != (st = hipGetLastError())) return st;
+	return hipDeviceSynchronize();
+}
+
+void poison_host(void *p, size_t n)
+{
+	if (!p) return;
+	u32 const salt(poison_mix(g_poison_salt++ ^ g_poison_seed.load()));
+	unsigned char *const b(static_cast<unsigned char *>(p));
+	for (size_t i(0); i < n / 4; ++i) { u32 const w(poison_mix(salt ^ u32(i) * 0x9E3779B1u)); std::memcpy(b + 4 * i, &w, 4); }
+	for (size_t i(n / 4 * 4); i < n; ++i) b[i] = (unsigned char) poison_mix(salt + u32(i));
+}
+#define V2M_POISON_HOST(p, n) poison_host((p), (n))
+#else
+#define V2M_POISON_HOST(p, n) ((void) 0)
+#endif
+
 struct dev_buf {
 	void *p{};
 	size_t bytes{};
@@ -51,9 +90,27 @@ struct dev_buf {
 		if (0 == n) return hipSuccess;
 		hipError_t const st(hipMalloc(&p, n));
 		if (hipSuccess == st) bytes = n; else p = nullptr;
+#ifdef V2M_CHECKED_BUILD
+		if (hipSuccess == st) return poison_device(p, n);
+#endif
 		return st;
 	}
 	template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+// Per-call scratch: in the checked build every ensure() -- each call or slice takes its scratch that way -- fills the buffer again.
+struct scratch_buf : dev_buf {
+	hipError_t ensure(size_t n)
+	{
+		bool const fresh(n > bytes);
+		hipError_t const st(dev_buf::ensure(n));
+#ifdef V2M_CHECKED_BUILD
+		if (hipSuccess == st && !fresh) return poison_device(p, bytes);
+#else
+		(void) fresh;
+#endif
+		return st;
+	}
 };
 
 struct pinned_buf {
@@ -171,9 +228,9 @@ struct v2m_ctx {
 	hipEvent_t ev_row_stage[2]{};
 	bool row_stage_in_flight[2]{};
 	int row_stage_next{};
-	dev_buf d_resolve_queue, d_resolve_count;   // (row, word) pairs the streaming resolve pass leaves to the dense one
-	dev_buf d_eff, d_row_bits, d_seg_offsets, d_seg_edge_begin, d_seg_copy, d_sums, d_lengths, d_needs_serial, d_tile_counts, d_row_lengths;
-	dev_buf ring[2];
+	scratch_buf d_resolve_queue, d_resolve_count;   // (row, word) pairs the streaming resolve pass leaves to the dense one
+	scratch_buf d_eff, d_row_bits, d_seg_offsets, d_seg_edge_begin, d_seg_copy, d_sums, d_lengths, d_needs_serial, d_tile_counts, d_row_lengths;
+	scratch_buf ring[2];
 	// pinned slots: the rows of v2m_splice_rows[_held] (a slot is kept until the sink has released its rows); slots 0 and 1 also stage
 	// the BGZF members and v2m_upload_path_blocks' columns
 	held_ring_state held_state;
@@ -181,7 +238,7 @@ struct v2m_ctx {
 	pinned_buf trials_stage[2];   // v2m_pbwt_cut_trials_streamed: the pairs' way back to the host
 	// BGZF (V2M_SPLICE_BGZF, v2m_bgzf_compress): one 64-KiB member slot per block of a slice, the members' sizes and scanned offsets,
 	// the dense members of a slice (two: one crossing the link while the next is compacted) and their row extents on the host
-	dev_buf d_bgzf_slots, d_bgzf_sizes, d_bgzf_offsets, d_bgzf_table, d_bgzf_dense[2], d_bgzf_in;
+	scratch_buf d_bgzf_slots, d_bgzf_sizes, d_bgzf_offsets, d_bgzf_table, d_bgzf_dense[2], d_bgzf_in;
 	pinned_buf h_bgzf_table[2];
 	hipEvent_t ev_compute[2]{};
 };
@@ -634,6 +691,7 @@ int prepare_rows(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row
 	}
 	V2M_HIP_TRY(ctx, ctx->h_row_stage[area].ensure(pad(n_rows + 1) + 2 * pad(max_segments)));
 	char *const base(static_cast<char *>(ctx->h_row_stage[area].p));
+	V2M_POISON_HOST(base, pad(n_rows + 1) + 2 * pad(max_segments));
 	out.seg_offsets = reinterpret_cast<u32 *>(base);
 	out.seg_edge_begin = reinterpret_cast<u32 *>(base + pad(n_rows + 1));
 	out.seg_copy = reinterpret_cast<u32 *>(base + pad(n_rows + 1) + pad(max_segments));
@@ -768,7 +826,7 @@ int resolve_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 ro
 	prepared_rows pr;
 	if (int const rc = prepare_rows(ctx, rows, row_begin, row_end, pr)) return rc;
 	if (wr.lo >= wr.hi) return V2M_OK;   // a column window that no edge reaches into
-	auto const upload([&](dev_buf &dst, u32 const *src, u64 count) -> int {
+	auto const upload([&](scratch_buf &dst, u32 const *src, u64 count) -> int {
 		V2M_HIP_TRY(ctx, dst.ensure(std::max<size_t>(count * sizeof(u32), 16)));
 		if (count) V2M_HIP_TRY(ctx, hipMemcpyAsync(dst.p, src, count * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
 		return V2M_OK;
@@ -799,6 +857,8 @@ int resolve_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 ro
 	v2m::row_segments rs{ctx->d_seg_offsets.as<u32>(), ctx->d_seg_edge_begin.as<u32>(), ctx->d_seg_copy.as<u32>(), d_row_bits, u32(eff_words)};
 	char const *const back_env(std::getenv("V2M_MAX_BACK_WORDS"));   // test knob: 0 forces the serial kernel for every cross-word restart
 	u32 const max_back_words((back_env && *back_env) ? u32(std::strtoul(back_env, nullptr, 10)) : v2m::kMaxBackWords);
+	char const *const capacity_env(std::getenv("V2M_RESOLVE_QUEUE_CAPACITY"));   // test knob: entries per queue shard, no floor (0: every hard word is decided in the streaming pass)
+	bool const capacity_forced(capacity_env && *capacity_env);
 	{
 		timed_launch tl(ctx, V2M_KERNEL_RESOLVE);
 		// rows per launch: queue entries are 32-bit (row, word) indices
@@ -812,7 +872,8 @@ int resolve_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 ro
 						ctx->d_paths, ctx->path_pitch, rs, d_row_bits, u32(n_words), u32(r0 + y0), u32(wr.restart));
 			// the queue's segments hold every word of the launch if they have to (iid random bits do that), up to 1 GiB in all;
 			// a workgroup whose segment is full decides its overflow itself
-			u64 const shard_capacity(std::max<u64>(256, std::min<u64>(nr * resolved_words, u64(1) << 28) / v2m::kResolveQueueShards));
+			u64 const shard_capacity(capacity_forced ? std::min<u64>(std::strtoull(capacity_env, nullptr, 10), (u64(1) << 28) / v2m::kResolveQueueShards)
+				: std::max<u64>(256, std::min<u64>(nr * resolved_words, u64(1) << 28) / v2m::kResolveQueueShards));
 			V2M_HIP_TRY(ctx, ctx->d_resolve_queue.ensure(shard_capacity * v2m::kResolveQueueShards * sizeof(u32)));
 			V2M_HIP_TRY(ctx, ctx->d_resolve_count.ensure(v2m::kResolveQueueShards * sizeof(u32)));
 			V2M_HIP_TRY(ctx, hipMemsetAsync(ctx->d_resolve_count.p, 0, v2m::kResolveQueueShards * sizeof(u32), ctx->stream));
@@ -1119,6 +1180,8 @@ int splice_rows_bgzf(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2
 		u64 r0, r1;
 		slice_rows(s, r0, r1);
 		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->host_slots[b]->copied, 0));   // d_bgzf_dense[b] has crossed the link
+		V2M_HIP_TRY(ctx, ctx->ring[b].ensure(p.slot_bytes));                 // (the slice takes its device slots: refilled in the checked build)
+		V2M_HIP_TRY(ctx, ctx->d_bgzf_dense[b].ensure(dense_bytes));
 		if (int const rc = unaligned
 				? splice_unaligned_slice(ctx, rows, r0, r1, ctx->ring[b].as<char>(), pitch)
 				: splice_aligned_slice(ctx, rows, r0, r1, ctx->ring[b].as<char>(), pitch))
@@ -1139,6 +1202,7 @@ int splice_rows_bgzf(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2
 		pinned_buf &host(ctx->host_slots[b]->host);
 		if (extents[b].back() > host.bytes)
 			return fail(ctx, V2M_ERR_HIP, "BGZF members of rows %llu.. exceed their bound", (unsigned long long) r0);
+		V2M_POISON_HOST(host.p, extents[b].back());
 		if (extents[b].back())
 			V2M_HIP_TRY(ctx, hipMemcpyAsync(host.p, ctx->d_bgzf_dense[b].p, extents[b].back(), hipMemcpyDeviceToHost, ctx->copy_stream));
 		V2M_HIP_TRY(ctx, hipEventRecord(ctx->host_slots[b]->copied, ctx->copy_stream));
@@ -1214,6 +1278,8 @@ int splice_rows_pipeline(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned
 		wait_released(ctx, slot);                                             // the slice that was here n_slots slices ago
 		// the device slot is written again only when the copy that reads it (slice s - 2) is over
 		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, slot_of(s - 2).copied, 0));
+		V2M_HIP_TRY(ctx, ctx->ring[d].ensure(p.slot_bytes));                 // (the slice takes its device slot: refilled in the checked build)
+		V2M_POISON_HOST(slot.host.p, p.slot_bytes + lengths_bytes);
 		if (int const rc = unaligned
 				? splice_unaligned_slice(ctx, rows, r0, r1, ctx->ring[d].as<char>(), p.pitch)
 				: splice_aligned_slice(ctx, rows, r0, r1, ctx->ring[d].as<char>(), p.pitch))
@@ -1339,6 +1405,15 @@ int v2m_ctx_create(int device_id, v2m_ctx **ctx_out)
 		return fail(nullptr, V2M_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 (MI355X) only", device_id, prop.gcnArchName);
 	st = hipSetDevice(device_id);
 	if (hipSuccess != st) return fail(nullptr, V2M_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(st));
+#ifdef V2M_CHECKED_BUILD
+	{   // the poison of this context's LDS and scratch (kernels.hpp): V2M_POISON_SEED, decimal or 0x-hex
+		char const *const e(std::getenv("V2M_POISON_SEED"));
+		u32 const seed((e && *e) ? u32(std::strtoul(e, nullptr, 0)) : 0x9E3779B9u);
+		g_poison_seed = seed;
+		st = hipMemcpyToSymbol(HIP_SYMBOL(v2m_lds_poison_seed), &seed, sizeof(seed));
+		if (hipSuccess != st) return fail(nullptr, V2M_ERR_HIP, "hipMemcpyToSymbol(v2m_lds_poison_seed): %s", hipGetErrorString(st));
+	}
+#endif
 
 	auto *ctx(new v2m_ctx);
 	ctx->device = device_id;
@@ -1357,6 +1432,11 @@ int v2m_ctx_create(int device_id, v2m_ctx **ctx_out)
 		v2m_ctx_destroy(ctx);   // destroys whatever was created
 		return fail(nullptr, V2M_ERR_HIP, "hipEventCreateWithFlags: %s", what.c_str());
 	}
+#ifdef V2M_CHECKED_BUILD
+	char seed_info[64];
+	std::snprintf(seed_info, sizeof(seed_info), "checked build: poison seed 0x%08x", g_poison_seed.load());
+	ctx->info = seed_info;
+#endif
 	*ctx_out = ctx;
 	return V2M_OK;
 }
@@ -1721,6 +1801,7 @@ int v2m_upload_path_blocks(v2m_ctx *ctx, const uint64_t *src_words, uint64_t n_r
 			int const b(int(slot_index & 1));
 			if (slot_index >= 2) V2M_HIP_TRY(ctx, hipEventSynchronize(sent[b]));   // the slot's previous upload has left the host buffer
 			char *const stage(ctx->host_slots[b]->host.as<char>());
+			V2M_POISON_HOST(stage, nc * col_bytes);
 			auto const pack([&](size_t lo, size_t hi) {
 				for (size_t c(lo); c < hi; ++c) {
 					char *const d(stage + c * col_bytes);
@@ -1951,6 +2032,7 @@ int pbwt_cut_trials_impl(v2m_ctx *ctx, uint64_t n_copies, uint64_t min_distance,
 	}
 	auto const issue([&](std::size_t i) -> int {
 		u32 *const pred(ctx->trials_stage[i & 1].as<u32>()), *const cls(pred + slot_pairs);
+		V2M_POISON_HOST(pred, 2 * slot_pairs * sizeof(u32));
 		u64 at(0);
 		for (u64 k(slices[i].first); k < slices[i].end; ++k) {
 			if (0 == produced[k]) continue;

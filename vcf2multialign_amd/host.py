@@ -12,16 +12,22 @@ _u64p = C.POINTER(C.c_uint64)
 _lib = None
 
 
+def library_path():
+	"""The host library; V2M_HOST_LIBRARY names another build (libv2m_host_checked.so, linked against the checked HIP library: tests only)."""
+	return os.environ.get("V2M_HOST_LIBRARY") or _build.HOST_LIB_PATH
+
+
 def _load():
 	global _lib
 	if _lib is None:
-		if not os.path.exists(_build.HOST_LIB_PATH):
-			raise ImportError(_build.HOST_LIB_PATH + " is missing: run __graft_entry__.build()")
+		path = library_path()
+		if not os.path.exists(path):
+			raise ImportError(path + " is missing: run __graft_entry__.build()")
 		try:
 			import torch  # noqa: F401  (one HIP runtime per process, see _native.load)
 		except ImportError:
 			pass
-		L = C.CDLL(_build.HOST_LIB_PATH)
+		L = C.CDLL(path)
 		L.v2mh_build_variant_graph.restype = C.c_void_p
 		L.v2mh_build_variant_graph.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint, C.c_char_p, C.c_size_t]
 		L.v2mh_free.argtypes = [C.c_void_p]
