@@ -34,8 +34,8 @@
  * v2m_profile_get_launches (v2m_bind_path_matrix_device followed without a step); 3 = + v2m_upload_path_blocks (and then
  * v2m_pbwt_cut_trials, v2m_pbwt_cut_records); 4 = + v2m_pbwt_cut_trials_streamed; 5 = + v2m_splice_rows_held / v2m_row_release (rows a
  * sink may keep until it says so).  Entries have only ever been added.  V2M_SPLICE_BGZF, v2m_bgzf_compress, v2m_bgzf_bound and
- * v2m_bgzf_frame_stored were added without a new version, and so were v2m_set_column_window and v2m_window_length: a caller
- * probes for them by symbol.
+ * v2m_bgzf_frame_stored were added without a new version, and so were v2m_set_column_window and v2m_window_length, and
+ * v2m_bgzf_scan and v2m_bgzf_decompress (with V2M_KERNEL_INFLATE): a caller probes for them by symbol.
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -96,7 +96,7 @@ int v2m_ctx_create(int device_id, v2m_ctx **ctx_out);
 void v2m_ctx_destroy(v2m_ctx *ctx);
 
 /* Message of the last failure on this ctx (or, with ctx == NULL, of the last failed
- * v2m_ctx_create on this thread).  Never NULL. */
+ * ctx-less call on this thread: v2m_ctx_create, v2m_bgzf_scan).  Never NULL. */
 const char *v2m_last_error(const v2m_ctx *ctx);
 
 /* Blocks until everything queued on the ctx's stream has finished. */
@@ -379,6 +379,37 @@ int v2m_bgzf_frame_stored(const void *src, uint64_t n, void *dst, uint64_t cap, 
  * (no EOF member).  V2M_ERR_INVALID_ARGUMENT when the members do not fit into cap (v2m_bgzf_bound(n) always does). */
 int v2m_bgzf_compress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out);
 
+/* ---- BGZF input ---------------------------------------------------------------------------------
+ *
+ * What v2m_bgzf_scan and v2m_bgzf_decompress accept (htslib's reader, and exactly zlib's inflate for the payload):
+ *   - Members back to back.  A member has the header bgzip writes: 1f 8b 08 04 (CM 8, FLG exactly FEXTRA), any MTIME, XFL and OS,
+ *     XLEN = 6 and one subfield 'B' 'C' of SLEN 2 holding BSIZE = the member's length - 1.  The deflate payload is bytes
+ *     [18, BSIZE + 1 - 8) of the member; the footer is CRC-32 (IEEE, reflected 0xEDB88320), then ISIZE <= 65 536.
+ *   - The payload is any RFC 1951 stream that zlib's inflate accepts: stored, fixed and dynamic Huffman blocks, any number of them,
+ *     distances up to 32 768 within the member (a member is inflated on its own; no window crosses members).  Refused as zlib refuses
+ *     them: block type 3; LEN != ~NLEN; HLIT > 286 or HDIST > 30; an over-subscribed code, or an incomplete one (a literal/length or
+ *     distance code may be incomplete only as a single code of length 1; the code-length code never); no end-of-block code; a repeat
+ *     code 16 with no previous length, or a repeat past HLIT + HDIST; length symbols 286 / 287 and distance symbols 30 / 31; a distance
+ *     before the member's first byte.  Also refused: output longer than ISIZE, a stream that reads past the payload, output shorter
+ *     than ISIZE, a CRC-32 that does not match.  Bytes after the final block inside the payload are ignored, as zlib leaves them.
+ *   - The members decompress to the concatenation of their bytes; the 28-byte EOF member and other empty members add nothing.
+ *   - Gzip that is not BGZF (the first member's header is gzip's, without the BC subfield) is V2M_ERR_UNSUPPORTED: the message says
+ *     so and that the file has to be recompressed with bgzip.  Broken framing and corrupt members are V2M_ERR_INVALID_ARGUMENT; the
+ *     message gives the compressed offset of the first bad member and what is wrong with it.
+ * n = 0 is an empty input: no members, no bytes. */
+
+/* Host only, no ctx: walks the BSIZE chain and checks the framing above (not the payloads); members, total decompressed bytes,
+ * whether the last member is the EOF member.  Messages go to v2m_last_error(NULL) on the calling thread. */
+int v2m_bgzf_scan(const void *src, uint64_t n, uint64_t *n_members_out, uint64_t *n_bytes_out, int *ends_with_eof_out);
+
+/* Inflates n host bytes of BGZF into dst (cap bytes of ordinary host memory) on the GPU; *n_out = the decompressed bytes.  Synchronous.
+ * A cap below what v2m_bgzf_scan reports is V2M_ERR_INVALID_ARGUMENT.  The framing is checked on the host first, every payload, CRC-32
+ * and ISIZE on the GPU (bgzf_inflate_kernel: one wave per member, the member's output in LDS).  Works in slices of whole members
+ * through the context's two streams and pinned slots (V2M_RING_SLOT_BYTES caps a slice, as for the row calls): the H2D copy of the
+ * next slice and the D2H copy of the previous one run under the kernel of the current one.  On failure dst holds an unspecified
+ * prefix. */
+int v2m_bgzf_decompress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out);
+
 /* ---- verification helper ------------------------------------------------------------------ */
 
 /* 64-bit position-sensitive checksum of each of n_rows device rows (row i = d_rows + i*row_pitch,
@@ -399,7 +430,8 @@ enum {
 	V2M_KERNEL_TEMPLATE = 4,        /* expand_reference_row_kernel (once per upload) */
 	V2M_KERNEL_UNALIGNED_COUNT = 5, /* count_unaligned_kernel + scan_tile_counts_kernel (pass 1 of unaligned mode) */
 	V2M_KERNEL_BGZF = 6,            /* bgzf_deflate_kernel + bgzf_scan_kernel + bgzf_compact_kernel (V2M_SPLICE_BGZF, v2m_bgzf_compress) */
-	V2M_KERNEL_COUNT = 7
+	V2M_KERNEL_INFLATE = 7,         /* bgzf_inflate_kernel (v2m_bgzf_decompress), one launch per slice */
+	V2M_KERNEL_COUNT = 8
 };
 
 /* When enabled, every launch of the kernels above is bracketed by HIP events on the ctx's

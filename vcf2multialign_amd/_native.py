@@ -24,8 +24,9 @@ V2M_SPLICE_BGZF = 0x2
 
 KERNEL_TRANSPOSE, KERNEL_RESOLVE, KERNEL_SPLICE_ALIGNED, KERNEL_SPLICE_UNALIGNED, KERNEL_TEMPLATE, KERNEL_UNALIGNED_COUNT = range(6)
 KERNEL_BGZF = 6
+KERNEL_INFLATE = 7
 KERNEL_NAMES = ["transpose_bits_kernel", "resolve_effective_edges_kernel", "splice_aligned_kernel", "splice_unaligned_kernel", "expand_reference_row_kernel", "count_unaligned_kernel",
-	"bgzf_deflate_kernel"]
+	"bgzf_deflate_kernel", "bgzf_inflate_kernel"]
 ABI_VERSION = 5
 
 
@@ -86,6 +87,8 @@ SIGNATURES = {
 	"v2m_bgzf_bound": (C.c_uint64, [C.c_uint64]),
 	"v2m_bgzf_frame_stored": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
 	"v2m_bgzf_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
+	"v2m_bgzf_scan": (C.c_int, [C.c_void_p, C.c_uint64, _u64p, _u64p, C.POINTER(C.c_int)]),
+	"v2m_bgzf_decompress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
 	"v2m_checksum_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
 	"v2m_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
 	"v2m_profile_reset": (C.c_int, [C.c_void_p]),

@@ -236,6 +236,15 @@ class Context:
 		self._check(self._lib.v2m_bgzf_compress(self._h, src if src else None, len(src), dst, cap, C.byref(n)))
 		return dst.raw[:n.value]
 
+	def bgzf_decompress(self, data):
+		"""v2m_bgzf_decompress: the bytes of BGZF `data`, inflated on the GPU (framing checked on the host first)."""
+		src = bytes(data)
+		_, n_bytes, _ = bgzf_scan(src)
+		dst = C.create_string_buffer(max(1, n_bytes))
+		n = C.c_uint64(0)
+		self._check(self._lib.v2m_bgzf_decompress(self._h, src if src else None, len(src), dst, n_bytes, C.byref(n)))
+		return dst.raw[:n.value]
+
 	def alloc_output(self, nbytes, candidates=3):
 		"""v2m_alloc_output: device memory for row output, picked among `candidates` allocations by measured write rate."""
 		p = C.c_void_p()
@@ -293,6 +302,18 @@ def bgzf_frame_stored(data):
 	if rc != N.V2M_OK:
 		raise V2MError(rc, "v2m_bgzf_frame_stored failed")
 	return dst.raw[:n.value]
+
+
+def bgzf_scan(data):
+	"""v2m_bgzf_scan (host only): (members, decompressed bytes, ends with the EOF member) of BGZF `data`; V2MError for gzip that is not
+	BGZF (V2M_ERR_UNSUPPORTED) and for broken framing (V2M_ERR_INVALID_ARGUMENT)."""
+	lib = N.load()
+	src = bytes(data)
+	m, n, eof = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+	rc = lib.v2m_bgzf_scan(src if src else None, len(src), C.byref(m), C.byref(n), C.byref(eof))
+	if rc != N.V2M_OK:
+		raise V2MError(rc, lib.v2m_last_error(None).decode(errors="replace"))
+	return m.value, n.value, bool(eof.value)
 
 
 def checksum_rows_host(rows_bytes):

@@ -13,6 +13,16 @@
 //   are applied once.
 // bgzf_scan_kernel: exclusive scan of the member sizes of a slice (one workgroup), row extents + slice total into a small table.
 // bgzf_compact_kernel: copies the members densely to their scanned offsets.
+//
+// bgzf_inflate_kernel: the decoder of BGZF input (v2m_bgzf_decompress), one wave (a workgroup of 64) per member.  The member's whole
+//   output (<= 64 KiB) stays in LDS, so back-references read LDS and never global memory the wave has just written.  Symbol decoding
+//   is serial and wave-uniform: the bit buffer, the block state and every decoded symbol live in scalar registers, the compressed
+//   words come in as two 64-word windows in VGPRs (lane k holds word base + k; v_readlane picks one), so one vector load serves 256
+//   bytes and the next window is in flight while the current one is used.  Canonical codes with a 10-bit (literal/length), 8-bit
+//   (distance) or 7-bit (code-length) root table and a per-length walk for longer codes.  The 64 lanes share the parallel work: a
+//   match copy (lane k writes out[p + k] = out[p - d + (k mod d)], right for overlapping copies without rounds), stored blocks, the
+//   table fills, the CRC-32 (a table CRC per lane over 1 KiB, combined with crc_shift as in the encoder) and the 16-B stores out.
+//   Every index that comes from the input is bounded before use; what zlib's inflate refuses is refused (kInflate* codes below).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -540,6 +550,317 @@ __global__ void __launch_bounds__(256) bgzf_compact_kernel(char const *__restric
 		reinterpret_cast<u32 *>(dst + head)[w] = u32(src[p]) | (u32(src[p + 1]) << 8) | (u32(src[p + 2]) << 16) | (u32(src[p + 3]) << 24);
 	}
 	for (u32 i(head + 4 * n_words + threadIdx.x); i < n; i += 256) dst[i] = src[i];
+}
+
+
+// ---- BGZF input: the decoder --------------------------------------------------------------------
+
+constexpr u32 kInflateThreads = 64;
+constexpr u32 kInflateLitRoot = 10, kInflateDistRoot = 8, kInflateClRoot = 7;
+constexpr u32 kInflateNoSymbol = 0xFFFFFFFFu;
+
+// status of a member (what was wrong with it; the host's names in v2m_hip.hip: inflate_status_text)
+enum : u32 {
+	kInflateOk = 0, kInflateBadBlockType, kInflateStoredLengths, kInflateTooManySymbols, kInflateBadCodeLengthCode, kInflateBadRepeat,
+	kInflateBadLitLenCode, kInflateBadDistCode, kInflateNoEndOfBlock, kInflateBadLitLenSymbol, kInflateBadDistSymbol, kInflateTooFarBack,
+	kInflateOutputTooLong, kInflatePastPayload, kInflateShortOutput, kInflateBadCrc, kInflateBadFraming, kInflateStatusCount
+};
+
+// A canonical Huffman code (RFC 1951 section 3.2.2): per length L, count[L] codes starting at first[L], whose symbols are
+// sorted[offs[L] ...] in symbol order; max = the longest length used.
+struct inflate_code {
+	u32 count[16], first[16], offs[16];
+	u32 max;
+};
+
+struct alignas(16) inflate_lds {
+	unsigned char out[kBgzfSlotBytes + 16];    // the member's output from out[o] on, o = its global address mod 16
+	u32 crc_table[256];
+	u16 lit_table[1u << kInflateLitRoot], dist_table[1u << kInflateDistRoot], cl_table[1u << kInflateClRoot];   // (symbol << 4 | length), 0: none
+	u16 lit_sorted[288], dist_sorted[32], cl_sorted[19];
+	unsigned char lens[320], cl_lens[20];      // HLIT + HDIST code lengths (fixed blocks: 288 + 32); the code-length code's
+	inflate_code lit, dist, cl;
+};
+
+__device__ inline u32 inflate_uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// The code of lens[0, n) into c, sorted and the root table (2^root entries).  false for a code zlib's inflate refuses: an over-subscribed
+// one, an incomplete one (allowed only as a single code of length 1, never for the code-length code), a code-length code without codes.
+// All 64 lanes call; all return the same.
+__device__ inline bool inflate_build(unsigned char const *lens, u32 n, u32 root, bool is_cl, inflate_code &c, u16 *sorted, u16 *table)
+{
+	u32 const lane(threadIdx.x);
+	u64 const below((u64(1) << lane) - 1);
+	int left(1);
+	u32 first(0), offs(0), max(0);
+#pragma unroll 1
+	for (u32 L(1); L <= 15; ++L) {
+		u32 cnt(0);
+#pragma unroll 1
+		for (u32 b(0); b < n; b += 64) {
+			u32 const sym(b + lane);
+			bool const hit(sym < n && u32(lens[sym]) == L);
+			u64 const m(__ballot(hit));
+			if (hit) sorted[offs + cnt + __popcll(m & below)] = u16(sym);   // < the sum of all counts <= n
+			cnt += __popcll(m);
+		}
+		if (0 == lane) { c.count[L] = cnt; c.first[L] = first; c.offs[L] = offs; }
+		left = 2 * left - int(cnt);
+		if (left < -65536) left = -65536;                                       // (stays negative: over-subscribed)
+		if (cnt) max = L;
+		offs += cnt;
+		first = (first + cnt) << 1;
+	}
+	if (0 == lane) c.max = max;
+	bgzf_sync();
+	u32 const size(1u << root);
+#pragma unroll 1
+	for (u32 e(lane); e < size; e += 64) {
+		u32 ent(0);
+#pragma unroll 1
+		for (u32 L(1); L <= root && L <= max; ++L) {
+			u32 const i((__builtin_bitreverse32(e) >> (32 - L)) - c.first[L]);
+			if (i < c.count[L]) { ent = (u32(sorted[c.offs[L] + i]) << 4) | L; break; }
+		}
+		table[e] = u16(ent);
+	}
+	bgzf_sync();
+	if (0 == max) return !is_cl;                                               // no codes: every lookup of this code fails
+	return 0 == left || (left > 0 && !is_cl && 1 == max);
+}
+
+// The symbol whose code starts the 15 bits `bits` (first bit = bit 0), its length in `len`; kInflateNoSymbol for none.
+__device__ inline u32 inflate_decode(u32 bits, u16 const *table, u32 root, inflate_code const &c, u16 const *sorted, u32 &len)
+{
+	u32 const ent(inflate_uni(table[bits & ((1u << root) - 1)]));
+	if (ent) { len = ent & 15; return ent >> 4; }
+	u32 const mx(inflate_uni(c.max));
+	if (mx <= root) return kInflateNoSymbol;
+	u32 const rev(__builtin_bitreverse32(bits & 0x7fffu) >> 17);   // the 15 bits with the first one as the most significant
+#pragma unroll 1
+	for (u32 L(root + 1); L <= mx; ++L) {
+		u32 const i((rev >> (15 - L)) - inflate_uni(c.first[L]));
+		if (i < inflate_uni(c.count[L])) { len = L; return inflate_uni(sorted[inflate_uni(c.offs[L]) + i]); }
+	}
+	return kInflateNoSymbol;
+}
+
+// LSB-first bits of one member's payload.  words = the payload's address rounded down to 4 bytes, lead_bits = 8 * (address mod 4);
+// words [0, n_words) cover the payload and lie inside the member (header before it, footer after it); reads past them give 0.
+// Two 64-word windows in VGPRs: lane k holds words[base + k] and words[base + 64 + k].
+struct inflate_bits {
+	u32 const *words;
+	u32 n_words, lead_bits;
+	u64 bb;
+	u32 nb, next, base;
+	u32 cur, ahead;
+
+	__device__ u32 load(u32 w) const { u32 const i(w + threadIdx.x); return i < n_words ? words[i] : 0u; }
+	__device__ void refill()   // at least 33 bits in bb
+	{
+#pragma unroll 1
+		while (nb <= 32) {
+			if (next - base >= 64) { cur = ahead; base += 64; ahead = load(base + 64); }
+			bb |= u64(inflate_uni(__builtin_amdgcn_readlane(cur, next - base))) << nb;
+			nb += 32;
+			++next;
+		}
+	}
+	__device__ void seek(u32 byte)   // to payload byte `byte`
+	{
+		u32 const a(lead_bits / 8 + byte);
+		next = base = a >> 2;
+		cur = load(base);
+		ahead = load(base + 64);
+		bb = 0;
+		nb = 0;
+		refill();
+		drop(8 * (a & 3));
+	}
+	__device__ u32 peek(u32 n) const { return u32(bb) & ((1u << n) - 1); }   // n <= 31
+	__device__ void drop(u32 n) { bb >>= n; nb -= n; }
+	__device__ u32 get(u32 n) { u32 const v(peek(n)); drop(n); return v; }
+	__device__ u32 used() const { return 32 * next - nb - lead_bits; }        // payload bits consumed
+};
+
+// members: member m of the slice at in + in_offsets[m], in_offsets[m + 1] - in_offsets[m] bytes (framing checked by the host: v2m_bgzf_scan);
+// its output to out + out_offsets[m], out_offsets[m + 1] - out_offsets[m] = ISIZE bytes (out 16-byte aligned); status[m] = kInflate*.
+// A member that fails writes no output.
+__global__ void __launch_bounds__(kInflateThreads) bgzf_inflate_kernel(unsigned char const *__restrict__ in, u64 const *__restrict__ in_offsets,
+	u64 const *__restrict__ out_offsets, unsigned char *__restrict__ out, u32 *__restrict__ status)
+{
+	__shared__ inflate_lds s;
+	V2M_POISON_LDS(s);
+	u32 const lane(threadIdx.x), m(blockIdx.x);
+	u64 const m0(in_offsets[m]), m1(in_offsets[m + 1]), o0(out_offsets[m]), o1(out_offsets[m + 1]);
+	if (m1 - m0 < kBgzfHeaderBytes + kBgzfFooterBytes || m1 - m0 > kBgzfSlotBytes || o1 - o0 > kBgzfSlotBytes) {
+		if (0 == lane) status[m] = kInflateBadFraming;
+		return;
+	}
+	u32 const msize(u32(m1 - m0)), plen(msize - kBgzfHeaderBytes - kBgzfFooterBytes), isize(u32(o1 - o0)), pbits(8 * plen);
+	unsigned char const *const mem(in + m0);
+	unsigned char *const ob(s.out + (o0 & 15));   // ob[0, isize) fits: (o0 & 15) + 65536 <= sizeof(s.out)
+
+	for (u32 i(lane); i < 256; i += 64) {
+		u32 c(i);
+		for (int b(0); b < 8; ++b) c = (c & 1) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+		s.crc_table[i] = c;
+	}
+
+	inflate_bits br;
+	{
+		unsigned char const *const pay(mem + kBgzfHeaderBytes);
+		u32 const lead(u32(reinterpret_cast<uintptr_t>(pay) & 3));
+		br.words = reinterpret_cast<u32 const *>(pay - lead);   // (pointer arithmetic, not integers: the loads stay global ones)
+		br.lead_bits = 8 * lead;
+		br.n_words = (br.lead_bits / 8 + plen + 3) / 4;
+		br.seek(0);
+	}
+	u32 st(kInflateOk), p(0);
+	bool last(false), fixed_ready(false);
+#pragma unroll 1
+	while (kInflateOk == st && !last) {
+		br.refill();
+		u32 const hdr(br.get(3));
+		last = hdr & 1;
+		u32 const type(hdr >> 1);
+		if (3 == type) { st = kInflateBadBlockType; break; }
+		if (0 == type) {   // stored: to a byte boundary, LEN, NLEN, LEN bytes
+			br.drop(br.nb & 7);
+			br.refill();
+			u32 const len(br.get(16)), nlen(br.get(16));
+			if (br.used() > pbits) { st = kInflatePastPayload; break; }
+			if (len != (~nlen & 0xffffu)) { st = kInflateStoredLengths; break; }
+			u32 const pos(br.used() / 8);
+			if (len > plen - pos) { st = kInflatePastPayload; break; }
+			if (len > isize - p) { st = kInflateOutputTooLong; break; }
+			for (u32 k(lane); k < len; k += 64) ob[p + k] = mem[kBgzfHeaderBytes + pos + k];
+			p += len;
+			br.seek(pos + len);
+			continue;
+		}
+		if (1 == type) {   // fixed codes (RFC 1951 section 3.2.6), built once per member
+			if (!fixed_ready) {
+				for (u32 i(lane); i < 320; i += 64) s.lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5;
+				bgzf_sync();
+				(void) inflate_build(s.lens, 288, kInflateLitRoot, false, s.lit, s.lit_sorted, s.lit_table);
+				(void) inflate_build(s.lens + 288, 32, kInflateDistRoot, false, s.dist, s.dist_sorted, s.dist_table);
+				fixed_ready = true;
+			}
+		} else {           // dynamic codes (section 3.2.7)
+			fixed_ready = false;
+			br.refill();
+			u32 const hlit(br.get(5) + 257), hdist(br.get(5) + 1), hclen(br.get(4) + 4);
+			if (hlit > 286 || hdist > 30) { st = kInflateTooManySymbols; break; }
+			if (lane < 20) s.cl_lens[lane] = 0;
+			bgzf_sync();
+#pragma unroll 1
+			for (u32 i(0); i < hclen; ++i) {
+				br.refill();
+				u32 const v(br.get(3));
+				if (0 == lane) s.cl_lens[kBgzfClOrder[i]] = v;
+			}
+			bgzf_sync();
+			if (!inflate_build(s.cl_lens, 19, kInflateClRoot, true, s.cl, s.cl_sorted, s.cl_table)) { st = kInflateBadCodeLengthCode; break; }
+			u32 const total(hlit + hdist);   // <= 316
+			u32 n(0);
+#pragma unroll 1
+			while (n < total) {
+				br.refill();
+				u32 len(0);
+				u32 const sym(inflate_decode(br.peek(15), s.cl_table, kInflateClRoot, s.cl, s.cl_sorted, len));
+				if (kInflateNoSymbol == sym) { st = kInflateBadCodeLengthCode; break; }
+				br.drop(len);
+				if (sym < 16) {
+					if (0 == lane) s.lens[n] = sym;
+					++n;
+					continue;
+				}
+				u32 rep, val(0);
+				if (16 == sym) {
+					if (0 == n) { st = kInflateBadRepeat; break; }
+					val = inflate_uni(s.lens[n - 1]);
+					rep = 3 + br.get(2);
+				} else if (17 == sym) rep = 3 + br.get(3);
+				else rep = 11 + br.get(7);
+				if (rep > total - n) { st = kInflateBadRepeat; break; }
+				for (u32 k(lane); k < rep; k += 64) s.lens[n + k] = val;
+				n += rep;
+			}
+			if (kInflateOk != st) break;
+			if (br.used() > pbits) { st = kInflatePastPayload; break; }
+			bgzf_sync();
+			if (0 == inflate_uni(s.lens[256])) { st = kInflateNoEndOfBlock; break; }
+			if (!inflate_build(s.lens, hlit, kInflateLitRoot, false, s.lit, s.lit_sorted, s.lit_table)) { st = kInflateBadLitLenCode; break; }
+			if (!inflate_build(s.lens + hlit, hdist, kInflateDistRoot, false, s.dist, s.dist_sorted, s.dist_table)) { st = kInflateBadDistCode; break; }
+		}
+#pragma unroll 1
+		for (;;) {   // the block's symbols
+			br.refill();
+			u32 len(0);
+			u32 const sym(inflate_decode(br.peek(15), s.lit_table, kInflateLitRoot, s.lit, s.lit_sorted, len));
+			if (kInflateNoSymbol == sym || sym >= 286) { st = kInflateBadLitLenSymbol; break; }
+			br.drop(len);
+			if (sym < 256) {
+				if (p >= isize) { st = kInflateOutputTooLong; break; }
+				if (0 == lane) ob[p] = static_cast<unsigned char>(sym);
+				++p;
+			} else if (256 == sym) {
+				break;
+			} else {
+				u32 const li(sym - 257);   // 0..28
+				u32 const leb(li < 8 || 28 == li ? 0 : (li >> 2) - 1);
+				u32 const mlen((li < 8 ? 3 + li : 28 == li ? 258 : ((4 + (li & 3)) << leb) + 3) + br.get(leb));
+				br.refill();
+				u32 dl(0);
+				u32 const dsym(inflate_decode(br.peek(15), s.dist_table, kInflateDistRoot, s.dist, s.dist_sorted, dl));
+				if (kInflateNoSymbol == dsym || dsym >= 30) { st = kInflateBadDistSymbol; break; }
+				br.drop(dl);
+				u32 const deb(dsym < 4 ? 0 : (dsym >> 1) - 1);
+				u32 const dist((dsym < 4 ? 1 + dsym : ((2 + (dsym & 1)) << deb) + 1) + br.get(deb));
+				if (br.used() > pbits) { st = kInflatePastPayload; break; }
+				if (dist > p) { st = kInflateTooFarBack; break; }
+				if (mlen > isize - p) { st = kInflateOutputTooLong; break; }
+				if (dist >= 64) {   // a round's sources lie before p or in earlier rounds
+#pragma unroll 1
+					for (u32 k(lane); k < mlen; k += 64) ob[p + k] = ob[p - dist + k];
+				} else {            // out[p + k] = out[p - dist + k mod dist]: every source lies before p
+					u32 r(lane % dist);
+					u32 const step(64 % dist);
+#pragma unroll 1
+					for (u32 k(lane); k < mlen; k += 64) {
+						ob[p + k] = ob[p - dist + r];
+						r += step;
+						if (r >= dist) r -= dist;
+					}
+				}
+				p += mlen;
+			}
+			if (br.used() > pbits) { st = kInflatePastPayload; break; }
+		}
+		if (kInflateOk == st && br.used() > pbits) st = kInflatePastPayload;
+	}
+	if (kInflateOk == st && p != isize) st = kInflateShortOutput;
+	bgzf_sync();
+	if (kInflateOk == st) {   // CRC-32 of ob[0, isize): a table CRC per lane over its 1 KiB, moved to the end and combined as in the encoder
+		u32 const s0(min(lane * 1024u, isize)), s1(min(s0 + 1024u, isize));
+		u32 crc(0);
+#pragma unroll 1
+		for (u32 i(s0); i < s1; ++i) crc = s.crc_table[(crc ^ ob[i]) & 255] ^ (crc >> 8);
+		u32 x(s0 < s1 ? crc_shift(crc, isize - s1) : 0);
+		for (int d(32); d; d >>= 1) x ^= __shfl_xor(x, d);
+		unsigned char const *const f(mem + msize - kBgzfFooterBytes);
+		u32 const want(u32(f[0]) | (u32(f[1]) << 8) | (u32(f[2]) << 16) | (u32(f[3]) << 24));
+		if (inflate_uni(~(crc_shift(0xFFFFFFFFu, isize) ^ x)) != want) st = kInflateBadCrc;
+	}
+	if (0 == lane) status[m] = st;
+	if (kInflateOk != st) return;
+	unsigned char *const g(out + o0);
+	u32 const head(min(isize, (16u - u32(o0 & 15)) & 15u));   // ob + head and g + head are both 16-byte aligned
+	if (lane < head) g[lane] = ob[lane];
+	u32 const n16((isize - head) / 16);
+	for (u32 j(lane); j < n16; j += 64) reinterpret_cast<vec4u *>(g + head)[j] = reinterpret_cast<vec4u const *>(ob + head)[j];
+	for (u32 i(head + 16 * n16 + lane); i < isize; i += 64) g[i] = ob[i];
 }
 
 } // namespace v2m

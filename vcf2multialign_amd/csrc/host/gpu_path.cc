@@ -1,5 +1,9 @@
 #include "gpu_path.hh"
 
+#include <sys/stat.h>
+
+#include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <exception>
 #include <stdexcept>
@@ -20,6 +24,41 @@ gpu_context::~gpu_context() { if (m_owned) v2m_ctx_destroy(m_ctx); }
 void gpu_context::check(int rc) const
 {
 	if (V2M_OK != rc) throw gpu_error(rc, v2m_last_error(m_ctx));
+}
+
+
+input_file::input_file(char const *path) : m_path(path)
+{
+	unsigned char magic[2]{};
+	{
+		// only a regular file is probed: reading two bytes of a pipe (-r <(samtools faidx ...)) would take them from the path reader
+		struct stat st;
+		if (0 != ::stat(path, &st) || !S_ISREG(st.st_mode)) return;
+		std::FILE *const f(std::fopen(path, "rb"));
+		if (!f) return;                                                // the path readers report a missing file as before
+		bool const got(2 == std::fread(magic, 1, 2, f));
+		std::fclose(f);
+		if (!got || 0x1f != magic[0] || 0x8b != magic[1]) return;      // plain text: no VCF or FASTA starts with these bytes
+	}
+	m_bgzf = true;
+	m_file.reset(new mapped_file(path));
+	int eof(0);
+	if (V2M_OK != v2m_bgzf_scan(m_file->data, m_file->size, &m_members, &m_bytes, &eof))
+		throw std::runtime_error(m_path + ": " + v2m_last_error(nullptr));
+	m_eof = 0 != eof;
+}
+
+std::string_view input_file::inflate(gpu_context &gpu)
+{
+	if (!m_bgzf) throw std::logic_error(m_path + " is not BGZF");
+	auto const t0(std::chrono::steady_clock::now());
+	m_text.reset(new char[std::max<u64>(1, m_bytes)]);
+	u64 n(0);
+	int const rc(v2m_bgzf_decompress(gpu.get(), m_file->data, m_file->size, m_text.get(), m_bytes, &n));
+	if (V2M_OK != rc) throw gpu_error(rc, m_path + ": " + v2m_last_error(gpu.get()));
+	m_file.reset();                                                    // the compressed bytes are not needed any more
+	m_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+	return std::string_view(m_text.get(), n);
 }
 
 

@@ -1,8 +1,10 @@
 // gpu_path.hh -- the host's view of the GPU hot path: thin C++ wrappers over the C ABI (include/v2m_hip.h).
 #pragma once
 
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 
 #include "../../../include/v2m_hip.h"
 #include "founder.hh"
@@ -29,6 +31,30 @@ public:
 private:
 	v2m_ctx *m_ctx{};
 	bool m_owned{true};
+};
+
+// An input file of the driver (-a, -r), recognised by content: a regular file that starts with the gzip magic 1f 8b is BGZF, mapped and
+// its framing checked at once (v2m_bgzf_scan, no device: std::runtime_error naming the file for gzip that is not BGZF and for broken
+// framing); anything else, pipes included (nothing is read from them here), is plain text, left to the path readers (readers.hh)
+// untouched.  inflate() decompresses a BGZF file on the
+// GPU (v2m_bgzf_decompress) into host memory as large as the text; it replaces vcf::mmap_input (variant_graph.cc:133-134) and
+// lb::read_single_fasta_sequence's file (vcf2multialign/main.cc:381) for compressed input.
+class input_file {
+public:
+	explicit input_file(char const *path);
+	bool bgzf() const { return m_bgzf; }
+	u64 members() const { return m_members; }
+	u64 bytes() const { return m_bytes; }
+	bool ends_with_eof() const { return m_eof; }
+	std::string_view inflate(gpu_context &gpu);   // BGZF only; throws gpu_error (a corrupt member: V2M_ERR_INVALID_ARGUMENT)
+	double inflate_seconds() const { return m_seconds; }
+private:
+	std::string m_path;
+	bool m_bgzf{}, m_eof{};
+	u64 m_members{}, m_bytes{};
+	std::unique_ptr<mapped_file> m_file;
+	std::unique_ptr<char[]> m_text;               // not value-initialised: its pages are first touched by the copy out of the pinned slots
+	double m_seconds{};
 };
 
 // transpose_matrix (include/vcf2multialign/transpose_matrix.hh:14) on the GPU.

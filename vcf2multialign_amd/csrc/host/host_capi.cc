@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 
@@ -48,20 +49,25 @@ struct recording_delegate final : vh::build_graph_delegate {
 
 bool g_stop_at_mismatch(false);
 
-} // namespace
-
-extern "C" {
-
-void *v2mh_build_variant_graph(char const *fasta, char const *seq_id, char const *vcf, char const *chr, char const *exclude_sample, int exclude_copy, unsigned threads, char *err, size_t errlen)
+// The host graph of the two files.  gpu == NULL: both through the path readers.  Otherwise either file may be BGZF (gpu_path.hh:
+// input_file), inflated on that context; plain files still go through the path readers.
+host_graph *build_host_graph(vh::gpu_context *gpu, char const *fasta, char const *seq_id, char const *vcf, char const *chr, char const *exclude_sample,
+	int exclude_copy, unsigned threads, char *err, size_t errlen)
 {
 	auto *hg(new host_graph);
 	try {
-		if (!vh::read_single_fasta_sequence(fasta, hg->ref, seq_id)) throw std::runtime_error("unable to read the reference sequence");
+		{
+			std::unique_ptr<vh::input_file> in(gpu ? new vh::input_file(fasta) : nullptr);
+			bool const ok(in && in->bgzf() ? vh::read_single_fasta_sequence(in->inflate(*gpu), hg->ref, seq_id) : vh::read_single_fasta_sequence(fasta, hg->ref, seq_id));
+			if (!ok) throw std::runtime_error("unable to read the reference sequence");
+		}
 		recording_delegate d;
 		d.hg = hg;
 		if (exclude_sample) { d.excluded_sample = exclude_sample; d.excluded_copy = exclude_copy; }
 		d.stop_at_mismatch = g_stop_at_mismatch;
-		vh::build_variant_graph(hg->ref, vcf, chr, hg->graph, hg->stats, d, threads);
+		std::unique_ptr<vh::input_file> in(gpu ? new vh::input_file(vcf) : nullptr);
+		if (in && in->bgzf()) vh::build_variant_graph(hg->ref, in->inflate(*gpu), chr, hg->graph, hg->stats, d, threads);
+		else vh::build_variant_graph(hg->ref, vcf, chr, hg->graph, hg->stats, d, threads);
 		for (auto const &s : hg->graph.sample_names) { hg->sample_blob += s; hg->sample_blob.push_back('\0'); }
 		return hg;
 	} catch (std::exception const &e) {
@@ -69,6 +75,28 @@ void *v2mh_build_variant_graph(char const *fasta, char const *seq_id, char const
 		delete hg;
 		return nullptr;
 	}
+}
+
+} // namespace
+
+extern "C" {
+
+void *v2mh_build_variant_graph(char const *fasta, char const *seq_id, char const *vcf, char const *chr, char const *exclude_sample, int exclude_copy, unsigned threads, char *err, size_t errlen)
+{
+	return build_host_graph(nullptr, fasta, seq_id, vcf, chr, exclude_sample, exclude_copy, threads, err, errlen);
+}
+
+// v2mh_build_variant_graph with BGZF input allowed for either file (gpu_path.hh: input_file), inflated on the GPU of `ctx` (a v2m_ctx the
+// caller owns); plain files are read exactly as v2mh_build_variant_graph reads them.
+void *v2mh_build_variant_graph_gpu(void *ctx, char const *fasta, char const *seq_id, char const *vcf, char const *chr, char const *exclude_sample, int exclude_copy,
+	unsigned threads, char *err, size_t errlen)
+{
+	if (!ctx) {
+		if (err && errlen) { std::strncpy(err, "v2mh_build_variant_graph_gpu needs a GPU context", errlen - 1); err[errlen - 1] = 0; }
+		return nullptr;
+	}
+	vh::gpu_context gpu(static_cast<v2m_ctx *>(ctx), vh::gpu_context::borrowed{});
+	return build_host_graph(&gpu, fasta, seq_id, vcf, chr, exclude_sample, exclude_copy, threads, err, errlen);
 }
 
 // A host graph from flat arrays (e.g. a synthetic dataset whose genotype matrix was generated on the GPU):

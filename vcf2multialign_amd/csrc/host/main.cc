@@ -56,9 +56,9 @@ void usage()
 	std::cerr <<
 		"Usage: vcf2multialign --haplotypes --input-reference=filename.fa --input-variants=filename.vcf --chromosome=id [<options>]\n"
 		"  -H, --haplotypes                   Produce predicted haplotype sequences\n"
-		"  -r, --input-reference=filename     Reference FASTA file path\n"
+		"  -r, --input-reference=filename     Reference FASTA file path (plain or BGZF)\n"
 		"  -e, --reference-sequence=id        Reference sequence identifier in the input FASTA\n"
-		"  -a, --input-variants=filename      Variant call file path\n"
+		"  -a, --input-variants=filename      Variant call file path (plain or BGZF)\n"
 		"  -c, --chromosome=id                Chromosome identifier\n"
 		"  -s, --output-sequences-a2m=file    Output reference-guided multiple alignment as A2M\n"
 		"      --output-sequences-separate    Output one sequence per file\n"
@@ -78,6 +78,8 @@ void usage()
 		"      --region=START-END             Output only the alignment columns of reference positions START..END (1-based,\n"
 		"                                     inclusive, as in samtools/bcftools), with the insertions anchored there\n"
 		"      --verbose\n"
+		"  BGZF input (bgzip, bcftools -Oz, a .fa.gz for samtools faidx) is recognised by its first bytes and inflated on the first\n"
+		"  GPU; the decompressed text is held in host memory (as large as the text).  Plain gzip has to be recompressed with bgzip.\n"
 		"  -F, --founder-sequences=count      Produce founder sequences instead of haplotypes\n"
 		"  -d, --minimum-distance=distance    Minimum node distance (MSA co-ordinates) between cut positions\n"
 		"      --keep-ref-edges               Take the reference edges into account when matching\n"
@@ -273,6 +275,22 @@ int main(int argc, char **argv)
 	}
 
 	try {
+		// BGZF inputs are recognised and their framing checked before any device is needed: gzip that is not BGZF and broken
+		// framing end the run here, with or without a GPU.
+		std::unique_ptr<vh::input_file> ref_input(new vh::input_file(opt.input_reference)), variants_input;
+		if (opt.input_variants) variants_input.reset(new vh::input_file(opt.input_variants));
+		for (auto const *in : {ref_input.get(), variants_input.get()}) {
+			if (!in || !in->bgzf()) continue;
+			char const *const path(in == ref_input.get() ? opt.input_reference : opt.input_variants);
+			if (!in->ends_with_eof())
+				std::cerr << "WARNING: " << path << " does not end with the BGZF EOF member; the file may be truncated.\n";
+		}
+		auto const report_inflate([&](vh::input_file const &in, char const *path) {
+			if (opt.verbose)
+				std::cerr << "BGZF input " << path << ": " << in.members() << " members, " << in.bytes() << " bytes, inflated on the GPU in "
+					<< in.inflate_seconds() << " s.\n";
+		});
+
 		// The GPU contexts come up on a second thread (HIP runtime start-up and stream creation: 0.2 s) while this one reads the
 		// reference and the graph; without a usable MI355X the run still fails, loudly, at the first use below.
 		auto contexts_coming(std::async(std::launch::async, [&opt] {
@@ -288,7 +306,14 @@ int main(int argc, char **argv)
 
 		vh::sequence_type ref_seq;
 		std::cerr << "Reading the reference sequence..." << std::flush;
-		if (!vh::read_single_fasta_sequence(opt.input_reference, ref_seq, opt.reference_sequence)) {
+		bool ref_read(false);
+		if (ref_input->bgzf()) {
+			std::string_view const text(ref_input->inflate(first_gpu()));
+			report_inflate(*ref_input, opt.input_reference);
+			ref_read = vh::read_single_fasta_sequence(text, ref_seq, opt.reference_sequence);
+		} else ref_read = vh::read_single_fasta_sequence(opt.input_reference, ref_seq, opt.reference_sequence);
+		ref_input.reset();
+		if (!ref_read) {
 			std::cerr << " ERROR: Unable to read the reference sequence.\n";
 			return EXIT_FAILURE;
 		}
@@ -301,7 +326,7 @@ int main(int argc, char **argv)
 		// HIP's start-up takes 0.2 s whether it ends in a context or in an error, so after a reference of any size (100 Mb: 0.07 s
 		// + 30 ms of grace here; a genome: seconds) the outcome is usually in; when it is not, waiting for it would only take the
 		// overlap with the graph's loading away (0.1 s at config 3), and the first use reports the failure all the same.
-		if (std::future_status::ready == contexts_coming.wait_for(std::chrono::milliseconds(30))) (void) first_gpu();
+		if (contexts.empty() && std::future_status::ready == contexts_coming.wait_for(std::chrono::milliseconds(30))) (void) first_gpu();   // (a BGZF reference took them already)
 
 		vh::variant_graph graph;
 		if (opt.input_graph) {                                  // main.cc:392-401
@@ -323,7 +348,13 @@ int main(int argc, char **argv)
 			}
 			std::cerr << "Building the variant graph...\n";
 			vh::build_graph_statistics stats;
-			vh::build_variant_graph(ref_seq, opt.input_variants, opt.chromosome, graph, stats, delegate, 0, 64);   // the reference's padding (variant_graph.cc:277,449)
+			if (variants_input->bgzf()) {
+				std::string_view const text(variants_input->inflate(first_gpu()));
+				report_inflate(*variants_input, opt.input_variants);
+				vh::build_variant_graph(ref_seq, text, opt.chromosome, graph, stats, delegate, 0, 64);
+			} else
+				vh::build_variant_graph(ref_seq, opt.input_variants, opt.chromosome, graph, stats, delegate, 0, 64);   // the reference's padding (variant_graph.cc:277,449)
+			variants_input.reset();                             // (the decompressed text)
 			// variant_graph.cc:453 (the transpose) happens on the GPU(s) below; the transposed matrix only comes back to the host
 			// when something on the host reads it: the founder search and the graph checkpoint.
 			if (opt.founder_mode || opt.output_graph) vh::transpose_paths(first_gpu(), graph);

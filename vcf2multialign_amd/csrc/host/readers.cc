@@ -45,35 +45,55 @@ bool read_single_fasta_sequence(char const *path, sequence_type &seq, char const
 	return found;
 }
 
+// Lines as std::getline splits them: at '\n', the last one without it, no empty line after a final '\n'.
+bool read_single_fasta_sequence(std::string_view text, sequence_type &seq, char const *seq_id)
+{
+	seq.clear();
+	bool wanted(false), found(false);
+	std::size_t pos(0);
+	while (pos < text.size()) {
+		std::size_t eol(text.find('\n', pos));
+		if (std::string_view::npos == eol) eol = text.size();
+		std::string_view line(text.substr(pos, eol - pos));
+		pos = eol + 1;
+		if (!line.empty() && '\r' == line.back()) line.remove_suffix(1);
+		if (!line.empty() && '>' == line.front()) {
+			if (found) break;
+			auto const stop(line.find_first_of(" \t", 1));
+			std::string_view const id(line.substr(1, std::string_view::npos == stop ? std::string_view::npos : stop - 1));
+			wanted = !seq_id || id == seq_id;
+			found = wanted;
+			continue;
+		}
+		if (wanted) seq.insert(seq.end(), line.begin(), line.end());
+	}
+	return found;
+}
+
+
+mapped_file::mapped_file(char const *path)
+{
+	fd = ::open(path, O_RDONLY);
+	if (fd < 0) throw std::runtime_error(std::string("unable to open ") + path);
+	struct stat st;
+	if (0 != ::fstat(fd, &st)) { ::close(fd); throw std::runtime_error(std::string("unable to stat ") + path); }
+	size = std::size_t(st.st_size);
+	if (size) {
+		void *p(::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0));
+		if (MAP_FAILED == p) { ::close(fd); throw std::runtime_error(std::string("unable to map ") + path); }
+		data = static_cast<char const *>(p);
+		::madvise(p, size, MADV_SEQUENTIAL);
+	}
+}
+
+mapped_file::~mapped_file()
+{
+	if (data) ::munmap(const_cast<char *>(data), size);
+	if (fd >= 0) ::close(fd);
+}
+
 
 namespace {
-
-// Read-only mapping of a whole file (the reference maps the VCF too: vcf::mmap_input, variant_graph.cc:133-134).
-struct mapped_file {
-	char const *data{};
-	std::size_t size{};
-	int fd{-1};
-
-	explicit mapped_file(char const *path)
-	{
-		fd = ::open(path, O_RDONLY);
-		if (fd < 0) throw std::runtime_error(std::string("unable to open ") + path);
-		struct stat st;
-		if (0 != ::fstat(fd, &st)) { ::close(fd); throw std::runtime_error(std::string("unable to stat ") + path); }
-		size = std::size_t(st.st_size);
-		if (size) {
-			void *p(::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0));
-			if (MAP_FAILED == p) { ::close(fd); throw std::runtime_error(std::string("unable to map ") + path); }
-			data = static_cast<char const *>(p);
-			::madvise(p, size, MADV_SEQUENTIAL);
-		}
-	}
-	~mapped_file()
-	{
-		if (data) ::munmap(const_cast<char *>(data), size);
-		if (fd >= 0) ::close(fd);
-	}
-};
 
 // Splits [begin, end) at `delim` without allocating: call next() until it returns false.
 struct field_cursor {
@@ -297,7 +317,14 @@ void build_variant_graph(
 	variant_graph &graph, build_graph_statistics &stats, build_graph_delegate &delegate, unsigned threads, u64 path_alignment)
 {
 	mapped_file const file(variants_path);
-	std::string_view const text(file.data, file.size);
+	build_variant_graph(ref_seq, std::string_view(file.data, file.size), chr_id, graph, stats, delegate, threads, path_alignment);
+}
+
+
+void build_variant_graph(
+	sequence_type const &ref_seq, std::string_view text, char const *chr_id,
+	variant_graph &graph, build_graph_statistics &stats, build_graph_delegate &delegate, unsigned threads, u64 path_alignment)
+{
 	std::string_view const ref_sv(ref_seq.data(), ref_seq.size());
 
 	graph = variant_graph{};

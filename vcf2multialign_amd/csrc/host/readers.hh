@@ -5,6 +5,7 @@
 // absent submodule, so only the behaviour visible at those call sites is reproduced.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <string_view>
@@ -18,6 +19,20 @@ typedef std::vector<char> sequence_type;   // variant_graph.hh:33
 
 // First sequence of the file, or the one whose identifier (text after '>' up to the first blank) equals seq_id.
 bool read_single_fasta_sequence(char const *path, sequence_type &seq, char const *seq_id = nullptr);
+// The same over FASTA text already in memory (a decompressed .fa.gz: gpu_path.hh, input_file).
+bool read_single_fasta_sequence(std::string_view text, sequence_type &seq, char const *seq_id = nullptr);
+
+// Read-only mapping of a whole file (the reference maps the VCF too: vcf::mmap_input, variant_graph.cc:133-134).  Throws
+// std::runtime_error when the file cannot be opened, stat'ed or mapped.
+struct mapped_file {
+	char const *data{};
+	std::size_t size{};
+	int fd{-1};
+	explicit mapped_file(char const *path);
+	~mapped_file();
+	mapped_file(mapped_file const &) = delete;
+	mapped_file &operator=(mapped_file const &) = delete;
+};
 
 // variant_graph.hh:138-158
 struct build_graph_delegate {
@@ -45,6 +60,10 @@ struct build_graph_statistics {
 // of a sequential pass.  threads == 0: one per hardware thread, at most 16.  path_alignment: see graph_builder.
 void build_variant_graph(
 	sequence_type const &ref_seq, char const *variants_path, char const *chr_id,
+	variant_graph &graph, build_graph_statistics &stats, build_graph_delegate &delegate, unsigned threads = 0, u64 path_alignment = 64);
+// The same over VCF text already in memory (a decompressed .vcf.gz: gpu_path.hh, input_file); the path version maps the file and calls this.
+void build_variant_graph(
+	sequence_type const &ref_seq, std::string_view variants_text, char const *chr_id,
 	variant_graph &graph, build_graph_statistics &stats, build_graph_delegate &delegate, unsigned threads = 0, u64 path_alignment = 64);
 
 } // namespace v2m::host

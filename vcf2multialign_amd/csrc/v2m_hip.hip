@@ -241,6 +241,10 @@ struct v2m_ctx {
 	scratch_buf d_bgzf_slots, d_bgzf_sizes, d_bgzf_offsets, d_bgzf_table, d_bgzf_dense[2], d_bgzf_in;
 	pinned_buf h_bgzf_table[2];
 	hipEvent_t ev_compute[2]{};
+	// BGZF input (v2m_bgzf_decompress): a slice's members and their member / output offsets, its output and the members' statuses, two
+	// of each (slice s + 1 crosses the link while slice s is inflated)
+	scratch_buf d_inflate_in[2], d_inflate_out[2], d_inflate_status[2];
+	hipEvent_t ev_inflate_in[2]{};
 };
 
 
@@ -1384,6 +1388,99 @@ void pbwt_dispatch_per_thread(u64 copies, t_launch &&launch)
 } // namespace
 
 
+// ---- BGZF input (bgzf_kernels.hpp: bgzf_inflate_kernel) ---------------------------------------------
+namespace {
+
+char const *inflate_status_text(u32 st)
+{
+	static char const *const text[v2m::kInflateStatusCount] = {"ok", "invalid block type", "stored block lengths do not match (LEN != ~NLEN)",
+		"too many length or distance symbols (HLIT > 286 or HDIST > 30)", "invalid code-length code (over-subscribed, incomplete or undecodable)",
+		"invalid code-length repeat (no previous length, or past HLIT + HDIST)", "invalid literal/length code (over-subscribed or incomplete)",
+		"invalid distance code (over-subscribed or incomplete)", "no end-of-block code", "invalid literal/length symbol",
+		"invalid distance symbol", "distance too far back", "output longer than ISIZE", "the deflate stream reads past the payload",
+		"output shorter than ISIZE", "CRC-32 mismatch", "bad framing"};
+	return st < v2m::kInflateStatusCount ? text[st] : "unknown status";
+}
+
+unsigned char const kBgzfEofMember[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// The members of n bytes of BGZF (the framing of include/v2m_hip.h): offsets[k] = member k's first byte (and offsets[members] = n),
+// isize[k] = its ISIZE.  On failure: a V2M_ERR_* code with the message in `what`.
+struct bgzf_members {
+	std::vector<u64> offsets;
+	std::vector<u32> isize;
+	u64 bytes{};
+	bool ends_with_eof{};
+};
+
+int walk_error(std::string &what, int code, char const *fmt, ...)
+{
+	char buf[320];
+	va_list ap;
+	va_start(ap, fmt);
+	std::vsnprintf(buf, sizeof(buf), fmt, ap);
+	va_end(ap);
+	what = buf;
+	return code;
+}
+
+int bgzf_walk(unsigned char const *src, u64 n, bgzf_members &out, std::string &what)
+{
+	auto const le16([&](u64 i) { return u32(src[i]) | (u32(src[i + 1]) << 8); });
+	auto const le32([&](u64 i) { return le16(i) | (le16(i + 2) << 16); });
+	u32 const head_bytes(v2m::kBgzfHeaderBytes), foot_bytes(v2m::kBgzfFooterBytes);
+	out = bgzf_members{};
+	u64 pos(0);
+	while (pos < n) {
+		unsigned long long const at(pos), left(n - pos);
+		if (left < 2 || 0x1f != src[pos] || 0x8b != src[pos + 1])
+			return walk_error(what, V2M_ERR_INVALID_ARGUMENT, "BGZF member at compressed offset %llu: no gzip magic (1f 8b)", at);
+		bool const bgzf_header(left >= 16 && 8 == src[pos + 2] && 4 == src[pos + 3] && 6 == le16(pos + 10) && 'B' == src[pos + 12] && 'C' == src[pos + 13]
+			&& 2 == le16(pos + 14));
+		if (!bgzf_header) {
+			if (0 == pos && left >= 4 && 8 == src[2] && 0 == (src[3] & 0xe0))   // a gzip header, deflate, valid flags: gzip, but not BGZF
+				return walk_error(what, V2M_ERR_UNSUPPORTED, "the input is gzip but not BGZF (its first member has no BC extra subfield); recompress it with bgzip");
+			if (left < 16) return walk_error(what, V2M_ERR_INVALID_ARGUMENT, "BGZF member at compressed offset %llu: truncated header (%llu bytes left)", at, left);
+			return walk_error(what, V2M_ERR_INVALID_ARGUMENT, "BGZF member at compressed offset %llu: not a BGZF header (1f 8b 08 04, XLEN 6, one BC subfield of SLEN 2)", at);
+		}
+		if (left < head_bytes) return walk_error(what, V2M_ERR_INVALID_ARGUMENT, "BGZF member at compressed offset %llu: truncated header (%llu bytes left)", at, left);
+		unsigned long long const size(le16(pos + 16) + 1ull);
+		if (size < head_bytes + foot_bytes)
+			return walk_error(what, V2M_ERR_INVALID_ARGUMENT, "BGZF member at compressed offset %llu: BSIZE %llu is shorter than a header and footer", at, size - 1);
+		if (size > left)
+			return walk_error(what, V2M_ERR_INVALID_ARGUMENT, "BGZF member at compressed offset %llu: BSIZE says %llu bytes, the input ends %llu bytes later (truncated)", at, size, left);
+		u32 const isize(le32(pos + size - 4));
+		if (isize > v2m::kBgzfSlotBytes)
+			return walk_error(what, V2M_ERR_INVALID_ARGUMENT, "BGZF member at compressed offset %llu: ISIZE %llu is above 65536", at, (unsigned long long) isize);
+		out.offsets.push_back(pos);
+		out.isize.push_back(isize);
+		out.bytes += isize;
+		out.ends_with_eof = sizeof(kBgzfEofMember) == size && 0 == std::memcmp(src + pos, kBgzfEofMember, size);
+		pos += size;
+	}
+	out.offsets.push_back(n);
+	return V2M_OK;
+}
+
+// memcpy on up to 8 threads for large copies (pageable <-> pinned).
+void host_copy(void *dst, void const *src, u64 n)
+{
+	u64 const piece(u64(8) << 20);
+	unsigned const k(unsigned(std::min<u64>(8, n / piece)));
+	if (k < 2) { std::memcpy(dst, src, n); return; }
+	u64 const share((n / k + 4095) & ~u64(4095));
+	std::vector<std::thread> pool;
+	for (unsigned t(1); t < k; ++t) {
+		u64 const a(std::min(n, t * share)), b(std::min(n, a + share));
+		if (a < b) pool.emplace_back([=] { std::memcpy(static_cast<char *>(dst) + a, static_cast<char const *>(src) + a, b - a); });
+	}
+	std::memcpy(dst, src, std::min(n, share));
+	for (auto &th : pool) th.join();
+}
+
+} // namespace
+
+
 extern "C" {
 
 uint32_t v2m_abi_version(void) { return V2M_ABI_VERSION; }
@@ -1426,6 +1523,7 @@ int v2m_ctx_create(int device_id, v2m_ctx **ctx_out)
 	for (int i(0); i < 2 && hipSuccess == st; ++i) {
 		st = hipEventCreateWithFlags(&ctx->ev_compute[i], hipEventDisableTiming);
 		if (hipSuccess == st) st = hipEventCreateWithFlags(&ctx->ev_row_stage[i], hipEventDisableTiming);
+		if (hipSuccess == st) st = hipEventCreateWithFlags(&ctx->ev_inflate_in[i], hipEventDisableTiming);
 	}
 	if (hipSuccess != st) {
 		std::string const what(hipGetErrorString(st));
@@ -1452,6 +1550,7 @@ void v2m_ctx_destroy(v2m_ctx *ctx)
 	for (int i(0); i < 2; ++i) {
 		if (ctx->ev_compute[i]) (void) hipEventDestroy(ctx->ev_compute[i]);
 		if (ctx->ev_row_stage[i]) (void) hipEventDestroy(ctx->ev_row_stage[i]);
+		if (ctx->ev_inflate_in[i]) (void) hipEventDestroy(ctx->ev_inflate_in[i]);
 	}
 	for (auto &slot : ctx->host_slots) if (slot && slot->copied) (void) hipEventDestroy(slot->copied);
 	(void) hipStreamDestroy(ctx->stream);
@@ -2406,6 +2505,186 @@ int v2m_bgzf_compress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, uint
 		done += chunk;
 	}
 	*n_out = written;
+	return V2M_OK;
+}
+
+int v2m_bgzf_scan(const void *src, uint64_t n, uint64_t *n_members_out, uint64_t *n_bytes_out, int *ends_with_eof_out)
+{
+	if ((n && !src) || !n_members_out || !n_bytes_out || !ends_with_eof_out) return fail(nullptr, V2M_ERR_INVALID_ARGUMENT, "src or an output pointer is NULL");
+	*n_members_out = 0;
+	*n_bytes_out = 0;
+	*ends_with_eof_out = 0;
+	bgzf_members mem;
+	std::string what;
+	if (int const rc = bgzf_walk(static_cast<unsigned char const *>(src), n, mem, what)) return fail(nullptr, rc, "%s", what.c_str());
+	*n_members_out = mem.isize.size();
+	*n_bytes_out = mem.bytes;
+	*ends_with_eof_out = mem.ends_with_eof ? 1 : 0;
+	return V2M_OK;
+}
+
+// Slices of whole members (at most `slot` compressed and `slot` decompressed bytes each) go round two device slots and host slots 0 / 1
+// (output) and 2 / 3 (input) of the ring: the host stages slice s + 1 into its pinned slot and queues its H2D copy and the D2H copy of
+// slice s on copy_stream while slice s is inflated on stream; then it waits for slice s - 1's D2H copy, checks its statuses and copies it
+// out to dst.  V2M_INFLATE_TIMING=1: where the call's time went, to stderr.
+int v2m_bgzf_decompress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if ((n && !src) || !n_out) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "src or n_out is NULL");
+	*n_out = 0;
+	auto const now([] { return std::chrono::steady_clock::now(); });
+	auto const since([&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(now() - t).count(); });
+	auto const t_call(now());
+	unsigned char const *const in(static_cast<unsigned char const *>(src));
+	bgzf_members mem;
+	{
+		std::string what;
+		if (int const rc = bgzf_walk(in, n, mem, what)) return fail(ctx, rc, "%s", what.c_str());
+	}
+	double const t_scan(since(t_call));
+	if (cap < mem.bytes)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "dst holds %llu bytes; the members decompress to %llu", (unsigned long long) cap, (unsigned long long) mem.bytes);
+	if (mem.bytes && !dst) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "dst is NULL");
+	u64 const n_members(mem.isize.size());
+	if (0 == n_members) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+	// slices: [first member, end member), cut greedily
+	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
+	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : (u64(64) << 20));
+	// (no larger than the input needs: a small file does not set up 256 MB of pinned slots)
+	u64 const slot(std::max<u64>(v2m::kBgzfSlotBytes, std::min(slot_target, (std::max<u64>(n, mem.bytes) + 0xffff) & ~u64(0xffff))));
+	std::vector<u64> cut(1, 0);
+	{
+		u64 cin(0), cout(0);
+		for (u64 k(0); k < n_members; ++k) {
+			u64 const msize(mem.offsets[k + 1] - mem.offsets[k]);
+			if (k > cut.back() && (cin + msize > slot || cout + mem.isize[k] > slot)) { cut.push_back(k); cin = 0; cout = 0; }
+			cin += msize;
+			cout += mem.isize[k];
+		}
+		cut.push_back(n_members);
+	}
+	u64 const n_slices(cut.size() - 1);
+	u64 max_members(0);
+	for (u64 s(0); s < n_slices; ++s) max_members = std::max(max_members, cut[s + 1] - cut[s]);
+	u64 const table_bytes(2 * (max_members + 1) * sizeof(u64));
+	u64 const in_slot((slot + 15) & ~u64(15)), status_bytes(max_members * sizeof(u32));
+	if (int const rc = ensure_host_slots(ctx, 4, std::max(in_slot + table_bytes, ((slot + 15) & ~u64(15)) + status_bytes))) return rc;
+	for (u64 i(0); i < 4; ++i) wait_released(ctx, *ctx->host_slots[i]);
+	std::vector<u64> out_base(n_slices + 1, 0);
+	for (u64 s(0); s < n_slices; ++s) {
+		u64 b(out_base[s]);
+		for (u64 k(cut[s]); k < cut[s + 1]; ++k) b += mem.isize[k];
+		out_base[s + 1] = b;
+	}
+
+	bool const timing(nullptr != std::getenv("V2M_INFLATE_TIMING"));
+	double t_stage(0), t_wait(0), t_copy_out(0), t_h2d(0), t_d2h(0);
+	scoped_events tev;
+	if (timing) V2M_HIP_TRY(ctx, tev.create(4 * n_slices));
+
+	std::vector<u64> slice_out(n_slices, 0), slice_tab(n_slices, 0);
+	// slice s in its input slots: its members' bytes, then (from slice_tab[s], the next multiple of 16) the member offsets and the output
+	// offsets; only those bytes cross the link
+	auto const stage([&](u64 s) -> int {   // slice s into its pinned input slot, and its H2D copy queued on copy_stream
+		int const b(int(s & 1));
+		u64 const k0(cut[s]), k1(cut[s + 1]), nm(k1 - k0);
+		u64 const c0(mem.offsets[k0]), c1(mem.offsets[k1]);
+		v2m_row_hold &slot_in(*ctx->host_slots[2 + b]);
+		if (s >= 2) V2M_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_inflate_in[b]));   // the H2D copy of slice s - 2 has left the slot
+		auto const t0(now());
+		V2M_POISON_HOST(slot_in.host.p, in_slot + table_bytes);
+		host_copy(slot_in.host.p, in + c0, c1 - c0);
+		u64 const tab_at((c1 - c0 + 15) & ~u64(15));                                        // <= in_slot
+		slice_tab[s] = tab_at;
+		u64 *const tab(reinterpret_cast<u64 *>(slot_in.host.as<char>() + tab_at));   // member offsets, then output offsets
+		for (u64 k(k0); k <= k1; ++k) tab[k - k0] = mem.offsets[k] - c0;
+		u64 o(0);
+		for (u64 k(k0); k < k1; ++k) { tab[nm + 1 + k - k0] = o; o += mem.isize[k]; }
+		tab[nm + 1 + nm] = o;
+		slice_out[s] = o;
+		t_stage += since(t0);
+		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));   // the kernel of slice s - 2 has read it
+		V2M_HIP_TRY(ctx, ctx->d_inflate_in[b].ensure(in_slot + table_bytes));
+		if (timing) V2M_HIP_TRY(ctx, hipEventRecord(tev[4 * s], ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_inflate_in[b].p, slot_in.host.p, tab_at + 2 * (nm + 1) * sizeof(u64), hipMemcpyHostToDevice, ctx->copy_stream));
+		if (timing) V2M_HIP_TRY(ctx, hipEventRecord(tev[4 * s + 1], ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_inflate_in[b], ctx->copy_stream));
+		return V2M_OK;
+	});
+	auto const launch([&](u64 s) -> int {   // the kernel of slice s on stream
+		int const b(int(s & 1));
+		u64 const nm(cut[s + 1] - cut[s]);
+		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_inflate_in[b], 0));
+		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->host_slots[b]->copied, 0));   // the D2H copy of slice s - 2 is over
+		V2M_HIP_TRY(ctx, ctx->d_inflate_out[b].ensure(std::max<u64>(16, in_slot)));
+		V2M_HIP_TRY(ctx, ctx->d_inflate_status[b].ensure(status_bytes));
+		char const *const d_in(ctx->d_inflate_in[b].as<char>());
+		u64 const *const d_tab(reinterpret_cast<u64 const *>(d_in + slice_tab[s]));
+		{
+			timed_launch tl(ctx, V2M_KERNEL_INFLATE);
+			hipLaunchKernelGGL(v2m::bgzf_inflate_kernel, dim3(unsigned(nm)), dim3(v2m::kInflateThreads), 0, ctx->stream,
+				reinterpret_cast<unsigned char const *>(d_in), d_tab, d_tab + nm + 1, ctx->d_inflate_out[b].as<unsigned char>(), ctx->d_inflate_status[b].as<u32>());
+			V2M_HIP_TRY(ctx, hipGetLastError());
+		}
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
+		return V2M_OK;
+	});
+	auto const copy_back([&](u64 s) -> int {   // the D2H copy of slice s (bytes and statuses) queued on copy_stream
+		int const b(int(s & 1));
+		v2m_row_hold &slot_out(*ctx->host_slots[b]);
+		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
+		V2M_POISON_HOST(slot_out.host.p, in_slot + status_bytes);
+		if (timing) V2M_HIP_TRY(ctx, hipEventRecord(tev[4 * s + 2], ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot_out.host.p, ctx->d_inflate_out[b].p, slice_out[s], hipMemcpyDeviceToHost, ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot_out.host.as<char>() + in_slot, ctx->d_inflate_status[b].p, (cut[s + 1] - cut[s]) * sizeof(u32), hipMemcpyDeviceToHost, ctx->copy_stream));
+		if (timing) V2M_HIP_TRY(ctx, hipEventRecord(tev[4 * s + 3], ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(slot_out.copied, ctx->copy_stream));
+		return V2M_OK;
+	});
+	auto const finish([&](u64 s) -> int {   // slice s: statuses, then its bytes to dst
+		v2m_row_hold &out_slot(*ctx->host_slots[s & 1]);
+		auto const t0(now());
+		V2M_HIP_TRY(ctx, hipEventSynchronize(out_slot.copied));
+		t_wait += since(t0);
+		u32 const *const st(reinterpret_cast<u32 const *>(out_slot.host.as<char>() + in_slot));
+		for (u64 k(cut[s]); k < cut[s + 1]; ++k)
+			if (st[k - cut[s]])
+				return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "BGZF member %llu at compressed offset %llu: %s", (unsigned long long) k, (unsigned long long) mem.offsets[k],
+					inflate_status_text(st[k - cut[s]]));
+		auto const t1(now());
+		host_copy(static_cast<char *>(dst) + out_base[s], out_slot.host.p, out_base[s + 1] - out_base[s]);
+		t_copy_out += since(t1);
+		return V2M_OK;
+	});
+
+	// copy_stream order: H2D 0, H2D 1, D2H 0, H2D 2, D2H 1, ...: the H2D copy of slice s + 1 and the D2H copy of slice s - 1 run under
+	// the kernel of slice s, and the host copies slice s - 1 out meanwhile
+	int rc(stage(0));
+	u64 copied(0);
+	for (u64 s(0); s < n_slices && V2M_OK == rc; ++s) {
+		if (V2M_OK != (rc = launch(s))) break;
+		if (s + 1 < n_slices && V2M_OK != (rc = stage(s + 1))) break;
+		if (V2M_OK != (rc = copy_back(s))) break;
+		copied = s + 1;
+		if (s >= 1 && V2M_OK != (rc = finish(s - 1))) break;
+	}
+	if (V2M_OK == rc && copied) rc = finish(copied - 1);
+	(void) hipStreamSynchronize(ctx->stream);
+	(void) hipStreamSynchronize(ctx->copy_stream);
+	if (V2M_OK != rc) return rc;
+	if (timing) {
+		for (u64 s(0); s < n_slices; ++s) {
+			float a(0), b(0);
+			if (hipSuccess == hipEventElapsedTime(&a, tev[4 * s], tev[4 * s + 1])) t_h2d += a / 1e3;
+			if (hipSuccess == hipEventElapsedTime(&b, tev[4 * s + 2], tev[4 * s + 3])) t_d2h += b / 1e3;
+		}
+		std::fprintf(stderr, "[v2m_bgzf_decompress] %llu members, %llu -> %llu bytes in %llu slices: %.4f s in all; scan %.4f s, host staging %.4f s, "
+			"H2D %.4f s, D2H %.4f s (device time), waiting for copies %.4f s, host copy out %.4f s\n", (unsigned long long) n_members, (unsigned long long) n,
+			(unsigned long long) mem.bytes, (unsigned long long) n_slices, since(t_call), t_scan, t_stage, t_h2d, t_d2h, t_wait, t_copy_out);
+	}
+	*n_out = mem.bytes;
 	return V2M_OK;
 }
 

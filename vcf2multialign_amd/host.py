@@ -3,6 +3,7 @@ used by the tests to compare it with the oracle's builder.  The transpose is not
 
 import ctypes as C
 import os
+import stat
 
 import numpy as np
 
@@ -30,6 +31,8 @@ def _load():
 		L = C.CDLL(path)
 		L.v2mh_build_variant_graph.restype = C.c_void_p
 		L.v2mh_build_variant_graph.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint, C.c_char_p, C.c_size_t]
+		L.v2mh_build_variant_graph_gpu.restype = C.c_void_p
+		L.v2mh_build_variant_graph_gpu.argtypes = [C.c_void_p] + L.v2mh_build_variant_graph.argtypes
 		L.v2mh_free.argtypes = [C.c_void_p]
 		L.v2mh_graph_from_arrays.restype = C.c_void_p
 		L.v2mh_graph_from_arrays.argtypes = [C.c_uint64, C.c_uint64] + [C.c_void_p] * 5 + [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
@@ -96,6 +99,17 @@ def read_cut_positions(path):
 	return cuts[:n.value].tolist(), md.value, sc.value
 
 
+def _has_gzip_magic(path):
+	"""A regular file that starts with 1f 8b (a pipe is never read here: its first bytes belong to the reader)."""
+	try:
+		if not stat.S_ISREG(os.stat(path).st_mode):
+			return False
+		with open(path, "rb") as f:
+			return f.read(2) == b"\x1f\x8b"
+	except OSError:
+		return False
+
+
 def _arr(ptr, n, dtype):
 	if n == 0 or not ptr:
 		return np.zeros(0, dtype=dtype)
@@ -105,14 +119,21 @@ def _arr(ptr, n, dtype):
 class HostGraph:
 	"""Result of the host's build_variant_graph (without the final transpose)."""
 
-	def __init__(self, fasta_path, vcf_path, chr_id, seq_id=None, exclude_sample=None, exclude_copy=-1, threads=0, _graph_file=None, _handle=None):
+	def __init__(self, fasta_path, vcf_path, chr_id, seq_id=None, exclude_sample=None, exclude_copy=-1, threads=0, _graph_file=None, _handle=None, ctx=None):
+		"""ctx: a Context whose GPU inflates BGZF input (either file, recognised by its first bytes); without one, BGZF input is an error."""
 		L = _load()
 		err = C.create_string_buffer(512)
 		if _handle is not None:
 			h = _handle
 		elif _graph_file is not None:
 			h = L.v2mh_read_graph(str(_graph_file).encode(), err, len(err))
+		elif ctx is not None:
+			h = L.v2mh_build_variant_graph_gpu(ctx._h, str(fasta_path).encode(), seq_id.encode() if seq_id else None, str(vcf_path).encode(), chr_id.encode(),
+				exclude_sample.encode() if exclude_sample else None, exclude_copy, threads, err, len(err))
 		else:
+			for path in (fasta_path, vcf_path):
+				if _has_gzip_magic(path):
+					raise ValueError("%s is BGZF-compressed: HostGraph(..., ctx=Context(...)) needs a GPU context to inflate it" % path)
 			h = L.v2mh_build_variant_graph(str(fasta_path).encode(), seq_id.encode() if seq_id else None, str(vcf_path).encode(), chr_id.encode(),
 				exclude_sample.encode() if exclude_sample else None, exclude_copy, threads, err, len(err))
 		if not h:
