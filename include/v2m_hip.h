@@ -315,8 +315,9 @@ uint64_t v2m_window_length(const v2m_ctx *ctx);
  *                                       divergence values BIASED by one (0 = the reference's DIVERGENCE_MAX, pbwt.hh:25-42)
  * Outputs (host): for chunk k up to trial_capacity pairs at trial_pred / trial_class_count + k * trial_capacity -- (earlier
  * candidate, class count) in the order the reference's loop tries them --, trial_end[c] = the pairs of c's chunk up to and
- * including candidate c (written for the candidates of this call's chunks only), and chunk_status[k] = 0, or 1 when the chunk was left undone (more than 1024 distinct earlier
- * candidates at one node, or trial_capacity exceeded): the caller walks that chunk itself.  Synchronous. */
+ * including candidate c (written for the candidates of this call's chunks only), and chunk_status[k] = 0, or 1 when the chunk was left undone (more than 1024 distinct bins at one
+ * node -- the candidates its divergence values other than the largest point to, the node itself and "none of them" counted --, or
+ * trial_capacity exceeded): the caller walks that chunk itself; its trial_end entries and its pairs are unspecified.  Synchronous. */
 int v2m_pbwt_cut_trials(v2m_ctx *ctx, uint64_t n_copies, uint64_t min_distance,
 	uint64_t n_candidates, const uint32_t *cand_edge, const uint64_t *cand_aligned_pos,
 	uint64_t n_chunks, const uint64_t *chunk_first, const uint32_t *start_order, const uint32_t *start_divergence,
@@ -348,7 +349,10 @@ int v2m_pbwt_cut_trials_streamed(v2m_ctx *ctx, uint64_t n_copies, uint64_t min_d
  * (0xFFFFFFFF = PLOIDY_MAX, "no class"); per cut j >= 1 rec_pool_end[j] (the chunk's joined classes up to and including cut j),
  * rec_distinct[j], rec_first_class[j], rec_first_is_ref[j]; chunk_status[k] = 0, or 1 when the chunk was left undone
  * (pool_capacity exceeded).  Same requirements on the ctx and the start states as v2m_pbwt_cut_trials; cut edges that decrease or
- * lie outside the graph are V2M_ERR_INVALID_ARGUMENT.  Synchronous. */
+ * lie outside the graph are V2M_ERR_INVALID_ARGUMENT, and so is cut_edge[j] == cut_edge[j - 2]: no copy starts a class of a two-block
+ * span without an edge (the reference asserts there, :245).  Two cuts in a row with the same edge count are taken: no copy that
+ * has matched another one starts a class of the block between them (0xFFFFFFFF on that side of its joined classes); csrc/host
+ * refuses such cut lists before it gets here, as the reference's assertions do.  Synchronous. */
 int v2m_pbwt_cut_records(v2m_ctx *ctx, uint64_t n_copies, uint64_t n_cuts, const uint32_t *cut_edge,
 	uint64_t n_chunks, const uint64_t *chunk_first_cut, const uint32_t *start_edge, const uint32_t *start_order, const uint32_t *start_divergence,
 	uint64_t pool_capacity, uint32_t *pool_lhs, uint32_t *pool_rhs, uint32_t *pool_size,

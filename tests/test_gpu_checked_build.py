@@ -8,7 +8,8 @@ before use (kernels.hpp: V2M_POISON_LDS; v2m_hip.hip: scratch_buf, V2M_POISON_HO
 The corpus is the existing tests themselves, run by pytest in a child process per seed (the parent has the product library loaded):
 reference fixtures and founder goldens, 32 fuzz seeds, dense iid path bits, the cache-limit graphs whole and windowed, window classes in
 all four forms, batches of more than 300 rows, the resolve queue's overflow branch, the BGZF encoder against tests/deflate_ref.py at its
-edges, founder cut positions against the host's search, the transposes, path slices and blocks, device checksums.  The second seed runs
+edges, founder cut positions against the host's search and the founder kernels' raw pairs and records against a plain pBWT, the
+transposes, path slices and blocks, device checksums.  The second seed runs
 only if the first passed; the child checks that only the checked builds are mapped."""
 
 import os
@@ -60,6 +61,26 @@ CORPUS = [
 	"tests/test_gpu_founders.py::test_streamed_and_array_form_of_the_chunk_walks_agree",
 	"tests/test_gpu_founders.py::test_every_copies_per_thread_instantiation[2200_copies]",
 	"tests/test_gpu_founders.py::test_every_copies_per_thread_instantiation[9400_copies]",
+	# what the founder kernels write, value for value: the copy counts below 2100 and one of 16 copies per thread, the bin limit, both hash tables
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[1]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[2]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[63]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[64]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[65]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[1023]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[1024]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[1025]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[2047]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[2048]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[2049]",
+	"tests/test_gpu_founder_kernels.py::test_copy_counts_at_every_seam[16384]",
+	"tests/test_gpu_founder_kernels.py::test_bin_limits",
+	"tests/test_gpu_founder_kernels.py::test_hash_collisions_in_both_tables",
+	"tests/test_gpu_founder_kernels.py::test_capacities",
+	"tests/test_gpu_founder_kernels.py::test_chunkings_the_host_never_makes",
+	"tests/test_gpu_founder_kernels.py::test_min_distance",
+	"tests/test_gpu_founder_kernels.py::test_streamed_form",
+	"tests/test_gpu_founder_kernels.py::test_cut_lists_the_search_never_produces",
 ]
 
 CHILD = r"""

@@ -131,3 +131,36 @@ def test_cut_position_file_round_trip(HostGraph, tmp_path):
 		p.write_bytes(bad)
 		with pytest.raises(ValueError):
 			host.read_cut_positions(p)
+
+
+def test_cut_lists_of_the_users_own_are_checked(HostGraph, tmp_path):
+	"""--input-cut-positions hands find_matchings a list no search made (read_cut_positions checks the file's framing only).  What the
+	reference asserts (founder_sequence_greedy_output.cc:58-59,169,200,205,245) is an error here: node 0 first, strictly ascending, inside
+	the graph, the last node last, an ALT edge in every block -- before any loop indexes the graph with it."""
+	import oracle
+	import synth
+	g = synth.build_case(tmp_path, 66, 20000, 300, 5)
+	h = HostGraph(str(tmp_path / "synth.fa"), str(tmp_path / "synth.vcf"), "1")
+	h.set_transposed_paths(g.paths_by_chrom_copy_and_edge, g.path_rows, g.path_cols)
+	cuts, assigned, _ = h.find_founders(3, 20)
+	last = len(h.reference_positions) - 1
+	assert len(cuts) >= 4 and 0 == cuts[0] and last == cuts[-1]
+	for threads in (1, 3):
+		assert h.find_matchings_walked_on_host(cuts, 3, threads=threads) == assigned
+		for bad, message in (
+			(cuts[:2] + cuts[1:], "does not lie after"),                       # a repeated node
+			([cuts[0], cuts[2], cuts[1]] + cuts[3:], "does not lie after"),    # a list that goes back
+			(cuts[:-1] + [last + 5], "lies outside the graph"),
+			(cuts[:-1] + [2 ** 63], "lies outside the graph"),
+			(cuts[1:], "must be node 0"),
+			(cuts[:-1], "must be the last node"),
+		):
+			with pytest.raises(RuntimeError, match=message):
+				h.find_matchings_walked_on_host(bad, 3, threads=threads)
+	# two cut nodes with no ALT edge between them: no copy starts a class of that block, and the assignment indexes with representatives
+	csum = g.alt_edge_count_csum
+	flat = next(n for n in range(1, last - 1) if csum[n] == csum[n + 1] and 0 < csum[n] < csum[last])
+	for bad in ([0, flat, flat + 1, last], [0, flat, flat + 1, flat + 2, last]):
+		with pytest.raises(RuntimeError, match="without any ALT edge"):
+			h.find_matchings_walked_on_host(bad, 3)
+	assert h.find_matchings_walked_on_host([0, flat, last], 3) is not None

@@ -16,6 +16,7 @@
 #include <memory>
 #include <numeric>
 #include <stdexcept>
+#include <string>
 
 namespace v2m::host {
 
@@ -1044,12 +1045,34 @@ bool find_matchings_walked(
 } // namespace
 
 
+// What find_matchings asks of a cut list that did not come from the search (--input-cut-positions; read_cut_positions checks the file's
+// framing only).  The reference states the same as assertions: node 0 first (:169), the nodes in walking order (:205) with the sink
+// last (:200, the list must not run out before the walk does), and a representative for every class (:58-59, :245) -- in a block
+// without an ALT edge no copy starts a class, its copies keep PLOIDY_MAX, and the greedy assignment indexes with representatives.
+// Every loop below indexes alt_edge_count_csum with the cut nodes and relies on their order.
+static void check_cut_positions(variant_graph const &graph, std::vector<u64> const &cut_positions)
+{
+	auto const bad([](std::size_t j, std::string const &why) { throw std::invalid_argument("cut position " + std::to_string(j) + " " + why); });
+	u64 const nodes(graph.node_count());
+	for (std::size_t j(0); j < cut_positions.size(); ++j) {
+		if (cut_positions[j] >= nodes) bad(j, "(node " + std::to_string(cut_positions[j]) + ") lies outside the graph (" + std::to_string(nodes) + " nodes)");
+		if (j && cut_positions[j] <= cut_positions[j - 1]) bad(j, "(node " + std::to_string(cut_positions[j]) + ") does not lie after the one before it (node " + std::to_string(cut_positions[j - 1]) + ")");
+	}
+	if (0 != cut_positions.front()) bad(0, "must be node 0");
+	if (nodes - 1 != cut_positions.back()) bad(cut_positions.size() - 1, "must be the last node (" + std::to_string(nodes - 1) + ")");
+	for (std::size_t j(1); j < cut_positions.size(); ++j)
+		if (graph.alt_edge_count_csum[cut_positions[j]] == graph.alt_edge_count_csum[cut_positions[j - 1]])
+			bad(j, "ends a block without any ALT edge (nodes " + std::to_string(cut_positions[j - 1]) + " to " + std::to_string(cut_positions[j]) + "): it has no path classes to match");
+}
+
+
 bool find_matchings(
 	variant_graph const &graph, std::vector<u64> const &cut_positions, u32 founder_count, bool keep_ref_edges,
 	std::vector<u32> &assigned, unsigned threads, founder_walker *walker)
 {
 	u32 const copies(graph.total_chromosome_copies());
 	if (cut_positions.size() < 2 || 0 == copies) return false;               // :163-167
+	check_cut_positions(graph, cut_positions);
 	if (0 == threads) threads = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
 	auto const &transposed(graph.paths_by_chrom_copy_and_edge);
 	bool const have_transposed(transposed.cols >= copies && transposed.rows >= graph.edge_count() && !transposed.words.empty());
@@ -1065,6 +1088,7 @@ bool find_matchings(
 {
 	u32 const copies(graph.total_chromosome_copies());
 	if (cut_positions.size() < 2 || 0 == copies) return false;               // :163-167
+	check_cut_positions(graph, cut_positions);
 	if (0 == threads) threads = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
 	auto const &transposed(graph.paths_by_chrom_copy_and_edge);
 	bool const have_transposed(transposed.cols >= copies && transposed.rows >= graph.edge_count() && !transposed.words.empty());

@@ -85,6 +85,9 @@ u32 find_cut_positions(variant_graph const &graph, u64 min_distance, std::vector
 // Greedy assignment of path equivalence classes to founders.  assigned_samples receives the
 // (cut_positions.size() - 1) x founder_count matrix, column-major, one column per founder; slots that stay
 // unassigned hold kPloidyMax.  Returns false when there is nothing to match.
+// The cut positions may be anybody's (--input-cut-positions): std::invalid_argument unless they start at node 0, ascend strictly, stay
+// inside the graph, end at the last node and have an ALT edge in every block -- what the reference asserts
+// (founder_sequence_greedy_output.cc:58-59,169,200,205,245).
 // threads: 1 = the reference's sequential loop; more (0 = up to 16 hardware threads) splits the cuts into chunks whose
 // pBWT state is built from scratch from paths_by_chrom_copy_and_edge (the transpose's result), with the same outcome;
 // without that matrix the search is sequential whatever `threads` says.

@@ -291,6 +291,26 @@ uint64_t v2mh_find_founders_walked_on_host(void *h, uint64_t min_distance, uint3
 	}
 }
 
+// find_matchings over the caller's cut positions with the host's own walker (what v2mh_find_founders_gpu does with with_search = 0, without a
+// GPU).  Returns 1, or 0 with a message in err (a cut list find_matchings refuses) or without one (nothing to match).
+int v2mh_find_matchings_walked_on_host(void *h, uint64_t const *cuts_in, uint64_t n_cuts, uint32_t founder_count, int keep_ref_edges, unsigned threads,
+	uint32_t *assigned_out, uint64_t assigned_capacity, char *err, size_t errlen)
+{
+	try {
+		auto const &g(HG(h).graph);
+		auto walker(vh::make_host_founder_walker(g, UINT64_MAX));
+		std::vector<vh::u64> const cuts(cuts_in, cuts_in + n_cuts);
+		std::vector<vh::u32> assigned;
+		if (!vh::find_matchings(g, cuts, founder_count, 0 != keep_ref_edges, assigned, threads, walker.get())) return 0;
+		if (assigned.size() > assigned_capacity) return 0;
+		std::copy(assigned.begin(), assigned.end(), assigned_out);
+		return 1;
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return 0;
+	}
+}
+
 uint64_t v2mh_find_founders(void *h, uint64_t min_distance, uint32_t founder_count, int keep_ref_edges,
 	uint64_t *cuts_out, uint32_t *assigned_out, uint64_t assigned_capacity, uint32_t *score_out)
 {

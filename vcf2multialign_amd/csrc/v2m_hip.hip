@@ -2201,6 +2201,8 @@ int v2m_pbwt_cut_records(v2m_ctx *ctx, uint64_t n_copies, uint64_t n_cuts, const
 		if (chunk_first_cut[k] < chunk_first_cut[k + 1] && start_edge[k] > cut_edge[chunk_first_cut[k] - 1]) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "chunk %llu: the start state lies past the cut before its first one", (unsigned long long) k);
 	}
 	for (u64 j(0); j < n_cuts; ++j) if ((j && cut_edge[j] < cut_edge[j - 1]) || cut_edge[j] > ctx->n_edges) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "cut edges must ascend and stay inside the graph");
+	// (no edge in a two-block span: no copy starts a joined class there, and the reference stops at its libbio_assert(!joined_path_eq_classes.empty()), :245)
+	for (u64 j(2); j < n_cuts; ++j) if (cut_edge[j] == cut_edge[j - 2]) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "cuts %llu to %llu have no ALT edge between them: the two-block span that ends at cut %llu has no path classes", (unsigned long long) (j - 2), (unsigned long long) j, (unsigned long long) j);
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 
 	u64 const rows(ctx->path_rows), cols(ctx->path_cols);

@@ -273,6 +273,21 @@ class HostGraph:
 			return None
 		return cuts[:k].tolist(), assigned[:(k - 1) * founder_count].tolist(), score.value
 
+	def find_matchings_walked_on_host(self, cut_positions, founder_count, keep_ref_edges=False, threads=2):
+		"""find_matchings over the given cut positions with the host's own walker: find_founders_gpu(..., cut_positions=...) without a GPU.
+		Returns assigned_samples column-major, None when there is nothing to match; RuntimeError for a cut list find_matchings refuses."""
+		L = _load()
+		L.v2mh_find_matchings_walked_on_host.restype = C.c_int
+		L.v2mh_find_matchings_walked_on_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		cuts = np.ascontiguousarray(cut_positions, dtype=np.uint64)
+		assigned = np.zeros(max(1, len(cuts) * founder_count), dtype=np.uint32)
+		err = C.create_string_buffer(512)
+		if not L.v2mh_find_matchings_walked_on_host(self._h, cuts.ctypes.data, len(cuts), founder_count, int(keep_ref_edges), threads, assigned.ctypes.data, assigned.size, err, len(err)):
+			if err.value:
+				raise RuntimeError(err.value.decode())
+			return None
+		return assigned[:(len(cuts) - 1) * founder_count].tolist()
+
 	def find_founders(self, founder_count, min_distance=0, keep_ref_edges=False, threads=1):
 		"""find_cut_positions + find_matchings (host algorithms).  Returns (cut_positions, assigned_samples column-major, score)
 		or None when there is no solution.  threads > 1 (0 = automatic) spreads the matching's pBWT over threads."""
