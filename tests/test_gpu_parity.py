@@ -222,7 +222,7 @@ def test_both_store_flavours(v2m, ctx, tmp_path, monkeypatch, nt):
 
 def test_extreme_spans_and_cache_limits(v2m, ctx, tmp_path, monkeypatch):
 	"""Spans and labels beyond what the workgroup's LDS cache can describe (>= 64 KiB spans, labels past the cached
-	2 KiB slice), more long patches in one tile-row than the long-span queue holds, and row groups larger than the
+	1 KiB slice, kLabelLds), more long patches in one tile-row than the long-span queue holds, and row groups larger than the
 	cached effective-bit rows: all must fall back to the global-memory path without changing a byte."""
 	g = synth.extreme_spans_case(tmp_path)
 	assert g.aligned_length > 470000
