@@ -47,15 +47,28 @@ def ctx(v2m):
 
 
 class Bound:
-	"""A chain graph of bits.shape[1] edges with the path matrix bits[copy, edge] (padded to path_cols copy columns), uploaded to ctx."""
+	"""A chain graph of bits.shape[1] edges with the path matrix bits[copy, edge] (padded to path_cols copy columns), uploaded to ctx.
+	device_bind: the graph goes up without its matrix and the edge-by-copy form is bound from device memory (v2m_bind_path_matrix_device):
+	the context's matrix is then its own line-aligned one, not the dense one of v2m_upload_graph."""
 
-	def __init__(self, v2m, ctx, bits, path_cols=None, seed=0):
+	def __init__(self, v2m, ctx, bits, path_cols=None, seed=0, device_bind=False):
 		self.ctx, self.bits = ctx, bits
 		self.n_edges = bits.shape[1]
 		arrays, ref = R.chain_graph_arrays(self.n_edges, seed)
 		rows, cols = R.round64(self.n_edges), path_cols or R.round64(bits.shape[0])
 		og = oracle.graph_from_arrays(path_words=R.pack_paths(bits, rows, cols), path_rows=rows, path_cols=cols, **arrays)
-		ctx.upload_graph(v2m.VariantGraph.from_object(og), ref)
+		vg = v2m.VariantGraph.from_object(og)
+		if device_bind:
+			import torch
+			vg.paths_by_chrom_copy_and_edge = None
+			ctx.upload_graph(vg, ref)
+			by_edge = R.pack_paths(bits.T, cols, rows)                              # one column of cols / 64 words per edge
+			d_by_edge = torch.from_numpy(by_edge.view(np.int64)).cuda()
+			torch.cuda.synchronize()
+			ctx.bind_path_matrix_device(d_by_edge.data_ptr(), cols, rows)
+			ctx.synchronize()                                                      # (the call is asynchronous and d_by_edge goes away here)
+		else:
+			ctx.upload_graph(vg, ref)
 		self.aligned = [int(a) for a in arrays["aligned_positions"]]             # of node n = the node after n edges
 
 	def candidates(self, edges):

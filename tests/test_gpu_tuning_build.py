@@ -26,7 +26,7 @@ KERNELS = ["4x16", "16x8", "16x4", "4x8", "8x4", "8x16", "ring:16,8,8,4,16", "ri
 	"ring:8,8,8,8,64", "ring:8,8,8,8,128", "lines8", "lines8:2,4", "lines8:0,88", "lines8:3,816", "lines8:0,16", "lines8:2,168/sf", "lines8:400,1",
 	"lines16", "lines16:2", "lines8:3,28", "lines8:400,281", "lines8:2,282/sf", "lines8:3,2816", "lines8:2,288/rr",
 	"rot8", "rot8:1", "rot8:2/sf", "rot8:5/rr", "rot8:400", "rot8:0,88", "rot8:3,4", "rot8:0,16", "rot8:2,1616"]
-SHAPES = [(1, 1), (1, 2), (3, 5), (9, 7), (16, 17), (79, 33), (5, 130), (17, 15), (2, 200)]
+SHAPES = [(1, 1), (1, 2), (3, 5), (9, 7), (16, 17), (79, 33), (5, 130), (17, 15), (2, 200), (3, 22), (17, 43)]   # (the last two: three blocks, DW mod 16 = 6 and 11)
 n = 0
 with v2m.Context(0) as ctx:
 	for kernel in KERNELS:
