@@ -35,7 +35,7 @@
  * v2m_pbwt_cut_trials, v2m_pbwt_cut_records); 4 = + v2m_pbwt_cut_trials_streamed; 5 = + v2m_splice_rows_held / v2m_row_release (rows a
  * sink may keep until it says so).  Entries have only ever been added.  V2M_SPLICE_BGZF, v2m_bgzf_compress, v2m_bgzf_bound and
  * v2m_bgzf_frame_stored were added without a new version, and so were v2m_set_column_window and v2m_window_length, and
- * v2m_bgzf_scan and v2m_bgzf_decompress (with V2M_KERNEL_INFLATE): a caller probes for them by symbol.
+ * v2m_bgzf_scan and v2m_bgzf_decompress (with V2M_KERNEL_INFLATE), and v2m_vcf_scan (with V2M_KERNEL_VCF): a caller probes for them by symbol.
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -414,6 +414,83 @@ int v2m_bgzf_scan(const void *src, uint64_t n, uint64_t *n_members_out, uint64_t
  * prefix. */
 int v2m_bgzf_decompress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out);
 
+/* ---- VCF scan ------------------------------------------------------------------------------------
+ *
+ * v2m_vcf_scan turns VCF text (plain, or BGZF inflated on the device) into what a graph builder needs of it without the text ever
+ * reaching the host: per line a record, for some lines a head (bytes of the line), and for the records on the wanted chromosome
+ * bit columns in the layout of paths_by_edge_and_chrom_copy (row r = bit r & 63 of word r >> 6 of a column).
+ *
+ * Lines.  A line is the bytes between '\n's; a last line without '\n' counts, a trailing '\n' adds no empty line.
+ *
+ * Kinds.  n_samples and ploidy(s) = copy_begin[s + 1] - copy_begin[s] come from the layout (below).
+ *   0  the line is empty or its first byte is '#'.  No head, except for a line that starts with "#CHROM": its whole text.
+ *   3  (declined) fewer than 7 tabs.  Head = the whole line.
+ *   1  column 1 is not wanted_chr.  No head.
+ *   2  (parsed) all of a - e hold.  Head = the bytes before the 9th tab (CHROM ... FORMAT); n_alts columns from column_begin on,
+ *      column a - 1 with bit `row` set exactly when an included copy `row` carries allele a >= 1.
+ *        a. the last byte is not '\r';
+ *        b. at least 9 tabs, and column 9 is "GT" or begins with "GT:";
+ *        c. column 5 has 1 to 8 comma-separated entries: n_alts = its commas + 1 (what the entries are is the caller's business);
+ *        d. exactly 8 + n_samples tabs;
+ *        e. for every sample s and every token index c < ploidy(s) the token exists and is "." or 1 - 3 decimal digits with value
+ *           <= n_alts.  Tokens: the sample column up to its first ':', split at '|' and '/'.  Tokens at c >= ploidy(s) are not
+ *           looked at.
+ *   3  otherwise.  Head = the whole line, no columns.  Declining is always safe: the caller parses the line from its text.
+ * Every record has head_offset = the head bytes and column_begin = the columns of the chunk's lines before it; n_alts is 0 unless
+ * the kind is 2.
+ *
+ * Layout.  The first line that is not of kind 0 and whose column 1 (up to the first tab; without a tab the whole line less a final
+ * '\r') is wanted_chr fixes the layout: `layout` is called exactly once, with that line's whole text, before any genotype of its
+ * slice is looked at.  The arrays it returns must stay valid until v2m_vcf_scan returns.  copy_begin must not decrease, row_lookup
+ * entries are -1 (copy not included) or < n_rows, n_rows <= 64 * words_per_column.  Lines before the layout line are of kinds 0, 1 or
+ * 3 by construction; when no line is a layout line, `layout` is never called.
+ * n_rows above 32 768 (or words_per_column above 512) is V2M_ERR_UNSUPPORTED.
+ *
+ * Chunks.  `chunk` is called once per slice, in file order, with whole lines only; a line that straddles a slice seam is carried
+ * to the next slice on the device.  One slice is the exception: the slice that holds the layout line is delivered as two chunks, the
+ * lines before the layout line (none: no such chunk) and, after `layout` has run, the lines from it on, so that the caller has seen
+ * every earlier line (the #CHROM line with the sample names among them) when `layout` is called.  A chunk therefore lies wholly
+ * before the layout line (words_per_column = 0, no columns) or wholly from it on.  A slice without a whole line gives no chunk.
+ * A slice's text (the carried bytes included) is at most V2M_RING_SLOT_BYTES (default 64 MiB; for
+ * BGZF, whole members: 64 KiB more when one member needs it); a line that does not fit into a slice's text makes the call return
+ * V2M_ERR_UNSUPPORTED.  Everything a chunk points to is pinned memory of the library's, valid only during the callback.
+ *
+ * src is BGZF when it starts with 1f 8b: then the framing and payload rules, codes and messages are those of v2m_bgzf_scan /
+ * v2m_bgzf_decompress.  Otherwise it is plain text.  A non-zero return from either callback ends the scan with V2M_ERR_SINK.
+ * Synchronous.  Nothing else of the context changes: a resident graph, a column window and output buffers are untouched. */
+
+typedef struct v2m_vcf_line {
+	uint32_t kind;         /* 0 - 3 */
+	uint32_t n_alts;       /* kind 2: 1 - 8; else 0 */
+	uint32_t head_offset;  /* into v2m_vcf_chunk.heads */
+	uint32_t head_length;
+	uint64_t column_begin; /* first of the line's n_alts columns */
+} v2m_vcf_line;
+
+typedef struct v2m_vcf_layout {
+	uint32_t n_samples;
+	uint32_t n_rows;              /* included chromosome copies */
+	uint64_t words_per_column;    /* of paths_by_edge_and_chrom_copy (its rows are padded) */
+	const uint32_t *copy_begin;   /* [n_samples + 1]: the copies of sample s are row_lookup[copy_begin[s] .. copy_begin[s + 1]) */
+	const int32_t *row_lookup;    /* [copy_begin[n_samples]]: the row of a copy, or -1 when it is not included */
+} v2m_vcf_layout;
+
+typedef struct v2m_vcf_chunk {
+	uint64_t first_line;          /* file-wide 0-based index of the chunk's first line */
+	uint64_t n_lines;
+	const v2m_vcf_line *lines;    /* [n_lines] */
+	const char *heads;
+	uint64_t head_bytes;
+	const uint64_t *columns;      /* [n_columns][words_per_column] */
+	uint64_t n_columns;
+	uint64_t words_per_column;    /* 0 before the layout is known */
+} v2m_vcf_chunk;
+
+typedef int (*v2m_vcf_layout_fn)(void *user, uint64_t line_index, const char *line, uint64_t length, v2m_vcf_layout *out);
+typedef int (*v2m_vcf_chunk_fn)(void *user, const v2m_vcf_chunk *chunk);
+
+int v2m_vcf_scan(v2m_ctx *ctx, const void *src, uint64_t n, const char *wanted_chr, v2m_vcf_layout_fn layout, v2m_vcf_chunk_fn chunk, void *user);
+
 /* ---- verification helper ------------------------------------------------------------------ */
 
 /* 64-bit position-sensitive checksum of each of n_rows device rows (row i = d_rows + i*row_pitch,
@@ -435,7 +512,8 @@ enum {
 	V2M_KERNEL_UNALIGNED_COUNT = 5, /* count_unaligned_kernel + scan_tile_counts_kernel (pass 1 of unaligned mode) */
 	V2M_KERNEL_BGZF = 6,            /* bgzf_deflate_kernel + bgzf_scan_kernel + bgzf_compact_kernel (V2M_SPLICE_BGZF, v2m_bgzf_compress) */
 	V2M_KERNEL_INFLATE = 7,         /* bgzf_inflate_kernel (v2m_bgzf_decompress), one launch per slice */
-	V2M_KERNEL_COUNT = 8
+	V2M_KERNEL_VCF = 8,             /* the line index, head and genotype launches of one slice of v2m_vcf_scan, as one group */
+	V2M_KERNEL_COUNT = 9
 };
 
 /* When enabled, every launch of the kernels above is bracketed by HIP events on the ctx's

@@ -25,8 +25,9 @@ V2M_SPLICE_BGZF = 0x2
 KERNEL_TRANSPOSE, KERNEL_RESOLVE, KERNEL_SPLICE_ALIGNED, KERNEL_SPLICE_UNALIGNED, KERNEL_TEMPLATE, KERNEL_UNALIGNED_COUNT = range(6)
 KERNEL_BGZF = 6
 KERNEL_INFLATE = 7
+KERNEL_VCF = 8
 KERNEL_NAMES = ["transpose_bits_kernel", "resolve_effective_edges_kernel", "splice_aligned_kernel", "splice_unaligned_kernel", "expand_reference_row_kernel", "count_unaligned_kernel",
-	"bgzf_deflate_kernel", "bgzf_inflate_kernel"]
+	"bgzf_deflate_kernel", "bgzf_inflate_kernel", "vcf_scan_kernels"]
 ABI_VERSION = 5
 
 
@@ -46,6 +47,26 @@ class RowBatchStruct(C.Structure):
 		("cut_nodes", C.c_void_p), ("cut_copies", C.c_void_p),
 	]
 
+
+class VcfLine(C.Structure):
+	"""v2m_vcf_line"""
+	_fields_ = [("kind", C.c_uint32), ("n_alts", C.c_uint32), ("head_offset", C.c_uint32), ("head_length", C.c_uint32), ("column_begin", C.c_uint64)]
+
+
+class VcfLayout(C.Structure):
+	"""v2m_vcf_layout"""
+	_fields_ = [("n_samples", C.c_uint32), ("n_rows", C.c_uint32), ("words_per_column", C.c_uint64), ("copy_begin", C.c_void_p), ("row_lookup", C.c_void_p)]
+
+
+class VcfChunk(C.Structure):
+	"""v2m_vcf_chunk"""
+	_fields_ = [("first_line", C.c_uint64), ("n_lines", C.c_uint64), ("lines", C.c_void_p), ("heads", C.c_void_p), ("head_bytes", C.c_uint64),
+		("columns", C.c_void_p), ("n_columns", C.c_uint64), ("words_per_column", C.c_uint64)]
+
+
+VCF_LAYOUT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(VcfLayout))   # v2m_vcf_layout_fn
+VCF_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(VcfChunk))   # v2m_vcf_chunk_fn
+VCF_LINE_DTYPE = [("kind", "<u4"), ("n_alts", "<u4"), ("head_offset", "<u4"), ("head_length", "<u4"), ("column_begin", "<u8")]
 
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
 HOLD_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p)   # v2m_hold_sink_fn
@@ -89,6 +110,7 @@ SIGNATURES = {
 	"v2m_bgzf_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
 	"v2m_bgzf_scan": (C.c_int, [C.c_void_p, C.c_uint64, _u64p, _u64p, C.POINTER(C.c_int)]),
 	"v2m_bgzf_decompress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
+	"v2m_vcf_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, VCF_LAYOUT_FN, VCF_CHUNK_FN, C.c_void_p]),
 	"v2m_checksum_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
 	"v2m_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
 	"v2m_profile_reset": (C.c_int, [C.c_void_p]),

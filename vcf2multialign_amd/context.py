@@ -49,6 +49,62 @@ class RowBatch:
 		return cls(rows)
 
 
+def first_record_layout(line, excluded=(), path_alignment=64):
+	"""The layout the host's first-record code derives from a VCF record (bytes): every sample's ploidy from the width of its GT, rows
+	numbered over the included copies in order; excluded: (sample index, copy index) pairs.  For Context.vcf_scan and host.scan_lines_host."""
+	fields = bytes(line).rstrip(b"\r").split(b"\t")
+	gt_index = fields[8].split(b":").index(b"GT")
+	copy_begin, row_lookup, row = [0], [], 0
+	for s, field in enumerate(fields[9:]):
+		gt = field.split(b":")[gt_index]
+		for c in range(1 + gt.count(b"|") + gt.count(b"/")):
+			if (s, c) in excluded:
+				row_lookup.append(-1)
+			else:
+				row_lookup.append(row)
+				row += 1
+		copy_begin.append(len(row_lookup))
+	return dict(n_samples=len(fields) - 9, n_rows=row, words_per_column=(row + path_alignment - 1) // path_alignment * (path_alignment // 64),
+		copy_begin=copy_begin, row_lookup=row_lookup)
+
+
+def collect_vcf_scan(call, layout):
+	"""Runs call(layout_fn, chunk_fn) -- v2m_vcf_scan or the host scanner, which share their callbacks -- and returns (code, chunks, layout
+	line index or None).  A chunk is a dict: first_line, lines (structured array, N.VCF_LINE_DTYPE), heads (bytes), columns (uint64 array
+	[n_columns, words_per_column]), words_per_column.  layout(line_index, line) returns what first_record_layout returns."""
+	chunks, keep, seen = [], [], []
+
+	def on_layout(_user, line_index, line, length, out):
+		try:
+			d = layout(line_index, C.string_at(line, length))
+			cb = np.ascontiguousarray(d["copy_begin"], dtype=np.uint32)
+			rl = np.ascontiguousarray(d["row_lookup"] if len(d["row_lookup"]) else [0], dtype=np.int32)
+			keep.extend([cb, rl])
+			out[0].n_samples, out[0].n_rows, out[0].words_per_column = d["n_samples"], d["n_rows"], d["words_per_column"]
+			out[0].copy_begin, out[0].row_lookup = cb.ctypes.data, rl.ctypes.data
+			seen.append(line_index)
+			return 0
+		except Exception as e:   # nothing may cross the C boundary
+			keep.append(e)
+			return 1
+
+	def on_chunk(_user, c):
+		c = c[0]
+		lines = np.frombuffer(C.string_at(c.lines, c.n_lines * C.sizeof(N.VcfLine)), dtype=N.VCF_LINE_DTYPE).copy()
+		heads = C.string_at(c.heads, c.head_bytes) if c.head_bytes else b""
+		n_words = c.n_columns * c.words_per_column
+		columns = np.frombuffer(C.string_at(c.columns, 8 * n_words), dtype=np.uint64).copy() if n_words else np.zeros(0, np.uint64)
+		chunks.append(dict(first_line=c.first_line, lines=lines, heads=heads, columns=columns.reshape(c.n_columns, c.words_per_column) if n_words else columns.reshape(0, c.words_per_column),
+			words_per_column=c.words_per_column))
+		return 0
+
+	rc = call(N.VCF_LAYOUT_FN(on_layout), N.VCF_CHUNK_FN(on_chunk))
+	for k in keep:
+		if isinstance(k, Exception):
+			raise k
+	return rc, chunks, (seen[0] if seen else None)
+
+
 class Context:
 	def __init__(self, device=0):
 		self._lib = N.load()
@@ -90,6 +146,17 @@ class Context:
 
 	def synchronize(self):
 		self._check(self._lib.v2m_ctx_synchronize(self._h))
+
+	# ---- VCF scan --------------------------------------------------------------------------------
+	def vcf_scan(self, data, wanted_chr, layout=first_record_layout):
+		"""v2m_vcf_scan over `data` (bytes: BGZF or plain VCF text).  Returns the chunks as collect_vcf_scan describes them; for tests and
+		tools.  layout(line_index, line) -> the layout of the first record on wanted_chr (default: first_record_layout, nothing excluded)."""
+		data = bytes(data)
+		fn = layout if layout is not first_record_layout else (lambda _i, line: first_record_layout(line))
+		rc, chunks, self.vcf_layout_line = collect_vcf_scan(
+			lambda lf, cf: self._lib.v2m_vcf_scan(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data), wanted_chr.encode(), lf, cf, None), fn)
+		self._check(rc)
+		return chunks
 
 	# ---- transpose_matrix (transpose_matrix.hh:14) --------------------------------------------
 	def transpose_matrix(self, words, n_rows, n_cols):

@@ -62,6 +62,28 @@ std::string_view input_file::inflate(gpu_context &gpu)
 }
 
 
+std::string_view input_file::compressed() const
+{
+	if (!m_bgzf || !m_file) throw std::logic_error(m_path + " is not BGZF, or has been inflated");
+	return std::string_view(m_file->data, m_file->size);
+}
+
+
+void build_variant_graph_gpu_parsed(
+	gpu_context &gpu, std::string const &name, std::string_view bytes, u64 text_bytes, sequence_type const &ref_seq, char const *chr_id,
+	variant_graph &graph, build_graph_statistics &stats, build_graph_delegate &delegate, scan_statistics *scan_stats, u64 path_alignment)
+{
+	line_scanner const scanner([&](char const *chr, v2m_vcf_layout_fn layout, v2m_vcf_chunk_fn chunk, void *user) {
+		return v2m_vcf_scan(gpu.get(), bytes.data(), bytes.size(), chr, layout, chunk, user);
+	});
+	try {
+		build_variant_graph_scanned(ref_seq, scanner, text_bytes, chr_id, graph, stats, delegate, scan_stats, path_alignment);
+	} catch (scan_failed const &e) {
+		throw gpu_error(e.code, name + ": " + v2m_last_error(gpu.get()));
+	}
+}
+
+
 bit_matrix transpose_matrix(gpu_context &gpu, bit_matrix const &mat)
 {
 	if (0 == mat.cols) return bit_matrix{};                           // transpose_matrix.cc:48-49

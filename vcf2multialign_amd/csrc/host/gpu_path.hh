@@ -47,6 +47,7 @@ public:
 	u64 bytes() const { return m_bytes; }
 	bool ends_with_eof() const { return m_eof; }
 	std::string_view inflate(gpu_context &gpu);   // BGZF only; throws gpu_error (a corrupt member: V2M_ERR_INVALID_ARGUMENT)
+	std::string_view compressed() const;          // BGZF only, before inflate(): the mapped file, for a scan that inflates it slice by slice on the device (build_variant_graph_gpu_parsed)
 	double inflate_seconds() const { return m_seconds; }
 private:
 	std::string m_path;
@@ -56,6 +57,14 @@ private:
 	std::unique_ptr<char[]> m_text;               // not value-initialised: its pages are first touched by the copy out of the pinned slots
 	double m_seconds{};
 };
+
+// build_variant_graph with the genotype columns parsed on the GPU (readers.hh: build_variant_graph_scanned over v2m_vcf_scan): `bytes` is
+// the whole VCF, BGZF or plain text, in host memory (a mapping); the text never reaches the host.  text_bytes: the decompressed size (a
+// hint).  Throws what build_variant_graph throws, and gpu_error (`name`: the file, for the message) when the scan itself fails --
+// V2M_ERR_UNSUPPORTED for a line longer than a slice or more than 32 768 chromosome copies: the caller then uses the text path.
+void build_variant_graph_gpu_parsed(
+	gpu_context &gpu, std::string const &name, std::string_view bytes, u64 text_bytes, sequence_type const &ref_seq, char const *chr_id,
+	variant_graph &graph, build_graph_statistics &stats, build_graph_delegate &delegate, scan_statistics *scan_stats = nullptr, u64 path_alignment = 64);
 
 // transpose_matrix (include/vcf2multialign/transpose_matrix.hh:14) on the GPU.
 [[nodiscard]] bit_matrix transpose_matrix(gpu_context &gpu, bit_matrix const &mat);

@@ -2,6 +2,7 @@
 // oracle's builder array by array (no GPU involved: the transpose is not part of the host builder).
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -24,6 +25,7 @@ struct host_graph {
 	vh::build_graph_statistics stats;
 	std::vector<recorded_overlap> overlaps;
 	std::string sample_blob;
+	vh::scan_statistics scan;      // the scanned builds: lines scanned, lines declined
 };
 
 struct recording_delegate final : vh::build_graph_delegate {
@@ -51,8 +53,10 @@ bool g_stop_at_mismatch(false);
 
 // The host graph of the two files.  gpu == NULL: both through the path readers.  Otherwise either file may be BGZF (gpu_path.hh:
 // input_file), inflated on that context; plain files still go through the path readers.
+// scanner: 0 = the text path; 1 = the VCF through v2m_vcf_scan on `gpu` (BGZF or plain, never inflated to the host); 2 = through scan_lines_host
+// (plain text only, no GPU).
 host_graph *build_host_graph(vh::gpu_context *gpu, char const *fasta, char const *seq_id, char const *vcf, char const *chr, char const *exclude_sample,
-	int exclude_copy, unsigned threads, char *err, size_t errlen)
+	int exclude_copy, unsigned threads, char *err, size_t errlen, int scanner = 0)
 {
 	auto *hg(new host_graph);
 	try {
@@ -66,7 +70,24 @@ host_graph *build_host_graph(vh::gpu_context *gpu, char const *fasta, char const
 		if (exclude_sample) { d.excluded_sample = exclude_sample; d.excluded_copy = exclude_copy; }
 		d.stop_at_mismatch = g_stop_at_mismatch;
 		std::unique_ptr<vh::input_file> in(gpu ? new vh::input_file(vcf) : nullptr);
-		if (in && in->bgzf()) vh::build_variant_graph(hg->ref, in->inflate(*gpu), chr, hg->graph, hg->stats, d, threads);
+		if (1 == scanner) {
+			if (!gpu) throw std::runtime_error("the GPU scanner needs a GPU context");
+			if (in->bgzf()) vh::build_variant_graph_gpu_parsed(*gpu, vcf, in->compressed(), in->bytes(), hg->ref, chr, hg->graph, hg->stats, d, &hg->scan);
+			else {
+				vh::mapped_file const file(vcf);
+				vh::build_variant_graph_gpu_parsed(*gpu, vcf, std::string_view(file.data, file.size), file.size, hg->ref, chr, hg->graph, hg->stats, d, &hg->scan);
+			}
+		} else if (2 == scanner) {
+			vh::mapped_file const file(vcf);
+			std::string_view const text(file.data, file.size);
+			std::size_t slice(0);
+			if (char const *const e = std::getenv("V2M_RING_SLOT_BYTES")) if (*e) slice = std::strtoull(e, nullptr, 10);   // test knob, as for v2m_vcf_scan
+			vh::line_scanner const host_scanner([&](char const *c, v2m_vcf_layout_fn layout, v2m_vcf_chunk_fn chunk, void *user) {
+				return vh::scan_lines_host(text, c, slice, layout, chunk, user);
+			});
+			vh::build_variant_graph_scanned(hg->ref, host_scanner, text.size(), chr, hg->graph, hg->stats, d, &hg->scan);
+		}
+		else if (in && in->bgzf()) vh::build_variant_graph(hg->ref, in->inflate(*gpu), chr, hg->graph, hg->stats, d, threads);
 		else vh::build_variant_graph(hg->ref, vcf, chr, hg->graph, hg->stats, d, threads);
 		for (auto const &s : hg->graph.sample_names) { hg->sample_blob += s; hg->sample_blob.push_back('\0'); }
 		return hg;
@@ -97,6 +118,38 @@ void *v2mh_build_variant_graph_gpu(void *ctx, char const *fasta, char const *seq
 	}
 	vh::gpu_context gpu(static_cast<v2m_ctx *>(ctx), vh::gpu_context::borrowed{});
 	return build_host_graph(&gpu, fasta, seq_id, vcf, chr, exclude_sample, exclude_copy, threads, err, errlen);
+}
+
+// The same with the VCF's genotype columns scanned instead of parsed from text (readers.hh: build_variant_graph_scanned).  scanner = 1:
+// v2m_vcf_scan on `ctx` (the VCF BGZF or plain; the FASTA as for v2mh_build_variant_graph_gpu); scanner = 2: scan_lines_host, plain files, ctx
+// may be NULL.  `threads` is accepted for symmetry: the scanned build assembles and merges on the scanner's thread.
+void *v2mh_build_variant_graph_scanned(void *ctx, char const *fasta, char const *seq_id, char const *vcf, char const *chr, char const *exclude_sample, int exclude_copy,
+	unsigned threads, char *err, size_t errlen, int scanner)
+{
+	if (1 != scanner && 2 != scanner) {
+		if (err && errlen) { std::strncpy(err, "v2mh_build_variant_graph_scanned: scanner must be 1 (GPU) or 2 (host)", errlen - 1); err[errlen - 1] = 0; }
+		return nullptr;
+	}
+	if (!ctx) {
+		if (1 == scanner) { if (err && errlen) { std::strncpy(err, "v2mh_build_variant_graph_scanned needs a GPU context for the GPU scanner", errlen - 1); err[errlen - 1] = 0; } return nullptr; }
+		return build_host_graph(nullptr, fasta, seq_id, vcf, chr, exclude_sample, exclude_copy, threads, err, errlen, scanner);
+	}
+	vh::gpu_context gpu(static_cast<v2m_ctx *>(ctx), vh::gpu_context::borrowed{});
+	return build_host_graph(&gpu, fasta, seq_id, vcf, chr, exclude_sample, exclude_copy, threads, err, errlen, scanner);
+}
+
+// Lines the scanned build scanned, and those of them it declined (kind 3: parsed from their text).
+void v2mh_scan_statistics(void *h, uint64_t *lines, uint64_t *declined)
+{
+	*lines = static_cast<host_graph *>(h)->scan.lines;
+	*declined = static_cast<host_graph *>(h)->scan.declined;
+}
+
+// scan_lines_host (readers.hh) over `n` bytes of text, for tests and tools: the callbacks are v2m_vcf_scan's.
+int v2mh_scan_lines_host(char const *text, uint64_t n, char const *wanted_chr, uint64_t slice_bytes, v2m_vcf_layout_fn layout, v2m_vcf_chunk_fn chunk, void *user)
+{
+	try { return vh::scan_lines_host(std::string_view(text, n), wanted_chr, slice_bytes, layout, chunk, user); }
+	catch (std::exception const &) { return V2M_ERR_INVALID_ARGUMENT; }
 }
 
 // A host graph from flat arrays (e.g. a synthetic dataset whose genotype matrix was generated on the GPU):

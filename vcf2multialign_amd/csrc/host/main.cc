@@ -46,6 +46,7 @@ struct options {
 	bool output_sequences_separate{}, separate_plain{}, omit_reference{}, unaligned{}, verbose{}, graph_statistics{};
 	bool ref_mismatch_error{};
 	bool bgzf{};
+	bool gpu_parse{};                     // --gpu-parse: the genotype columns of -a become path bits on the GPU (v2m_vcf_scan)
 	char const *region{};                 // --region=START-END: 1-based inclusive positions on the reference sequence
 	std::uint64_t region_start{}, region_end{};
 	std::vector<int> devices{0};
@@ -77,6 +78,11 @@ void usage()
 		"                                     reader gives the plain A2M back; not with --pipe or --output-sequences-separate)\n"
 		"      --region=START-END             Output only the alignment columns of reference positions START..END (1-based,\n"
 		"                                     inclusive, as in samtools/bcftools), with the insertions anchored there\n"
+		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
+		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
+		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
+		"                                     than a 64-MiB slice) is parsed on the host instead when that shows before the first\n"
+		"                                     record is merged; a too-long line after that is an error\n"
 		"      --verbose\n"
 		"  BGZF input (bgzip, bcftools -Oz, a .fa.gz for samtools faidx) is recognised by its first bytes and inflated on the first\n"
 		"  GPU; the decompressed text is held in host memory (as large as the text).  Plain gzip has to be recompressed with bgzip.\n"
@@ -189,7 +195,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -201,7 +207,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -245,6 +251,7 @@ int main(int argc, char **argv)
 			case o_verbose: opt.verbose = true; break;
 			case o_pipe: opt.pipe = optarg; break;
 			case o_bgzf: opt.bgzf = true; break;
+			case o_gpu_parse: opt.gpu_parse = true; break;
 			case o_region: opt.region = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
@@ -269,6 +276,7 @@ int main(int argc, char **argv)
 	if (opt.bgzf && !opt.output_sequences_a2m) { std::cerr << "ERROR: --bgzf requires -s / --output-sequences-a2m.\n"; return EXIT_FAILURE; }
 	if (opt.bgzf && opt.pipe) { std::cerr << "ERROR: --bgzf cannot be combined with --pipe (the piped command compresses).\n"; return EXIT_FAILURE; }
 	if (opt.bgzf && opt.output_sequences_separate) { std::cerr << "ERROR: --bgzf cannot be combined with --output-sequences-separate.\n"; return EXIT_FAILURE; }
+	if (opt.gpu_parse && !opt.input_variants) { std::cerr << "ERROR: --gpu-parse parses --input-variants; it cannot be combined with --input-graph.\n"; return EXIT_FAILURE; }
 	if (opt.region && !parse_region(opt.region, opt.region_start, opt.region_end)) {
 		std::cerr << "ERROR: --region must be START-END with 1 <= START <= END (1-based, inclusive), got \"" << opt.region << "\".\n";
 		return EXIT_FAILURE;
@@ -348,12 +356,36 @@ int main(int argc, char **argv)
 			}
 			std::cerr << "Building the variant graph...\n";
 			vh::build_graph_statistics stats;
-			if (variants_input->bgzf()) {
-				std::string_view const text(variants_input->inflate(first_gpu()));
-				report_inflate(*variants_input, opt.input_variants);
-				vh::build_variant_graph(ref_seq, text, opt.chromosome, graph, stats, delegate, 0, 64);
-			} else
-				vh::build_variant_graph(ref_seq, opt.input_variants, opt.chromosome, graph, stats, delegate, 0, 64);   // the reference's padding (variant_graph.cc:277,449)
+			bool scanned(false);
+			if (opt.gpu_parse) {
+				// the compressed members (or the plain text) go to the GPU slice by slice; what comes back is line records, the records'
+				// first nine columns and the path bits
+				vh::scan_statistics scan;
+				try {
+					if (variants_input->bgzf())
+						vh::build_variant_graph_gpu_parsed(first_gpu(), opt.input_variants, variants_input->compressed(), variants_input->bytes(), ref_seq, opt.chromosome, graph, stats, delegate, &scan, 64);
+					else {
+						vh::mapped_file const file(opt.input_variants);
+						vh::build_variant_graph_gpu_parsed(first_gpu(), opt.input_variants, std::string_view(file.data, file.size), file.size, ref_seq, opt.chromosome, graph, stats, delegate, &scan, 64);
+					}
+					scanned = true;
+					if (opt.verbose) std::cerr << "GPU parse of " << opt.input_variants << ": " << scan.lines << " lines scanned, " << scan.declined << " declined (parsed from their text).\n";
+				} catch (vh::gpu_error const &e) {
+					// nothing has been merged when the layout is refused; a line longer than a slice may turn up later, and the records
+					// before it have been reported to the delegate by then
+					if (V2M_ERR_UNSUPPORTED != e.code || stats.handled_variants) throw;
+					if (opt.verbose) std::cerr << "GPU parse not supported for this input (" << e.what() << "); parsing the text on the host.\n";
+					stats = vh::build_graph_statistics{};
+				}
+			}
+			if (!scanned) {
+				if (variants_input->bgzf()) {
+					std::string_view const text(variants_input->inflate(first_gpu()));
+					report_inflate(*variants_input, opt.input_variants);
+					vh::build_variant_graph(ref_seq, text, opt.chromosome, graph, stats, delegate, 0, 64);
+				} else
+					vh::build_variant_graph(ref_seq, opt.input_variants, opt.chromosome, graph, stats, delegate, 0, 64);   // the reference's padding (variant_graph.cc:277,449)
+			}
 			variants_input.reset();                             // (the decompressed text)
 			// variant_graph.cc:453 (the transpose) happens on the GPU(s) below; the transposed matrix only comes back to the host
 			// when something on the host reads it: the founder search and the graph checkpoint.

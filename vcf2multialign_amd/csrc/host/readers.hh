@@ -11,6 +11,10 @@
 #include <string_view>
 #include <vector>
 
+#include <functional>
+#include <stdexcept>
+
+#include "../../../include/v2m_hip.h"
 #include "variant_graph.hh"
 
 namespace v2m::host {
@@ -65,5 +69,38 @@ void build_variant_graph(
 void build_variant_graph(
 	sequence_type const &ref_seq, std::string_view variants_text, char const *chr_id,
 	variant_graph &graph, build_graph_statistics &stats, build_graph_delegate &delegate, unsigned threads = 0, u64 path_alignment = 64);
+
+// ---- the scanned path: the graph from line records, heads and bit columns instead of text (include/v2m_hip.h, "VCF scan") ----
+
+// A scan of the whole VCF for `chr_id`: v2m_vcf_scan on a GPU context (gpu_path.hh: build_variant_graph_gpu_parsed), or scan_lines_host below.
+// Returns a V2M_* code.
+typedef std::function<int(char const *chr_id, v2m_vcf_layout_fn layout, v2m_vcf_chunk_fn chunk, void *user)> line_scanner;
+
+struct scan_statistics {
+	u64 lines{};       // lines scanned
+	u64 declined{};    // of them of kind 3: parsed from their text by the host
+};
+
+// The scanner returned a code other than V2M_OK and no callback had failed (V2M_ERR_UNSUPPORTED: the caller uses the text path).
+struct scan_failed : std::runtime_error {
+	int code;
+	explicit scan_failed(int code_) : std::runtime_error("the VCF scan failed with code " + std::to_string(code_)), code(code_) {}
+};
+
+// The rule of v2m_vcf_scan in plain C++, over text in memory: the same chunks from the same text (a slice = the line the
+// previous slice ended in, carried over, plus as many new bytes as slice_bytes still holds, its whole lines delivered; 0 = 64 MiB; a line
+// that no slice holds is V2M_ERR_UNSUPPORTED), byte for byte what the kernels give for the same lines.  It is what the GPU
+// tests compare the kernels with, and it makes the assembler testable without a GPU.
+int scan_lines_host(std::string_view text, char const *wanted_chr, std::size_t slice_bytes, v2m_vcf_layout_fn layout, v2m_vcf_chunk_fn chunk, void *user);
+
+// build_variant_graph through a scanner: the layout callback runs the first-record code on the line it is given, the chunk callback fills
+// a chunk of the merge stage from the scanned lines (lines of kind 2: the head through the text parser's head part, the bit columns mapped
+// to edge columns; kind 3: the text parser on the whole line, with its errors; kinds 0 and 1: counted) and merges it, on the scanner's
+// thread (a delegate that stops the build at a REF mismatch ends the scan there; the scan statistics then cover the lines up to that
+// chunk).  The graph, the statistics, the delegate calls and the errors are those of build_variant_graph on the same text.  Throws
+// scan_failed when the scanner itself fails; expected_text_bytes: the size of the text (a hint for the path matrix's allocation).
+void build_variant_graph_scanned(
+	sequence_type const &ref_seq, line_scanner const &scanner, u64 expected_text_bytes, char const *chr_id,
+	variant_graph &graph, build_graph_statistics &stats, build_graph_delegate &delegate, scan_statistics *scan_stats = nullptr, u64 path_alignment = 64);
 
 } // namespace v2m::host

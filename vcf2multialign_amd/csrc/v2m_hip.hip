@@ -28,6 +28,7 @@
 #include "kernels.hpp"
 #include "founder_kernels.hpp"
 #include "bgzf_kernels.hpp"
+#include "vcf_kernels.hpp"
 
 using v2m::u32;
 using v2m::u64;
@@ -245,6 +246,11 @@ struct v2m_ctx {
 	// of each (slice s + 1 crosses the link while slice s is inflated)
 	scratch_buf d_inflate_in[2], d_inflate_out[2], d_inflate_status[2];
 	hipEvent_t ev_inflate_in[2]{};
+	// VCF scan (v2m_vcf_scan): the text of a slice, two buffers used in turn (the line a slice ends in is carried into the other one's
+	// front), the slice's compressed members, and what the passes of vcf_kernels.hpp leave
+	dev_buf d_vcf_text[2];
+	scratch_buf d_vcf_in, d_vcf_status, d_vcf_tiles, d_vcf_tile_offsets, d_vcf_line_start, d_vcf_lines, d_vcf_gt_off, d_vcf_flags, d_vcf_tmp_begin,
+		d_vcf_tmp_columns, d_vcf_totals, d_vcf_heads, d_vcf_columns, d_vcf_layout, d_vcf_wanted;
 };
 
 
@@ -2687,6 +2693,279 @@ int v2m_bgzf_decompress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, ui
 			(unsigned long long) mem.bytes, (unsigned long long) n_slices, since(t_call), t_scan, t_stage, t_h2d, t_d2h, t_wait, t_copy_out);
 	}
 	*n_out = mem.bytes;
+	return V2M_OK;
+}
+
+
+// ---- VCF scan (vcf_kernels.hpp) ----------------------------------------------------------------------
+
+// One slice at a time, on the context's stream: its text into the slice buffer behind the carried line (plain: H2D from the caller's
+// text; BGZF: the members through pinned slot 2, inflated by bgzf_inflate_kernel), the passes of vcf_kernels.hpp, the chunk into pinned
+// slot 0, the callback.  The host waits for the device where the next launch's size depends on a count (lines, candidates' columns,
+// head bytes and columns); nothing of the text crosses the link except the layout line, once.
+int v2m_vcf_scan(v2m_ctx *ctx, const void *src, uint64_t n, const char *wanted_chr, v2m_vcf_layout_fn layout, v2m_vcf_chunk_fn chunk, void *user)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if ((n && !src) || !wanted_chr || !*wanted_chr || !layout || !chunk) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "src, wanted_chr, layout or chunk is NULL (or wanted_chr empty)");
+	unsigned char const *const in(static_cast<unsigned char const *>(src));
+	bool const bgzf(n >= 2 && 0x1f == in[0] && 0x8b == in[1]);
+	bgzf_members mem;
+	if (bgzf) {
+		std::string what;
+		if (int const rc = bgzf_walk(in, n, mem, what)) return fail(ctx, rc, "%s", what.c_str());
+	}
+	u64 const text_bytes(bgzf ? mem.bytes : n), n_members(bgzf ? mem.isize.size() : 0);
+	if (0 == text_bytes) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
+	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : (u64(64) << 20));
+	u64 const slot(std::max<u64>(16, std::min<u64>({slot_target, u64(256) << 20, (text_bytes + 0xffff) & ~u64(0xffff)})));
+	u64 const text_cap(slot + (bgzf ? v2m::kBgzfSlotBytes : 0));      // a slice's text at most; the carried line is no longer
+	u64 const front((text_cap + 15) & ~u64(15));                      // the slice's new bytes begin here, the carried line ends here
+	for (auto &b : ctx->d_vcf_text) { b.reset(); V2M_HIP_TRY(ctx, b.ensure(2 * front + 16)); }
+	u32 const wanted_len(u32(std::strlen(wanted_chr)));
+	V2M_HIP_TRY(ctx, ctx->d_vcf_wanted.ensure(wanted_len + 16));
+	V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vcf_wanted.p, wanted_chr, wanted_len, hipMemcpyHostToDevice, ctx->stream));
+	V2M_HIP_TRY(ctx, ctx->d_vcf_totals.ensure(64));
+
+	bool have_layout(false);
+	v2m_vcf_layout lay{};
+	v2m::vcf_layout_view view{};
+	u64 carry(0), first_line(0), consumed(0), next_member(0);         // consumed: plain bytes taken so far
+	for (u64 s(0);; ++s) {
+		unsigned char *const buf(ctx->d_vcf_text[s & 1].as<unsigned char>());
+		// ---- the slice's new bytes
+		u64 fresh(0);
+		bool last(false);
+		u64 k0(next_member), k1(next_member);
+		if (bgzf) {
+			while (k1 < n_members && (carry + fresh + mem.isize[k1] <= slot || (k1 == k0 && carry + mem.isize[k1] <= text_cap))) fresh += mem.isize[k1++];
+			last = k1 == n_members;
+			if (k1 == k0 && !last)
+				return fail(ctx, V2M_ERR_UNSUPPORTED, "VCF line %llu is longer than a slice can hold (%llu bytes)", (unsigned long long) first_line + 1, (unsigned long long) slot);
+			u64 const nm(k1 - k0);
+			if (nm) {
+				u64 const c0(mem.offsets[k0]), c1(mem.offsets[k1]);
+				u64 const tab_at((c1 - c0 + 15) & ~u64(15)), tab_bytes(2 * (nm + 1) * sizeof(u64));
+				if (int const rc = ensure_host_slots(ctx, 3, tab_at + tab_bytes)) return rc;
+				for (u64 i(0); i < 3; ++i) wait_released(ctx, *ctx->host_slots[i]);
+				char *const stage(ctx->host_slots[2]->host.as<char>());
+				V2M_POISON_HOST(stage, tab_at + tab_bytes);
+				host_copy(stage, in + c0, c1 - c0);
+				u64 *const tab(reinterpret_cast<u64 *>(stage + tab_at));   // member offsets, then output offsets
+				for (u64 k(k0); k <= k1; ++k) tab[k - k0] = mem.offsets[k] - c0;
+				u64 o(0);
+				for (u64 k(k0); k < k1; ++k) { tab[nm + 1 + k - k0] = o; o += mem.isize[k]; }
+				tab[2 * nm + 1] = o;
+				V2M_HIP_TRY(ctx, ctx->d_vcf_in.ensure(tab_at + tab_bytes));
+				V2M_HIP_TRY(ctx, ctx->d_vcf_status.ensure(nm * sizeof(u32)));
+				V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vcf_in.p, stage, tab_at + tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+				char const *const d_in(ctx->d_vcf_in.as<char>());
+				u64 const *const d_tab(reinterpret_cast<u64 const *>(d_in + tab_at));
+				{
+					timed_launch tl(ctx, V2M_KERNEL_INFLATE);
+					hipLaunchKernelGGL(v2m::bgzf_inflate_kernel, dim3(unsigned(nm)), dim3(v2m::kInflateThreads), 0, ctx->stream,
+						reinterpret_cast<unsigned char const *>(d_in), d_tab, d_tab + nm + 1, buf + front, ctx->d_vcf_status.as<u32>());
+					V2M_HIP_TRY(ctx, hipGetLastError());
+				}
+				std::vector<u32> status(nm);
+				V2M_HIP_TRY(ctx, hipMemcpyAsync(status.data(), ctx->d_vcf_status.p, nm * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+				V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+				for (u64 k(0); k < nm; ++k)
+					if (status[k])
+						return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "BGZF member %llu at compressed offset %llu: %s", (unsigned long long) (k0 + k), (unsigned long long) mem.offsets[k0 + k],
+							inflate_status_text(status[k]));
+			}
+			next_member = k1;
+		} else {
+			fresh = std::min(n - consumed, slot - std::min(slot, carry));
+			last = consumed + fresh == n;
+			if (0 == fresh && !last)
+				return fail(ctx, V2M_ERR_UNSUPPORTED, "VCF line %llu is longer than a slice can hold (%llu bytes)", (unsigned long long) first_line + 1, (unsigned long long) slot);
+			if (fresh) V2M_HIP_TRY(ctx, hipMemcpyAsync(buf + front, in + consumed, fresh, hipMemcpyHostToDevice, ctx->stream));
+			consumed += fresh;
+		}
+		u64 const length(carry + fresh);                              // the slice's text: buf[front - carry, front + fresh)
+		if (0 == length) break;                                       // (only at the end: nothing carried, nothing left)
+		unsigned char const *const text(buf + front - carry);
+		u32 const lead(u32(reinterpret_cast<uintptr_t>(text) & 15));
+		unsigned char const *const base16(text - lead);
+		u64 const end(lead + length);
+		u32 const n_tiles(u32((end + v2m::kVcfTileBytes - 1) / v2m::kVcfTileBytes));
+
+		u64 n_lines(0), tail_begin(0);
+		u32 n_newlines(0);
+		{
+			// (one event pair per slice, closed after the slice's last kernel: the callbacks and the chunk's way to the host are not in it,
+			// except, once, those of the chunk before the layout line)
+			std::unique_ptr<timed_launch> tl(new timed_launch(ctx, V2M_KERNEL_VCF));
+			// ---- the line index
+			V2M_HIP_TRY(ctx, ctx->d_vcf_tiles.ensure(n_tiles * sizeof(u32)));
+			V2M_HIP_TRY(ctx, ctx->d_vcf_tile_offsets.ensure((n_tiles + 1) * sizeof(u32)));
+			hipLaunchKernelGGL(v2m::vcf_count_newlines_kernel, dim3(n_tiles), dim3(v2m::kVcfThreads), 0, ctx->stream, base16, lead, end, ctx->d_vcf_tiles.as<u32>());
+			V2M_HIP_TRY(ctx, hipGetLastError());
+			hipLaunchKernelGGL(v2m::vcf_scan_u32_kernel, dim3(1), dim3(v2m::kVcfScanThreads), 0, ctx->stream, ctx->d_vcf_tiles.as<u32>(), n_tiles, ctx->d_vcf_tile_offsets.as<u32>());
+			V2M_HIP_TRY(ctx, hipGetLastError());
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(&n_newlines, ctx->d_vcf_tile_offsets.as<u32>() + n_tiles, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+			V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			V2M_HIP_TRY(ctx, ctx->d_vcf_line_start.ensure((u64(n_newlines) + 2) * sizeof(u32)));
+			// (a last line without '\n' is a line once the input has ended; whether there is one is known from the last line start)
+			hipLaunchKernelGGL(v2m::vcf_line_starts_kernel, dim3(n_tiles), dim3(v2m::kVcfThreads), 0, ctx->stream, base16, lead, end,
+				ctx->d_vcf_tile_offsets.as<u32>(), n_newlines, last ? 1u : 0u, ctx->d_vcf_line_start.as<u32>());
+			V2M_HIP_TRY(ctx, hipGetLastError());
+			{
+				u32 tail(0);
+				V2M_HIP_TRY(ctx, hipMemcpyAsync(&tail, ctx->d_vcf_line_start.as<u32>() + n_newlines, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+				V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+				if (tail > length) return fail(ctx, V2M_ERR_HIP, "VCF scan: a line start lies past the slice");
+				tail_begin = tail;
+			}
+			n_lines = u64(n_newlines) + ((last && tail_begin < length) ? 1 : 0);
+			if (0 == n_lines && !last && length >= slot)
+				return fail(ctx, V2M_ERR_UNSUPPORTED, "VCF line %llu is longer than a slice can hold (%llu bytes)", (unsigned long long) first_line + 1, (unsigned long long) slot);
+
+			if (n_lines) {
+				// ---- heads
+				V2M_HIP_TRY(ctx, ctx->d_vcf_lines.ensure(n_lines * sizeof(v2m_vcf_line)));
+				V2M_HIP_TRY(ctx, ctx->d_vcf_gt_off.ensure(n_lines * sizeof(u32)));
+				V2M_HIP_TRY(ctx, ctx->d_vcf_flags.ensure(n_lines * sizeof(u32)));
+				V2M_HIP_TRY(ctx, ctx->d_vcf_tmp_begin.ensure(n_lines * sizeof(u32)));
+				u32 const nl = u32(n_lines);
+				u32 const *const d_ls(ctx->d_vcf_line_start.as<u32>());
+				v2m_vcf_line *const d_lines(ctx->d_vcf_lines.as<v2m_vcf_line>());
+				hipLaunchKernelGGL(v2m::vcf_head_kernel, dim3((nl + v2m::kVcfLinesPerHeadBlock - 1) / v2m::kVcfLinesPerHeadBlock), dim3(v2m::kVcfThreads), 0, ctx->stream,
+					text, d_ls, nl, ctx->d_vcf_wanted.as<unsigned char>(), wanted_len, d_lines, ctx->d_vcf_gt_off.as<u32>(), ctx->d_vcf_flags.as<u32>());
+				V2M_HIP_TRY(ctx, hipGetLastError());
+
+				// ---- the layout, from the first line on the wanted chromosome
+				u64 layout_at(n_lines);
+				if (!have_layout) {
+					std::vector<u32> flags(n_lines);
+					V2M_HIP_TRY(ctx, hipMemcpyAsync(flags.data(), ctx->d_vcf_flags.p, n_lines * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+					V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					layout_at = 0;
+					while (layout_at < n_lines && !(flags[layout_at] & v2m::kVcfLineOnChromosome)) ++layout_at;
+				}
+
+				// lines [lo, hi) of the slice as one chunk: the genotypes of its candidates, its pools allocated in line order, the callback
+				auto const deliver([&](u64 lo, u64 hi, bool closes) -> int {
+					u32 const cl(u32(hi - lo));
+					u32 const *const c_ls(d_ls + lo);
+					v2m_vcf_line *const c_lines(d_lines + lo);
+					u32 *const c_tmp_begin(ctx->d_vcf_tmp_begin.as<u32>() + lo);
+					u64 totals[2] = {0, 0};
+					if (have_layout) {
+						hipLaunchKernelGGL(v2m::vcf_alloc_scan_kernel, dim3(1), dim3(v2m::kVcfScanThreads), 0, ctx->stream, c_lines, cl, 1u, c_tmp_begin, ctx->d_vcf_totals.as<u64>());
+						V2M_HIP_TRY(ctx, hipGetLastError());
+						V2M_HIP_TRY(ctx, hipMemcpyAsync(totals, ctx->d_vcf_totals.p, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+						V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+						if (totals[0] > u64(cl) * v2m::kVcfMaxAlts) return fail(ctx, V2M_ERR_HIP, "VCF scan: bad candidate column count");
+						V2M_HIP_TRY(ctx, ctx->d_vcf_tmp_columns.ensure(std::max<u64>(16, totals[0] * lay.words_per_column * sizeof(u64))));
+						if (totals[0]) {
+							// the instance whose LDS columns are just wide enough
+							auto const launch([&](auto kernel) {
+								hipLaunchKernelGGL(kernel, dim3(cl), dim3(64), 0, ctx->stream, text, c_ls, cl, c_lines, ctx->d_vcf_gt_off.as<u32>() + lo,
+									c_tmp_begin, view, ctx->d_vcf_tmp_columns.as<u64>());
+							});
+							if (lay.words_per_column <= 4) launch(v2m::vcf_genotype_kernel<4>);
+							else if (lay.words_per_column <= 32) launch(v2m::vcf_genotype_kernel<32>);
+							else if (lay.words_per_column <= 128) launch(v2m::vcf_genotype_kernel<128>);
+							else launch(v2m::vcf_genotype_kernel<v2m::kVcfMaxWordsPerColumn>);
+							V2M_HIP_TRY(ctx, hipGetLastError());
+						}
+					}
+					hipLaunchKernelGGL(v2m::vcf_alloc_scan_kernel, dim3(1), dim3(v2m::kVcfScanThreads), 0, ctx->stream, c_lines, cl, 0u, c_tmp_begin, ctx->d_vcf_totals.as<u64>());
+					V2M_HIP_TRY(ctx, hipGetLastError());
+					V2M_HIP_TRY(ctx, hipMemcpyAsync(totals, ctx->d_vcf_totals.p, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+					V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					u64 const head_bytes(totals[0]), n_columns(totals[1]);
+					if (head_bytes > length || n_columns > u64(cl) * v2m::kVcfMaxAlts || (n_columns && !have_layout)) return fail(ctx, V2M_ERR_HIP, "VCF scan: bad pool sizes");
+					u64 const column_bytes(n_columns * lay.words_per_column * sizeof(u64));
+					V2M_HIP_TRY(ctx, ctx->d_vcf_heads.ensure(std::max<u64>(16, head_bytes)));
+					V2M_HIP_TRY(ctx, ctx->d_vcf_columns.ensure(std::max<u64>(16, column_bytes)));
+					if (!ctx->d_vcf_tmp_columns.p) V2M_HIP_TRY(ctx, ctx->d_vcf_tmp_columns.ensure(16));
+					hipLaunchKernelGGL(v2m::vcf_gather_kernel, dim3(cl), dim3(v2m::kVcfThreads), 0, ctx->stream, text, c_ls, cl, c_lines, c_tmp_begin,
+						ctx->d_vcf_tmp_columns.as<u64>(), u32(lay.words_per_column), head_bytes, n_columns, ctx->d_vcf_heads.as<unsigned char>(), ctx->d_vcf_columns.as<u64>());
+					V2M_HIP_TRY(ctx, hipGetLastError());
+					if (closes) tl.reset();
+
+					u64 const columns_at((u64(cl) * sizeof(v2m_vcf_line) + 15) & ~u64(15)), heads_at(columns_at + ((column_bytes + 15) & ~u64(15)));
+					u64 const out_bytes(heads_at + head_bytes + 16);
+					if (int const rc = ensure_host_slots(ctx, 1, out_bytes)) return rc;
+					wait_released(ctx, *ctx->host_slots[0]);
+					char *const host(ctx->host_slots[0]->host.as<char>());
+					V2M_POISON_HOST(host, out_bytes);
+					V2M_HIP_TRY(ctx, hipMemcpyAsync(host, c_lines, u64(cl) * sizeof(v2m_vcf_line), hipMemcpyDeviceToHost, ctx->stream));
+					if (column_bytes) V2M_HIP_TRY(ctx, hipMemcpyAsync(host + columns_at, ctx->d_vcf_columns.p, column_bytes, hipMemcpyDeviceToHost, ctx->stream));
+					if (head_bytes) V2M_HIP_TRY(ctx, hipMemcpyAsync(host + heads_at, ctx->d_vcf_heads.p, head_bytes, hipMemcpyDeviceToHost, ctx->stream));
+					V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					v2m_vcf_chunk c{};
+					c.first_line = first_line + lo;
+					c.n_lines = cl;
+					c.lines = reinterpret_cast<v2m_vcf_line const *>(host);
+					c.heads = host + heads_at;
+					c.head_bytes = head_bytes;
+					c.columns = reinterpret_cast<u64 const *>(host + columns_at);
+					c.n_columns = n_columns;
+					c.words_per_column = have_layout ? lay.words_per_column : 0;
+					if (0 != chunk(user, &c)) return fail(ctx, V2M_ERR_SINK, "chunk callback asked to stop at line %llu", (unsigned long long) c.first_line);
+					return V2M_OK;
+				});
+
+				if (layout_at < n_lines) {
+					// the lines before the layout line are a chunk of their own: the caller has seen the #CHROM line when `layout` runs
+					if (layout_at) if (int const rc = deliver(0, layout_at, false)) return rc;
+					u32 be[2];
+					V2M_HIP_TRY(ctx, hipMemcpyAsync(be, d_ls + layout_at, sizeof(be), hipMemcpyDeviceToHost, ctx->stream));
+					V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					if (be[0] >= be[1] || be[1] - 1 > length) return fail(ctx, V2M_ERR_HIP, "VCF scan: bad line index");
+					u32 const line_len(be[1] - 1 - be[0]);
+					std::vector<char> line(u64(line_len) + 1);
+					V2M_HIP_TRY(ctx, hipMemcpyAsync(line.data(), text + be[0], line_len, hipMemcpyDeviceToHost, ctx->stream));
+					V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					if (0 != layout(user, first_line + layout_at, line.data(), line_len, &lay)) return fail(ctx, V2M_ERR_SINK, "layout callback asked to stop");
+					if (lay.n_rows > v2m::kVcfMaxRows || lay.words_per_column > v2m::kVcfMaxWordsPerColumn)
+						return fail(ctx, V2M_ERR_UNSUPPORTED, "VCF scan: %u chromosome copies (%llu words per column); at most %u (%u words) are supported", lay.n_rows,
+							(unsigned long long) lay.words_per_column, v2m::kVcfMaxRows, v2m::kVcfMaxWordsPerColumn);
+					if ((lay.n_samples && (!lay.copy_begin || (lay.copy_begin[lay.n_samples] && !lay.row_lookup))) || u64(lay.n_rows) > 64 * lay.words_per_column)
+						return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "VCF scan: incomplete layout");
+					u32 n_copies(0);
+					for (u32 i(0); i < lay.n_samples; ++i) {
+						if (lay.copy_begin[i + 1] < lay.copy_begin[i]) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "VCF scan: copy_begin decreases at sample %u", i);
+						n_copies = lay.copy_begin[i + 1];
+					}
+					for (u32 i(lay.n_samples ? lay.copy_begin[0] : 0); i < n_copies; ++i)
+						if (lay.row_lookup[i] < -1 || lay.row_lookup[i] >= std::int64_t(lay.n_rows)) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "VCF scan: row_lookup[%u] is outside the rows", i);
+					u64 const cb_bytes(((u64(lay.n_samples) + 1) * sizeof(u32) + 15) & ~u64(15));
+					V2M_HIP_TRY(ctx, ctx->d_vcf_layout.ensure(cb_bytes + std::max<u64>(16, u64(n_copies) * sizeof(std::int32_t))));
+					u32 const zero(0);
+					V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vcf_layout.p, lay.n_samples ? lay.copy_begin : &zero, (u64(lay.n_samples) + 1) * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+					if (n_copies) V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vcf_layout.as<char>() + cb_bytes, lay.row_lookup, u64(n_copies) * sizeof(std::int32_t), hipMemcpyHostToDevice, ctx->stream));
+					V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					view.copy_begin = ctx->d_vcf_layout.as<u32>();
+					view.row_lookup = reinterpret_cast<std::int32_t const *>(ctx->d_vcf_layout.as<char>() + cb_bytes);
+					view.n_samples = lay.n_samples;
+					view.n_rows = lay.n_rows;
+					view.words_per_column = u32(lay.words_per_column);
+					have_layout = true;
+					if (int const rc = deliver(layout_at, n_lines, true)) return rc;
+				}
+				else if (int const rc = deliver(0, n_lines, true)) return rc;
+			}
+		}
+
+		// ---- the line the slice ends in goes in front of the next slice's bytes (the other buffer)
+		u64 const next_carry(last ? 0 : length - tail_begin);
+		if (next_carry) {
+			if (next_carry > front) return fail(ctx, V2M_ERR_UNSUPPORTED, "VCF line %llu is longer than a slice can hold (%llu bytes)", (unsigned long long) (first_line + n_lines + 1), (unsigned long long) slot);
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vcf_text[(s + 1) & 1].as<unsigned char>() + front - next_carry, text + tail_begin, next_carry, hipMemcpyDeviceToDevice, ctx->stream));
+		}
+		first_line += n_lines;
+		carry = next_carry;
+		if (last) break;
+	}
+	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return V2M_OK;
 }
 

@@ -33,6 +33,11 @@ def _load():
 		L.v2mh_build_variant_graph.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint, C.c_char_p, C.c_size_t]
 		L.v2mh_build_variant_graph_gpu.restype = C.c_void_p
 		L.v2mh_build_variant_graph_gpu.argtypes = [C.c_void_p] + L.v2mh_build_variant_graph.argtypes
+		L.v2mh_build_variant_graph_scanned.restype = C.c_void_p
+		L.v2mh_build_variant_graph_scanned.argtypes = L.v2mh_build_variant_graph_gpu.argtypes + [C.c_int]
+		L.v2mh_scan_statistics.argtypes = [C.c_void_p, _u64p, _u64p]
+		L.v2mh_scan_lines_host.restype = C.c_int
+		L.v2mh_scan_lines_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
 		L.v2mh_free.argtypes = [C.c_void_p]
 		L.v2mh_graph_from_arrays.restype = C.c_void_p
 		L.v2mh_graph_from_arrays.argtypes = [C.c_uint64, C.c_uint64] + [C.c_void_p] * 5 + [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
@@ -110,6 +115,19 @@ def _has_gzip_magic(path):
 		return False
 
 
+def scan_lines_host(text, wanted_chr, layout=None, slice_bytes=0):
+	"""The host's implementation of the VCF scan rule (csrc/host/readers.cc: scan_lines_host) over plain VCF text: the chunks v2m_vcf_scan
+	gives for the same text and slice size, as Context.vcf_scan returns them.  Returns (code, chunks)."""
+	from . import context as _context
+	from . import _native as N
+	L = _load()
+	text = bytes(text)
+	fn = layout or (lambda _i, line: _context.first_record_layout(line))
+	rc, chunks, _ = _context.collect_vcf_scan(
+		lambda lf, cf: L.v2mh_scan_lines_host(text, len(text), wanted_chr.encode(), slice_bytes, C.cast(lf, C.c_void_p), C.cast(cf, C.c_void_p), None), fn)
+	return rc, chunks
+
+
 def _arr(ptr, n, dtype):
 	if n == 0 or not ptr:
 		return np.zeros(0, dtype=dtype)
@@ -119,14 +137,26 @@ def _arr(ptr, n, dtype):
 class HostGraph:
 	"""Result of the host's build_variant_graph (without the final transpose)."""
 
-	def __init__(self, fasta_path, vcf_path, chr_id, seq_id=None, exclude_sample=None, exclude_copy=-1, threads=0, _graph_file=None, _handle=None, ctx=None):
-		"""ctx: a Context whose GPU inflates BGZF input (either file, recognised by its first bytes); without one, BGZF input is an error."""
+	def __init__(self, fasta_path, vcf_path, chr_id, seq_id=None, exclude_sample=None, exclude_copy=-1, threads=0, _graph_file=None, _handle=None, ctx=None,
+			gpu_parse=False, host_scan=False):
+		"""ctx: a Context whose GPU inflates BGZF input (either file, recognised by its first bytes); without one, BGZF input is an error.
+		gpu_parse (with ctx): the VCF's genotype columns become path bits on the GPU (v2m_vcf_scan), the text never reaches the host.
+		host_scan: the same build through the host's implementation of the scan rule (plain files, no GPU).  Both leave
+		scanned_lines / declined_lines."""
 		L = _load()
 		err = C.create_string_buffer(512)
 		if _handle is not None:
 			h = _handle
 		elif _graph_file is not None:
 			h = L.v2mh_read_graph(str(_graph_file).encode(), err, len(err))
+		elif gpu_parse or host_scan:
+			if gpu_parse and ctx is None:
+				raise ValueError("HostGraph(..., gpu_parse=True) needs ctx=Context(...)")
+			for path in (fasta_path, vcf_path) if ctx is None else ():
+				if _has_gzip_magic(path):
+					raise ValueError("%s is BGZF-compressed: HostGraph(..., ctx=Context(...)) needs a GPU context to inflate it" % path)
+			h = L.v2mh_build_variant_graph_scanned(ctx._h if ctx is not None else None, str(fasta_path).encode(), seq_id.encode() if seq_id else None, str(vcf_path).encode(),
+				chr_id.encode(), exclude_sample.encode() if exclude_sample else None, exclude_copy, threads, err, len(err), 1 if gpu_parse else 2)
 		elif ctx is not None:
 			h = L.v2mh_build_variant_graph_gpu(ctx._h, str(fasta_path).encode(), seq_id.encode() if seq_id else None, str(vcf_path).encode(), chr_id.encode(),
 				exclude_sample.encode() if exclude_sample else None, exclude_copy, threads, err, len(err))
@@ -139,6 +169,9 @@ class HostGraph:
 		if not h:
 			raise ValueError(err.value.decode())
 		self._h = h
+		a, b = C.c_uint64(), C.c_uint64()
+		L.v2mh_scan_statistics(h, C.byref(a), C.byref(b))
+		self.scanned_lines, self.declined_lines = a.value, b.value
 		if True:
 			N, E, S = L.v2mh_node_count(h), L.v2mh_edge_count(h), L.v2mh_sample_count(h)
 			self.ref = C.string_at(L.v2mh_reference(h), L.v2mh_ref_length(h))
