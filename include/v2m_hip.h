@@ -437,7 +437,8 @@ int v2m_bgzf_decompress(v2m_ctx *ctx, const void *src, uint64_t n, void *dst, ui
  *           looked at.
  *   3  otherwise.  Head = the whole line, no columns.  Declining is always safe: the caller parses the line from its text.
  * Every record has head_offset = the head bytes and column_begin = the columns of the chunk's lines before it; n_alts is 0 unless
- * the kind is 2.
+ * the kind is 2.  The chunk's heads are exactly its lines' heads in line order, its n_columns the sum of its lines' n_alts -- also
+ * when words_per_column is 0 (a layout that includes no copy): the columns then have no words, and they are counted all the same.
  *
  * Layout.  The first line that is not of kind 0 and whose column 1 (up to the first tab; without a tab the whole line less a final
  * '\r') is wanted_chr fixes the layout: `layout` is called exactly once, with that line's whole text, before any genotype of its

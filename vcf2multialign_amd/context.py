@@ -71,7 +71,7 @@ def first_record_layout(line, excluded=(), path_alignment=64):
 def collect_vcf_scan(call, layout):
 	"""Runs call(layout_fn, chunk_fn) -- v2m_vcf_scan or the host scanner, which share their callbacks -- and returns (code, chunks, layout
 	line index or None).  A chunk is a dict: first_line, lines (structured array, N.VCF_LINE_DTYPE), heads (bytes), columns (uint64 array
-	[n_columns, words_per_column]), words_per_column.  layout(line_index, line) returns what first_record_layout returns."""
+	[n_columns, words_per_column]), words_per_column, n_columns.  layout(line_index, line) returns what first_record_layout returns."""
 	chunks, keep, seen = [], [], []
 
 	def on_layout(_user, line_index, line, length, out):
@@ -95,7 +95,7 @@ def collect_vcf_scan(call, layout):
 		n_words = c.n_columns * c.words_per_column
 		columns = np.frombuffer(C.string_at(c.columns, 8 * n_words), dtype=np.uint64).copy() if n_words else np.zeros(0, np.uint64)
 		chunks.append(dict(first_line=c.first_line, lines=lines, heads=heads, columns=columns.reshape(c.n_columns, c.words_per_column) if n_words else columns.reshape(0, c.words_per_column),
-			words_per_column=c.words_per_column))
+			words_per_column=c.words_per_column, n_columns=c.n_columns))
 		return 0
 
 	rc = call(N.VCF_LAYOUT_FN(on_layout), N.VCF_CHUNK_FN(on_chunk))

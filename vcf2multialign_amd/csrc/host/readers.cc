@@ -767,6 +767,7 @@ int scan_lines_host(std::string_view text, char const *wanted_chr, std::size_t s
 	std::vector<v2m_vcf_line> lines;
 	std::string heads;
 	std::vector<u64> columns;
+	u64 n_columns(0);                                                 // counted on their own: with words_per_column == 0 the columns have no words
 	auto const flush([&]() -> int {
 		if (lines.empty()) return V2M_OK;
 		v2m_vcf_chunk c{};
@@ -776,13 +777,14 @@ int scan_lines_host(std::string_view text, char const *wanted_chr, std::size_t s
 		c.heads = heads.data();
 		c.head_bytes = heads.size();
 		c.columns = columns.data();
-		c.n_columns = lay.words_per_column ? columns.size() / lay.words_per_column : 0;
+		c.n_columns = n_columns;
 		c.words_per_column = have_layout ? lay.words_per_column : 0;
 		if (0 != chunk(user, &c)) return V2M_ERR_SINK;
 		first_line += lines.size();
 		lines.clear();
 		heads.clear();
 		columns.clear();
+		n_columns = 0;
 		return V2M_OK;
 	});
 	// slices as v2m_vcf_scan cuts plain text: the line the previous slice ended in, then as many new bytes as the slot still holds
@@ -791,6 +793,7 @@ int scan_lines_host(std::string_view text, char const *wanted_chr, std::size_t s
 		lines.clear();
 		heads.clear();
 		columns.clear();
+		n_columns = 0;
 		std::size_t const carry(taken - pos), fresh(std::min(text.size() - taken, slot - std::min(slot, carry)));
 		taken += fresh;
 		bool const last(taken == text.size());
@@ -806,7 +809,7 @@ int scan_lines_host(std::string_view text, char const *wanted_chr, std::size_t s
 
 			v2m_vcf_line r{};
 			r.head_offset = std::uint32_t(heads.size());
-			r.column_begin = lay.words_per_column ? columns.size() / lay.words_per_column : 0;
+			r.column_begin = n_columns;
 			auto const whole([&] { r.head_length = std::uint32_t(line.size()); heads.append(line); });
 			if (line.empty() || '#' == line.front()) {
 				r.kind = 0;
@@ -883,6 +886,7 @@ int scan_lines_host(std::string_view text, char const *wanted_chr, std::size_t s
 				r.n_alts = n_alts;
 				r.head_length = std::uint32_t(tabs[8]);
 				heads.append(line.substr(0, tabs[8]));
+				n_columns += n_alts;
 			} else {
 				columns.resize(columns_before);
 				whole();
