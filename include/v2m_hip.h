@@ -36,6 +36,7 @@
  * sink may keep until it says so).  Entries have only ever been added.  V2M_SPLICE_BGZF, v2m_bgzf_compress, v2m_bgzf_bound and
  * v2m_bgzf_frame_stored were added without a new version, and so were v2m_set_column_window and v2m_window_length, and
  * v2m_bgzf_scan and v2m_bgzf_decompress (with V2M_KERNEL_INFLATE), and v2m_vcf_scan (with V2M_KERNEL_VCF): a caller probes for them by symbol.
+ * The window-set calls (v2m_window_set_layout, v2m_set_window_set, v2m_splice_window_set[_device]) were added the same way.
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -289,6 +290,45 @@ uint64_t v2m_max_unaligned_length(const v2m_ctx *ctx);
 int v2m_set_column_window(v2m_ctx *ctx, uint64_t col_begin, uint64_t col_end);
 /* col_end - col_begin of the window; L without one (0 before an upload). */
 uint64_t v2m_window_length(const v2m_ctx *ctx);
+
+/* ---- window sets ------------------------------------------------------------------------------
+ *
+ * A set of column windows is a third view beside whole rows and the column window: window k is [col_begin[k], col_end[k]) with
+ * 0 <= col_begin[k] < col_end[k] <= L.  Windows may overlap, repeat and come in any order; order k is the caller's and is kept.
+ * One row call splices every window of the set: a row's RECORD is record_pitch bytes, and piece k of it sits at slot_offset[k]:
+ *   slot_offset[0] = 0, slot_offset[k + 1] = slot_offset[k] + (col_end[k] - col_begin[k] rounded up to 16),
+ *   record_pitch = the end of the last slot rounded up to 256 (the v2m_min_row_pitch rule, applied to the record).
+ * The 16 is that of the 16-byte row stores: every slot starts 16-byte aligned relative to its record.
+ * Piece (row, k) is exactly the body that v2m_set_column_window(ctx, col_begin[k], col_end[k]) followed by a row call gives for
+ * that row in the same mode (see "column windows": the aligned slice, the unaligned "emitted bytes whose column lies in the
+ * window", founder rows with cuts, the REF row).  Its length lengths[k] is the window's length in aligned mode and the emitted
+ * count (at most the window's length) in unaligned mode.
+ * What a call may write into a record: aligned, bytes [slot_offset[k], slot_offset[k] + (length of window k rounded up to 16)) --
+ * the tail of the last 16-byte chunk is clobbered; unaligned, bytes [slot_offset[k], slot_offset[k] + lengths[k]) and nothing else.
+ * The set is independent of the column window: the set calls use it whatever v2m_set_column_window says, and v2m_splice_rows,
+ * v2m_splice_rows_held and v2m_splice_rows_device never see it.  v2m_upload_graph drops it.  V2M_SPLICE_BGZF and a held form are
+ * not available through the set calls (V2M_ERR_UNSUPPORTED).
+ * Errors: V2M_ERR_STATE before an upload or when a splice call finds no set; V2M_ERR_INVALID_ARGUMENT for n_windows == 0 or an
+ * empty or out-of-range window (the message names the window's index); V2M_ERR_UNSUPPORTED when the end of the last slot reaches
+ * 2^32 or the tile count does not fit 32 bits (the unaligned kernels keep per-tile destinations in 32 bits); V2M_SPLICE_UNALIGNED
+ * on a graph with a NUL byte refuses as the row calls do. */
+
+/* The layout of a set (context-free, no device needed): slot_offset[n_windows] and *record_pitch.  Only begin < end is checked
+ * here (the aligned length is a context's). */
+int v2m_window_set_layout(uint64_t n_windows, const uint64_t *col_begin, const uint64_t *col_end,
+                          uint64_t *slot_offset /* [n_windows] */, uint64_t *record_pitch);
+/* Makes the windows the context's set (replacing an earlier one).  Synchronous. */
+int v2m_set_window_set(v2m_ctx *ctx, uint64_t n_windows, const uint64_t *col_begin, const uint64_t *col_end);
+uint64_t v2m_window_set_size(const v2m_ctx *ctx);      /* number of windows; 0 when none is set */
+uint64_t v2m_window_set_pitch(const v2m_ctx *ctx);     /* record_pitch of the set; 0 when none is set */
+/* One call per row, in row order: the row's record (piece k at record + slot_offset[k], lengths[k] bytes); both are the
+ * library's and valid for the duration of the call. */
+typedef int (*v2m_window_sink_fn)(void *user, uint64_t row_index, const char *record, const uint32_t *lengths /* [n_windows] */);
+int v2m_splice_window_set(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_window_sink_fn sink, void *user);
+/* Records into device memory: row r's record at d_out + r * record_pitch; record_pitch is any multiple of 16 that is at least
+ * the end of the last slot.  d_out is 16-byte aligned. */
+int v2m_splice_window_set_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, void *d_out, uint64_t record_pitch,
+                                 uint32_t *lengths_out /* host, optional, [n_rows][n_windows] */);
 
 /* ---- founder search: the chunk walks ---------------------------------- */
 

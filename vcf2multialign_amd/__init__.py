@@ -6,6 +6,6 @@ There is no CPU implementation in here.
 """
 
 from ._native import V2M_PLOIDY_MAX, load as load_library  # noqa: F401
-from .context import Context, RowBatch, V2MError, bgzf_bound, bgzf_frame_stored, bgzf_scan, checksum_rows_host  # noqa: F401
+from .context import Context, RowBatch, V2MError, bgzf_bound, bgzf_frame_stored, bgzf_scan, checksum_rows_host, window_set_layout  # noqa: F401
 from .output import FounderSequenceGreedyOutput, HaplotypeOutput  # noqa: F401
 from .variant_graph import PLOIDY_MAX, VariantGraph  # noqa: F401

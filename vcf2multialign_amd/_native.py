@@ -70,6 +70,7 @@ VCF_LINE_DTYPE = [("kind", "<u4"), ("n_alts", "<u4"), ("head_offset", "<u4"), ("
 
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
 HOLD_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p)   # v2m_hold_sink_fn
+WINDOW_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32))   # v2m_window_sink_fn
 TRIALS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_trials_sink
 
 # every symbol include/v2m_hip.h declares: (restype, argtypes)
@@ -93,6 +94,12 @@ SIGNATURES = {
 	"v2m_max_unaligned_length": (C.c_uint64, [C.c_void_p]),
 	"v2m_set_column_window": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
 	"v2m_window_length": (C.c_uint64, [C.c_void_p]),
+	"v2m_window_set_layout": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, _u64p]),
+	"v2m_set_window_set": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+	"v2m_window_set_size": (C.c_uint64, [C.c_void_p]),
+	"v2m_window_set_pitch": (C.c_uint64, [C.c_void_p]),
+	"v2m_splice_window_set": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, WINDOW_SINK_FN, C.c_void_p]),
+	"v2m_splice_window_set_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
 	"v2m_splice_rows": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, SINK_FN, C.c_void_p]),
 	"v2m_splice_rows_held": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint32, HOLD_SINK_FN, C.c_void_p]),
 	"v2m_row_release": (None, [C.c_void_p]),

@@ -232,6 +232,61 @@ class Context:
 		"""v2m_window_length: col_end - col_begin of the column window, the aligned length without one."""
 		return self._lib.v2m_window_length(self._h)
 
+	# ---- window sets ---------------------------------------------------------------------------
+	def set_window_set(self, windows):
+		"""v2m_set_window_set: `windows`, an iterable of (begin, end) column ranges in any order, overlapping or repeated, become the
+		context's window set, which splice_window_set[_device] splice in one launch per row batch.  Independent of set_column_window;
+		a new upload drops it."""
+		begin, end = _window_arrays(windows)
+		self._check(self._lib.v2m_set_window_set(self._h, begin.size, begin.ctypes.data if begin.size else None, end.ctypes.data if end.size else None))
+		self._window_set = (begin, end)
+
+	@property
+	def window_set_size(self):
+		return self._lib.v2m_window_set_size(self._h)
+
+	@property
+	def window_set_layout(self):
+		"""(slot offsets, record pitch) of the window set: piece k of a row sits at offsets[k] of the row's record."""
+		if not self.window_set_size:
+			raise V2MError(N.V2M_ERR_STATE, "no window set")
+		offsets, _ = window_set_layout(zip(*self._window_set))
+		return offsets, int(self._lib.v2m_window_set_pitch(self._h))
+
+	def splice_window_set(self, rows, unaligned=False, bgzf=False):
+		"""v2m_splice_window_set: per row a list of bytes, one per window of the set, each what set_column_window + splice_rows gives
+		for that window.  (bgzf exists to be refused: V2M_ERR_UNSUPPORTED.)"""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = self.window_set_size
+		offsets = self.window_set_layout[0] if n else []
+		collected, error = [], []
+
+		def _cb(_user, _row_index, record, lengths):
+			try:
+				base = record or 0
+				collected.append([C.string_at(base + offsets[k], lengths[k]) if lengths[k] else b"" for k in range(n)])
+				return 0
+			except BaseException as e:  # propagate through the C frame as V2M_ERR_SINK
+				error.append(e)
+				return 1
+
+		flags = (N.V2M_SPLICE_UNALIGNED if unaligned else 0) | (N.V2M_SPLICE_BGZF if bgzf else 0)
+		rc = self._lib.v2m_splice_window_set(self._h, C.byref(rows.struct), flags, N.WINDOW_SINK_FN(_cb), None)
+		if error:
+			raise error[0]
+		self._check(rc)
+		return collected
+
+	def splice_window_set_device(self, rows, d_out, record_pitch, unaligned=False, want_lengths=False):
+		"""v2m_splice_window_set_device: records of record_pitch bytes at d_out; returns the [n_rows, n_windows] lengths when asked."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		lengths = np.zeros((rows.n_rows, self.window_set_size), dtype=np.uint32) if want_lengths else None
+		self._check(self._lib.v2m_splice_window_set_device(self._h, C.byref(rows.struct), N.V2M_SPLICE_UNALIGNED if unaligned else 0,
+			d_out, record_pitch, lengths.ctypes.data if want_lengths and lengths.size else None))
+		return lengths
+
 	# ---- rows ----------------------------------------------------------------------------------
 	def splice_rows(self, rows, sink=None, unaligned=False, bgzf=False):
 		"""v2m_splice_rows.  sink(row_index, body: bytes) is called per row in order; without a sink the
@@ -351,6 +406,26 @@ def _profile_launches(self, kernel):
 
 
 Context.profile_launches = _profile_launches
+
+
+def _window_arrays(windows):
+	pairs = [(int(b), int(e)) for b, e in windows]
+	begin = np.ascontiguousarray([b for b, _ in pairs], dtype=np.uint64)
+	end = np.ascontiguousarray([e for _, e in pairs], dtype=np.uint64)
+	return begin, end
+
+
+def window_set_layout(windows):
+	"""v2m_window_set_layout (host only, no context): (slot offsets, record pitch) of the windows as a set."""
+	lib = N.load()
+	begin, end = _window_arrays(windows)
+	offsets = np.zeros(begin.size, dtype=np.uint64)
+	pitch = C.c_uint64(0)
+	rc = lib.v2m_window_set_layout(begin.size, begin.ctypes.data if begin.size else None, end.ctypes.data if end.size else None,
+		offsets.ctypes.data if begin.size else None, C.byref(pitch))
+	if rc != N.V2M_OK:
+		raise V2MError(rc, lib.v2m_last_error(None).decode(errors="replace"))
+	return [int(o) for o in offsets], pitch.value
 
 
 def bgzf_bound(n):

@@ -5,12 +5,14 @@
 // transpose run on the GPU (there is no CPU path); everything else is host code.
 
 #include <getopt.h>
+#include <sys/resource.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <future>
+#include <map>
 #include <thread>
 #include <iostream>
 #include <memory>
@@ -49,6 +51,7 @@ struct options {
 	bool gpu_parse{};                     // --gpu-parse: the genotype columns of -a become path bits on the GPU (v2m_vcf_scan)
 	char const *region{};                 // --region=START-END: 1-based inclusive positions on the reference sequence
 	std::uint64_t region_start{}, region_end{};
+	char const *regions_file{};           // --regions-file=FILE.bed: one output file per BED region, all spliced as one window set per pass
 	std::vector<int> devices{0};
 };
 
@@ -78,6 +81,13 @@ void usage()
 		"                                     reader gives the plain A2M back; not with --pipe or --output-sequences-separate)\n"
 		"      --region=START-END             Output only the alignment columns of reference positions START..END (1-based,\n"
 		"                                     inclusive, as in samtools/bcftools), with the insertions anchored there\n"
+		"      --regions-file=FILE.bed        Write one file per BED region (chrom, 0-based start, exclusive end, optional name;\n"
+		"                                     tab-separated) into the working directory: <name>.a2m, or <name>.fa with --unaligned,\n"
+		"                                     each holding every sequence cut to the region as -s with --region=<start+1>-<end>\n"
+		"                                     would write it.  Lines of other chromosomes than --chromosome are skipped; a region\n"
+		"                                     without a name is called <chrom>_<start>_<end>.  All regions are spliced together,\n"
+		"                                     one launch per row batch.  Not with --region, -s, --output-sequences-separate,\n"
+		"                                     --pipe, --bgzf or several --device entries\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -182,6 +192,74 @@ bool parse_region(char const *text, std::uint64_t &start, std::uint64_t &end)
 	return number(s.substr(0, dash), start) && number(s.substr(dash + 1), end) && 1 <= start && start <= end;
 }
 
+// One region of --regions-file: reference range [start, end) (0-based, half-open) and the name of its output file.
+struct bed_region {
+	std::string name;
+	std::uint64_t start{}, end{}, line{};
+};
+
+// Reads --regions-file.  Lines that are empty or start with '#', "track" or "browser" are skipped, and so are the lines of other
+// chromosomes than `chromosome` (counted in skipped; without a chromosome every line is taken).  Returns an empty string, or what is
+// wrong with the file -- with the line number where a line is at fault.
+std::string read_regions_file(char const *path, char const *chromosome, std::uint64_t ref_len, std::vector<bed_region> &regions, std::uint64_t &skipped)
+{
+	std::ifstream is(path);
+	if (!is) return std::string("unable to open ") + path;
+	auto const at([&](std::uint64_t line, std::string const &what) { return std::string(path) + " line " + std::to_string(line) + ": " + what; });
+	auto const number([](std::string const &t, std::uint64_t &out) {
+		if (t.empty() || t.size() > 18 || std::string::npos != t.find_first_not_of("0123456789")) return false;
+		out = std::stoull(t);
+		return true;
+	});
+	std::map<std::string, std::uint64_t> seen;
+	std::string text;
+	skipped = 0;
+	for (std::uint64_t line(1); std::getline(is, text); ++line) {
+		if (!text.empty() && '\r' == text.back()) text.pop_back();
+		if (text.empty() || '#' == text[0] || 0 == text.compare(0, 5, "track") || 0 == text.compare(0, 7, "browser")) continue;
+		std::vector<std::string> fields;
+		for (std::size_t pos(0);;) {
+			auto const tab(text.find('\t', pos));
+			fields.push_back(text.substr(pos, std::string::npos == tab ? tab : tab - pos));
+			if (std::string::npos == tab) break;
+			pos = tab + 1;
+		}
+		if (fields.size() < 3) return at(line, "a region needs at least three tab-separated fields (chrom, start, end)");
+		if (chromosome && fields[0] != chromosome) { ++skipped; continue; }
+		bed_region r;
+		r.line = line;
+		if (!number(fields[1], r.start) || !number(fields[2], r.end)) return at(line, "start and end must be non-negative decimal integers, got \"" + fields[1] + "\" and \"" + fields[2] + "\"");
+		if (r.start >= r.end) return at(line, "start " + fields[1] + " is not less than end " + fields[2] + " (0-based start, exclusive end)");
+		if (r.end > ref_len) return at(line, "end " + fields[2] + " is past the end of the reference sequence (" + std::to_string(ref_len) + ")");
+		r.name = fields.size() >= 4 ? fields[3] : fields[0] + "_" + fields[1] + "_" + fields[2];
+		if (r.name.empty() || "." == r.name || ".." == r.name || std::string::npos != r.name.find('/') || std::string::npos != r.name.find('\0'))
+			return at(line, "region name \"" + r.name + "\" cannot name a file (empty, \".\", \"..\", or holding '/' or NUL)");
+		auto const ins(seen.emplace(r.name, line));
+		if (!ins.second) return at(line, "duplicate region name \"" + r.name + "\" (first on line " + std::to_string(ins.first->second) + ")");
+		regions.push_back(std::move(r));
+	}
+	if (regions.empty())
+		return std::string(path) + (chromosome && skipped ? std::string(" holds no region on chromosome \"") + chromosome + "\"" : std::string(" holds no region"));
+	return {};
+}
+
+// Regions per pass of --regions-file: one file is open per region, so as many as the process may have open -- the soft limit is raised
+// to the hard one -- less a margin for everything else it holds.  V2M_REGIONS_PER_PASS overrides (tests).
+std::size_t regions_per_pass()
+{
+	char const *const e(std::getenv("V2M_REGIONS_PER_PASS"));
+	if (e && *e && std::atol(e) > 0) return std::size_t(std::atol(e));
+	struct rlimit lim{};
+	if (0 != ::getrlimit(RLIMIT_NOFILE, &lim)) return 192;
+	if (lim.rlim_cur != lim.rlim_max) {
+		struct rlimit raised(lim);
+		raised.rlim_cur = RLIM_INFINITY == lim.rlim_max ? rlim_t(1) << 20 : lim.rlim_max;
+		if (0 == ::setrlimit(RLIMIT_NOFILE, &raised)) lim = raised;
+	}
+	rlim_t const margin(64);
+	return RLIM_INFINITY == lim.rlim_cur ? (std::size_t(1) << 20) : lim.rlim_cur > 2 * margin ? std::size_t(lim.rlim_cur - margin) : std::size_t(margin);
+}
+
 } // namespace
 
 
@@ -195,7 +273,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -207,7 +285,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -253,6 +331,7 @@ int main(int argc, char **argv)
 			case o_bgzf: opt.bgzf = true; break;
 			case o_gpu_parse: opt.gpu_parse = true; break;
 			case o_region: opt.region = optarg; break;
+			case o_regions_file: opt.regions_file = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -277,6 +356,12 @@ int main(int argc, char **argv)
 	if (opt.bgzf && opt.pipe) { std::cerr << "ERROR: --bgzf cannot be combined with --pipe (the piped command compresses).\n"; return EXIT_FAILURE; }
 	if (opt.bgzf && opt.output_sequences_separate) { std::cerr << "ERROR: --bgzf cannot be combined with --output-sequences-separate.\n"; return EXIT_FAILURE; }
 	if (opt.gpu_parse && !opt.input_variants) { std::cerr << "ERROR: --gpu-parse parses --input-variants; it cannot be combined with --input-graph.\n"; return EXIT_FAILURE; }
+	if (opt.regions_file) {
+		// one file per region, written by one context from one window set per pass: the other ways out do not apply
+		char const *const other(opt.region ? "--region" : opt.output_sequences_a2m ? "-s / --output-sequences-a2m" : opt.output_sequences_separate ? "--output-sequences-separate"
+			: opt.pipe ? "--pipe" : opt.bgzf ? "--bgzf" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
+		if (other) { std::cerr << "ERROR: --regions-file cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+	}
 	if (opt.region && !parse_region(opt.region, opt.region_start, opt.region_end)) {
 		std::cerr << "ERROR: --region must be START-END with 1 <= START <= END (1-based, inclusive), got \"" << opt.region << "\".\n";
 		return EXIT_FAILURE;
@@ -329,6 +414,13 @@ int main(int argc, char **argv)
 		if (opt.region && opt.region_end > ref_seq.size()) {
 			std::cerr << "ERROR: --region end " << opt.region_end << " is past the end of the reference sequence (" << ref_seq.size() << ").\n";
 			return EXIT_FAILURE;
+		}
+		std::vector<bed_region> bed_regions;
+		if (opt.regions_file) {
+			std::uint64_t skipped(0);
+			std::string const problem(read_regions_file(opt.regions_file, opt.chromosome, ref_seq.size(), bed_regions, skipped));
+			if (!problem.empty()) { std::cerr << "ERROR: --regions-file: " << problem << ".\n"; return EXIT_FAILURE; }
+			if (opt.verbose) std::cerr << "Regions file " << opt.regions_file << ": " << bed_regions.size() << " regions taken, " << skipped << " lines of other chromosomes skipped.\n";
 		}
 		// A missing or unusable GPU, or a bad --device, should end the run here, before the variants are parsed, not minutes later.
 		// HIP's start-up takes 0.2 s whether it ends in a context or in an error, so after a reference of any size (100 Mb: 0.07 s
@@ -466,6 +558,18 @@ int main(int argc, char **argv)
 			for (auto *g : all_gpus) g->check(v2m_set_column_window(g->get(), w.begin, w.end));
 		});
 		auto const do_output([&](vh::output &output) {   // main.cc:456-473
+			if (opt.regions_file) {
+				std::vector<vh::output_region> regions;
+				for (auto const &r : bed_regions) {
+					auto const w(vh::columns_of_reference_range(graph, ref_seq.size(), r.start, r.end));
+					regions.push_back({r.name, w.begin, w.end});
+				}
+				std::size_t const per_pass(regions_per_pass());
+				std::cerr << "Outputting " << regions.size() << " regions, one file each..." << std::flush;
+				if (opt.verbose) std::cerr << " (" << (regions.size() + per_pass - 1) / per_pass << " passes of at most " << per_pass << " regions)" << std::flush;
+				output.output_regions(graph, regions, per_pass);
+				std::cerr << " Done.\n";
+			}
 			if (opt.output_sequences_a2m) {
 				std::cerr << "Outputting sequences as A2M...\n";
 				output.output_a2m(graph, opt.output_sequences_a2m);

@@ -543,6 +543,72 @@ void output::write_separate(row_set const &rows)
 
 
 namespace {
+	struct regions_state {
+		std::vector<std::ofstream> *files;
+		std::vector<std::uint64_t> const *slot_offset;
+		std::vector<std::string> const *ids;
+		output_delegate *delegate;          // told about the rows on the last pass only
+	};
+
+	int regions_sink(void *user, uint64_t row, char const *record, uint32_t const *lengths)
+	{
+		auto &st(*static_cast<regions_state *>(user));
+		auto const &id((*st.ids)[row]);
+		for (std::size_t k(0); k < st.files->size(); ++k) {
+			auto &os((*st.files)[k]);
+			os << '>' << id << '\n';                                           // as a2m_sink writes a row
+			os.write(record + (*st.slot_offset)[k], std::streamsize(lengths[k]));
+			os << '\n';
+			if (!os.good()) return 1;
+		}
+		if (st.delegate) st.delegate->handled_sequences(u32(1 + row));
+		return 0;
+	}
+}
+
+
+void output::output_regions(variant_graph const &graph, std::vector<output_region> const &regions, std::size_t regions_per_pass)
+{
+	row_set const rows(a2m_rows(graph));
+	v2m_row_batch batch{};
+	batch.n_rows = rows.copy_index.size();
+	batch.copy_index = rows.copy_index.data();
+	std::vector<std::uint32_t> rebased;
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) {
+		rebased = rebased_copies(rows, 0, rows.copy_index.size(), m_copy_shards.front());
+		batch.copy_index = rebased.data();
+	}
+	if (rows.any_cuts) {
+		batch.cut_offsets = rows.cut_offsets.data();
+		batch.cut_nodes = rows.cut_nodes.data();
+		batch.cut_copies = rows.cut_copies.data();
+	}
+	char const *const suffix(m_should_output_unaligned ? ".fa" : ".a2m");
+	std::size_t const per_pass(std::max<std::size_t>(1, regions_per_pass));
+	for (std::size_t first(0); first < regions.size(); first += per_pass) {
+		std::size_t const n(std::min(per_pass, regions.size() - first));
+		std::vector<std::uint64_t> begin(n), end(n), slot_offset(n);
+		for (std::size_t k(0); k < n; ++k) { begin[k] = regions[first + k].col_begin; end[k] = regions[first + k].col_end; }
+		std::uint64_t pitch(0);
+		if (V2M_OK != v2m_window_set_layout(n, begin.data(), end.data(), slot_offset.data(), &pitch)) throw std::runtime_error(v2m_last_error(nullptr));
+		m_gpu.check(v2m_set_window_set(m_gpu.get(), n, begin.data(), end.data()));
+		std::vector<std::ofstream> files(n);
+		for (std::size_t k(0); k < n; ++k) {
+			std::string const name(regions[first + k].name + suffix);
+			files[k].open(name, std::ios::binary | std::ios::trunc);
+			if (!files[k]) throw std::runtime_error("unable to open " + name + " for writing");
+		}
+		regions_state st{&files, &slot_offset, &rows.ids, first + n == regions.size() ? m_delegate : nullptr};
+		m_gpu.check(v2m_splice_window_set(m_gpu.get(), &batch, m_should_output_unaligned ? V2M_SPLICE_UNALIGNED : 0u, regions_sink, &st));
+		for (std::size_t k(0); k < n; ++k) {
+			files[k].close();
+			if (!files[k]) throw std::runtime_error("error while writing " + regions[first + k].name + suffix);
+		}
+	}
+}
+
+
+namespace {
 	// One shard of an aligned A2M file: rows [first, first + n) of the batch, written at precomputed file offsets.
 	struct shard_state {
 		int fd;

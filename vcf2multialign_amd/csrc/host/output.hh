@@ -29,6 +29,12 @@ struct null_output_delegate final : output_delegate {
 	void handled_sequences(u32) override {}
 };
 
+// One region of --regions-file: alignment columns [col_begin, col_end) go to the file `name` + ".a2m" (".fa" unaligned).
+struct output_region {
+	std::string name;
+	u64 col_begin{}, col_end{};
+};
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -63,6 +69,12 @@ public:
 	// Only output_a2m() uses it; with several contexts the rows take the interleaved path (set_copy_interleave()), never the sharded
 	// one, whose file offsets are known up front.
 	void set_bgzf(bool bgzf) { m_bgzf = bgzf; }
+
+	// --regions-file: one file per region in the working directory, each holding every row of the A2M output (same order, same
+	// identifiers) cut to the region's columns -- byte for byte what output_a2m() writes under that region's column window.  The
+	// regions of a pass are one window set (include/v2m_hip.h, "window sets") spliced in one call; a pass holds at most
+	// regions_per_pass regions (as many files are open at once), more regions take more passes.  First context only.
+	void output_regions(variant_graph const &graph, std::vector<output_region> const &regions, std::size_t regions_per_pass);
 	virtual void output_a2m(variant_graph const &graph, std::ostream &stream) = 0;
 
 protected:

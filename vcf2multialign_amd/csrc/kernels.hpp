@@ -972,17 +972,15 @@ __global__ __launch_bounds__(64 * kWaves) void transpose_bits_rot_kernel(
 // graph; every aligned output row equals it outside the spans of its effective ALT edges.
 // One thread per 16 output bytes; bytes past L are zero.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void expand_reference_row_kernel(
+// Columns [p0, p0 + 16) of the REF row; the bytes from column L on are `past`.
+__device__ __forceinline__ uint4 expand_reference_chunk(
 	char const *__restrict__ ref, u32 const *__restrict__ ref_pos, u32 const *__restrict__ aln_pos,
-	u32 n_nodes, u32 L, u64 n_chunks, uint4 *__restrict__ out, char gap, u32 col_base = 0)
+	u32 n_nodes, u32 L, u64 p0, char gap, unsigned char past)
 {
-	u64 const c = (u64) blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= n_chunks) return;
-	u64 const p0 = col_base + c * 16;   // a column window's template starts at its first column (L is then the window's end)
 	unsigned char bytes[16];
 	if (p0 >= L) {
-		out[c] = make_uint4(0, 0, 0, 0);
-		return;
+		u32 const w = past * 0x01010101u;
+		return make_uint4(w, w, w, w);
 	}
 	// node containing p0: last n with aln_pos[n] <= p0
 	u32 lo = 0, hi = n_nodes;   // invariant: aln_pos[lo] <= p0 < aln_pos[hi] (hi == n_nodes means +inf)
@@ -997,7 +995,7 @@ __global__ __launch_bounds__(256) void expand_reference_row_kernel(
 #pragma unroll
 	for (int b = 0; b < 16; ++b) {
 		u64 const p = p0 + b;
-		unsigned char v = 0;
+		unsigned char v = past;
 		if (p < L) {
 			while (p >= a1) {
 				++n;
@@ -1015,7 +1013,46 @@ __global__ __launch_bounds__(256) void expand_reference_row_kernel(
 	o.y = bytes[4] | (bytes[5] << 8) | (bytes[6] << 16) | ((u32) bytes[7] << 24);
 	o.z = bytes[8] | (bytes[9] << 8) | (bytes[10] << 16) | ((u32) bytes[11] << 24);
 	o.w = bytes[12] | (bytes[13] << 8) | (bytes[14] << 16) | ((u32) bytes[15] << 24);
-	out[c] = o;
+	return o;
+}
+
+__global__ __launch_bounds__(256) void expand_reference_row_kernel(
+	char const *__restrict__ ref, u32 const *__restrict__ ref_pos, u32 const *__restrict__ aln_pos,
+	u32 n_nodes, u32 L, u64 n_chunks, uint4 *__restrict__ out, char gap, u32 col_base = 0)
+{
+	u64 const c = (u64) blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= n_chunks) return;
+	u64 const p0 = col_base + c * 16;   // a column window's template starts at its first column (L is then the window's end)
+	out[c] = expand_reference_chunk(ref, ref_pos, aln_pos, n_nodes, L, p0, gap, 0);
+}
+
+// The tiles of a window set (v2m_set_window_set), numbered across the windows in set order: window k contributes
+// ceil(len_k / kTileBytes) tiles, its tile j is columns begin_k + j * kTileBytes on, clipped to end_k.  Per tile: its columns
+// [col_begin, col_end), the byte offset of its first column in a row's record (slot_offset[k] + j * kTileBytes, a multiple of 16),
+// and the end of the edge range that begins in it (tile_tables::edge_begin[t + 1] is the NEXT tile's begin, which in a set is a
+// tile somewhere else).  The template of a set is the REF row in the record's layout, so the record offset addresses it too.
+struct set_tile_tables {
+	u32 const *col_begin;      // [n_tiles]
+	u32 const *col_end;        // [n_tiles]
+	u32 const *record_offset;  // [n_tiles]
+	u32 const *edge_end;       // [n_tiles]
+};
+
+// The REF row in the record layout of a window set: one thread per 16-B chunk of the record up to the end of the last slot.  The
+// chunk's tile is the last one whose record offset is not past it; every slot is padded to its 16-B capacity with `gap`.
+__global__ __launch_bounds__(256) void expand_reference_set_kernel(
+	char const *__restrict__ ref, u32 const *__restrict__ ref_pos, u32 const *__restrict__ aln_pos,
+	u32 n_nodes, set_tile_tables st, u32 n_tiles, u64 n_chunks, uint4 *__restrict__ out, char gap)
+{
+	u64 const c = (u64) blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= n_chunks) return;
+	u32 lo = 0, hi = n_tiles;   // invariant: record_offset[lo] <= 16 c < record_offset[hi] (hi == n_tiles means +inf)
+	while (hi - lo > 1) {
+		u32 const mid = lo + (hi - lo) / 2;
+		if ((u64) st.record_offset[mid] <= c * 16) lo = mid; else hi = mid;
+	}
+	u64 const p0 = (u64) st.col_begin[lo] + (c * 16 - st.record_offset[lo]);
+	out[c] = expand_reference_chunk(ref, ref_pos, aln_pos, n_nodes, st.col_end[lo], p0, gap, (unsigned char) gap);
 }
 
 
@@ -1443,17 +1480,25 @@ __device__ __forceinline__ void load_eff_cache(
 
 // kWindow: the tiles are those of the column window [col_base, col_end) (tile t = columns col_base + t * kTileBytes on, clipped to
 // col_end); without it tile t is columns t * kTileBytes on and col_base / col_end are not read.
-template <bool kWindow = false>
+// kSet (with kWindow: spans are clipped to the tile's end): the tiles are those of a window set, each with columns and an edge range
+// of its own in `st` (set_tile_tables), and col_base / col_end are not read.
+template <bool kWindow = false, bool kSet = false>
 __device__ __forceinline__ void load_patch_cache(
 	patch_cache &pc, tile_job &job, tile_tables const &tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
-	u64 const *__restrict__ eff, u64 eff_words_per_row, u32 tile, u32 row_begin, u32 n_group_rows, int t, u32 col_base = 0, u32 col_end = 0)
+	u64 const *__restrict__ eff, u64 eff_words_per_row, u32 tile, u32 row_begin, u32 n_group_rows, int t, u32 col_base = 0, u32 col_end = 0,
+	set_tile_tables const st = set_tile_tables{})
 {
-	job.tile_base = (kWindow ? col_base : 0u) + tile * (u32) kTileBytes;
-	job.tile_end = (kWindow && col_end - job.tile_base < (u32) kTileBytes) ? col_end : job.tile_base + kTileBytes;
+	if (kSet) {
+		job.tile_base = st.col_begin[tile];
+		job.tile_end = st.col_end[tile];
+	} else {
+		job.tile_base = (kWindow ? col_base : 0u) + tile * (u32) kTileBytes;
+		job.tile_end = (kWindow && col_end - job.tile_base < (u32) kTileBytes) ? col_end : job.tile_base + kTileBytes;
+	}
 	job.cross_begin = tt.cross_offsets[tile];
 	job.n_cross = tt.cross_offsets[tile + 1] - job.cross_begin;
 	job.range_begin = tt.edge_begin[tile];
-	job.n_range = tt.edge_begin[tile + 1] - job.range_begin;
+	job.n_range = (kSet ? st.edge_end[tile] : tt.edge_begin[tile + 1]) - job.range_begin;
 	job.n_lds = job.n_range < (u32) kCandLds ? job.n_range : (u32) kCandLds;
 	job.w0 = job.range_begin >> 6;
 	if (job.n_lds) {
@@ -1616,12 +1661,20 @@ __device__ __forceinline__ void map_block(u32 b, u32 n_groups, u32 n_tiles, u32 
 	tile = t0 + within % run;
 }
 
-template <bool kNonTemporal, bool kWindow>
+// The 16-B chunks of tile `tile` of a window set: most tiles of a set are far shorter than kTileBytes, and every loop over a tile's
+// chunks covers only these.  That is correctness, not tuning: the set's template is the record, so past a short tile's chunks lie the
+// NEXT window's bytes, not padding.  Workgroup-uniform.
+__device__ __forceinline__ u32 set_tile_chunks(set_tile_tables const &st, u32 tile)
+{
+	return (st.col_end[tile] - st.col_begin[tile] + 15u) >> 4;
+}
+
+template <bool kNonTemporal, bool kWindow, bool kSet = false>
 __device__ __forceinline__ void splice_aligned_tiles(
 	vec4u const *__restrict__ tmpl, u64 const *__restrict__ eff, u64 eff_words_per_row,
 	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
 	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 n_tiles, u32 tile_run,
-	u64 store_limit, char gap, u32 col_base, u32 col_end)
+	u64 store_limit, char gap, u32 col_base, u32 col_end, set_tile_tables const st = set_tile_tables{})
 {
 	__shared__ vec4u lds[2][kTileChunks];
 	__shared__ patch_cache pc;
@@ -1634,13 +1687,18 @@ __device__ __forceinline__ void splice_aligned_tiles(
 	V2M_POISON_LDS(lds);
 	V2M_POISON_LDS(pc);
 
+	// (a set: the tile's chunks and where they sit in the record -- and in the template, which has the record's layout)
+	u32 const n_chunks = kSet ? set_tile_chunks(st, tile) : (u32) kTileChunks;
+	u32 const record_offset = kSet ? st.record_offset[tile] : 0u;
 	vec4u pristine[kChunksPerThread];
 #pragma unroll
-	for (int k = 0; k < kChunksPerThread; ++k)
-		pristine[k] = tmpl[(u64) tile * kTileChunks + t + kSpliceThreads * k];
+	for (int k = 0; k < kChunksPerThread; ++k) {
+		if (kSet) pristine[k] = (u32) (t + kSpliceThreads * k) < n_chunks ? tmpl[(record_offset >> 4) + t + kSpliceThreads * k] : vec4u{0, 0, 0, 0};
+		else pristine[k] = tmpl[(u64) tile * kTileChunks + t + kSpliceThreads * k];
+	}
 
 	tile_job job;
-	load_patch_cache<kWindow>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end);
+	load_patch_cache<kWindow, kSet>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end, st);
 	u32 const tile_base = job.tile_base;
 
 	for (u32 row = row_begin; row < row_end; ++row) {
@@ -1653,16 +1711,17 @@ __device__ __forceinline__ void splice_aligned_tiles(
 			load_eff_cache(pc, job, eff, eff_words_per_row, row, row_end - row, t);
 #pragma unroll
 		for (int k = 0; k < kChunksPerThread; ++k)
-			buf[t + kSpliceThreads * k] = pristine[k];
+			if (!kSet || (u32) (t + kSpliceThreads * k) < n_chunks) buf[t + kSpliceThreads * k] = pristine[k];
 		__syncthreads();
 
 		patch_row_tile<kWindow>((unsigned char *) buf, pc, job, tt, patches, labels, eff + (u64) row * eff_words_per_row, cached_row, t, gap);
 
-		char *const dst = out + (u64) row * row_pitch + (u64) tile * kTileBytes;
+		char *const dst = out + (u64) row * row_pitch + (kSet ? (u64) record_offset : (u64) tile * kTileBytes);
 #pragma unroll
 		for (int k = 0; k < kChunksPerThread; ++k) {
 			int const c = t + kSpliceThreads * k;
-			if ((kWindow ? (u64) tile * kTileBytes : (u64) tile_base) + (u64) c * 16 < store_limit) {
+			// (a set: the tile's own chunks, whose stores stay inside the window's slot)
+			if (kSet ? (u32) c < n_chunks : (kWindow ? (u64) tile * kTileBytes : (u64) tile_base) + (u64) c * 16 < store_limit) {
 				vec4u const nv = buf[c];
 				if (kNonTemporal)
 					__builtin_nontemporal_store(nv, (vec4u *) (dst + c * 16));
@@ -1698,6 +1757,20 @@ __global__ __launch_bounds__(kSpliceThreads) void splice_aligned_window_kernel(
 {
 	splice_aligned_tiles<kNonTemporal, true>(tmpl, eff, eff_words_per_row, tt, patches, labels, out, row_pitch, n_rows, rows_per_group, n_groups,
 		n_tiles, tile_run, store_limit, gap, col_base, col_end);
+}
+
+// The same for the tiles of a window set (v2m_set_window_set): `out` holds records of row_pitch bytes, tmpl is the REF row in the
+// record's layout, tt and st are the set's tile tables.  A tile's columns, its edge range's end and its place in the record are read
+// per tile; a tile stores its own chunks only (workgroups of neighbouring windows run concurrently: a store that left its slot
+// would be a race).
+template <bool kNonTemporal>
+__global__ __launch_bounds__(kSpliceThreads) void splice_aligned_set_kernel(
+	vec4u const *__restrict__ tmpl, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, set_tile_tables st, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 n_tiles, u32 tile_run, char gap)
+{
+	splice_aligned_tiles<kNonTemporal, true, true>(tmpl, eff, eff_words_per_row, tt, patches, labels, out, row_pitch, n_rows, rows_per_group, n_groups,
+		n_tiles, tile_run, 0, gap, 0u, 0u, st);
 }
 
 
@@ -1774,12 +1847,12 @@ __device__ __forceinline__ u32 count_nonzero_bytes(unsigned char const *tile, u3
 constexpr int kCountRowsMax = 256;   // rows per group the count kernel can hold (host clamps rows_per_group)
 constexpr int kCandDeltaLds = 1024;  // candidates per tile whose (row-independent) count change is kept in LDS
 
-template <bool kWindow>
+template <bool kWindow, bool kSet = false>
 __device__ __forceinline__ void count_unaligned_tiles(
 	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
 	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
 	u32 *__restrict__ tile_counts /* [n_rows][n_tiles] */, u32 n_tiles,
-	u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end)
+	u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end, set_tile_tables const st = set_tile_tables{})
 {
 	__shared__ vec4u lds[kTileChunks];        // the pristine template tile, shared by all rows of the group
 	__shared__ patch_cache pc;
@@ -1798,10 +1871,12 @@ __device__ __forceinline__ void count_unaligned_tiles(
 	V2M_POISON_LDS(cand_delta);
 	V2M_POISON_LDS(wave_sums);
 
+	u32 const n_chunks = kSet ? set_tile_chunks(st, tile) : (u32) kTileChunks;   // (a set: only the tile's own chunks are loaded, kept and counted)
 	u32 mine = 0;
 #pragma unroll
 	for (int k = 0; k < kChunksPerThread; ++k) {
-		vec4u const v = tmpl0[(u64) tile * kTileChunks + t + kSpliceThreads * k];
+		if (kSet && (u32) (t + kSpliceThreads * k) >= n_chunks) continue;
+		vec4u const v = tmpl0[(kSet ? (u64) (st.record_offset[tile] >> 4) : (u64) tile * kTileChunks) + t + kSpliceThreads * k];
 		lds[t + kSpliceThreads * k] = v;
 #pragma unroll
 		for (int d = 0; d < 4; ++d)
@@ -1813,7 +1888,7 @@ __device__ __forceinline__ void count_unaligned_tiles(
 	for (u32 r = t; r < (u32) kCountRowsMax; r += kSpliceThreads) row_delta[r] = 0;
 
 	tile_job job;
-	load_patch_cache<kWindow>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end);
+	load_patch_cache<kWindow, kSet>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end, st);
 	__syncthreads();
 	u32 tile_count = 0;
 #pragma unroll
@@ -1895,6 +1970,16 @@ __global__ __launch_bounds__(kSpliceThreads) void count_unaligned_window_kernel(
 	u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end)
 {
 	count_unaligned_tiles<true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_counts, n_tiles, n_rows, rows_per_group, n_groups, tile_run, col_base, col_end);
+}
+
+// The same over the tiles of a window set (as splice_aligned_set_kernel; tmpl0 = the REF row in the record's layout with 0 as padding).
+__global__ __launch_bounds__(kSpliceThreads) void count_unaligned_set_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, set_tile_tables st, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 *__restrict__ tile_counts /* [n_rows][n_tiles] */, u32 n_tiles,
+	u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
+{
+	count_unaligned_tiles<true, true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_counts, n_tiles, n_rows, rows_per_group, n_groups, tile_run, 0u, 0u, st);
 }
 
 // v_perm_b32 selector that moves the bytes of a dword named by the 4-bit mask `keep` to its low end, in order (0x0c = a
@@ -2121,12 +2206,13 @@ __device__ __forceinline__ void pack_chunk_and_store_exact(vec4u const x, u32 co
 // chunks no longer fit the queue (tiles inside long insertions) are packed where they are by their own wave.
 // Measured (profiles/r05/unaligned_shared_pack.txt): config 5 11.5 -> 10.95 ms per 244 rows (aligned kernel, same rows: 9.03), VALU 308 -> 256, SALU 213 -> ~156
 // per wave and row tile (the scans in lockstep took the rest); config 3 within what two boxes differ by.
-template <bool kNonTemporal, u32 kQueue, bool kWindow>
+template <bool kNonTemporal, u32 kQueue, bool kWindow, bool kSet = false>
 __device__ __forceinline__ void splice_unaligned_tiles(
 	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
 	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
 	u32 const *__restrict__ tile_offsets /* [n_rows][n_tiles]: where each tile's bytes start in its row */, u32 n_tiles,
-	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end)
+	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run, u32 col_base, u32 col_end,
+	set_tile_tables const st = set_tile_tables{})
 {
 	constexpr int kWaves = kSpliceThreads / 64, kSlots = kChunksPerThread * kWaves;
 	// kQueue: short chunks of a row tile that wait for the packing wave(s)
@@ -2159,13 +2245,18 @@ __device__ __forceinline__ void splice_unaligned_tiles(
 	u32 const row_begin = group * rows_per_group;
 	u32 const row_end = (row_begin + rows_per_group < n_rows) ? row_begin + rows_per_group : n_rows;
 
+	// (a set: the chunks past the tile's own are neither loaded nor put into LDS, and enter the scan below as zero -- in the set's template
+	// they are the next window's bytes)
+	u32 const n_chunks = kSet ? set_tile_chunks(st, tile) : (u32) kTileChunks;
 	vec4u pristine[kChunksPerThread];
 #pragma unroll
-	for (int k = 0; k < kChunksPerThread; ++k)
-		pristine[k] = tmpl0[(u64) tile * kTileChunks + t + kSpliceThreads * k];
+	for (int k = 0; k < kChunksPerThread; ++k) {
+		if (kSet) pristine[k] = (u32) (t + kSpliceThreads * k) < n_chunks ? tmpl0[(st.record_offset[tile] >> 4) + t + kSpliceThreads * k] : vec4u{0, 0, 0, 0};
+		else pristine[k] = tmpl0[(u64) tile * kTileChunks + t + kSpliceThreads * k];
+	}
 
 	tile_job job;
-	load_patch_cache<kWindow>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end);
+	load_patch_cache<kWindow, kSet>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t, col_base, col_end, st);
 
 	char *dst_prev = out;
 	for (u32 row = row_begin; ; ++row) {                                      // (one round more than there are rows: the last one only packs the last row's queue)
@@ -2176,7 +2267,7 @@ __device__ __forceinline__ void splice_unaligned_tiles(
 				load_eff_cache(pc, job, eff, eff_words_per_row, row, row_end - row, t);
 #pragma unroll
 			for (int k = 0; k < kChunksPerThread; ++k)
-				lds[t + kSpliceThreads * k] = pristine[k];
+				if (!kSet || (u32) (t + kSpliceThreads * k) < n_chunks) lds[t + kSpliceThreads * k] = pristine[k];
 		}
 		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                  // (the previous row's queue writes precede this barrier across the loop's back edge)
 		__syncthreads();
@@ -2204,7 +2295,10 @@ __device__ __forceinline__ void splice_unaligned_tiles(
 		vec4u v[kChunksPerThread];
 		u32 mine[kChunksPerThread], incl[kChunksPerThread];
 #pragma unroll
-		for (int k = 0; k < kChunksPerThread; ++k) v[k] = lds[t + kSpliceThreads * k];
+		for (int k = 0; k < kChunksPerThread; ++k) {
+			if (kSet) v[k] = (u32) (t + kSpliceThreads * k) < n_chunks ? lds[t + kSpliceThreads * k] : vec4u{0, 0, 0, 0};
+			else v[k] = lds[t + kSpliceThreads * k];
+		}
 #pragma unroll
 		for (int k = 0; k < kChunksPerThread; ++k) {
 			u32 bytes = 0;
@@ -2289,6 +2383,20 @@ __global__ __launch_bounds__(kSpliceThreads) void splice_unaligned_window_kernel
 {
 	splice_unaligned_tiles<kNonTemporal, 128, true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_offsets, n_tiles, out, row_pitch,
 		n_rows, rows_per_group, n_groups, tile_run, col_base, col_end);
+}
+
+// The same over the tiles of a window set (as splice_aligned_set_kernel).  tile_offsets are those of scan_window_set_kernel: a tile's
+// bytes go to its window's slot, behind the bytes of the window's tiles before it.  Every store is exact (a 16-B store only for a chunk
+// with 16 surviving bytes), so nothing outside [slot_offset, slot_offset + length) of a piece is written.
+template <bool kNonTemporal>
+__global__ __launch_bounds__(kSpliceThreads) void splice_unaligned_set_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, set_tile_tables st, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 const *__restrict__ tile_offsets, u32 n_tiles,
+	char *__restrict__ out, u64 row_pitch, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
+{
+	splice_unaligned_tiles<kNonTemporal, 128, true, true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_offsets, n_tiles, out, row_pitch,
+		n_rows, rows_per_group, n_groups, tile_run, 0u, 0u, st);
 }
 
 // Exclusive prefix sum of the per-tile byte counts of each row (in place) and the row lengths.
@@ -2385,6 +2493,29 @@ __global__ __launch_bounds__(256) void checksum_rows_kernel(
 	}
 	if ((threadIdx.x & 63) == 0 && acc)
 		atomicAdd(&sums[row], (unsigned long long) acc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Window sets: the scan of scan_tile_counts_kernel segmented at each window's first tile.  From a row's exclusive prefix sums over
+// all tiles of the set (tile_prefix, with the row's total in row_totals): the destination of tile t in the record, slot_offset[k] +
+// the bytes of window k's tiles before t, and the length of every (row, window) piece.  One workgroup per row.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void scan_window_set_kernel(
+	u32 const *__restrict__ tile_prefix /* [n_rows][n_tiles] */, u64 const *__restrict__ row_totals, u32 n_tiles, u32 n_windows,
+	u32 const *__restrict__ window_first_tile /* [n_windows + 1] */, u32 const *__restrict__ tile_window /* [n_tiles] */,
+	u32 const *__restrict__ slot_offset /* [n_windows] */,
+	u32 *__restrict__ tile_offsets /* [n_rows][n_tiles] */, u32 *__restrict__ lengths /* [n_rows][n_windows] */)
+{
+	u32 const *const prefix = tile_prefix + (u64) blockIdx.x * n_tiles;
+	u32 const total = (u32) row_totals[blockIdx.x];
+	for (u32 t = threadIdx.x; t < n_tiles; t += 256) {
+		u32 const k = tile_window[t];
+		tile_offsets[(u64) blockIdx.x * n_tiles + t] = slot_offset[k] + (prefix[t] - prefix[window_first_tile[k]]);
+	}
+	for (u32 k = threadIdx.x; k < n_windows; k += 256) {
+		u32 const end = k + 1 < n_windows ? prefix[window_first_tile[k + 1]] : total;
+		lengths[(u64) blockIdx.x * n_windows + k] = end - prefix[window_first_tile[k]];
+	}
 }
 
 } // namespace v2m

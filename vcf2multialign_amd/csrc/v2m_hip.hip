@@ -200,8 +200,22 @@ struct v2m_ctx {
 	// and the window's is in force only while `windowed`, which also picks the window instances of the splice kernels
 	row_view whole, window;
 	bool windowed{};
-	row_view &view() { return windowed ? window : whole; }
-	row_view const &view() const { return windowed ? window : whole; }
+	row_view &view() { return set_call ? set.view : windowed ? window : whole; }
+	row_view const &view() const { return set_call ? set.view : windowed ? window : whole; }
+
+	// The window set (v2m_set_window_set): a third view, in force only inside the set calls (`set_call`), which the row calls never see.
+	// Its "columns" are a record's bytes up to the end of the last slot; its tiles are numbered across the windows in set order and carry
+	// their columns, edge range end and record offset in tables of their own (kernels.hpp: set_tile_tables); the scan of the unaligned
+	// tile counts is segmented by tile_window / first_tile / slot_offset32.
+	struct window_set {
+		row_view view;
+		u64 n_windows{}, pitch{}, mean_tile_bytes{};
+		std::vector<u32> lengths;           // [n_windows] the windows' lengths: every row's lengths in aligned mode
+		dev_buf d_col_begin, d_col_end, d_record_offset, d_edge_end, d_tile_window, d_first_tile, d_slot_offset32;
+	} set;
+	bool has_set{}, set_call{};
+	scratch_buf d_set_tile_offsets, d_set_lengths[2];   // unaligned: the tiles' destinations; [rows][n_windows] lengths of a slice, two in turn (s & 1)
+	int set_lengths_slot{};
 
 	// paths_by_chrom_copy_and_edge
 	u64 const *d_paths{};
@@ -810,6 +824,20 @@ u32 rows_per_group_for(u64 n_rows)
 }
 
 
+// Rows per workgroup over the tiles of a window set.  A workgroup pays its prologue (the tile tables, load_patch_cache, the first effective-
+// edge words: a chain of dependent L2 / HBM round trips) once per group whatever the tile's length, and a 300-byte tile gives it next to
+// nothing to store per row.  So a group takes as many rows as keep the bytes it writes at what 32 rows of a full tile come to
+// (32 * kTileBytes / mean tile length), up to the 256 rows the count kernel holds (V2M_ROWS_PER_GROUP's ceiling as well).  A guess
+// until measured.  V2M_ROWS_PER_GROUP overrides it as everywhere.
+u32 rows_per_group_for_set(u64 n_rows, u64 mean_tile_bytes)
+{
+	char const *e = std::getenv("V2M_ROWS_PER_GROUP");
+	if (e && *e && std::atoi(e) > 0) return rows_per_group_for(n_rows);
+	u64 const by_bytes(32 * u64(v2m::kTileBytes) / std::max<u64>(1, mean_tile_bytes));
+	return u32(std::min<u64>(std::max<u64>(1, n_rows), std::min<u64>(256, std::max<u64>(32, by_bytes))));
+}
+
+
 // The REF row of a view with `gap` as padding ('-', or 0 for the unaligned kernels) into dst: chunk c holds columns view.begin + 16 c on.
 int expand_reference(v2m_ctx *ctx, row_view const &v, dev_buf &dst, char gap)
 {
@@ -923,7 +951,7 @@ u32 tile_run_for(u32 n_tiles)
 
 int make_grid(v2m_ctx *ctx, u64 n_rows, splice_grid &g)
 {
-	g.rows_per_group = rows_per_group_for(n_rows);
+	g.rows_per_group = ctx->set_call ? rows_per_group_for_set(n_rows, ctx->set.mean_tile_bytes) : rows_per_group_for(n_rows);
 	g.n_groups = u32((n_rows + g.rows_per_group - 1) / g.rows_per_group);
 	g.n_blocks = u64(ctx->view().n_tiles) * g.n_groups;
 	g.tile_run = tile_run_for(ctx->view().n_tiles);
@@ -978,6 +1006,15 @@ int store_flavour_launch(v2m_ctx *ctx, bool unaligned, u64 n_rows, u64 bytes, F 
 }
 
 
+v2m::set_tile_tables set_tables(v2m_ctx const *ctx)
+{
+	auto const &s(ctx->set);
+	return {s.d_col_begin.as<u32>(), s.d_col_end.as<u32>(), s.d_record_offset.as<u32>(), s.d_edge_end.as<u32>()};
+}
+
+int expand_reference_set(v2m_ctx *ctx, dev_buf &dst, char gap);
+
+
 // Resolve + aligned splice of rows [row_begin, row_end) of the batch into d_out.
 int splice_aligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row_end, char *d_out, u64 row_pitch)
 {
@@ -996,7 +1033,16 @@ int splice_aligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin,
 				v.d_template.as<v2m::vec4u>(), ctx->d_eff.as<u64>() - v.words.restart, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
 				d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, v.n_tiles, g.tile_run, store_limit, '-', window...);
 		});
-		if (ctx->windowed) {
+		if (ctx->set_call) {
+			auto const go_set([&](auto kernel) {
+				hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+					v.d_template.as<v2m::vec4u>(), ctx->d_eff.as<u64>() - v.words.restart, v.words.stride, tt, set_tables(ctx), ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+					d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, v.n_tiles, g.tile_run, '-');
+			});
+			if (nt) go_set(v2m::splice_aligned_set_kernel<true>);
+			else go_set(v2m::splice_aligned_set_kernel<false>);
+		}
+		else if (ctx->windowed) {
 			if (nt) go(v2m::splice_aligned_window_kernel<true>, u32(v.begin), u32(v.end));
 			else go(v2m::splice_aligned_window_kernel<false>, u32(v.begin), u32(v.end));
 		}
@@ -1019,8 +1065,9 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 		return V2M_OK;
 	}
 	row_view &v(ctx->view());
+	bool const set(ctx->set_call);
 	if (!v.has_template0) {   // the REF row with 0 as padding, built on first use
-		if (int const rc = expand_reference(ctx, v, v.d_template0, 0)) return rc;
+		if (int const rc = set ? expand_reference_set(ctx, v.d_template0, 0) : expand_reference(ctx, v, v.d_template0, 0)) return rc;
 		v.has_template0 = true;
 	}
 	if (int const rc = resolve_slice(ctx, rows, row_begin, row_end)) return rc;
@@ -1028,6 +1075,10 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 	splice_grid g;
 	if (int const rc = make_grid(ctx, n_rows, g)) return rc;
 	V2M_HIP_TRY(ctx, ctx->d_tile_counts.ensure(n_rows * v.n_tiles * sizeof(u32)));
+	if (set) {
+		V2M_HIP_TRY(ctx, ctx->d_set_tile_offsets.ensure(n_rows * v.n_tiles * sizeof(u32)));
+		V2M_HIP_TRY(ctx, ctx->d_set_lengths[ctx->set_lengths_slot].ensure(n_rows * ctx->set.n_windows * sizeof(u32)));
+	}
 	bool const windowed(ctx->windowed);
 	v2m::tile_tables const tt{v.d_edge_begin.as<u32>(), v.d_cross_offsets.as<u32>(), v.d_cross_edges.as<u32>()};
 	u64 const *const d_eff(ctx->d_eff.as<u64>() - v.words.restart);
@@ -1044,10 +1095,19 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 				v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
 				ctx->d_tile_counts.as<u32>(), v.n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run, window...);
 		});
-		if (windowed) count(v2m::count_unaligned_window_kernel, u32(v.begin), u32(v.end));
+		if (set)
+			hipLaunchKernelGGL(v2m::count_unaligned_set_kernel, dim3(unsigned(u64(v.n_tiles) * count_groups)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+				v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, set_tables(ctx), ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+				ctx->d_tile_counts.as<u32>(), v.n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run);
+		else if (windowed) count(v2m::count_unaligned_window_kernel, u32(v.begin), u32(v.end));
 		else count(v2m::count_unaligned_kernel);
 		hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(unsigned(n_rows)), dim3(256), 0, ctx->stream,
 			ctx->d_tile_counts.as<u32>(), v.n_tiles, ctx->d_row_lengths.as<u64>());
+		if (set)   // the scan segmented at each window's first tile: the tiles' destinations in the record, the pieces' lengths
+			hipLaunchKernelGGL(v2m::scan_window_set_kernel, dim3(unsigned(n_rows)), dim3(256), 0, ctx->stream,
+				ctx->d_tile_counts.as<u32>(), ctx->d_row_lengths.as<u64>(), v.n_tiles, u32(ctx->set.n_windows),
+				ctx->set.d_first_tile.as<u32>(), ctx->set.d_tile_window.as<u32>(), ctx->set.d_slot_offset32.as<u32>(),
+				ctx->d_set_tile_offsets.as<u32>(), ctx->d_set_lengths[ctx->set_lengths_slot].as<u32>());
 	}
 	auto const launch([&](bool nt) {
 		auto const go([&](auto kernel, auto... window) {
@@ -1055,6 +1115,16 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 				v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
 				ctx->d_tile_counts.as<u32>(), v.n_tiles, d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run, window...);
 		});
+		if (set) {
+			auto const go_set([&](auto kernel) {
+				hipLaunchKernelGGL(kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+					v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, set_tables(ctx), ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+					ctx->d_set_tile_offsets.as<u32>(), v.n_tiles, d_out, row_pitch, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run);
+			});
+			if (nt) go_set(v2m::splice_unaligned_set_kernel<true>);
+			else go_set(v2m::splice_unaligned_set_kernel<false>);
+			return;
+		}
 		if (windowed) {
 			if (nt) go(v2m::splice_unaligned_window_kernel<true>, u32(v.begin), u32(v.end));
 			else go(v2m::splice_unaligned_window_kernel<false>, u32(v.begin), u32(v.end));
@@ -1069,7 +1139,7 @@ int splice_unaligned_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begi
 		if (nt) go(v2m::splice_unaligned_kernel<true>);
 		else go(v2m::splice_unaligned_kernel<false>);
 	});
-	return store_flavour_launch(ctx, true, n_rows, n_rows * (windowed ? v.length() : ctx->ref_len), launch);
+	return store_flavour_launch(ctx, true, n_rows, n_rows * ((set || windowed) ? v.length() : ctx->ref_len), launch);
 }
 
 
@@ -1100,7 +1170,7 @@ struct slice_plan { u64 pitch, rows_per_slice, n_slices, slot_bytes; };
 slice_plan plan_slices(v2m_ctx const *ctx, u64 n_rows, bool unaligned, u64 max_rows_per_slice = ~u64(0))
 {
 	slice_plan p;
-	p.pitch = unaligned ? ((v2m_max_unaligned_length(ctx) + 255) & ~u64(255)) : v2m_min_row_pitch(ctx);
+	p.pitch = ctx->set_call ? ctx->set.pitch : unaligned ? ((v2m_max_unaligned_length(ctx) + 255) & ~u64(255)) : v2m_min_row_pitch(ctx);
 	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
 	u64 const slot_default(n_rows * p.pitch < (u64(8) << 30) ? (u64(128) << 20) : (u64(512) << 20));
 	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : slot_default);
@@ -1253,6 +1323,7 @@ struct slot_rows {
 	char const *base;
 	u64 pitch, length;
 	u64 const *lengths;
+	u32 const *set_lengths;   // a window set in unaligned mode: [r1 - r0][n_windows]
 	char const *row(u64 r) const { return base + (r - r0) * pitch; }
 	u64 bytes(u64 r) const { return lengths ? lengths[r - r0] : length; }
 };
@@ -1268,12 +1339,14 @@ int splice_rows_pipeline(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned
 	u64 const L(ctx->view().length());
 	if (0 == L) {   // rows without a byte: nothing to copy, nothing to hold on to
 		if (int const rc = ensure_host_slots(ctx, 1, 0)) return rc;
-		int const rc(deliver(*ctx->host_slots[0], slot_rows{0, rows->n_rows, "", 0, 0, nullptr}));
+		int const rc(deliver(*ctx->host_slots[0], slot_rows{0, rows->n_rows, "", 0, 0, nullptr, nullptr}));
 		wait_released(ctx, *ctx->host_slots[0]);
 		return rc;
 	}
 	slice_plan const p(plan_slices(ctx, rows->n_rows, unaligned));
-	u64 const lengths_bytes(p.rows_per_slice * sizeof(u64));   // unaligned: row lengths ride at the end of the pinned slot
+	// unaligned: row lengths ride at the end of the pinned slot (of a window set: the slice's [rows][n_windows] lengths table)
+	bool const set_lengths(ctx->set_call && unaligned);
+	u64 const lengths_bytes(set_lengths ? ((p.rows_per_slice * ctx->set.n_windows * sizeof(u32) + 7) & ~u64(7)) : p.rows_per_slice * sizeof(u64));
 	u64 const slots_used(std::min(n_slots, p.n_slices));
 	for (int i(0); i < (p.n_slices > 1 ? 2 : 1); ++i) V2M_HIP_TRY(ctx, ctx->ring[i].ensure(p.slot_bytes));
 	if (int const rc = ensure_host_slots(ctx, slots_used, p.slot_bytes + lengths_bytes)) return rc;
@@ -1290,14 +1363,17 @@ int splice_rows_pipeline(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned
 		if (s >= 2) V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, slot_of(s - 2).copied, 0));
 		V2M_HIP_TRY(ctx, ctx->ring[d].ensure(p.slot_bytes));                 // (the slice takes its device slot: refilled in the checked build)
 		V2M_POISON_HOST(slot.host.p, p.slot_bytes + lengths_bytes);
+		ctx->set_lengths_slot = d;   // (a window set's lengths table is rewritten, like the device slot, only after slice s - 2's copies)
 		if (int const rc = unaligned
 				? splice_unaligned_slice(ctx, rows, r0, r1, ctx->ring[d].as<char>(), p.pitch)
 				: splice_aligned_slice(ctx, rows, r0, r1, ctx->ring[d].as<char>(), p.pitch))
 			return rc;
-		if (unaligned)   // d_row_lengths is reused by the next slice: take the copy on the compute stream
+		if (unaligned && !set_lengths)   // d_row_lengths is reused by the next slice: take the copy on the compute stream
 			V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.as<char>() + p.slot_bytes, ctx->d_row_lengths.p, (r1 - r0) * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
 		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[d], ctx->stream));
 		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[d], 0));
+		if (set_lengths)   // the lengths table has a buffer per device slot: it travels on the copy stream, ahead of the rows it describes
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.as<char>() + p.slot_bytes, ctx->d_set_lengths[d].p, (r1 - r0) * ctx->set.n_windows * sizeof(u32), hipMemcpyDeviceToHost, ctx->copy_stream));
 		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, ctx->ring[d].p, (r1 - r0) * p.pitch, hipMemcpyDeviceToHost, ctx->copy_stream));
 		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
 		return V2M_OK;
@@ -1306,7 +1382,8 @@ int splice_rows_pipeline(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned
 		v2m_row_hold &slot(slot_of(s));
 		V2M_HIP_TRY(ctx, hipEventSynchronize(slot.copied));
 		char const *const base(slot.host.as<char>());
-		return deliver(slot, slot_rows{first_row(s), end_row(s), base, p.pitch, L, unaligned ? reinterpret_cast<u64 const *>(base + p.slot_bytes) : nullptr});
+		return deliver(slot, slot_rows{first_row(s), end_row(s), base, p.pitch, L, (unaligned && !set_lengths) ? reinterpret_cast<u64 const *>(base + p.slot_bytes) : nullptr,
+			set_lengths ? reinterpret_cast<u32 const *>(base + p.slot_bytes) : nullptr});
 	});
 
 	// V2M_SPLICE_TIMING=1: where the host's time of this call went (row tables + launches / waiting for copies + the sink), to stderr
@@ -1739,6 +1816,7 @@ int v2m_upload_graph(v2m_ctx *ctx, const v2m_graph_view *g, const char *ref_seq,
 	// --- upload ------------------------------------------------------------------------------
 	ctx->has_graph = false;
 	ctx->windowed = false;              // a new graph: whole rows again
+	ctx->has_set = false;               // ... and no window set
 	ctx->n_nodes = N; ctx->n_edges = E; ctx->ref_len = ref_len; ctx->aligned_len = L; ctx->label_bytes = label_total;
 	V2M_HIP_TRY(ctx, ctx->d_ref.ensure(std::max<u64>(ref_len, 16)));
 	if (ref_len) V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref.p, ref_seq, ref_len, hipMemcpyHostToDevice, ctx->stream));
@@ -1943,6 +2021,73 @@ uint64_t v2m_min_row_pitch(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) 
 uint64_t v2m_max_unaligned_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ctx->view().max_unaligned : 0; }
 uint64_t v2m_window_length(const v2m_ctx *ctx) { return (ctx && ctx->has_graph) ? ctx->view().length() : 0; }
 
+namespace {
+
+// The per-tile tables of column windows (v2m_set_column_window: one window; v2m_set_window_set: the windows' tiles one after another).
+struct window_tile_tables {
+	std::vector<u32> edge_begin, edge_end, cross_offsets{0}, cross_edges;
+	u32 n_tiles() const { return u32(edge_end.size()); }   // (edge_begin may carry one more entry: the [n_tiles + 1] shape of tile_tables)
+};
+
+u32 first_edge_beginning_at(v2m_ctx const *ctx, u64 col)   // first edge with aln_begin >= col
+{
+	auto const &patches(ctx->h_patches);
+	return u32(std::partition_point(patches.begin(), patches.end(), [&](v2m::edge_patch const &p) { return p.aln_begin < col; }) - patches.begin());
+}
+
+// Appends the tiles of the window [col_begin, col_end).  Tile t of the window is columns [B_t, B_t + kTileBytes) clipped to col_end,
+// B_t = col_begin + t * kTileBytes.  Its range: the edges that begin in it (edges are ordered by aligned begin).  Its crossing edges
+// (aln_begin < B_t < aln_end): those of the whole-row tile T = B_t / kTileBytes that still reach past B_t, then those that begin in
+// [T * kTileBytes, B_t) and reach past it -- ascending.
+void append_window_tiles(v2m_ctx const *ctx, u64 col_begin, u64 col_end, window_tile_tables &tb)
+{
+	auto const &patches(ctx->h_patches);
+	u64 const n_tiles((col_end - col_begin + v2m::kTileBytes - 1) / v2m::kTileBytes);
+	u32 begin(first_edge_beginning_at(ctx, col_begin));
+	for (u64 t(0); t < n_tiles; ++t) {
+		u64 const B(col_begin + t * v2m::kTileBytes), T(B / v2m::kTileBytes);
+		u32 const end(first_edge_beginning_at(ctx, std::min<u64>(B + v2m::kTileBytes, col_end)));
+		for (u32 i(ctx->h_cross_offsets[T]); i < ctx->h_cross_offsets[T + 1]; ++i)
+			if (patches[ctx->h_cross_edges[i]].aln_end > B) tb.cross_edges.push_back(ctx->h_cross_edges[i]);
+		for (u32 e(ctx->h_tile_edge_begin[T]); e < begin; ++e)
+			if (patches[e].aln_end > B) tb.cross_edges.push_back(e);
+		tb.edge_begin.push_back(begin);
+		tb.edge_end.push_back(end);
+		tb.cross_offsets.push_back(u32(tb.cross_edges.size()));
+		begin = end;
+	}
+}
+
+// The edges a window's rows depend on, [e_lo, e_hi): from the first edge whose span reaches past col_begin (the running maximum of the
+// edges' targets is ordered, and so are the targets' aligned positions) to the last one that begins before col_end (e_hi: the end of
+// the window's last tile's range).  Empty when no edge reaches into the window.
+u64 first_edge_reaching_past(v2m_ctx const *ctx, u64 col_begin, u32 e_hi)
+{
+	u64 e_lo(0), hi(e_hi);
+	while (e_lo < hi) {
+		u64 const mid((e_lo + hi) / 2);
+		if (ctx->h_aln_pos[ctx->h_tgt_prefix_max[mid + 1]] > col_begin) hi = mid; else e_lo = mid + 1;
+	}
+	return e_lo;
+}
+
+// The edge words resolve decides for edges [e_lo, e_hi) (none when the range is empty).  Their restart points (the nearest earlier edge
+// that is not overlappable, kernels.hpp) lie at or after the last word whose first edge is not overlappable.
+word_range words_of_edges(v2m_ctx const *ctx, u64 e_lo, u64 e_hi)
+{
+	u64 restart(0), lo(0), word_hi(0);   // no edge reaches into the columns: nothing to resolve
+	if (e_lo < e_hi) {
+		lo = e_lo / 64;
+		word_hi = (e_hi + 63) / 64;
+		restart = lo;
+		while (restart > 0 && (ctx->h_overlappable[restart] & 1)) --restart;
+	}
+	return {restart, lo, word_hi, (word_hi - restart + 15) & ~u64(15)};
+}
+
+} // namespace
+
+
 int v2m_set_column_window(v2m_ctx *ctx, uint64_t col_begin, uint64_t col_end)
 {
 	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
@@ -1955,55 +2100,198 @@ int v2m_set_column_window(v2m_ctx *ctx, uint64_t col_begin, uint64_t col_end)
 	if (0 == col_begin && L == col_end) return V2M_OK;   // the whole row: the whole-row view and kernels
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-	// Tile t of the window is columns [B_t, B_t + kTileBytes) clipped to col_end, B_t = col_begin + t * kTileBytes.  Its range: the edges
-	// that begin in it (edges are ordered by aligned begin).  Its crossing edges (aln_begin < B_t < aln_end): those of the whole-row tile
-	// T = B_t / kTileBytes that still reach past B_t, then those that begin in [T * kTileBytes, B_t) and reach past it -- ascending.
-	auto const &patches(ctx->h_patches);
-	u64 const W(col_end - col_begin);
-	u32 const n_tiles(u32((W + v2m::kTileBytes - 1) / v2m::kTileBytes));
-	auto const first_beginning_at([&](u64 col) -> u32 {   // first edge with aln_begin >= col
-		return u32(std::partition_point(patches.begin(), patches.end(), [&](v2m::edge_patch const &p) { return p.aln_begin < col; }) - patches.begin());
-	});
-	std::vector<u32> edge_begin(n_tiles + 1), cross_offsets(n_tiles + 1, 0), cross_edges;
-	for (u32 t(0); t <= n_tiles; ++t) edge_begin[t] = first_beginning_at(std::min<u64>(col_begin + u64(t) * v2m::kTileBytes, col_end));
-	for (u32 t(0); t < n_tiles; ++t) {
-		u64 const B(col_begin + u64(t) * v2m::kTileBytes), T(B / v2m::kTileBytes);
-		for (u32 i(ctx->h_cross_offsets[T]); i < ctx->h_cross_offsets[T + 1]; ++i)
-			if (patches[ctx->h_cross_edges[i]].aln_end > B) cross_edges.push_back(ctx->h_cross_edges[i]);
-		for (u32 e(ctx->h_tile_edge_begin[T]); e < edge_begin[t]; ++e)
-			if (patches[e].aln_end > B) cross_edges.push_back(e);
-		cross_offsets[t + 1] = u32(cross_edges.size());
-	}
-
-	// The edge words resolve decides: from the first edge whose span reaches past col_begin (the running maximum of the edges' targets
-	// is ordered, and so are the targets' aligned positions) to the last one that begins before col_end.  Their restart points (the
-	// nearest earlier edge that is not overlappable, kernels.hpp) lie at or after the last word whose first edge is not overlappable.
-	u32 const e_hi(edge_begin[n_tiles]);
-	u64 e_lo(0), hi(e_hi);
-	while (e_lo < hi) {
-		u64 const mid((e_lo + hi) / 2);
-		if (ctx->h_aln_pos[ctx->h_tgt_prefix_max[mid + 1]] > col_begin) hi = mid; else e_lo = mid + 1;
-	}
+	window_tile_tables tb;
+	append_window_tiles(ctx, col_begin, col_end, tb);
+	u32 const e_hi(tb.edge_end.back());
+	tb.edge_begin.push_back(e_hi);       // (one window: edge_begin[t + 1] is the end of tile t's range)
 	row_view &w(ctx->window);
-	u64 restart(0), lo(0), word_hi(0);   // no edge reaches into the window: nothing to resolve
-	if (e_lo < e_hi) {
-		lo = e_lo / 64;
-		word_hi = (u64(e_hi) + 63) / 64;
-		restart = lo;
-		while (restart > 0 && (ctx->h_overlappable[restart] & 1)) --restart;
-	}
-	w.words = {restart, lo, word_hi, (word_hi - restart + 15) & ~u64(15)};
+	w.words = words_of_edges(ctx, first_edge_reaching_past(ctx, col_begin, e_hi), e_hi);
 	w.begin = col_begin;
 	w.end = col_end;
-	w.max_unaligned = W;                 // a window's unaligned body never exceeds its columns
-	w.n_tiles = n_tiles;
+	w.max_unaligned = col_end - col_begin;   // a window's unaligned body never exceeds its columns
+	w.n_tiles = u32(tb.edge_end.size());
 	w.has_template0 = false;
-	if (int const rc = upload_vec(ctx, w.d_edge_begin, edge_begin)) return rc;
-	if (int const rc = upload_vec(ctx, w.d_cross_offsets, cross_offsets)) return rc;
-	if (int const rc = upload_vec(ctx, w.d_cross_edges, cross_edges)) return rc;
+	if (int const rc = upload_vec(ctx, w.d_edge_begin, tb.edge_begin)) return rc;
+	if (int const rc = upload_vec(ctx, w.d_cross_offsets, tb.cross_offsets)) return rc;
+	if (int const rc = upload_vec(ctx, w.d_cross_edges, tb.cross_edges)) return rc;
 	if (int const rc = expand_reference(ctx, w, w.d_template, '-')) return rc;
 	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->windowed = true;
+	return V2M_OK;
+}
+
+
+// ---- window sets ------------------------------------------------------------------------------------
+
+int v2m_window_set_layout(uint64_t n_windows, const uint64_t *col_begin, const uint64_t *col_end, uint64_t *slot_offset, uint64_t *record_pitch)
+{
+	if (0 == n_windows) return fail(nullptr, V2M_ERR_INVALID_ARGUMENT, "a window set needs at least one window");
+	if (!col_begin || !col_end) return fail(nullptr, V2M_ERR_INVALID_ARGUMENT, "NULL array");
+	u64 at(0);
+	for (u64 k(0); k < n_windows; ++k) {
+		if (!(col_begin[k] < col_end[k]))
+			return fail(nullptr, V2M_ERR_INVALID_ARGUMENT, "window %llu, [%llu, %llu), is empty", (unsigned long long) k, (unsigned long long) col_begin[k], (unsigned long long) col_end[k]);
+		if (slot_offset) slot_offset[k] = at;
+		u64 const len(col_end[k] - col_begin[k]);
+		// (the unaligned kernels keep per-tile destinations in 32 bits; checked window by window, so that the sum cannot wrap either)
+		if (len >= (u64(1) << 32) || (at += (len + 15) & ~u64(15)) >= (u64(1) << 32))
+			return fail(nullptr, V2M_ERR_UNSUPPORTED, "the slots of the window set reach 2^32 bytes at window %llu: split the set", (unsigned long long) k);
+	}
+	if (record_pitch) *record_pitch = (at + 255) & ~u64(255);
+	return V2M_OK;
+}
+
+uint64_t v2m_window_set_size(const v2m_ctx *ctx) { return (ctx && ctx->has_graph && ctx->has_set) ? ctx->set.n_windows : 0; }
+uint64_t v2m_window_set_pitch(const v2m_ctx *ctx) { return (ctx && ctx->has_graph && ctx->has_set) ? ctx->set.pitch : 0; }
+
+namespace {
+
+// The REF row in the set's record layout with `gap` as padding (kernels.hpp: expand_reference_set_kernel): one launch over the tile
+// table, one record long.
+int expand_reference_set(v2m_ctx *ctx, dev_buf &dst, char gap)
+{
+	u64 const n_chunks(ctx->set.view.end / 16);
+	V2M_HIP_TRY(ctx, dst.ensure(n_chunks * 16));
+	{
+		timed_launch tl(ctx, V2M_KERNEL_TEMPLATE);
+		hipLaunchKernelGGL(v2m::expand_reference_set_kernel, dim3(unsigned((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream,
+			ctx->d_ref.as<char>(), ctx->d_ref_pos.as<u32>(), ctx->d_aln_pos.as<u32>(), u32(ctx->n_nodes), set_tables(ctx), ctx->set.view.n_tiles, n_chunks, dst.as<uint4>(), gap);
+	}
+	V2M_HIP_TRY(ctx, hipGetLastError());
+	return V2M_OK;
+}
+
+struct scoped_set_call {
+	v2m_ctx *ctx;
+	explicit scoped_set_call(v2m_ctx *c) : ctx(c) { c->set_call = true; }
+	~scoped_set_call() { ctx->set_call = false; }
+};
+
+int check_set_call(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags)
+{
+	if (int const rc = check_batch(ctx, rows, flags)) return rc;
+	if (!ctx->has_set) return fail(ctx, V2M_ERR_STATE, "no window set (v2m_set_window_set)");
+	if (flags & V2M_SPLICE_BGZF) return fail(ctx, V2M_ERR_UNSUPPORTED, "V2M_SPLICE_BGZF is not supported by the window-set calls");
+	return V2M_OK;
+}
+
+} // namespace
+
+int v2m_set_window_set(v2m_ctx *ctx, uint64_t n_windows, const uint64_t *col_begin, const uint64_t *col_end)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!ctx->has_graph) return fail(ctx, V2M_ERR_STATE, "no graph uploaded");
+	if (0 == n_windows) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "a window set needs at least one window");
+	if (!col_begin || !col_end) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "NULL array");
+	u64 const L(ctx->aligned_len);
+	u64 n_tiles(0);
+	for (u64 k(0); k < n_windows; ++k) {
+		if (!(col_begin[k] < col_end[k] && col_end[k] <= L))
+			return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "window %llu, [%llu, %llu), is empty or not within the aligned length %llu",
+				(unsigned long long) k, (unsigned long long) col_begin[k], (unsigned long long) col_end[k], (unsigned long long) L);
+		n_tiles += (col_end[k] - col_begin[k] + v2m::kTileBytes - 1) / v2m::kTileBytes;
+	}
+	std::vector<u64> slot_offset(n_windows);
+	u64 pitch(0);
+	if (int const rc = v2m_window_set_layout(n_windows, col_begin, col_end, slot_offset.data(), &pitch)) return fail(ctx, rc, "%s", g_create_error.c_str());
+	if (n_windows >= 0xFFFFFFFFull || n_tiles >= 0x7FFFFFFFull)
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "the window set has too many tiles (%llu) for one set: split it", (unsigned long long) n_tiles);
+	ctx->has_set = false;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+	// The tiles of all windows in set order, each with its columns, its place in the record and its window; the resolve range is the
+	// hull of the windows' ranges (a whole-row resolve is small beside the splice, so the hull costs nothing worth splitting).
+	auto &set(ctx->set);
+	window_tile_tables tb;
+	std::vector<u32> tile_col_begin, tile_col_end, tile_record_offset, tile_window, first_tile(n_windows + 1), slot_offset32(n_windows);
+	tile_col_begin.reserve(n_tiles); tile_col_end.reserve(n_tiles); tile_record_offset.reserve(n_tiles); tile_window.reserve(n_tiles);
+	set.lengths.resize(n_windows);
+	u64 e_lo(~u64(0)), e_hi(0), slots_end(0);
+	for (u64 k(0); k < n_windows; ++k) {
+		u64 const len(col_end[k] - col_begin[k]);
+		first_tile[k] = tb.n_tiles();
+		slot_offset32[k] = u32(slot_offset[k]);
+		set.lengths[k] = u32(len);
+		slots_end = slot_offset[k] + ((len + 15) & ~u64(15));
+		append_window_tiles(ctx, col_begin[k], col_end[k], tb);
+		for (u64 j(0); j * v2m::kTileBytes < len; ++j) {
+			tile_col_begin.push_back(u32(col_begin[k] + j * v2m::kTileBytes));
+			tile_col_end.push_back(u32(std::min<u64>(col_begin[k] + (j + 1) * v2m::kTileBytes, col_end[k])));
+			tile_record_offset.push_back(u32(slot_offset[k] + j * v2m::kTileBytes));
+			tile_window.push_back(u32(k));
+		}
+		u32 const w_hi(tb.edge_end.back());
+		u64 const w_lo(first_edge_reaching_past(ctx, col_begin[k], w_hi));
+		if (w_lo < w_hi) { e_lo = std::min(e_lo, w_lo); e_hi = std::max<u64>(e_hi, w_hi); }
+	}
+	first_tile[n_windows] = tb.n_tiles();
+	tb.edge_begin.push_back(0);          // (tile_tables' [n_tiles + 1] shape; a set's range ends are edge_end)
+	row_view &v(set.view);
+	v.words = words_of_edges(ctx, std::min(e_lo, e_hi), e_hi);
+	v.begin = 0;                         // the view's "columns" are a record's bytes
+	v.end = slots_end;
+	v.max_unaligned = slots_end;
+	v.n_tiles = tb.n_tiles();
+	v.has_template0 = false;
+	set.n_windows = n_windows;
+	set.pitch = pitch;
+	u64 total(0);
+	for (u32 const len : set.lengths) total += len;
+	set.mean_tile_bytes = std::max<u64>(1, total / v.n_tiles);
+	if (int const rc = upload_vec(ctx, v.d_edge_begin, tb.edge_begin)) return rc;
+	if (int const rc = upload_vec(ctx, v.d_cross_offsets, tb.cross_offsets)) return rc;
+	if (int const rc = upload_vec(ctx, v.d_cross_edges, tb.cross_edges)) return rc;
+	if (int const rc = upload_vec(ctx, set.d_edge_end, tb.edge_end)) return rc;
+	if (int const rc = upload_vec(ctx, set.d_col_begin, tile_col_begin)) return rc;
+	if (int const rc = upload_vec(ctx, set.d_col_end, tile_col_end)) return rc;
+	if (int const rc = upload_vec(ctx, set.d_record_offset, tile_record_offset)) return rc;
+	if (int const rc = upload_vec(ctx, set.d_tile_window, tile_window)) return rc;
+	if (int const rc = upload_vec(ctx, set.d_first_tile, first_tile)) return rc;
+	if (int const rc = upload_vec(ctx, set.d_slot_offset32, slot_offset32)) return rc;
+	if (int const rc = expand_reference_set(ctx, v.d_template, '-')) return rc;
+	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the uploads read this call's vectors)
+	ctx->has_set = true;
+	return V2M_OK;
+}
+
+int v2m_splice_window_set(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_window_sink_fn sink, void *user)
+{
+	if (int const rc = check_set_call(ctx, rows, flags)) return rc;
+	if (!sink) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "sink is NULL");
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	scoped_set_call const in_set(ctx);
+	u64 const n_windows(ctx->set.n_windows);
+	return splice_rows_pipeline(ctx, rows, flags & V2M_SPLICE_UNALIGNED, 2, "v2m_splice_window_set", [&](v2m_row_hold &, slot_rows const &sl) -> int {
+		for (u64 r(sl.r0); r < sl.r1; ++r)
+			if (sink(user, r, sl.row(r), sl.set_lengths ? sl.set_lengths + (r - sl.r0) * n_windows : ctx->set.lengths.data()))
+				return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
+		return V2M_OK;
+	});
+}
+
+int v2m_splice_window_set_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, void *d_out, uint64_t record_pitch, uint32_t *lengths_out)
+{
+	if (int const rc = check_set_call(ctx, rows, flags)) return rc;
+	if (0 == rows->n_rows) return V2M_OK;
+	if (!d_out || ((uintptr_t) d_out & 15)) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_out must be a 16-byte aligned device pointer");
+	if (record_pitch % 16 || record_pitch < ctx->set.view.end)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "record_pitch must be a multiple of 16 and at least the end of the last slot, %llu", (unsigned long long) ctx->set.view.end);
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	scoped_set_call const in_set(ctx);
+	u64 const n_windows(ctx->set.n_windows);
+	if (!(flags & V2M_SPLICE_UNALIGNED)) {
+		if (int const rc = splice_aligned_slice(ctx, rows, 0, rows->n_rows, static_cast<char *>(d_out), record_pitch)) return rc;
+		if (lengths_out)
+			for (u64 r(0); r < rows->n_rows; ++r) std::copy(ctx->set.lengths.begin(), ctx->set.lengths.end(), lengths_out + r * n_windows);
+		return V2M_OK;
+	}
+	ctx->set_lengths_slot = 0;
+	if (int const rc = splice_unaligned_slice(ctx, rows, 0, rows->n_rows, static_cast<char *>(d_out), record_pitch)) return rc;
+	if (lengths_out) {
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(lengths_out, ctx->d_set_lengths[0].p, rows->n_rows * n_windows * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	}
 	return V2M_OK;
 }
 
