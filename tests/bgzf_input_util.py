@@ -123,16 +123,27 @@ def write_fixed_block(w, tokens, final=True):
 	write_tokens(w, tokens, lit, dist)
 
 
-def write_dynamic_block(w, lit_lens, dist_lens, tokens, final=True, cl_lens=None, cl_seq=None, hlit=None, hdist=None):
+def write_stored_block(w, data, final=True, nlen=None):
+	"""A stored block (final or not): header, zero bits to the byte boundary, LEN, NLEN (~LEN unless given), the bytes."""
+	w.put(1 if final else 0, 1)
+	w.put(0, 2)
+	w.align()
+	w.put(len(data) & 0xffff, 16)
+	w.put((~len(data) if nlen is None else nlen) & 0xffff, 16)
+	w.raw(data)
+
+
+def write_dynamic_block(w, lit_lens, dist_lens, tokens, final=True, cl_lens=None, cl_seq=None, hlit=None, hdist=None, hclen=19):
 	"""A dynamic block.  cl_seq: the code-length symbols as (symbol, extra) pairs (default: the lengths one by one); hlit / hdist override
-	the counts written into the header."""
+	the counts written into the header; hclen: how many of the code-length code's lengths the header lists (the rest must be 0)."""
 	cl_lens = CL_LENS if cl_lens is None else cl_lens
 	w.put(1 if final else 0, 1)
 	w.put(2, 2)
 	w.put((len(lit_lens) if hlit is None else hlit) - 257, 5)
 	w.put((len(dist_lens) if hdist is None else hdist) - 1, 5)
-	w.put(19 - 4, 4)
-	for s in CL_ORDER:
+	assert 4 <= hclen <= 19 and not any(cl_lens[s] for s in CL_ORDER[hclen:])
+	w.put(hclen - 4, 4)
+	for s in CL_ORDER[:hclen]:
 		w.put(cl_lens[s], 3)
 	cl_codes = canonical(cl_lens)
 	for sym, extra in (cl_seq if cl_seq is not None else [(L, 0) for L in list(lit_lens) + list(dist_lens)]):
