@@ -36,7 +36,8 @@
  * sink may keep until it says so).  Entries have only ever been added.  V2M_SPLICE_BGZF, v2m_bgzf_compress, v2m_bgzf_bound and
  * v2m_bgzf_frame_stored were added without a new version, and so were v2m_set_column_window and v2m_window_length, and
  * v2m_bgzf_scan and v2m_bgzf_decompress (with V2M_KERNEL_INFLATE), and v2m_vcf_scan (with V2M_KERNEL_VCF): a caller probes for them by symbol.
- * The window-set calls (v2m_window_set_layout, v2m_set_window_set, v2m_splice_window_set[_device]) were added the same way.
+ * The window-set calls (v2m_window_set_layout, v2m_set_window_set, v2m_splice_window_set[_device]) were added the same way, and so was
+ * v2m_row_ops (with v2m_aln_op, v2m_ops_sink_fn and the V2M_KERNEL_ROW_OPS_* ids).
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -330,6 +331,37 @@ int v2m_splice_window_set(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flag
 int v2m_splice_window_set_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, void *d_out, uint64_t record_pitch,
                                  uint32_t *lengths_out /* host, optional, [n_rows][n_windows] */);
 
+/* ---- row alignment ops --------------------------------------------------------------------------
+ *
+ * The coordinate map between a row and the reference, as run-length ops (what a chain or a CIGAR is made of).
+ * For a row, every aligned column c in [0, L) has two facts:
+ *   ref -- the REF row holds a reference byte there, not the walk's padding;
+ *   row -- this row holds a reference or label byte there, not the walk's padding.
+ * "Padding" is the walk's padding exactly as the unaligned mode defines it (sequence_writer.cc:80-83): a literal '-' inside the
+ * reference or inside a label is a byte, not padding.  The column's class:
+ *   ref and row -> M     row only -> I     ref only -> D     neither -> none (the column is skipped)
+ * The row's ops are the run-length encoding of the classes of its non-skipped columns, in column order; skipped columns do not break
+ * a run.  Op codes are BAM's: M = 0, I = 1, D = 2.  Codes 7 and 8 stay free for a later '=' / 'X' split: M covers match and mismatch.
+ * Guarantees: no op has length 0; no two neighbouring ops have the same code; the lengths of M and D sum to the reference length;
+ * those of M and I to the row's unaligned length (what v2m_splice_rows_device reports for the row with V2M_SPLICE_UNALIGNED, passed
+ * to the sink as row_length); the REF row (V2M_PLOIDY_MAX, no cuts) is the single op M R (no op for an empty reference); rows with
+ * cuts follow the same rule on the row they would splice.
+ * Rows arrive in batch order, one call per row, on the calling thread; `ops` is library-owned and valid during the call only; a
+ * non-zero return ends the call with V2M_ERR_SINK.  Synchronous.  flags must be 0.  Errors as for v2m_splice_rows: V2M_ERR_STATE
+ * before an upload, V2M_ERR_PRECONDITION for bad cuts; a graph with a NUL byte is refused as V2M_SPLICE_UNALIGNED refuses it.
+ * The ops always describe the WHOLE row: a column window or window set in force is neither used nor disturbed.
+ * A row's first op is never I: column 0 holds the first reference byte (node 0 sits at reference and aligned position 0), so its class is M or D.
+ * The call works through the batch in slices of as many rows as keep the per-row tables of its first two passes (three words per tile
+ * and the effective-edge words) within 256 MiB of device memory; a slice is counted once and its rows' records (12 bytes per op) come to
+ * the host in pieces of consecutive rows that fit 64 MiB of device and of pinned memory each (V2M_OPS_SLICE_BYTES overrides the 64 MiB, a
+ * test knob; a single row goes through whatever it takes). */
+typedef struct v2m_aln_op { uint32_t op; uint32_t length; } v2m_aln_op;
+#define V2M_OP_M 0u
+#define V2M_OP_I 1u
+#define V2M_OP_D 2u
+typedef int (*v2m_ops_sink_fn)(void *user, uint64_t row_index, const v2m_aln_op *ops, uint64_t n_ops, uint64_t row_length /* unaligned length */);
+int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 */, v2m_ops_sink_fn sink, void *user);
+
 /* ---- founder search: the chunk walks ---------------------------------- */
 
 /* The edge-by-edge part of find_initial_cut_positions_lambda_min (libvcf2multialign/find_cut_positions.cc:126-176): the pBWT
@@ -555,6 +587,14 @@ enum {
 	V2M_KERNEL_INFLATE = 7,         /* bgzf_inflate_kernel (v2m_bgzf_decompress), one launch per slice */
 	V2M_KERNEL_VCF = 8,             /* the line index, head and genotype launches of one slice of v2m_vcf_scan, as one group */
 	V2M_KERNEL_COUNT = 9
+};
+/* The passes of v2m_row_ops, added behind the ids above (V2M_KERNEL_COUNT keeps counting those; V2M_KERNEL_END bounds what
+ * v2m_profile_get accepts).  The call's count_unaligned_kernel + scan_tile_counts_kernel launches are timed as V2M_KERNEL_UNALIGNED_COUNT. */
+enum {
+	V2M_KERNEL_ROW_OPS_COUNT = 9,   /* count_row_ops_kernel (pass 1: breakpoints, first and last class per row tile) */
+	V2M_KERNEL_ROW_OPS_SCAN = 10,   /* scan_row_ops_kernel (pass 2: op offsets and carried classes per row) */
+	V2M_KERNEL_ROW_OPS_EMIT = 11,   /* emit_row_ops_kernel (pass 3: the breakpoint records) */
+	V2M_KERNEL_END = 12
 };
 
 /* When enabled, every launch of the kernels above is bracketed by HIP events on the ctx's

@@ -26,8 +26,10 @@ KERNEL_TRANSPOSE, KERNEL_RESOLVE, KERNEL_SPLICE_ALIGNED, KERNEL_SPLICE_UNALIGNED
 KERNEL_BGZF = 6
 KERNEL_INFLATE = 7
 KERNEL_VCF = 8
+KERNEL_ROW_OPS_COUNT, KERNEL_ROW_OPS_SCAN, KERNEL_ROW_OPS_EMIT = 9, 10, 11   # the passes of v2m_row_ops
 KERNEL_NAMES = ["transpose_bits_kernel", "resolve_effective_edges_kernel", "splice_aligned_kernel", "splice_unaligned_kernel", "expand_reference_row_kernel", "count_unaligned_kernel",
-	"bgzf_deflate_kernel", "bgzf_inflate_kernel", "vcf_scan_kernels"]
+	"bgzf_deflate_kernel", "bgzf_inflate_kernel", "vcf_scan_kernels", "count_row_ops_kernel", "scan_row_ops_kernel", "emit_row_ops_kernel"]
+OP_M, OP_I, OP_D = 0, 1, 2   # v2m_aln_op.op (BAM's codes)
 ABI_VERSION = 5
 
 
@@ -71,6 +73,7 @@ VCF_LINE_DTYPE = [("kind", "<u4"), ("n_alts", "<u4"), ("head_offset", "<u4"), ("
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
 HOLD_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p)   # v2m_hold_sink_fn
 WINDOW_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32))   # v2m_window_sink_fn
+OPS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_ops_sink_fn
 TRIALS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_trials_sink
 
 # every symbol include/v2m_hip.h declares: (restype, argtypes)
@@ -104,6 +107,7 @@ SIGNATURES = {
 	"v2m_splice_rows_held": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint32, HOLD_SINK_FN, C.c_void_p]),
 	"v2m_row_release": (None, [C.c_void_p]),
 	"v2m_splice_rows_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+	"v2m_row_ops": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, OPS_SINK_FN, C.c_void_p]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -349,6 +349,28 @@ class Context:
 			d_out, row_pitch, lengths.ctypes.data if want_lengths and rows.n_rows else None))
 		return lengths
 
+	def row_ops(self, rows):
+		"""v2m_row_ops: per row ((n, 2) uint32 array of (op, length) with op 0 = M, 1 = I, 2 = D; the row's unaligned length) -- the row's
+		alignment to the reference, always of the whole row whatever column window or window set is in force."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		collected, error = [], []
+
+		def _cb(_user, _row_index, ops, n_ops, row_length):
+			try:
+				a = np.frombuffer(C.string_at(ops, 8 * n_ops), dtype=np.uint32).reshape(n_ops, 2).copy() if n_ops else np.zeros((0, 2), np.uint32)
+				collected.append((a, int(row_length)))
+				return 0
+			except BaseException as e:  # propagate through the C frame as V2M_ERR_SINK
+				error.append(e)
+				return 1
+
+		rc = self._lib.v2m_row_ops(self._h, C.byref(rows.struct), 0, N.OPS_SINK_FN(_cb), None)
+		if error:
+			raise error[0]
+		self._check(rc)
+		return collected
+
 	def bgzf_compress(self, data):
 		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
 		src = bytes(data)

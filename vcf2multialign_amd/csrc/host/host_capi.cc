@@ -11,6 +11,7 @@
 #include "founder.hh"
 #include "gpu_path.hh"
 #include "graph_file.hh"
+#include "output.hh"
 #include "readers.hh"
 
 namespace vh = v2m::host;
@@ -414,6 +415,21 @@ void v2mh_shard_copies(uint64_t n_copies, uint32_t world, uint32_t rank, uint64_
 	auto const s(vh::shard_copies(n_copies, world, rank));
 	*first = s.first;
 	*end = s.end;
+}
+
+// chain_text() of output.hh (no GPU): the chain's bytes into dst when they fit `capacity`; returns their number, 0 for ops without any
+// M (no chain), -1 with a message in err for ops that are none of M, I, D.
+int64_t v2mh_chain_text(v2m_aln_op const *ops, uint64_t n_ops, char const *t_name, uint64_t t_size, char const *q_name, uint64_t q_size, uint64_t id,
+	char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		std::string const text(vh::chain_text(ops, n_ops, t_name, t_size, q_name, q_size, id));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
 }
 
 } // extern "C"

@@ -51,6 +51,7 @@ struct options {
 	bool gpu_parse{};                     // --gpu-parse: the genotype columns of -a become path bits on the GPU (v2m_vcf_scan)
 	char const *region{};                 // --region=START-END: 1-based inclusive positions on the reference sequence
 	std::uint64_t region_start{}, region_end{};
+	char const *output_chain{};           // --output-chain=FILE: one UCSC chain per output row (reference -> row), from v2m_row_ops
 	char const *regions_file{};           // --regions-file=FILE.bed: one output file per BED region, all spliced as one window set per pass
 	std::vector<int> devices{0};
 };
@@ -88,6 +89,11 @@ void usage()
 		"                                     without a name is called <chrom>_<start>_<end>.  All regions are spliced together,\n"
 		"                                     one launch per row batch.  Not with --region, -s, --output-sequences-separate,\n"
 		"                                     --pipe, --bgzf or several --device entries\n"
+		"      --output-chain=FILE            Write one UCSC chain per output sequence (the reference as target, the sequence as\n"
+		"                                     query; names as --output-sequences-separate forms them) that maps reference positions\n"
+		"                                     to positions in the --unaligned sequence, e.g. for liftOver or CrossMap.  The REF row\n"
+		"                                     has no chain.  Alone or beside -s / --output-sequences-separate; not with --region,\n"
+		"                                     --regions-file or several --device entries\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -273,7 +279,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -285,7 +291,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -332,6 +338,7 @@ int main(int argc, char **argv)
 			case o_gpu_parse: opt.gpu_parse = true; break;
 			case o_region: opt.region = optarg; break;
 			case o_regions_file: opt.regions_file = optarg; break;
+			case o_output_chain: opt.output_chain = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -361,6 +368,11 @@ int main(int argc, char **argv)
 		char const *const other(opt.region ? "--region" : opt.output_sequences_a2m ? "-s / --output-sequences-a2m" : opt.output_sequences_separate ? "--output-sequences-separate"
 			: opt.pipe ? "--pipe" : opt.bgzf ? "--bgzf" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
 		if (other) { std::cerr << "ERROR: --regions-file cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+	}
+	if (opt.output_chain) {
+		// a chain describes whole rows, from one context that holds every chromosome copy
+		char const *const other(opt.region ? "--region" : opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
+		if (other) { std::cerr << "ERROR: --output-chain cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
 	}
 	if (opt.region && !parse_region(opt.region, opt.region_start, opt.region_end)) {
 		std::cerr << "ERROR: --region must be START-END with 1 <= START <= END (1-based, inclusive), got \"" << opt.region << "\".\n";
@@ -578,6 +590,11 @@ int main(int argc, char **argv)
 			if (opt.output_sequences_separate) {
 				std::cerr << "Outputting sequences one by one..." << std::flush;
 				output.output_separate(graph, !opt.separate_plain);
+				std::cerr << " Done.\n";
+			}
+			if (opt.output_chain) {
+				std::cerr << "Outputting chains..." << std::flush;
+				output.output_chain(graph, opt.output_chain);
 				std::cerr << " Done.\n";
 			}
 		});

@@ -9,6 +9,8 @@
 #include <unistd.h>
 
 #include <atomic>
+#include <algorithm>
+#include <cctype>
 #include <cerrno>
 #include <condition_variable>
 #include <cstring>
@@ -759,6 +761,117 @@ void output::output_a2m(variant_graph const &graph, char const *dst_name)       
 	output_a2m(graph, stream);
 	stream.flush();
 	if (!stream) throw std::runtime_error(std::string("error while writing ") + dst_name);
+}
+
+
+// --- chains (--output-chain) ----------------------------------------------------------------------------------
+std::string chain_text(v2m_aln_op const *ops, u64 n_ops, std::string const &t_name, u64 t_size, std::string const &q_name, u64 q_size, u64 id)
+{
+	u64 first(n_ops), last(0), score(0);
+	for (u64 i(0); i < n_ops; ++i) {
+		if (ops[i].op > V2M_OP_D) throw std::invalid_argument("alignment op code " + std::to_string(ops[i].op) + " is none of M, I, D");
+		if (V2M_OP_M != ops[i].op) continue;
+		if (n_ops == first) first = i;
+		last = i;
+		score += ops[i].length;
+	}
+	if (n_ops == first) return std::string();
+	u64 t_start(0), q_start(0), t_end(t_size), q_end(q_size);
+	for (u64 i(0); i < first; ++i) (V2M_OP_D == ops[i].op ? t_start : q_start) += ops[i].length;
+	for (u64 i(last + 1); i < n_ops; ++i) (V2M_OP_D == ops[i].op ? t_end : q_end) -= ops[i].length;
+	std::string text("chain " + std::to_string(score) + ' ' + t_name + ' ' + std::to_string(t_size) + " + " + std::to_string(t_start) + ' ' + std::to_string(t_end)
+		+ ' ' + q_name + ' ' + std::to_string(q_size) + " + " + std::to_string(q_start) + ' ' + std::to_string(q_end) + ' ' + std::to_string(id) + '\n');
+	u64 size(ops[first].length), dt(0), dq(0);
+	for (u64 i(first + 1); i <= last; ++i) {
+		if (V2M_OP_D == ops[i].op) dt += ops[i].length;
+		else if (V2M_OP_I == ops[i].op) dq += ops[i].length;
+		else if (0 == dt && 0 == dq) size += ops[i].length;   // (two M ops in a row: one block)
+		else {
+			text += std::to_string(size) + ' ' + std::to_string(dt) + ' ' + std::to_string(dq) + '\n';
+			size = ops[i].length;
+			dt = dq = 0;
+		}
+	}
+	text += std::to_string(size) + "\n\n";
+	return text;
+}
+
+
+namespace {
+	struct chain_state { std::ostream *stream; std::vector<std::string> const *names; std::string const *t_name; std::exception_ptr error; };
+
+	int chain_sink(void *user, uint64_t row, v2m_aln_op const *ops, uint64_t n_ops, uint64_t row_length)
+	{
+		auto &st(*static_cast<chain_state *>(user));
+		try {
+			u64 t_size(0);
+			for (u64 i(0); i < n_ops; ++i) if (V2M_OP_I != ops[i].op) t_size += ops[i].length;
+			std::string const text(chain_text(ops, n_ops, *st.t_name, t_size, (*st.names)[row], row_length, row + 1));
+			if (text.empty()) std::fprintf(stderr, "Warning: %s shares no column with the reference; it gets no chain.\n", (*st.names)[row].c_str());
+			else st.stream->write(text.data(), std::streamsize(text.size()));
+			return st.stream->good() ? 0 : 1;
+		} catch (...) {   // nothing may cross the C boundary
+			st.error = std::current_exception();
+			return 1;
+		}
+	}
+}
+
+
+void output::output_chain(variant_graph const &graph, std::ostream &stream)
+{
+	write_chains(graph, [&stream]() -> std::ostream & { return stream; });
+}
+
+
+void output::write_chains(variant_graph const &graph, std::function<std::ostream &()> const &open)
+{
+	if (!m_more_gpus.empty()) throw std::runtime_error("--output-chain needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-chain needs every chromosome copy on one GPU context");
+	row_set const all(chain_rows(graph));
+	std::string const t_name(prefixed("REF", '.'));
+	auto const has_space([](std::string const &s) { return std::any_of(s.begin(), s.end(), [](char c) { return std::isspace(static_cast<unsigned char>(c)); }); });
+	if (has_space(t_name)) throw std::runtime_error("the chain's target name \"" + t_name + "\" holds whitespace");
+	// the rows but REF (the row that follows no copy and has no cuts)
+	row_set rows;
+	rows.any_cuts = all.any_cuts;
+	for (std::size_t r(0); r < all.copy_index.size(); ++r) {
+		bool const has_cuts(all.any_cuts && all.cut_offsets[r + 1] != all.cut_offsets[r]);
+		if (V2M_PLOIDY_MAX == all.copy_index[r] && !has_cuts) continue;
+		if (has_space(all.ids[r])) throw std::runtime_error("the sequence name \"" + all.ids[r] + "\" holds whitespace, which a chain's qName cannot");
+		rows.ids.push_back(all.ids[r]);
+		rows.copy_index.push_back(all.copy_index[r]);
+		if (all.any_cuts) {
+			rows.cut_nodes.insert(rows.cut_nodes.end(), all.cut_nodes.begin() + all.cut_offsets[r], all.cut_nodes.begin() + all.cut_offsets[r + 1]);
+			rows.cut_copies.insert(rows.cut_copies.end(), all.cut_copies.begin() + all.cut_offsets[r], all.cut_copies.begin() + all.cut_offsets[r + 1]);
+			rows.cut_offsets.push_back(rows.cut_nodes.size());
+		}
+	}
+	v2m_row_batch batch{};
+	batch.n_rows = rows.copy_index.size();
+	batch.copy_index = rows.copy_index.data();
+	if (rows.any_cuts) {
+		batch.cut_offsets = rows.cut_offsets.data();
+		batch.cut_nodes = rows.cut_nodes.data();
+		batch.cut_copies = rows.cut_copies.data();
+	}
+	chain_state st{&open(), &rows.ids, &t_name, nullptr};
+	int const rc(v2m_row_ops(m_gpu.get(), &batch, 0, chain_sink, &st));
+	if (st.error) std::rethrow_exception(st.error);
+	m_gpu.check(rc);
+}
+
+
+void output::output_chain(variant_graph const &graph, char const *path)
+{
+	std::ofstream stream;
+	write_chains(graph, [&]() -> std::ostream & {
+		stream.open(path, std::ios::binary | std::ios::trunc);
+		if (!stream) throw std::runtime_error(std::string("unable to open ") + path + " for writing");
+		return stream;
+	});
+	stream.flush();
+	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
 }
 
 

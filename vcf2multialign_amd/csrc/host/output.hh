@@ -8,6 +8,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <ostream>
 #include <string>
 #include <vector>
@@ -34,6 +35,15 @@ struct output_region {
 	std::string name;
 	u64 col_begin{}, col_end{};
 };
+
+// One UCSC chain (reference -> row) from a row's alignment ops (include/v2m_hip.h, "row alignment ops"): a pure function of its arguments.
+//   chain <score> <t_name> <t_size> + <tStart> <tEnd> <q_name> <q_size> + <qStart> <qEnd> <id>
+//   <size> <dt> <dq>      one line per M op but the last: dt / dq are the summed D / I lengths between it and the next M op
+//   <size>                the last M op
+//   (a blank line)
+// score = the summed M lengths; leading and trailing I / D ops move tStart / qStart and tEnd / qEnd inward from 0 and the sizes.
+// Ops without any M give the empty string (no chain).  Throws std::invalid_argument for an op code other than M, I, D.
+std::string chain_text(v2m_aln_op const *ops, u64 n_ops, std::string const &t_name, u64 t_size, std::string const &q_name, u64 q_size, u64 id);
 
 class output {
 public:
@@ -77,6 +87,14 @@ public:
 	void output_regions(variant_graph const &graph, std::vector<output_region> const &regions, std::size_t regions_per_pass);
 	virtual void output_a2m(variant_graph const &graph, std::ostream &stream) = 0;
 
+	// --output-chain: one chain per output row (chain_text above: the reference as target, the row as query) into `path`, from
+	// v2m_row_ops on the first context, which must hold every copy.  Rows and order are those of the A2M output minus the REF row
+	// (which has no chain, whatever should_output_reference says); tName is prefixed("REF", '.'), qName the row's name as
+	// output_separate() forms it without a suffix, id the 1-based number of the chain's row.  A name with whitespace in it is a
+	// std::runtime_error before any GPU work; a row without any M op gets no chain and a warning on stderr.
+	void output_chain(variant_graph const &graph, char const *path);
+	void output_chain(variant_graph const &graph, std::ostream &stream);
+
 protected:
 	struct row_set {
 		std::vector<std::string> ids;           // FASTA identifiers (a2m) or file names (separate)
@@ -94,6 +112,8 @@ protected:
 	void write_a2m(row_set const &rows, std::ostream &stream);
 	void write_a2m_sharded(row_set const &rows, char const *dst_name);
 	virtual row_set a2m_rows(variant_graph const &graph) = 0;
+	void write_chains(variant_graph const &graph, std::function<std::ostream &()> const &open);   // `open` is called once the names are checked
+	virtual row_set chain_rows(variant_graph const &graph) = 0;   // the rows of a2m_rows() under the names of output_separate()
 	void write_separate(row_set const &rows);
 	std::string prefixed(std::string const &name, char sep) const;
 
@@ -119,6 +139,7 @@ public:
 private:
 	row_set rows_for(variant_graph const &graph, char sep, char const *suffix);
 	row_set a2m_rows(variant_graph const &graph) override { return rows_for(graph, '\t', ""); }
+	row_set chain_rows(variant_graph const &graph) override { return rows_for(graph, '.', ""); }
 };
 
 class founder_sequence_greedy_output final : public output {
@@ -134,6 +155,7 @@ public:
 private:
 	row_set rows_for(char sep, char const *suffix);
 	row_set a2m_rows(variant_graph const &) override { return rows_for('\t', ""); }
+	row_set chain_rows(variant_graph const &) override { return rows_for('.', ""); }
 	std::vector<u64> m_cut_positions;
 	std::vector<u32> m_assigned_samples;
 	u32 m_founder_count{};

@@ -2433,6 +2433,336 @@ __global__ __launch_bounds__(256) void scan_tile_counts_kernel(u32 *__restrict__
 
 
 // ---------------------------------------------------------------------------------------------
+// Row alignment ops (v2m_row_ops, include/v2m_hip.h "row alignment ops"): the run-length encoding of every row's
+// alignment to the REF row.  Column c of a row has two bits -- ref: the 0-padded template holds a byte there; row: the
+// row's tile, built exactly as the unaligned stream-out builds it (patch_row_tile with 0 as padding), holds one --
+// and a class code ref | row << 1: 3 = M, 2 = I, 1 = D, 0 = the column is skipped.  A BREAKPOINT is a non-skipped
+// column whose class differs from that of the non-skipped column before it; the ops are the breakpoints.
+//   pass 1  count_row_ops_kernel      per (row, tile): breakpoints with nothing carried into the tile (its first
+//                                     non-skipped column always counts), the tile's first and last class
+//   pass 2  scan_row_ops_kernel       per row over its tiles, carrying the class of the last non-skipped column:
+//                                     a tile whose first class equals the carry loses its first breakpoint, an
+//                                     all-skipped tile passes the carry on -> per tile the op offset and the carry
+//                                     into it, per row the op count
+//   pass 3  emit_row_ops_kernel       the walk of pass 1 again, started from the carry: breakpoint `rank` of a tile
+//                                     goes to op_base[row] + offset + rank as (class, reference bytes before the
+//                                     column, row bytes before the column).  An op's length is the distance to the
+//                                     next breakpoint -- in reference bytes for M and D, in row bytes for I --
+//                                     which the host takes where it reads the records.
+// Work item and grid are the row kernels' (map_block).  Thread t owns the 16-B chunks t + 256 k; in column order the
+// tile is 16 slots of 1 KiB, slot k * 4 + wave = that wave's chunks of round k, so what is carried from column to
+// column (the class of the last non-skipped column; the running counts) is one wave scan per slot plus a carry over
+// the 16 slots, as in the stream-out.
+// ---------------------------------------------------------------------------------------------
+struct row_op_record { u32 cls, ref_pos, row_pos; };   // cls: ref | row << 1
+
+// Bit i set for every non-zero byte i of the 16-B chunk.
+__device__ __forceinline__ u32 nonzero_byte_bits(vec4u const v)
+{
+	u32 bits = 0;
+#pragma unroll
+	for (int d = 0; d < 4; ++d) {
+		u32 const keep = ~zero_bytes_mask(v[d]) & 0x80808080u;   // bits 7, 15, 23, 31
+		bits |= (((keep >> 7) | (keep >> 14) | (keep >> 21) | (keep >> 28)) & 0xFu) << (4 * d);
+	}
+	return bits;
+}
+
+constexpr int kOpsSlots = kChunksPerThread * (kSpliceThreads / 64);   // 16
+
+template <bool kEmit>
+__device__ __forceinline__ void row_ops_tiles(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 *__restrict__ tile_info /* [n_rows][n_tiles]; count: written (breakpoints | first class << 16 | last class << 18); emit: the carry into the tile */,
+	u32 n_tiles, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run,
+	u32 const *__restrict__ op_offsets /* [n_rows][n_tiles] */, u32 const *__restrict__ tile_ref_before /* [n_tiles] */,
+	u32 const *__restrict__ tile_row_before /* [n_rows][n_tiles] */, u64 const *__restrict__ op_base /* [n_rows] */,
+	row_op_record *__restrict__ out, u64 out_capacity)
+{
+	constexpr int kWaves = kSpliceThreads / 64;
+	__shared__ vec4u lds[kTileChunks];
+	__shared__ patch_cache pc;
+	__shared__ u32 slot_last[kOpsSlots];      // class of each slot's last non-skipped column (0: none)
+	__shared__ u32 slot_sums[2][kOpsSlots];   // emit: per slot, breakpoints | reference bytes << 16, and row bytes
+	__shared__ u32 wave_sums[kWaves];         // count: breakpoints per wave
+	__shared__ u32 first_class;               // count: class of the tile's first non-skipped column
+
+	V2M_POISON_LDS(lds);
+	V2M_POISON_LDS(pc);
+	V2M_POISON_LDS(slot_last);
+	V2M_POISON_LDS(slot_sums);
+	V2M_POISON_LDS(wave_sums);
+	V2M_POISON_LDS(first_class);
+	int const t = threadIdx.x;
+	int const lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+	u32 tile, group;
+	map_block(blockIdx.x, n_groups, n_tiles, tile_run, tile, group);
+	u32 const row_begin = group * rows_per_group;
+	u32 const row_end = (row_begin + rows_per_group < n_rows) ? row_begin + rows_per_group : n_rows;
+
+	vec4u pristine[kChunksPerThread];
+	u32 ref_bits[kChunksPerThread];
+#pragma unroll
+	for (int k = 0; k < kChunksPerThread; ++k) {
+		pristine[k] = tmpl0[(u64) tile * kTileChunks + t + kSpliceThreads * k];
+		ref_bits[k] = nonzero_byte_bits(pristine[k]);
+	}
+	u32 const ref_before_tile = kEmit ? tile_ref_before[tile] : 0u;
+
+	tile_job job;
+	load_patch_cache<false, false>(pc, job, tt, patches, labels, eff, eff_words_per_row, tile, row_begin, row_end - row_begin, t);
+	u64 const below_lanes = (1ULL << lane) - 1;
+
+	for (u32 row = row_begin; row < row_end; ++row) {
+		if (row != row_begin && 0 == (row - row_begin) % (u32) kGroupRowsLds)   // (as in the row kernels: the next kGroupRowsLds rows' effective-edge words)
+			load_eff_cache(pc, job, eff, eff_words_per_row, row, row_end - row, t);
+#pragma unroll
+		for (int k = 0; k < kChunksPerThread; ++k) lds[t + kSpliceThreads * k] = pristine[k];
+		if (!kEmit && 0 == t) first_class = 0;
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                      // (a barrier at the loop's head)
+		__syncthreads();
+
+		patch_row_tile<false>((unsigned char *) lds, pc, job, tt, patches, labels, eff + (u64) row * eff_words_per_row, (row - row_begin) % (u32) kGroupRowsLds, t, 0);
+
+		// per chunk: the row's bits, the class of its last non-skipped column, and (from ballots, no LDS) that of the last
+		// non-skipped column of the wave's earlier chunks of the same slot
+		u32 row_bits[kChunksPerThread], wave_carry[kChunksPerThread];
+#pragma unroll
+		for (int k = 0; k < kChunksPerThread; ++k) {
+			row_bits[k] = nonzero_byte_bits(lds[t + kSpliceThreads * k]);
+			u32 const live = ref_bits[k] | row_bits[k];
+			u32 last = 0;
+			if (live) {
+				u32 const top = 31u - (u32) __builtin_clz(live);
+				last = ((ref_bits[k] >> top) & 1u) | (((row_bits[k] >> top) & 1u) << 1);
+			}
+			u64 const b0 = __ballot(last & 1u), b1 = __ballot(last & 2u);
+			u64 const any = b0 | b1, before = any & below_lanes;
+			u32 carry = 0;
+			if (before) {
+				u32 const p = 63u - (u32) __builtin_clzll(before);
+				carry = (u32) ((b0 >> p) & 1u) | ((u32) ((b1 >> p) & 1u) << 1);
+			}
+			wave_carry[k] = carry;
+			if (0 == lane) {
+				u32 slot_class = 0;
+				if (any) {
+					u32 const p = 63u - (u32) __builtin_clzll(any);
+					slot_class = (u32) ((b0 >> p) & 1u) | ((u32) ((b1 >> p) & 1u) << 1);
+				}
+				slot_last[k * kWaves + wave] = slot_class;
+			}
+		}
+		__syncthreads();
+
+		// the breakpoints of every chunk, with the class carried into the tile (count: none) handed from slot to slot
+		u32 const tile_carry = kEmit ? tile_info[(u64) row * n_tiles + tile] : 0u;
+		u32 breaks[kChunksPerThread], slot_carry[kChunksPerThread];
+		u32 tile_last = tile_carry;
+#pragma unroll
+		for (int s = 0; s < kOpsSlots; ++s) {   // (slot s is round s / kWaves of wave s % kWaves: every thread walks all 16, no loop that depends on the wave)
+			if (wave == s % kWaves) slot_carry[s / kWaves] = tile_last;
+			u32 const c = slot_last[s];
+			if (c) tile_last = c;
+		}
+#pragma unroll
+		for (int k = 0; k < kChunksPerThread; ++k) {
+			u32 const carry = wave_carry[k] ? wave_carry[k] : slot_carry[k];
+			u32 const live = ref_bits[k] | row_bits[k];
+			// bit i of prev_ref / prev_row: the bit of the last non-skipped column before column i (known[i]: there is one), filled forward over the skipped columns
+			u32 known = ((live << 1) | (carry ? 1u : 0u)) & 0xFFFFu;
+			u32 prev_ref = ((ref_bits[k] << 1) | (carry & 1u)) & 0xFFFFu;
+			u32 prev_row = ((row_bits[k] << 1) | (carry >> 1)) & 0xFFFFu;
+#pragma unroll
+			for (int d = 1; d < 16; d <<= 1) {
+				prev_ref |= (prev_ref << d) & ~known & 0xFFFFu;
+				prev_row |= (prev_row << d) & ~known & 0xFFFFu;
+				known |= (known << d) & 0xFFFFu;
+			}
+			breaks[k] = live & ((ref_bits[k] ^ prev_ref) | (row_bits[k] ^ prev_row));
+			if (!kEmit && live && 0 == carry) {   // (one chunk per tile at most: the first one with a non-skipped column)
+				u32 const low = (u32) __builtin_ctz(live);
+				first_class = ((ref_bits[k] >> low) & 1u) | (((row_bits[k] >> low) & 1u) << 1);
+			}
+		}
+
+		if (!kEmit) {
+			u32 mine = 0;
+#pragma unroll
+			for (int k = 0; k < kChunksPerThread; ++k) mine += (u32) __builtin_popcount(breaks[k]);
+#pragma unroll
+			for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d, kWave);
+			if (0 == lane) wave_sums[wave] = mine;
+			__syncthreads();
+			if (0 == t) {
+				u32 total = 0;
+#pragma unroll
+				for (int wv = 0; wv < kWaves; ++wv) total += wave_sums[wv];
+				tile_info[(u64) row * n_tiles + tile] = total | first_class << 16 | tile_last << 18;   // total <= kTileBytes = 1 << 14
+			}
+		} else {
+			// running counts before every chunk: breakpoints | reference bytes << 16 (each at most kTileBytes in a tile) and row bytes
+			u32 mine[2 * kChunksPerThread], incl[2 * kChunksPerThread];
+#pragma unroll
+			for (int k = 0; k < kChunksPerThread; ++k) {
+				incl[k] = mine[k] = (u32) __builtin_popcount(breaks[k]) | (u32) __builtin_popcount(ref_bits[k]) << 16;
+				incl[kChunksPerThread + k] = mine[kChunksPerThread + k] = (u32) __builtin_popcount(row_bits[k]);
+			}
+			wave_inclusive_scan_u32_lockstep(incl);
+			if (63 == lane) {
+#pragma unroll
+				for (int k = 0; k < kChunksPerThread; ++k) {
+					slot_sums[0][k * kWaves + wave] = incl[k];
+					slot_sums[1][k * kWaves + wave] = incl[kChunksPerThread + k];
+				}
+			}
+			__syncthreads();
+			u64 const row_tile = (u64) row * n_tiles + tile;
+			u64 const first_op = op_base[row] + op_offsets[row_tile];
+			u32 const row_before_tile = tile_row_before[row_tile];
+			u32 slot_a[kChunksPerThread], slot_b[kChunksPerThread];
+			{
+				u32 run_a = 0, run_b = 0;
+#pragma unroll
+				for (int s = 0; s < kOpsSlots; ++s) {
+					if (wave == s % kWaves) { slot_a[s / kWaves] = run_a; slot_b[s / kWaves] = run_b; }
+					run_a += slot_sums[0][s];
+					run_b += slot_sums[1][s];
+				}
+			}
+#pragma unroll
+			for (int k = 0; k < kChunksPerThread; ++k) {
+				u32 const before_a = slot_a[k] + incl[k] - mine[k];
+				u32 const before_b = slot_b[k] + incl[kChunksPerThread + k] - mine[kChunksPerThread + k];
+				for (u32 b = breaks[k]; b; b &= b - 1) {
+					u32 const i = (u32) __builtin_ctz(b), lower = (1u << i) - 1u;
+					row_op_record rec;
+					rec.cls = ((ref_bits[k] >> i) & 1u) | (((row_bits[k] >> i) & 1u) << 1);
+					rec.ref_pos = ref_before_tile + (before_a >> 16) + (u32) __builtin_popcount(ref_bits[k] & lower);
+					rec.row_pos = row_before_tile + before_b + (u32) __builtin_popcount(row_bits[k] & lower);
+					u64 const at = first_op + (before_a & 0xFFFFu) + (u32) __builtin_popcount(breaks[k] & lower);
+					if (at < out_capacity) out[at] = rec;   // (always, when the offsets are pass 2's: the guard keeps a wrong table from writing past the buffer)
+				}
+			}
+		}
+		// slot_last, slot_sums, wave_sums and first_class are rewritten only after the next row's barriers
+	}
+}
+
+__global__ __launch_bounds__(kSpliceThreads) void count_row_ops_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 *__restrict__ tile_info /* [n_rows][n_tiles] */, u32 n_tiles, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
+{
+	row_ops_tiles<false>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_info, n_tiles, n_rows, rows_per_group, n_groups, tile_run,
+		nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+}
+
+__global__ __launch_bounds__(kSpliceThreads) void emit_row_ops_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 *__restrict__ tile_info /* [n_rows][n_tiles]: the carry into each tile (pass 2) */, u32 n_tiles, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run,
+	u32 const *__restrict__ op_offsets, u32 const *__restrict__ tile_ref_before, u32 const *__restrict__ tile_row_before, u64 const *__restrict__ op_base,
+	row_op_record *__restrict__ out, u64 out_capacity)
+{
+	row_ops_tiles<true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_info, n_tiles, n_rows, rows_per_group, n_groups, tile_run,
+		op_offsets, tile_ref_before, tile_row_before, op_base, out, out_capacity);
+}
+
+// Pass 2, one workgroup per row: tile_info[row][tile] (pass 1's breakpoints | first class << 16 | last class << 18) becomes the class
+// carried INTO the tile, op_offsets[row][tile] the ops of the row's tiles before it, n_ops[row] the row's ops.
+__global__ __launch_bounds__(256) void scan_row_ops_kernel(u32 *__restrict__ tile_info, u32 *__restrict__ op_offsets, u32 n_tiles, u32 *__restrict__ n_ops)
+{
+	__shared__ u32 wave_sums[4];
+	__shared__ u32 wave_last[4];
+	__shared__ u32 carry_s[2];   // ops so far, class of the last non-skipped column so far
+	V2M_POISON_LDS(wave_sums);
+	V2M_POISON_LDS(wave_last);
+	V2M_POISON_LDS(carry_s);
+	u32 *const info = tile_info + (u64) blockIdx.x * n_tiles;
+	u32 *const offsets = op_offsets + (u64) blockIdx.x * n_tiles;
+	int const t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	if (t == 0) { carry_s[0] = 0; carry_s[1] = 0; }
+	__syncthreads();
+	for (u32 base = 0; base < n_tiles; base += 256) {
+		u32 const i = base + t;
+		u32 const mine = i < n_tiles ? info[i] : 0u;
+		u32 const breaks = mine & 0xFFFFu, first = (mine >> 16) & 3u, last = (mine >> 18) & 3u;
+		u64 const b0 = __ballot(last & 1u), b1 = __ballot(last & 2u);
+		u64 const any = b0 | b1, before = any & ((1ULL << lane) - 1);
+		u32 wave_carry = 0;
+		if (before) {
+			u32 const p = 63u - (u32) __builtin_clzll(before);
+			wave_carry = (u32) ((b0 >> p) & 1u) | ((u32) ((b1 >> p) & 1u) << 1);
+		}
+		if (0 == lane) {
+			u32 c = 0;
+			if (any) {
+				u32 const p = 63u - (u32) __builtin_clzll(any);
+				c = (u32) ((b0 >> p) & 1u) | ((u32) ((b1 >> p) & 1u) << 1);
+			}
+			wave_last[wave] = c;
+		}
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		__syncthreads();
+		u32 carry = carry_s[1], block_last = carry_s[1];
+#pragma unroll
+		for (int wv = 0; wv < 4; ++wv) {
+			u32 const c = wave_last[wv];
+			if (c) { if (wv < wave) carry = c; block_last = c; }
+		}
+		if (wave_carry) carry = wave_carry;
+		u32 const ops = breaks - ((breaks && first == carry) ? 1u : 0u);
+		u32 const incl = wave_inclusive_scan_u32(ops);
+		if (lane == 63) wave_sums[wave] = incl;
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		__syncthreads();
+		u32 ops_before = carry_s[0], total = 0;
+#pragma unroll
+		for (int wv = 0; wv < 4; ++wv) {
+			u32 const ws = wave_sums[wv];
+			if (wv < wave) ops_before += ws;
+			total += ws;
+		}
+		if (i < n_tiles) {
+			info[i] = carry;
+			offsets[i] = ops_before + incl - ops;
+		}
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		__syncthreads();
+		if (t == 0) { carry_s[0] += total; carry_s[1] = block_last; }
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		__syncthreads();
+	}
+	if (t == 0) n_ops[blockIdx.x] = carry_s[0];
+}
+
+// Non-zero bytes of every tile of the 0-padded template (one workgroup per tile): scan_tile_counts_kernel over them as one "row" gives
+// the reference bytes before each tile, the table pass 3 starts its reference positions from.
+__global__ __launch_bounds__(kSpliceThreads) void count_template_tiles_kernel(vec4u const *__restrict__ tmpl0, u32 *__restrict__ tile_counts)
+{
+	__shared__ u32 wave_sums[kSpliceThreads / 64];
+	V2M_POISON_LDS(wave_sums);
+	int const t = threadIdx.x;
+	u32 mine = 0;
+#pragma unroll
+	for (int k = 0; k < kChunksPerThread; ++k)
+		mine += (u32) __builtin_popcount(nonzero_byte_bits(tmpl0[(u64) blockIdx.x * kTileChunks + t + kSpliceThreads * k]));
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d, kWave);
+	if ((t & 63) == 0) wave_sums[t >> 6] = mine;
+	__syncthreads();
+	if (0 == t) {
+		u32 total = 0;
+#pragma unroll
+		for (int wv = 0; wv < kSpliceThreads / 64; ++wv) total += wave_sums[wv];
+		tile_counts[blockIdx.x] = total;
+	}
+}
+
+
+// ---------------------------------------------------------------------------------------------
 // Write-rate probe for output buffers (v2m_alloc_output): the splice kernel's store pattern -- n_groups x 16
 // rows `pitch` apart advancing together in 16-KiB segments, nontemporal 16-B/lane stores -- with no reads.
 // On MI355X the rate this pattern reaches differs by ~25 % between physical regions of HBM

@@ -180,7 +180,7 @@ struct v2m_ctx {
 
 	// profiling
 	bool profiling{};
-	std::vector<event_pair> events[V2M_KERNEL_COUNT];
+	std::vector<event_pair> events[V2M_KERNEL_END];
 	std::vector<event_pair> free_events;
 
 	// graph
@@ -246,6 +246,13 @@ struct v2m_ctx {
 	scratch_buf d_resolve_queue, d_resolve_count;   // (row, word) pairs the streaming resolve pass leaves to the dense one
 	scratch_buf d_eff, d_row_bits, d_seg_offsets, d_seg_edge_begin, d_seg_copy, d_sums, d_lengths, d_needs_serial, d_tile_counts, d_row_lengths;
 	scratch_buf ring[2];
+	// row alignment ops (v2m_row_ops): the reference bytes before each tile of the whole view (once per upload), a slice's per-tile
+	// breakpoint words / carried classes, op offsets, per-row op counts and bases, its breakpoint records, and their pinned staging
+	dev_buf d_ops_ref_before;
+	bool has_ops_ref_before{};
+	scratch_buf d_ops_info, d_ops_offsets, d_ops_counts, d_ops_base, d_ops_out;
+	pinned_buf h_ops_stage, h_ops_out;
+	std::vector<v2m_aln_op> ops_row;
 	// pinned slots: the rows of v2m_splice_rows[_held] (a slot is kept until the sink has released its rows); slots 0 and 1 also stage
 	// the BGZF members and v2m_upload_path_blocks' columns
 	held_ring_state held_state;
@@ -1838,6 +1845,7 @@ int v2m_upload_graph(v2m_ctx *ctx, const v2m_graph_view *g, const char *ref_seq,
 	v.max_unaligned = ref_len + label_total;
 	v.n_tiles = n_tiles;
 	v.has_template0 = false;
+	ctx->has_ops_ref_before = false;
 	v.words = {0, 0, (E + 63) / 64, (((E + 63) / 64) + 15) & ~u64(15)};
 	if (int const rc = upload_vec(ctx, v.d_edge_begin, tile_edge_begin)) return rc;
 	if (int const rc = upload_vec(ctx, v.d_cross_offsets, cross_offsets)) return rc;
@@ -2645,6 +2653,188 @@ void v2m_row_release(v2m_row_hold *hold)
 
 
 
+// ---- row alignment ops ------------------------------------------------------------------------------
+
+namespace {
+
+// The whole-row view for the duration of a call, whatever column window is in force; the window comes back untouched.
+struct scoped_whole_rows {
+	v2m_ctx *ctx;
+	bool was;
+	explicit scoped_whole_rows(v2m_ctx *c) : ctx(c), was(c->windowed) { c->windowed = false; }
+	~scoped_whole_rows() { ctx->windowed = was; }
+};
+
+u64 ops_slice_budget()
+{
+	char const *const e(std::getenv("V2M_OPS_SLICE_BYTES"));   // test knob: small slices on small graphs
+	return (e && *e) ? std::strtoull(e, nullptr, 10) : (u64(64) << 20);
+}
+
+// Passes 1 and 2 for rows [row_begin, row_end) of the batch over the whole view: effective edges, the unaligned tile offsets and row lengths
+// (count_unaligned_kernel + scan_tile_counts_kernel, as the unaligned splice has them), breakpoints per row tile, op offsets and carried
+// classes.  Leaves the rows' op counts (u32) and lengths (u64) in ctx->h_ops_stage, in that order, and returns their sum in *total_ops.
+int row_ops_count_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row_end, u64 *total_ops)
+{
+	u64 const n_rows(row_end - row_begin);
+	row_view &v(ctx->whole);
+	if (int const rc = resolve_slice(ctx, rows, row_begin, row_end)) return rc;
+	splice_grid g;
+	if (int const rc = make_grid(ctx, n_rows, g)) return rc;
+	u64 const cells(n_rows * v.n_tiles);
+	V2M_HIP_TRY(ctx, ctx->d_row_lengths.ensure(n_rows * sizeof(u64)));
+	V2M_HIP_TRY(ctx, ctx->d_tile_counts.ensure(cells * sizeof(u32)));
+	V2M_HIP_TRY(ctx, ctx->d_ops_info.ensure(cells * sizeof(u32)));
+	V2M_HIP_TRY(ctx, ctx->d_ops_offsets.ensure(cells * sizeof(u32)));
+	V2M_HIP_TRY(ctx, ctx->d_ops_counts.ensure(n_rows * sizeof(u32)));
+	v2m::tile_tables const tt{v.d_edge_begin.as<u32>(), v.d_cross_offsets.as<u32>(), v.d_cross_edges.as<u32>()};
+	u64 const *const d_eff(ctx->d_eff.as<u64>() - v.words.restart);
+	{
+		u32 const count_rows(u32(std::min<u64>(n_rows, u64(v2m::kCountRowsMax))));
+		u32 const count_groups(u32((n_rows + count_rows - 1) / count_rows));
+		timed_launch tl(ctx, V2M_KERNEL_UNALIGNED_COUNT);
+		hipLaunchKernelGGL(v2m::count_unaligned_kernel, dim3(unsigned(u64(v.n_tiles) * count_groups)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+			v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+			ctx->d_tile_counts.as<u32>(), v.n_tiles, u32(n_rows), count_rows, count_groups, g.tile_run);
+		hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(unsigned(n_rows)), dim3(256), 0, ctx->stream,
+			ctx->d_tile_counts.as<u32>(), v.n_tiles, ctx->d_row_lengths.as<u64>());
+	}
+	{
+		timed_launch tl(ctx, V2M_KERNEL_ROW_OPS_COUNT);
+		hipLaunchKernelGGL(v2m::count_row_ops_kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+			v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+			ctx->d_ops_info.as<u32>(), v.n_tiles, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run);
+	}
+	{
+		timed_launch tl(ctx, V2M_KERNEL_ROW_OPS_SCAN);
+		hipLaunchKernelGGL(v2m::scan_row_ops_kernel, dim3(unsigned(n_rows)), dim3(256), 0, ctx->stream,
+			ctx->d_ops_info.as<u32>(), ctx->d_ops_offsets.as<u32>(), v.n_tiles, ctx->d_ops_counts.as<u32>());
+	}
+	V2M_HIP_TRY(ctx, hipGetLastError());
+	u64 const counts_bytes((n_rows * sizeof(u32) + 7) & ~u64(7));
+	V2M_HIP_TRY(ctx, ctx->h_ops_stage.ensure(counts_bytes + 2 * n_rows * sizeof(u64)));
+	V2M_POISON_HOST(ctx->h_ops_stage.p, counts_bytes + 2 * n_rows * sizeof(u64));
+	char *const stage(ctx->h_ops_stage.as<char>());
+	V2M_HIP_TRY(ctx, hipMemcpyAsync(stage, ctx->d_ops_counts.p, n_rows * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+	V2M_HIP_TRY(ctx, hipMemcpyAsync(stage + counts_bytes, ctx->d_row_lengths.p, n_rows * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	u32 const *const counts(reinterpret_cast<u32 const *>(stage));
+	*total_ops = 0;
+	for (u64 r(0); r < n_rows; ++r) *total_ops += counts[r];
+	return V2M_OK;
+}
+
+// Pass 3 for rows [piece_begin, piece_end) of the slice of slice_rows rows that row_ops_count_slice has just counted (slice_begin = the slice's
+// first row in the batch), and those rows to the sink.  The slice's tables are indexed by row, so a piece needs nothing counted again: it takes
+// them from its first row on.
+int row_ops_emit_piece(v2m_ctx *ctx, u64 slice_begin, u64 slice_rows, u64 piece_begin, u64 piece_end, v2m_ops_sink_fn sink, void *user)
+{
+	u64 const n_rows(piece_end - piece_begin);
+	row_view &v(ctx->whole);
+	u64 const counts_bytes((slice_rows * sizeof(u32) + 7) & ~u64(7));
+	char *const stage(ctx->h_ops_stage.as<char>());
+	u32 const *const counts(reinterpret_cast<u32 const *>(stage) + piece_begin);
+	u64 const *const lengths(reinterpret_cast<u64 const *>(stage + counts_bytes) + piece_begin);
+	u64 *const bases(reinterpret_cast<u64 *>(stage + counts_bytes + slice_rows * sizeof(u64)) + piece_begin);
+	u64 total_ops(0);
+	for (u64 r(0); r < n_rows; ++r) { bases[r] = total_ops; total_ops += counts[r]; }
+	v2m::row_op_record const *records(nullptr);
+	if (total_ops) {
+		splice_grid g;
+		if (int const rc = make_grid(ctx, n_rows, g)) return rc;
+		V2M_HIP_TRY(ctx, ctx->d_ops_base.ensure(n_rows * sizeof(u64)));
+		V2M_HIP_TRY(ctx, ctx->d_ops_out.ensure(total_ops * sizeof(v2m::row_op_record)));
+		V2M_HIP_TRY(ctx, ctx->h_ops_out.ensure(total_ops * sizeof(v2m::row_op_record)));
+		V2M_POISON_HOST(ctx->h_ops_out.p, total_ops * sizeof(v2m::row_op_record));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ops_base.p, bases, n_rows * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+		v2m::tile_tables const tt{v.d_edge_begin.as<u32>(), v.d_cross_offsets.as<u32>(), v.d_cross_edges.as<u32>()};
+		u64 const first_cell(piece_begin * v.n_tiles);
+		{
+			timed_launch tl(ctx, V2M_KERNEL_ROW_OPS_EMIT);
+			hipLaunchKernelGGL(v2m::emit_row_ops_kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+				v.d_template0.as<v2m::vec4u>(), ctx->d_eff.as<u64>() - v.words.restart + piece_begin * v.words.stride, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
+				ctx->d_ops_info.as<u32>() + first_cell, v.n_tiles, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run,
+				ctx->d_ops_offsets.as<u32>() + first_cell, ctx->d_ops_ref_before.as<u32>(), ctx->d_tile_counts.as<u32>() + first_cell, ctx->d_ops_base.as<u64>(),
+				ctx->d_ops_out.as<v2m::row_op_record>(), total_ops);
+		}
+		V2M_HIP_TRY(ctx, hipGetLastError());
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ops_out.p, ctx->d_ops_out.p, total_ops * sizeof(v2m::row_op_record), hipMemcpyDeviceToHost, ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		records = ctx->h_ops_out.as<v2m::row_op_record>();
+	}
+	// an op runs to the next breakpoint, the last one to the row's end (reference length, row length): in reference bytes for M and D, in row bytes for I
+	for (u64 r(0); r < n_rows; ++r) {
+		u64 const n(counts[r]);
+		ctx->ops_row.resize(n);
+		for (u64 i(0); i < n; ++i) {
+			v2m::row_op_record const &rec(records[bases[r] + i]);
+			bool const last(i + 1 == n);
+			u64 const next_ref(last ? ctx->ref_len : records[bases[r] + i + 1].ref_pos), next_row(last ? lengths[r] : records[bases[r] + i + 1].row_pos);
+			bool const insertion(2 == rec.cls);
+			ctx->ops_row[i].op = 3 == rec.cls ? V2M_OP_M : insertion ? V2M_OP_I : V2M_OP_D;
+			ctx->ops_row[i].length = u32(insertion ? next_row - rec.row_pos : next_ref - rec.ref_pos);
+		}
+		u64 const row(slice_begin + piece_begin + r);
+		if (sink(user, row, ctx->ops_row.data(), n, lengths[r]))
+			return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) row);
+	}
+	return V2M_OK;
+}
+
+} // namespace
+
+int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_ops_sink_fn sink, void *user)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (flags) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "v2m_row_ops takes no flags (got 0x%x)", flags);
+	if (int const rc = check_batch(ctx, rows, V2M_SPLICE_UNALIGNED)) return rc;   // (the ops are read off the unaligned kernels' 0-padded rows: a NUL byte refuses as there)
+	if (!sink) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "sink is NULL");
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	scoped_whole_rows const whole(ctx);
+	row_view &v(ctx->whole);
+	if (0 == ctx->aligned_len) {   // no column, no op
+		for (u64 r(0); r < rows->n_rows; ++r)
+			if (sink(user, r, nullptr, 0, 0)) return fail(ctx, V2M_ERR_SINK, "sink aborted at row %llu", (unsigned long long) r);
+		return V2M_OK;
+	}
+	if (!v.has_template0) {
+		if (int const rc = expand_reference(ctx, v, v.d_template0, 0)) return rc;
+		v.has_template0 = true;
+	}
+	if (!ctx->has_ops_ref_before) {   // once per upload: the reference bytes before every tile
+		scratch_buf total;
+		V2M_HIP_TRY(ctx, ctx->d_ops_ref_before.ensure(std::max<size_t>(v.n_tiles * sizeof(u32), 16)));
+		V2M_HIP_TRY(ctx, total.ensure(sizeof(u64)));
+		hipLaunchKernelGGL(v2m::count_template_tiles_kernel, dim3(v.n_tiles), dim3(v2m::kSpliceThreads), 0, ctx->stream, v.d_template0.as<v2m::vec4u>(), ctx->d_ops_ref_before.as<u32>());
+		hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->d_ops_ref_before.as<u32>(), v.n_tiles, total.as<u64>());
+		V2M_HIP_TRY(ctx, hipGetLastError());
+		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		ctx->has_ops_ref_before = true;
+	}
+
+	// Slices: as many rows as keep what pass 1 and 2 leave per row -- three words per tile, and the effective-edge words (twice for rows with
+	// cuts: their assembled bits) -- within 256 MiB.  A slice is counted once; what the scan says its rows' breakpoint records take then cuts it
+	// into pieces of consecutive rows that fit the record budget (a single row goes through whatever it takes), each emitted from the slice's tables.
+	u64 const budget_ops(std::max<u64>(1, ops_slice_budget() / sizeof(v2m::row_op_record)));
+	u64 const row_bytes(12 * u64(v.n_tiles) + 16 * v.words.stride);
+	u64 const want(std::max<u64>(1, std::min<u64>(rows->n_rows, (u64(256) << 20) / row_bytes)));
+	for (u64 r0(0); r0 < rows->n_rows; r0 += want) {
+		u64 const n(std::min<u64>(want, rows->n_rows - r0));
+		u64 total_ops(0);
+		if (int const rc = row_ops_count_slice(ctx, rows, r0, r0 + n, &total_ops)) return rc;
+		u32 const *const counts(ctx->h_ops_stage.as<u32>());
+		for (u64 p0(0); p0 < n;) {
+			u64 p1(p0 + 1), piece_ops(counts[p0]);
+			while (p1 < n && piece_ops + counts[p1] <= budget_ops) piece_ops += counts[p1++];
+			if (int const rc = row_ops_emit_piece(ctx, r0, n, p0, p1, sink, user)) return rc;
+			p0 = p1;
+		}
+	}
+	return V2M_OK;
+}
+
+
 // ---- output buffers ------------------------------------------------------------------------------
 
 namespace {
@@ -3319,7 +3509,7 @@ int v2m_profile_reset(v2m_ctx *ctx)
 int v2m_profile_get(v2m_ctx *ctx, int kernel, uint64_t *launches_out, double *total_ms_out)
 {
 	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
-	if (kernel < 0 || kernel >= V2M_KERNEL_COUNT) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown kernel id %d", kernel);
+	if (kernel < 0 || kernel >= V2M_KERNEL_END) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown kernel id %d", kernel);
 	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	double total(0);
 	for (auto const &e : ctx->events[kernel]) {
@@ -3335,7 +3525,7 @@ int v2m_profile_get(v2m_ctx *ctx, int kernel, uint64_t *launches_out, double *to
 int v2m_profile_get_launches(v2m_ctx *ctx, int kernel, double *ms_out, uint64_t capacity, uint64_t *launches_out)
 {
 	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
-	if (kernel < 0 || kernel >= V2M_KERNEL_COUNT) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown kernel id %d", kernel);
+	if (kernel < 0 || kernel >= V2M_KERNEL_END) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown kernel id %d", kernel);
 	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	auto const &ev(ctx->events[kernel]);
 	for (u64 i(0); i < ev.size() && i < capacity && ms_out; ++i) {

@@ -26,6 +26,25 @@ class Output:
 	def _fasta_id(self, name):
 		return ((self.chromosome_id + "\t") if self.chromosome_id else "") + name
 
+	def _chain_name(self, name):
+		return ((self.chromosome_id + ".") if self.chromosome_id else "") + name
+
+	def _write_chains(self, stream, names, rows):
+		"""One UCSC chain per row (reference -> row) from Context.row_ops, formatted by the host library (host.chain_text); the REF row has
+		no chain; a row without any M op gets none either.  Returns the number of chains written."""
+		from . import host
+		keep = [(n, r) for n, r in zip(names, rows) if not (isinstance(r, int) and r == PLOIDY_MAX)]
+		for name in [self._chain_name("REF")] + [n for n, _ in keep]:
+			if any(c.isspace() for c in name):
+				raise ValueError("the sequence name %r holds whitespace, which a chain cannot" % name)
+		written = 0
+		for i, ((name, _), (ops, length)) in enumerate(zip(keep, self.ctx.row_ops(RowBatch([r for _, r in keep])))):
+			t_size = int(ops[ops[:, 0] != 1, 1].astype("u8").sum())
+			text = host.chain_text(ops, self._chain_name("REF"), t_size, name, length, 1 + i)
+			stream.write(text)
+			written += 1 if text else 0
+		return written
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -66,6 +85,15 @@ class HaplotypeOutput(Output):
 		self._write_rows(stream, ids, rows, graph)
 		return len(rows)
 
+	def output_chain(self, graph, stream):
+		"""--output-chain: the chains of the rows of output_a2m (without REF), named as one file per sequence would be."""
+		names, rows = [], []
+		for sample_idx, sample in enumerate(graph.sample_names):
+			for chr_copy_idx in range(graph.sample_ploidy(sample_idx)):
+				names.append(self._chain_name("%s.%d" % (sample, 1 + chr_copy_idx)))
+				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
+		return self._write_chains(stream, names, rows)
+
 
 class FounderSequenceGreedyOutput(Output):
 	"""The output half of founder_sequence_greedy_output (output.hh:81-130): given cut positions and the
@@ -84,3 +112,14 @@ class FounderSequenceGreedyOutput(Output):
 			rows.append(list(zip(cut_positions[:-1], col)))               # delegate: switch copy at each cut node (:106-114)
 		self._write_rows(stream, ids, rows, graph)
 		return len(rows)
+
+	def output_chain(self, graph, cut_positions, assigned_samples_column_major, stream):
+		"""--output-chain for the founder rows of output_a2m."""
+		n_rows = len(cut_positions) - 1
+		n_founders = len(assigned_samples_column_major) // n_rows if n_rows else 0
+		names, rows = [], []
+		for col_idx in range(n_founders):
+			names.append(self._chain_name(str(1 + col_idx)))
+			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
+			rows.append(list(zip(cut_positions[:-1], col)))
+		return self._write_chains(stream, names, rows)
