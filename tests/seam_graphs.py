@@ -13,7 +13,12 @@ oracle.graph_from_arrays / VariantGraph.from_object.  Three independent things t
 tests/test_seam_graphs_host.py holds the first two equal on a machine without a GPU and runs the census: from the arrays, with the kernels'
 own definitions of tile, range, crossing edge, slot and chunk, it recomputes the quantities the kernels branch on and asserts that every
 seam value a graph is meant to reach is reached.  Every number comes from csrc/kernels.hpp (kernel_constants()): a changed constant moves
-the graphs with it, a renamed one fails loudly."""
+the graphs with it, a renamed one fails loudly.
+
+A row is a chromosome copy (or PLOIDY_MAX, the REF row) or a founder row, a list of (cut node, copy) pairs.  The model of a founder row
+is its assembled bit column: per edge the bit of the copy in force at the edge's source node (SeamGraph.assembled, a plain loop).
+SegmentCensus recomputes what assemble_row_bits_kernel sees of such a row: the segment table, and per wave span and word what the
+kernel's search, lane loop and masks come to (tests/test_gpu_assemble_seams.py)."""
 
 import functools
 import os
@@ -171,7 +176,7 @@ class SeamGraph:
 		self.n_edges = begin.size
 		self.ref_row = np.full(self.length, GAP, dtype=np.uint8)
 		self.ref_row[kept] = ref
-		self._aligned, self._oracle = {}, {}
+		self._aligned, self._oracle, self._bits, self._assembled = {}, {}, {}, {}
 		self.notes = {}          # what a graph's maker wants its tests to know: tiles, edges, windows by name
 
 	@property
@@ -180,12 +185,41 @@ class SeamGraph:
 		return [PLOIDY_MAX] + list(range(len(self.copies)))
 
 	# -- the model ---------------------------------------------------------------------------------------------------------------------
+	# A row is an int (a chromosome copy, or PLOIDY_MAX for REF) or a list of (cut node, copy) pairs, as Context.splice_rows takes them.
+	@staticmethod
+	def row_key(row):
+		return int(row) if isinstance(row, (int, np.integer)) else tuple((int(node), int(copy)) for node, copy in row)
+
+	def copy_bits(self, copy):
+		"""Copy `copy`'s path bits, one bool per edge."""
+		if copy not in self._bits:
+			b = np.zeros(self.n_edges, dtype=bool)
+			b[self.copies[copy]] = True
+			self._bits[copy] = b
+		return self._bits[copy]
+
+	def assembled(self, row):
+		"""The bit column of a row: a copy's own bits; for a row with cuts, per edge the bit of the copy in force at the edge's source node
+		(the copy of the last cut at or before that node; PLOIDY_MAX, which sets nothing, before the first cut)."""
+		key = self.row_key(row)
+		if isinstance(key, int):
+			return np.zeros(self.n_edges, dtype=bool) if key == PLOIDY_MAX else self.copy_bits(key)
+		if key not in self._assembled:
+			bits = np.zeros(self.n_edges, dtype=bool)
+			k, copy = 0, PLOIDY_MAX
+			for e, node in enumerate(self.src.tolist()):
+				while k < len(key) and key[k][0] <= node:
+					copy = key[k][1]
+					k += 1
+				if copy != PLOIDY_MAX:
+					bits[e] = self.copy_bits(copy)[e]
+			self._assembled[key] = bits
+		return self._assembled[key]
+
 	def effective(self, row):
 		"""The model's walk: of the row's set edges, in order, those that begin at or after the node the walk stands on."""
-		if row == PLOIDY_MAX:
-			return []
 		out, cur = [], 0
-		for e in self.copies[row].tolist():
+		for e in np.flatnonzero(self.assembled(row)).tolist():
 			if self.src[e] >= cur:
 				out.append(e)
 				cur = self.tgt[e]
@@ -193,9 +227,10 @@ class SeamGraph:
 
 	def aligned(self, row):
 		"""The row's aligned columns (kept per row: the callers slice it many times)."""
-		if row not in self._aligned:
-			self._aligned[row] = self._aligned_uncached(row)
-		return self._aligned[row]
+		key = self.row_key(row)
+		if key not in self._aligned:
+			self._aligned[key] = self._aligned_uncached(row)
+		return self._aligned[key]
 
 	def _aligned_uncached(self, row):
 		a = self.ref_row.copy()
@@ -213,13 +248,26 @@ class SeamGraph:
 
 	def oracle_body(self, row, unaligned=False, window=None):
 		"""The oracle's row; a window of it is cut from its aligned row (a column window is defined on aligned columns)."""
-		key = (row, bool(unaligned and window is None))
+		key = (self.row_key(row), bool(unaligned and window is None))
 		if key not in self._oracle:
-			self._oracle[key] = self.g.output_sequence(self.g.ref, copy_index=row, unaligned=key[1])
+			if isinstance(key[0], int):
+				self._oracle[key] = self.g.output_sequence(self.g.ref, copy_index=key[0], unaligned=key[1])
+			else:
+				self._oracle[key] = self.g.output_sequence(self.g.ref, cuts=list(key[0]), unaligned=key[1])
 		if window is None:
 			return self._oracle[key]
 		a = np.frombuffer(self._oracle[key], dtype=np.uint8)[window[0]:window[1]]
 		return (a[a != GAP] if unaligned else a).tobytes()
+
+	# -- cuts ------------------------------------------------------------------------------------------------------------------------------
+	def first_edge_of_node(self, node):
+		"""The host's h_csum[node]: the first edge that begins at `node` or after it."""
+		return int(np.searchsorted(self.src, node, side="left"))
+
+	def is_bridge(self, node):
+		"""No edge jumps over the node: every edge that begins before it ends at or before it (where v2m_splice_rows lets a row cut)."""
+		first = self.first_edge_of_node(node)
+		return 0 == first or int(self.tgt[:first].max()) <= node
 
 
 # ---- the census: what the kernels see ------------------------------------------------------------------------------------------------
@@ -296,6 +344,79 @@ class RowCensus:
 				continue
 			for t in range(max(0, int(tt.tile_of(sg.begin[e]))), min(tt.n_tiles - 1, int(tt.tile_of(sg.end[e] - 1))) + 1):
 				self.n_long[t] += tt.clipped(sg, e, t) > K.kLongPatch
+
+
+class SegmentCensus:
+	"""One row as assemble_row_bits_kernel sees it.  The segment table is the one prepare_rows (csrc/v2m_hip.hip) builds: a row without cuts is
+	one segment (edge 0, its copy); a row with cuts has one segment per cut, (the first edge at or after the cut node, the cut's copy), and a
+	leading (edge 0, PLOIDY_MAX) one unless its first cut is node 0.  Segment s covers the edges from its first edge to the next segment's;
+	the last one goes on to the end.  The kernel puts words [word_base, n_words) together, one wave per 64 of them from word_base on.
+
+	spans        per wave span (first word, segments that begin on its first edge, segments the lane loop walks, rounds of the lane loop):
+	             the walk begins at the last segment whose first edge is <= the span's first edge and ends before the first segment that
+	             begins at or after the span's end; 64 segments per round
+	masks        {(from, to)}: per (segment, word) the first bit of the word in the segment and one past the last, REF segments left out
+	mask_at      {(segment, word): (from, to)}
+	writers      per word the number of segments that OR bits into it
+	empty        the segments that hold no edge (their first edge is the next segment's too)
+	ref          the PLOIDY_MAX segments"""
+
+	def __init__(self, sg, row, word_base=0, n_words=None):
+		key = sg.row_key(row)
+		if isinstance(key, int):
+			table = [(0, key)]
+		else:
+			table = [] if key[0][0] == 0 else [(0, PLOIDY_MAX)]
+			table += [(sg.first_edge_of_node(node), copy) for node, copy in key]
+		self.seg_begin = np.array([b for b, _ in table], dtype=np.int64)
+		self.seg_copy = [c for _, c in table]
+		assert np.all(np.diff(self.seg_begin) >= 0) and 0 == self.seg_begin[0]
+		n_seg = len(table)
+		self.n_words = n_words = (sg.n_edges + 63) // 64 if n_words is None else n_words
+		self.word_base = word_base
+		seg_end = np.r_[self.seg_begin[1:], np.iinfo(np.int64).max]
+		self.empty = [s for s in range(n_seg) if seg_end[s] == self.seg_begin[s]]
+		self.ref = [s for s in range(n_seg) if self.seg_copy[s] == PLOIDY_MAX]
+		self.spans = []
+		for w0 in range(word_base, n_words, 64):
+			e_lo, e_hi = 64 * w0, 64 * min(w0 + 64, n_words)
+			first = int(np.flatnonzero(self.seg_begin <= e_lo)[-1])
+			walked = int(np.count_nonzero(self.seg_begin[first:] < e_hi))
+			self.spans.append((w0, int(np.count_nonzero(self.seg_begin == e_lo)), walked, (walked + 63) // 64))
+		self.masks, self.mask_at, self.writers = set(), {}, np.zeros(n_words, dtype=np.int64)
+		lo_edge, hi_edge = 64 * word_base, 64 * n_words
+		for s in range(n_seg):
+			b, e = max(int(self.seg_begin[s]), lo_edge), min(int(seg_end[s]), hi_edge)
+			if b >= e or self.seg_copy[s] == PLOIDY_MAX:
+				continue
+			for w in range(b >> 6, ((e - 1) >> 6) + 1):
+				ft = (max(b - 64 * w, 0), min(e - 64 * w, 64))
+				if ft != (0, 64):                   # (whole words are counted, not listed: a long segment has thousands)
+					self.mask_at[(s, w)] = ft
+				self.masks.add(ft)
+			self.writers[b >> 6:((e - 1) >> 6) + 1] += 1
+
+	def neighbours(self):
+		"""(cut edge, copy before, copy after) at every change from a segment that holds edges to the next one that does."""
+		held = [s for s in range(len(self.seg_copy)) if s not in self.empty]
+		return [(int(self.seg_begin[t]), self.seg_copy[s], self.seg_copy[t]) for s, t in zip(held, held[1:])]
+
+
+def window_words(sg, col_begin, col_end):
+	"""(restart, lo, hi) of a column window, by the host's rule (csrc/v2m_hip.hip: first_edge_reaching_past, words_of_edges): the edges from
+	the first one whose span, or an earlier edge's, reaches past col_begin to the last one that begins before col_end; lo and hi are
+	their words, restart the last word at or before lo whose first edge is not overlappable.  (0, 0, 0): no edge reaches the window."""
+	e_hi = int(np.searchsorted(sg.begin, col_end, side="left"))
+	reach = np.maximum.accumulate(sg.end[:e_hi]) if e_hi else np.zeros(0, dtype=np.int64)
+	e_lo = int(np.searchsorted(reach, col_begin, side="right"))
+	if e_lo >= e_hi:
+		return 0, 0, 0
+	furthest = np.r_[0, np.maximum.accumulate(sg.tgt)][:-1]
+	overlappable = sg.src < furthest
+	lo = restart = e_lo // 64
+	while restart > 0 and overlappable[64 * restart]:
+		restart -= 1
+	return restart, lo, (e_hi + 63) // 64
 
 
 def mask_phase_coverage(censuses):
@@ -644,3 +765,154 @@ def resolve_graph(tail_edges):
 	sg = b.finish(copies, "resolve_%d" % tail_edges)
 	sg.notes.update(pairs=pairs, deletion=deletion, under=under, back_words=bw)
 	return sg
+
+
+# ---- group f: founder rows: assemble_row_bits_kernel, and resolve on assembled rows -------------------------------------------------------
+
+ASSEMBLE_GAPS = (64 * 10 + 17, 64 * 64, 64 * 256)        # an ordinary edge, a wave span's first edge, a workgroup's first edge
+ASSEMBLE_PAIRS = ((0, 1), (2, 3), (4, 5))                # complementary copies: all-one / all-zero, even / odd edges, a random half / the rest
+ASSEMBLE_WINDOW_WORDS = (1, 63, 64, 65, 257)             # wr.lo of the column windows
+
+
+@functools.lru_cache(maxsize=None)
+def assemble_graph(tail_edges, label_len=1):
+	"""A chain of one-column sites with one edge each (edge i = site i; the label is one byte, which is never the reference's: acgt against
+	ACGT).  No edge overlaps another and every node is a bridge, so the effective edges are the assembled bits and aligned column
+	begin[i] shows bit i: every bit assemble_row_bits_kernel writes is visible.  64 x (256 + 64 + 3) + tail_edges edges: a workgroup's
+	four wave spans, one more wave span, a short last one.  The sites of ASSEMBLE_GAPS follow a reference byte without an edge: the edge
+	before ends on that byte's node, the site has its own, both can be cut and both have the same first edge.
+	label_len = 0: the same graph with empty labels.  A set bit is then a deleted reference byte, which the row's alignment ops show (a
+	one-byte substitution leaves them one M run whatever the bits are); nodes, edges, copies and so the cut rows are the same."""
+	n = 64 * (256 + 64 + 3) + tail_edges
+	b = Builder(6000 + tail_edges)
+	at = 0
+	for g in ASSEMBLE_GAPS:
+		b.add_sites(g - at, 1, 1, label_len)
+		b.add_ref(1)
+		at = g
+	b.add_sites(n - at, 1, 1, label_len)
+	b.add_ref(40)
+	every = np.arange(n)
+	half = np.sort(np.random.default_rng(6100 + tail_edges).choice(n, size=n // 2, replace=False))
+	copies = [every, [], every[0::2], every[1::2], half, np.setdiff1d(every, half)]
+	sg = b.finish(copies, "assemble_%d%s" % (tail_edges, "" if label_len else "_deletions"))
+	assert sg.n_edges == n
+	return sg
+
+
+def cut_row(sg, segments):
+	"""[(where, copy)] -> [(cut node, copy)].  where: the segment's first edge (the cut is at the edge's own node; n_edges: at the node
+	the last edge ends on), or ("gap", e): the node before edge e's, which must hold no edge (so the segment is empty)."""
+	out = []
+	for where, copy in segments:
+		if isinstance(where, tuple):
+			node = int(sg.src[where[1]]) - 1
+			assert "gap" == where[0] and sg.first_edge_of_node(node) == where[1] and not np.any(sg.src == node)
+		else:
+			node = int(sg.tgt[-1]) if where == sg.n_edges else int(sg.src[where])
+			assert sg.first_edge_of_node(node) == where
+		assert sg.is_bridge(node) and (not out or node > out[-1][0]), (where, node)
+		out.append((node, copy))
+	return out
+
+
+def _alternate(edges, pair, first=0):
+	return [(e, pair[(i + first) & 1]) for i, e in enumerate(edges)]
+
+
+def _differing(sg, copy, edge, among):
+	"""The copy of `among` whose bit at `edge` is not `copy`'s."""
+	return next(c for c in among if sg.copy_bits(c)[edge] != sg.copy_bits(copy)[edge])
+
+
+@functools.lru_cache(maxsize=None)
+def assemble_rows(tail_edges):
+	"""{name: row} for the whole-row cases; the first letter of a name is its class (the issue's letters a - f)."""
+	sg = assemble_graph(tail_edges)
+	n, R = sg.n_edges, PLOIDY_MAX
+	seg = {}
+	# a. cuts either side of a word's first and last edge, for words at the limits of a wave span and of a workgroup
+	edges = sorted({0} | {64 * k + d for k in (1, 63, 64, 65, 255, 256, 257) for d in (-1, 0, 1, 63)})
+	for i, pair in enumerate(ASSEMBLE_PAIRS):
+		seg["a_word_edges_%d%d" % pair] = _alternate(edges, pair, i)
+	# b. segment lengths against the spans
+	seg["b_word_span_65"] = _alternate([0, 64 * 20, 64 * 21, 64 * 100, 64 * 165, 64 * 192, 64 * 256], (4, 5))   # one word; 65 words across word 128; the span [192, 256)
+	seg["b_across_workgroups"] = _alternate([0, 64 * 250 + 7, 64 * 262 + 9], (2, 3))
+	seg["b_two_long_01"] = _alternate([0, 64 * 260 + 13], (0, 1))
+	seg["b_two_long_45"] = _alternate([0, 64 * 260 + 13], (5, 4))
+	# c. runs of one-edge segments under one wave span: 64 / 65 / 66 / 129 / 130 segments for the lane loop to walk
+	for name, first, count, pair in (("c_63", 64 * 3 + 1, 63, (0, 1)), ("c_64", 64 * 3, 64, (4, 5)), ("c_65_01", 64 * 70, 65, (0, 1)), ("c_65_45", 64 * 70, 65, (4, 5)),
+			("c_128", 64 * 130 + 3, 128, (2, 3)), ("c_129", 64 * 200 + 60, 129, (4, 5))):
+		seg[name] = _alternate([0] + list(range(first, first + count)), pair)
+	# d. REF segments beside the all-one copy (copy 0: a REF segment read as a copy would show too): before the first cut, one bit, one word, up to a wave span's first edge, the last segment
+	seg["d_ref"] = [(64 * 5 + 2, 0), (64 * 30 + 7, R), (64 * 30 + 8, 0), (64 * 40, R), (64 * 41, 0), (64 * 120 + 5, R), (64 * 128, 0), (64 * 300 + 1, R)]
+	seg["d_first_cut_late"] = [(64 * 63 + 9, 0)]
+	# e. last segments
+	seg["e_last_edge_45"] = [(0, 4), (n - 1, 5)]
+	seg["e_last_edge_01"] = [(0, 0), (n - 1, 1)]
+	seg["e_last_edge_10"] = [(0, 1), (n - 1, 0)]
+	seg["e_past_every_edge_45"] = [(0, 4), (64 * 322 + 1, 5), (n, 4)]
+	seg["e_past_every_edge_10"] = [(0, 1), (n, 0)]
+	seg["e_past_every_edge_01"] = [(0, 0), (n, 1)]
+	# f. empty segments: two cuts with one first edge; the second one's copy holds from there, the first one's differs from it at that edge
+	for name, pair, others in (("f_empty_45", (4, 5), (0, 1)), ("f_empty_10", (1, 0), (4, 5))):
+		s = [(0, pair[0])]
+		for i, g in enumerate(ASSEMBLE_GAPS):
+			winner = pair[(i + 1) & 1]
+			s += [(("gap", g), _differing(sg, winner, g, others)), (g, winner)]
+		seg[name] = s
+	return {name: cut_row(sg, s) for name, s in seg.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def assemble_windows(tail_edges):
+	"""[(name, first column, end column, {name: row})]: windows whose first edge word is k, for k in ASSEMBLE_WINDOW_WORDS, each with cuts
+	against the wave spans as the window shifts them (first words k + 64 j): either side of the first and of the second span's first
+	edge, and 65 one-edge segments under the second span; and a window no edge reaches."""
+	sg = assemble_graph(tail_edges)
+	out = []
+	for k in ASSEMBLE_WINDOW_WORDS:
+		last = 64 * (k + 130) + 9
+		end = int(sg.begin[last]) + 1 if last < sg.n_edges else sg.length - 10
+		second = 64 * (k + 64)
+		edges = [0, 64 * k - 30, 64 * k - 1, 64 * k, 64 * k + 1, second - 1, second, second + 1] + list(range(second + 3, second + 3 + 65))
+		rows = {"h_w%d_%d%d" % ((k,) + pair): cut_row(sg, _alternate(edges, pair, k)) for pair in ((4, 5), (0, 1))}
+		out.append(("lo_%d" % k, int(sg.begin[64 * k + 5]), end, rows))
+	rows = {"h_none_45": out[0][3]["h_w1_45"], "h_none_past": assemble_rows(tail_edges)["e_past_every_edge_45"]}
+	out.append(("no_edge", sg.length - 30, sg.length - 2, rows))
+	return out
+
+
+@functools.lru_cache(maxsize=None)
+def resolve_cut_rows(tail_edges):
+	"""{name: row} on resolve_graph(tail_edges): rows that switch copy at the source node of every blocker of notes["pairs"] and at the node
+	right after its blocked edge, at the deletion's source node and at the first bridge after its end.  `inside` names the copy between
+	such a pair of cuts, `outside` the copy elsewhere (the first segment's).  Copy 0 sets every blocker with its blocked edge, the
+	deletion and the edge bw words under it; 1 the blocked edges and both edges under the deletion, not the deletion; 2 the deletion and
+	the edge bw + 1 words under it, no pair's edge; 3 the blockers alone; 4 every seventh edge around the deletion; 5 every fifth edge."""
+	sg = resolve_graph(tail_edges)
+	d = sg.notes["deletion"]
+	after = int(sg.tgt[d])
+	while not sg.is_bridge(after):
+		after += 1
+	places = sorted([(int(sg.src[p]), int(sg.tgt[q])) for p, q in sg.notes["pairs"]] + [(int(sg.src[d]), after)])
+	rows = {}
+	for name, outside, inside in (("both_inside", 2, 0), ("both_outside", 0, 2), ("blocked_alone_inside", 0, 1), ("blocked_alone_outside", 1, 0),
+			("blockers_inside", 5, 3), ("sevenths_inside", 1, 4)):
+		row = [(0, outside)]
+		for begin, end in places:
+			assert sg.is_bridge(begin) and sg.is_bridge(end) and row[-1][0] < begin < end
+			row += [(begin, inside), (end, outside)]
+		rows[name] = row
+	return rows
+
+
+def resolve_cut_windows(tail_edges):
+	"""A window that begins under the deletion (restart == lo: the deletion is its word's first edge and nothing reaches over it), and one
+	that begins on the column the blocked edge at bit 0 of word kResolveWordsPerThread ends on: the first edge that reaches into it is bit
+	1 of that word, whose first edge is overlappable, so the words assembled begin a word before the words resolved (restart < lo)."""
+	sg = resolve_graph(tail_edges)
+	under = sg.notes["under"]
+	q = 64 * kernel_constants().kResolveWordsPerThread
+	assert (q - 1, q) in sg.notes["pairs"]
+	return [("under_deletion", int(sg.begin[under[0]]) - 30, int(sg.begin[under[1]]) + 9), ("after_blocked_bit_0", int(sg.end[q]), int(sg.end[q]) + 3000)]

@@ -58,13 +58,20 @@ def _same(got, want, what):
 		what, a.size, w.size, d.size, at, at // T, at % T // 16, got[max(0, at - 8):at + 24], want[max(0, at - 8):at + 24]))
 
 
+def _row_name(row):
+	"""A copy's number; a row with cuts by its first cuts."""
+	return str(row) if isinstance(row, (int, np.integer)) else "%d cuts: %s ..." % (len(row), list(row[:3]))
+
+
 def _expected(sg, rows, unaligned, window):
 	"""The model's bodies, held equal to the oracle's."""
 	by_row = {}
-	for r in set(rows):
-		by_row[r] = sg.body(r, unaligned, window)
-		assert by_row[r] == sg.oracle_body(r, unaligned, window), "model and oracle differ: %s row %d" % (sg.name, r)
-	return [by_row[r] for r in rows]
+	for r in rows:
+		key = sg.row_key(r)
+		if key not in by_row:
+			by_row[key] = sg.body(r, unaligned, window)
+			assert by_row[key] == sg.oracle_body(r, unaligned, window), "model and oracle differ: %s row %s" % (sg.name, r)
+	return [by_row[sg.row_key(r)] for r in rows]
 
 
 def check(v2m, ctx, sg, rows, windows=(None,), device=False, modes=(False, True), upload=True):
@@ -79,7 +86,7 @@ def check(v2m, ctx, sg, rows, windows=(None,), device=False, modes=(False, True)
 			got = ctx.splice_rows(rows, unaligned=unaligned)
 			assert len(got) == len(want)
 			for i, (a, w) in enumerate(zip(got, want)):
-				_same(a, w, "%s unaligned=%s row %d (%d)" % (name, unaligned, i, rows[i]))
+				_same(a, w, "%s unaligned=%s row %d (%s)" % (name, unaligned, i, _row_name(rows[i])))
 			if device:
 				_check_device(ctx, rows, want, unaligned, name)
 	ctx.set_column_window(0, sg.length)
@@ -97,7 +104,7 @@ def _check_device(ctx, rows, want, unaligned, name):
 	for i, w in enumerate(want):
 		row = host[i * pitch:(i + 1) * pitch]
 		assert int(lengths[i]) == len(w), "%s device unaligned=%s row %d: length %d, expected %d" % (name, unaligned, i, int(lengths[i]), len(w))
-		_same(row[:len(w)].tobytes(), w, "%s device unaligned=%s row %d (%d)" % (name, unaligned, i, rows[i]))
+		_same(row[:len(w)].tobytes(), w, "%s device unaligned=%s row %d (%s)" % (name, unaligned, i, _row_name(rows[i])))
 		written_to = len(w) if unaligned else (len(w) + 15) // 16 * 16
 		stray = np.flatnonzero(row[written_to:] != GUARD)
 		assert 0 == stray.size, "%s device unaligned=%s row %d: %d bytes written past the row, the first at %d (row length %d)" % (name, unaligned, i, stray.size, written_to + int(stray[0]), len(w))

@@ -7,6 +7,7 @@ input is what its docstring says.  Move one edge of a graph by a column and a ce
 import numpy as np
 import pytest
 
+import row_ops_model as M
 import seam_graphs as S
 
 K = S.kernel_constants()
@@ -281,3 +282,227 @@ def test_resolve_graph(tail):
 		assert restart == d and (u >> 6) - (restart >> 6) == bw + i
 		assert not (~overlappable[(u >> 6) * 64:u]).any()            # nothing in its own word ends the search
 	assert under[0] not in sg.effective(0) and under[0] in sg.effective(1) and under[1] not in sg.effective(2) and under[1] in sg.effective(1)
+
+
+# ---- f. founder rows: the segment table in front of assemble_row_bits_kernel -----------------------------------------------------------------
+
+TAILS = (0, 1, 63)
+R = S.PLOIDY_MAX
+
+
+def _row_bits(sg, copy):
+	return np.zeros(sg.n_edges, dtype=bool) if copy == R else sg.copy_bits(copy)
+
+
+def _all_assemble_rows(tail):
+	"""(name, row, word_base, n_words) of every row of the assemble graph: whole rows and rows under the windows."""
+	sg = S.assemble_graph(tail)
+	out = [(name, row, 0, None) for name, row in S.assemble_rows(tail).items()]
+	for wname, b, e, rows in S.assemble_windows(tail):
+		_, lo, hi = S.window_words(sg, b, e)
+		out += [(wname + "/" + name, row, lo, hi) for name, row in rows.items() if hi]
+	return out
+
+
+@pytest.mark.parametrize("tail", TAILS)
+def test_assemble_graph_shows_every_bit(tail):
+	sg = S.assemble_graph(tail)
+	n = sg.n_edges
+	assert n == 64 * (256 + 64 + 3) + tail and n % 64 == tail
+	assert np.all(sg.end - sg.begin == 1) and np.all(sg.label_len == 1) and np.all(sg.tgt - sg.src == 1)
+	assert np.all(sg.end[:-1] <= sg.begin[1:])                                        # no edge overlaps another: effective == assembled
+	assert np.all(sg.label_bytes != sg.ref_row[sg.begin])                             # a taken edge is seen in its column
+	assert all(sg.is_bridge(v) for v in range(int(sg.tgt[-1]) + 1))
+	for g in S.ASSEMBLE_GAPS:                                                         # two nodes, one first edge
+		node = int(sg.src[g])
+		assert sg.tgt[g - 1] == node - 1 and sg.first_edge_of_node(node - 1) == sg.first_edge_of_node(node) == g
+	assert sg.first_edge_of_node(int(sg.tgt[-1])) == n and int(sg.tgt[-1]) < sg.g.node_count - 1   # a node past every edge that is not the last one
+	for a, b in S.ASSEMBLE_PAIRS:
+		assert np.all(sg.copy_bits(a) != sg.copy_bits(b))
+	assert sg.copy_bits(0).all()                                                      # a REF segment read as copy 0 would set every bit of it
+	row = S.assemble_rows(tail)["c_65_45"]
+	assert sg.effective(row) == np.flatnonzero(sg.assembled(row)).tolist()
+	assert np.array_equal(np.frombuffer(sg.body(row), np.uint8)[sg.begin] != sg.ref_row[sg.begin], sg.assembled(row))
+
+
+@pytest.mark.parametrize("tail", TAILS)
+def test_cut_rows_model_equals_oracle(tail):
+	sg = S.assemble_graph(tail)
+	windows = S.assemble_windows(tail)
+	rows = list(S.assemble_rows(tail).items()) + [item for w in windows for item in w[3].items()]
+	for name, row in rows:
+		assert sg.body(row) == sg.oracle_body(row), name
+		assert sg.body(row, unaligned=True) == sg.oracle_body(row, unaligned=True), name
+	for wname, b, e, wrows in windows:
+		assert 0 <= b < e <= sg.length
+		for name, row in wrows.items():
+			assert sg.body(row, True, (b, e)) == sg.oracle_body(row, True, (b, e)), (wname, name)
+	rg = S.resolve_graph(tail)
+	for name, row in S.resolve_cut_rows(tail).items():
+		assert rg.body(row) == rg.oracle_body(row), name
+		assert rg.body(row, unaligned=True) == rg.oracle_body(row, unaligned=True), name
+	# the twin with empty labels, for the alignment ops: the same nodes, edges and copies, and a D of one byte per set bit
+	dg = S.assemble_graph(tail, 0)
+	assert np.array_equal(dg.src, sg.src) and np.array_equal(dg.tgt, sg.tgt) and not dg.label_len.any()
+	assert all(np.array_equal(dg.copies[c], sg.copies[c]) for c in range(len(sg.copies)))
+	for name, row in S.assemble_rows(tail).items():
+		if name[0] in "acdf":
+			assert dg.body(row) == dg.oracle_body(row) and dg.body(row, unaligned=True) == dg.oracle_body(row, unaligned=True), name
+			ops, length = M.seam_ops(dg, row)
+			deleted = np.zeros(dg.length, dtype=bool)
+			deleted[dg.begin[dg.assembled(row)]] = True
+			assert dg.kept.all() and np.array_equal(np.repeat(ops[:, 0], ops[:, 1]) == M.OP_D, deleted) and length == dg.length - deleted.sum(), name
+			assert len(M.seam_ops(sg, row)[0]) == 1
+
+
+@pytest.mark.parametrize("tail", TAILS)
+def test_every_cut_is_visible(tail):
+	"""At every change of copy the two copies differ at the last edge before the cut and at the first edge after it (REF counts as no bit
+	set, so the copy beside it has both bits set): a mask one bit short or long changes a column.  An empty segment's copy differs at
+	that edge from the copy that holds from there."""
+	sg = S.assemble_graph(tail)
+	for name, row, base, n_words in _all_assemble_rows(tail):
+		c = S.SegmentCensus(sg, row, base, n_words)
+		assert len(c.seg_copy) >= 2, name
+		for edge, before, after in c.neighbours():
+			assert edge >= 1 and before != after, (name, edge)
+			for e in (edge - 1, edge):
+				assert e >= sg.n_edges or _row_bits(sg, before)[e] != _row_bits(sg, after)[e], (name, edge, e)
+		for s in c.empty:
+			edge = int(c.seg_begin[s])
+			holder = next(t for t in range(s + 1, len(c.seg_copy)) if t not in c.empty)
+			assert c.seg_begin[holder] == edge and _row_bits(sg, c.seg_copy[s])[edge] != _row_bits(sg, c.seg_copy[holder])[edge], (name, s)
+			assert sg.assembled(row)[edge] == _row_bits(sg, c.seg_copy[holder])[edge]
+
+
+def _segments(c):
+	"""(first edge, end edge or None, copy) of the census' segments."""
+	ends = c.seg_begin[1:].tolist() + [None]
+	return list(zip(c.seg_begin.tolist(), ends, c.seg_copy))
+
+
+@pytest.mark.parametrize("tail", TAILS)
+def test_segment_census_whole_rows(tail):
+	sg = S.assemble_graph(tail)
+	n = sg.n_edges
+	rows = S.assemble_rows(tail)
+	census = {name: S.SegmentCensus(sg, row) for name, row in rows.items()}
+	assert {name[0] for name in rows} == set("abcdef")
+	span_firsts = list(range(0, (n + 63) // 64, 64))
+	for c in census.values():
+		assert [s[0] for s in c.spans] == span_firsts and len(span_firsts) == 6 and c.n_words - span_firsts[-1] in (3, 4)
+
+	# a. one-bit segments at bit 63 and at bit 0, from in {0, 1, 63} x to in {1, 63, 64}, at the words beside every span and workgroup edge
+	for name in ("a_word_edges_01", "a_word_edges_23", "a_word_edges_45"):
+		c = census[name]
+		by_word = {}
+		for (s, w), ft in c.mask_at.items():
+			by_word.setdefault(w, set()).add(ft)
+		for k in (1, 63, 64, 65, 255, 256, 257):
+			assert by_word[k - 1] >= {(63, 64)} and by_word[k] >= {(0, 1), (1, 63), (63, 64)}, (name, k)
+		assert c.masks >= {(0, 1), (1, 63), (63, 64), (0, 63), (0, 64)}
+		assert {f for f, _ in c.masks} == {0, 1, 63} and {t for _, t in c.masks} == {1, 63, 64}
+		assert c.writers.max() == 3 and not c.empty and not c.ref
+
+	# b. a segment of one word, of one wave span, of 65 words across a span edge, across the workgroup edge; a segment longer than a workgroup
+	segs = _segments(census["b_word_span_65"])
+	assert (64 * 20, 64 * 21, 5) in segs
+	assert any(b % (64 * 64) == 0 and e == b + 64 * 64 for b, e, _ in segs if e)
+	assert any(e and e - b == 64 * 65 and b % 64 == 0 and b // (64 * 64) != (e - 1) // (64 * 64) for b, e, _ in segs)
+	assert any(e and b % 64 and e % 64 and b < 64 * 256 < e for b, e, _ in _segments(census["b_across_workgroups"]))
+	for name in ("b_two_long_01", "b_two_long_45"):
+		(b0, e0, _), (b1, e1, _) = _segments(census[name])
+		assert b0 == 0 and e0 == b1 > 64 * 256 and b1 % 64 and e1 is None            # every wave of the first workgroup sees one segment
+		assert [s[2] for s in census[name].spans] == [1, 1, 1, 1, 2, 1]
+
+	# c. 64, 65, 66, 129, 130 segments for one wave's lane loop; 64 writers into one word, the run going on in the next word
+	for name, span, walked, rounds in (("c_63", 0, 64, 1), ("c_64", 0, 65, 2), ("c_65_01", 1, 66, 2), ("c_65_45", 1, 66, 2), ("c_128", 2, 129, 3), ("c_129", 3, 130, 3)):
+		c = census[name]
+		assert c.spans[span][2:] == (walked, rounds), (name, c.spans)
+		assert all(s[3] == 1 for i, s in enumerate(c.spans) if i != span)
+	assert census["c_64"].writers.max() == 64
+	for name in ("c_65_01", "c_65_45"):
+		c = census[name]
+		w = int(np.argmax(c.writers))
+		assert c.writers[w] == 64 and c.writers[w + 1] >= 1 and {64 * w + 63, 64 * w + 64} <= set(c.seg_begin.tolist())
+	assert {64 * 201 - 1, 64 * 201, 64 * 202 - 1, 64 * 202} <= set(census["c_129"].seg_begin.tolist())
+
+	# d. REF: before the first cut, one bit, one word, up to a wave span's first edge, the last segment
+	c = census["d_ref"]
+	segs = _segments(c)
+	ref = [(b, e) for b, e, copy in segs if copy == R]
+	assert ref[0][0] == 0 and ref[0][1] % 64 and c.ref[0] == 0 and rows["d_ref"][0][0] != 0
+	assert any(e == b + 1 for b, e in ref[1:-1]) and any(b % 64 == 0 and e == b + 64 for b, e in ref[1:-1])
+	assert any(b % 64 and e % (64 * 64) == 0 for b, e in ref[1:-1]) and ref[-1][1] is None and len(ref) == 5
+	c = census["d_first_cut_late"]
+	assert c.ref == [0] and len(c.seg_copy) == 2 and c.seg_begin[1] % 64
+
+	# e. a last segment of the one last edge, and one that begins past every edge
+	for name in ("e_last_edge_45", "e_last_edge_01", "e_last_edge_10"):
+		assert census[name].seg_begin[-1] == n - 1
+	for name in ("e_past_every_edge_45", "e_past_every_edge_10", "e_past_every_edge_01"):
+		assert census[name].seg_begin[-1] == n and not census[name].empty
+	assert ((n - 1) & 63, 64) in census["e_last_edge_45"].masks               # the last segment's end is the end of the words, not of the edges
+
+	# f. empty segments at an ordinary edge, at a wave span's first edge, at a workgroup's
+	for name in ("f_empty_45", "f_empty_10"):
+		c = census[name]
+		at = [int(c.seg_begin[s]) for s in c.empty]
+		assert at == list(S.ASSEMBLE_GAPS) and at[0] % 64 and at[1] % (64 * 64) == 0 and at[1] % (64 * 256) and at[2] % (64 * 256) == 0
+		assert c.spans[1][:2] == (64, 2) and c.spans[4][:2] == (256, 2) and c.spans[0][1] == 1
+
+
+@pytest.mark.parametrize("tail", TAILS)
+def test_segment_census_under_windows(tail):
+	"""The windows' first edge words, and the cuts against the wave spans as the windows shift them."""
+	sg = S.assemble_graph(tail)
+	windows = S.assemble_windows(tail)
+	assert [S.window_words(sg, b, e)[1] for _, b, e, _ in windows[:-1]] == list(S.ASSEMBLE_WINDOW_WORDS)
+	for (wname, b, e, rows), k in zip(windows, S.ASSEMBLE_WINDOW_WORDS):
+		restart, lo, hi = S.window_words(sg, b, e)
+		assert restart == lo == k and hi == min(k + 131, (sg.n_edges + 63) // 64), wname
+		for name, row in rows.items():
+			c = S.SegmentCensus(sg, row, lo, hi)
+			assert [s[0] for s in c.spans][:2] == [k, k + 64] and k % 64 or k == 64
+			begins = set(c.seg_begin.tolist())
+			for first in (64 * k, 64 * (k + 64)):
+				assert {first - 1, first, first + 1} <= begins
+			assert c.spans[0][1] == 1 and c.spans[1][1:] == (1, 67, 2), (wname, name, c.spans)
+			assert any(0 < x < 64 * k for x in begins)                              # a cut before the window's words
+	wname, b, e, rows = windows[-1]
+	assert S.window_words(sg, b, e) == (0, 0, 0) and b >= sg.end[-1] and len(rows) == 2
+
+
+@pytest.mark.parametrize("tail", TAILS)
+def test_resolve_cut_rows(tail):
+	"""Resolve on assembled rows: which copy's bits lie between the cuts and outside them, and what that makes effective."""
+	sg = S.resolve_graph(tail)
+	rows = S.resolve_cut_rows(tail)
+	d, under = sg.notes["deletion"], sg.notes["under"]
+	eff = {name: set(sg.effective(row)) for name, row in rows.items()}
+	bits = {name: sg.assembled(row) for name, row in rows.items()}
+	for p, q in sg.notes["pairs"]:
+		for name, row in rows.items():
+			cuts = [node for node, _ in row]
+			assert int(sg.src[p]) in cuts and int(sg.tgt[q]) in cuts
+		assert sg.copy_bits(0)[p] and sg.copy_bits(0)[q] and not sg.copy_bits(2)[p] and not sg.copy_bits(2)[q]
+		for e in (p - 1, p, q, q + 1):                  # blocker and blocked edge from the one copy, the edges either side from the other
+			assert bits["both_inside"][e] == sg.copy_bits(0 if e in (p, q) else 2)[e] and bits["both_outside"][e] == sg.copy_bits(2 if e in (p, q) else 0)[e]
+		assert p in eff["both_inside"] and q not in eff["both_inside"] and not bits["both_outside"][p] and not bits["both_outside"][q]
+		assert q in eff["blocked_alone_inside"] and not bits["blocked_alone_inside"][p] and sg.copy_bits(0)[p]     # the first segment's copy would block it
+		assert p in eff["blocked_alone_outside"] and q not in eff["blocked_alone_outside"] and bits["blocked_alone_outside"][q]
+		assert p in eff["blockers_inside"] and not bits["blockers_inside"][q]
+	# under the deletion: the row's word and the first segment's copy disagree about the deletion, so a walk back that reads the copy decides wrongly
+	assert not bits["blocked_alone_inside"][d] and sg.copy_bits(0)[d] and {under[0], under[1]} <= eff["blocked_alone_inside"]
+	assert bits["blocked_alone_outside"][d] and not sg.copy_bits(1)[d] and bits["blocked_alone_outside"][under[0]] and under[0] not in eff["blocked_alone_outside"]
+	assert bits["both_outside"][d] and bits["both_outside"][under[1]] and under[1] not in eff["both_outside"]       # bw + 1 words back: the serial kernel's
+	inside = bits["sevenths_inside"][d:d + 64 * 4]                            # nine overlappable edges a word and no deletion: words decided by a walk back that blocks nothing
+	assert not inside[0] and inside.reshape(4, 64)[:3].sum(axis=1).min() >= 9 and set(np.flatnonzero(inside) + d) <= eff["sevenths_inside"]
+	for name, row in rows.items():
+		c = S.SegmentCensus(sg, row)
+		assert len(c.seg_copy) == 2 * (len(sg.notes["pairs"]) + 1) + 1 and not c.empty and not c.ref, name
+	(_, b0, e0), (_, b1, e1) = S.resolve_cut_windows(tail)
+	restart, lo, hi = S.window_words(sg, b0, e0)
+	assert restart == lo == d >> 6 and hi > under[1] >> 6
+	restart, lo, hi = S.window_words(sg, b1, e1)
+	assert restart == lo - 1 == K.kResolveWordsPerThread - 1 and hi > under[1] >> 6      # a word is assembled that is not resolved
