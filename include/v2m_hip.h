@@ -37,7 +37,8 @@
  * v2m_bgzf_frame_stored were added without a new version, and so were v2m_set_column_window and v2m_window_length, and
  * v2m_bgzf_scan and v2m_bgzf_decompress (with V2M_KERNEL_INFLATE), and v2m_vcf_scan (with V2M_KERNEL_VCF): a caller probes for them by symbol.
  * The window-set calls (v2m_window_set_layout, v2m_set_window_set, v2m_splice_window_set[_device]) were added the same way, and so was
- * v2m_row_ops (with v2m_aln_op, v2m_ops_sink_fn and the V2M_KERNEL_ROW_OPS_* ids).
+ * v2m_row_ops (with v2m_aln_op, v2m_ops_sink_fn and the V2M_KERNEL_ROW_OPS_* ids), and v2m_splice_window_set_distinct (with
+ * v2m_distinct_sink_fn and the V2M_KERNEL_DISTINCT_* ids).
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -331,6 +332,41 @@ int v2m_splice_window_set(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flag
 int v2m_splice_window_set_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, void *d_out, uint64_t record_pitch,
                                  uint32_t *lengths_out /* host, optional, [n_rows][n_windows] */);
 
+/* ---- distinct pieces of a window set ------------------------------------------------------------
+ *
+ * Within a window most rows are byte-identical.  v2m_splice_window_set_distinct splices the set as v2m_splice_window_set does, but
+ * the records stay in device memory: it finds the distinct pieces of every window there and reports each once, with the table of
+ * which row has which.
+ *   Equality.  Piece (r, k) is exactly the piece v2m_splice_window_set gives for that row, window and mode.  Two pieces of the same
+ *     window are equal when they have the same length and the same bytes -- by bytes, not by path bits or effective edges: two
+ *     different ALT records with the same label give equal pieces.
+ *   Class numbering.  The classes of window k are numbered 0, 1, ... in the order of their first row in batch order.
+ *     class_of_out[r * n_windows + k] is the class of piece (r, k); n_classes_out[k] the number of classes of window k.  Repeated or
+ *     overlapping windows are independent windows.  All empty pieces of a window (unaligned mode) form one class of length 0.
+ *   Sink.  `sink` is called once per class, on the calling thread, before the call returns: (user, window, class index, the class's
+ *     first row, its bytes, their number).  Calls come in ascending first_row, and for equal first_row in ascending window.  `bytes`
+ *     is library-owned pinned memory, valid during the call only.  A non-zero return ends the call with V2M_ERR_SINK.  With
+ *     sink == NULL only the class tables are produced and no piece crosses the link.
+ *   Errors.  V2M_SPLICE_BGZF (and a held form) is V2M_ERR_UNSUPPORTED.  As for v2m_splice_window_set: V2M_ERR_STATE without a graph
+ *     or without a set, V2M_ERR_PRECONDITION for bad cuts, V2M_ERR_UNSUPPORTED for V2M_SPLICE_UNALIGNED on a graph with a NUL byte.
+ *     A NULL class_of_out is V2M_ERR_INVALID_ARGUMENT.  n_rows == 0 returns V2M_OK with n_classes_out zeroed.
+ *   State.  The column window, the set and every other call are untouched.
+ *   Pool limit.  The distinct pieces of one call are kept in a device pool (each once, 16-byte aligned) until the call returns.  When
+ *     they exceed V2M_DISTINCT_POOL_BYTES (environment, read per call; default 4 GiB; clamped to the free device memory) the call
+ *     returns V2M_ERR_OUT_OF_MEMORY; the message names the knob and the bytes needed so far; the outputs are then unspecified.
+ * How: the batch goes through the device in row slices (V2M_RING_SLOT_BYTES caps a slice's records plus tables, as elsewhere).  Per
+ * slice hash_pieces_kernel gives every piece a 64-bit key -- the checksum of v2m_checksum_rows_device ("verification helper") of the
+ * piece --, the host looks the keys up per (window, key, length), gather_pieces_kernel copies the pieces with unknown keys into the
+ * pool as their classes' representatives, and verify_pieces_kernel compares every other piece with its candidate byte for byte.  A
+ * mismatch is a key collision: the piece tries the next class with that key or becomes a representative in a further round, so the
+ * result never depends on the key's quality (V2M_DISTINCT_HASH_BITS = 0 ... 64, a test knob read per call, keeps only that many low
+ * bits of every key: the same classes after more rounds).  Synchronous. */
+typedef int (*v2m_distinct_sink_fn)(void *user, uint64_t window, uint64_t class_index, uint64_t first_row, const char *bytes, uint64_t length);
+int v2m_splice_window_set_distinct(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_SPLICE_UNALIGNED */,
+                                   v2m_distinct_sink_fn sink /* may be NULL */, void *user,
+                                   uint32_t *class_of_out /* host, [n_rows][n_windows] */,
+                                   uint32_t *n_classes_out /* host, optional, [n_windows] */);
+
 /* ---- row alignment ops --------------------------------------------------------------------------
  *
  * The coordinate map between a row and the reference, as run-length ops (what a chain or a CIGAR is made of).
@@ -594,7 +630,11 @@ enum {
 	V2M_KERNEL_ROW_OPS_COUNT = 9,   /* count_row_ops_kernel (pass 1: breakpoints, first and last class per row tile) */
 	V2M_KERNEL_ROW_OPS_SCAN = 10,   /* scan_row_ops_kernel (pass 2: op offsets and carried classes per row) */
 	V2M_KERNEL_ROW_OPS_EMIT = 11,   /* emit_row_ops_kernel (pass 3: the breakpoint records) */
-	V2M_KERNEL_END = 12
+	/* v2m_splice_window_set_distinct, per slice: one group of hash launches, then per round one of gather and one of verify launches */
+	V2M_KERNEL_DISTINCT_HASH = 12,  /* hash_pieces_kernel */
+	V2M_KERNEL_DISTINCT_GATHER = 13, /* gather_pieces_kernel */
+	V2M_KERNEL_DISTINCT_VERIFY = 14, /* verify_pieces_kernel */
+	V2M_KERNEL_END = 15
 };
 
 /* When enabled, every launch of the kernels above is bracketed by HIP events on the ctx's

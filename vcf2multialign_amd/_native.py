@@ -27,8 +27,14 @@ KERNEL_BGZF = 6
 KERNEL_INFLATE = 7
 KERNEL_VCF = 8
 KERNEL_ROW_OPS_COUNT, KERNEL_ROW_OPS_SCAN, KERNEL_ROW_OPS_EMIT = 9, 10, 11   # the passes of v2m_row_ops
+KERNEL_DISTINCT_HASH, KERNEL_DISTINCT_GATHER, KERNEL_DISTINCT_VERIFY = 12, 13, 14   # the kernels of v2m_splice_window_set_distinct
 KERNEL_NAMES = ["transpose_bits_kernel", "resolve_effective_edges_kernel", "splice_aligned_kernel", "splice_unaligned_kernel", "expand_reference_row_kernel", "count_unaligned_kernel",
-	"bgzf_deflate_kernel", "bgzf_inflate_kernel", "vcf_scan_kernels", "count_row_ops_kernel", "scan_row_ops_kernel", "emit_row_ops_kernel"]
+	"bgzf_deflate_kernel", "bgzf_inflate_kernel", "vcf_scan_kernels", "count_row_ops_kernel", "scan_row_ops_kernel", "emit_row_ops_kernel",
+	"hash_pieces_kernel", "gather_pieces_kernel", "verify_pieces_kernel"]
+# csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
+# kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
+DISTINCT_CHUNK_BYTES = 8192
+DISTINCT_LONG_BYTES = 16384
 OP_M, OP_I, OP_D = 0, 1, 2   # v2m_aln_op.op (BAM's codes)
 ABI_VERSION = 5
 
@@ -73,6 +79,7 @@ VCF_LINE_DTYPE = [("kind", "<u4"), ("n_alts", "<u4"), ("head_offset", "<u4"), ("
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
 HOLD_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p)   # v2m_hold_sink_fn
 WINDOW_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32))   # v2m_window_sink_fn
+DISTINCT_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64)   # v2m_distinct_sink_fn
 OPS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_ops_sink_fn
 TRIALS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_trials_sink
 
@@ -103,6 +110,7 @@ SIGNATURES = {
 	"v2m_window_set_pitch": (C.c_uint64, [C.c_void_p]),
 	"v2m_splice_window_set": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, WINDOW_SINK_FN, C.c_void_p]),
 	"v2m_splice_window_set_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+	"v2m_splice_window_set_distinct": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, DISTINCT_SINK_FN, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_splice_rows": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, SINK_FN, C.c_void_p]),
 	"v2m_splice_rows_held": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint32, HOLD_SINK_FN, C.c_void_p]),
 	"v2m_row_release": (None, [C.c_void_p]),

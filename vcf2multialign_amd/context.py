@@ -287,6 +287,42 @@ class Context:
 			d_out, record_pitch, lengths.ctypes.data if want_lengths and lengths.size else None))
 		return lengths
 
+	def splice_window_set_distinct(self, rows, unaligned=False, want_pieces=True, bgzf=False, on_class=None):
+		"""v2m_splice_window_set_distinct: (pieces, class_of).  pieces[k] is the list of window k's distinct bodies (bytes) in class order,
+		or pieces is None with want_pieces=False (a NULL sink: no piece crosses the link); class_of is a uint32 array [n_rows, n_windows],
+		class_of[r, k] the class of piece (r, k).  self.distinct_class_counts is the call's n_classes_out.  on_class(window, class_index,
+		first_row, body) sees every sink call in order.  (bgzf exists to be refused: V2M_ERR_UNSUPPORTED.)"""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = self.window_set_size
+		class_of = np.zeros((rows.n_rows, n), dtype=np.uint32)
+		counts = np.zeros(max(1, n), dtype=np.uint32)
+		pieces, error = [[] for _ in range(n)], []
+
+		def _cb(_user, window, class_index, first_row, ptr, length):
+			try:
+				body = C.string_at(ptr, length) if length else b""
+				if class_index != len(pieces[window]):
+					raise AssertionError("class %d of window %d arrived after %d classes" % (class_index, window, len(pieces[window])))
+				pieces[window].append(body)
+				if on_class is not None:
+					on_class(int(window), int(class_index), int(first_row), body)
+				return 0
+			except BaseException as e:  # propagate through the C frame as V2M_ERR_SINK
+				error.append(e)
+				return 1
+
+		flags = (N.V2M_SPLICE_UNALIGNED if unaligned else 0) | (N.V2M_SPLICE_BGZF if bgzf else 0)
+		sink = N.DISTINCT_SINK_FN(_cb) if want_pieces else C.cast(None, N.DISTINCT_SINK_FN)
+		buf = np.zeros(max(1, class_of.size), dtype=np.uint32)   # (never a NULL pointer for an empty table)
+		rc = self._lib.v2m_splice_window_set_distinct(self._h, C.byref(rows.struct), flags, sink, None, buf.ctypes.data, counts.ctypes.data)
+		if error:
+			raise error[0]
+		self._check(rc)
+		class_of[...] = buf[:class_of.size].reshape(class_of.shape)
+		self.distinct_class_counts = counts[:n].copy()
+		return (pieces if want_pieces else None), class_of
+
 	# ---- rows ----------------------------------------------------------------------------------
 	def splice_rows(self, rows, sink=None, unaligned=False, bgzf=False):
 		"""v2m_splice_rows.  sink(row_index, body: bytes) is called per row in order; without a sink the

@@ -53,6 +53,7 @@ struct options {
 	std::uint64_t region_start{}, region_end{};
 	char const *output_chain{};           // --output-chain=FILE: one UCSC chain per output row (reference -> row), from v2m_row_ops
 	char const *regions_file{};           // --regions-file=FILE.bed: one output file per BED region, all spliced as one window set per pass
+	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
 	std::vector<int> devices{0};
 };
 
@@ -89,6 +90,10 @@ void usage()
 		"                                     without a name is called <chrom>_<start>_<end>.  All regions are spliced together,\n"
 		"                                     one launch per row batch.  Not with --region, -s, --output-sequences-separate,\n"
 		"                                     --pipe, --bgzf or several --device entries\n"
+		"      --distinct                     With --regions-file: write every distinct sequence of a region once -- the region's file\n"
+		"                                     without the records whose sequence occurred earlier in it -- and <name>.classes.tsv with a\n"
+		"                                     line per sequence: its identifier, the identifier of the first sequence equal to it, and\n"
+		"                                     that one's index in the file.  The duplicates are found on the GPU and never leave it\n"
 		"      --output-chain=FILE            Write one UCSC chain per output sequence (the reference as target, the sequence as\n"
 		"                                     query; names as --output-sequences-separate forms them) that maps reference positions\n"
 		"                                     to positions in the --unaligned sequence, e.g. for liftOver or CrossMap.  The REF row\n"
@@ -250,8 +255,9 @@ std::string read_regions_file(char const *path, char const *chromosome, std::uin
 }
 
 // Regions per pass of --regions-file: one file is open per region, so as many as the process may have open -- the soft limit is raised
-// to the hard one -- less a margin for everything else it holds.  V2M_REGIONS_PER_PASS overrides (tests).
-std::size_t regions_per_pass()
+// to the hard one -- less a margin for everything else it holds --, divided by the files a region takes (two with --distinct).
+// V2M_REGIONS_PER_PASS overrides (tests).
+std::size_t regions_per_pass(std::size_t files_per_region)
 {
 	char const *const e(std::getenv("V2M_REGIONS_PER_PASS"));
 	if (e && *e && std::atol(e) > 0) return std::size_t(std::atol(e));
@@ -263,7 +269,7 @@ std::size_t regions_per_pass()
 		if (0 == ::setrlimit(RLIMIT_NOFILE, &raised)) lim = raised;
 	}
 	rlim_t const margin(64);
-	return RLIM_INFINITY == lim.rlim_cur ? (std::size_t(1) << 20) : lim.rlim_cur > 2 * margin ? std::size_t(lim.rlim_cur - margin) : std::size_t(margin);
+	return (RLIM_INFINITY == lim.rlim_cur ? (std::size_t(1) << 20) : lim.rlim_cur > 2 * margin ? std::size_t(lim.rlim_cur - margin) : std::size_t(margin)) / files_per_region;
 }
 
 } // namespace
@@ -279,7 +285,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -291,7 +297,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -339,6 +345,7 @@ int main(int argc, char **argv)
 			case o_region: opt.region = optarg; break;
 			case o_regions_file: opt.regions_file = optarg; break;
 			case o_output_chain: opt.output_chain = optarg; break;
+			case o_distinct: opt.distinct = true; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -363,6 +370,7 @@ int main(int argc, char **argv)
 	if (opt.bgzf && opt.pipe) { std::cerr << "ERROR: --bgzf cannot be combined with --pipe (the piped command compresses).\n"; return EXIT_FAILURE; }
 	if (opt.bgzf && opt.output_sequences_separate) { std::cerr << "ERROR: --bgzf cannot be combined with --output-sequences-separate.\n"; return EXIT_FAILURE; }
 	if (opt.gpu_parse && !opt.input_variants) { std::cerr << "ERROR: --gpu-parse parses --input-variants; it cannot be combined with --input-graph.\n"; return EXIT_FAILURE; }
+	if (opt.distinct && !opt.regions_file) { std::cerr << "ERROR: --distinct requires --regions-file.\n"; return EXIT_FAILURE; }
 	if (opt.regions_file) {
 		// one file per region, written by one context from one window set per pass: the other ways out do not apply
 		char const *const other(opt.region ? "--region" : opt.output_sequences_a2m ? "-s / --output-sequences-a2m" : opt.output_sequences_separate ? "--output-sequences-separate"
@@ -576,10 +584,10 @@ int main(int argc, char **argv)
 					auto const w(vh::columns_of_reference_range(graph, ref_seq.size(), r.start, r.end));
 					regions.push_back({r.name, w.begin, w.end});
 				}
-				std::size_t const per_pass(regions_per_pass());
-				std::cerr << "Outputting " << regions.size() << " regions, one file each..." << std::flush;
+				std::size_t const per_pass(regions_per_pass(opt.distinct ? 2 : 1));
+				std::cerr << "Outputting " << regions.size() << " regions, " << (opt.distinct ? "the distinct sequences of each in one file..." : "one file each...") << std::flush;
 				if (opt.verbose) std::cerr << " (" << (regions.size() + per_pass - 1) / per_pass << " passes of at most " << per_pass << " regions)" << std::flush;
-				output.output_regions(graph, regions, per_pass);
+				output.output_regions(graph, regions, per_pass, opt.distinct, opt.verbose);
 				std::cerr << " Done.\n";
 			}
 			if (opt.output_sequences_a2m) {

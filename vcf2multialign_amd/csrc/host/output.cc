@@ -20,6 +20,7 @@
 #include <fstream>
 #include <stdexcept>
 #include <streambuf>
+#include <iostream>
 #include <thread>
 
 namespace v2m::host {
@@ -566,10 +567,30 @@ namespace {
 		if (st.delegate) st.delegate->handled_sequences(u32(1 + row));
 		return 0;
 	}
+
+	struct distinct_state {
+		std::vector<std::ofstream> *files;
+		std::vector<std::string> const *ids;
+		std::vector<std::vector<std::uint64_t>> first_rows;   // per region: the first row of each class, in class order
+		std::uint64_t bytes{};
+	};
+
+	int distinct_sink(void *user, uint64_t window, uint64_t class_index, uint64_t first_row, char const *bytes, uint64_t length)
+	{
+		auto &st(*static_cast<distinct_state *>(user));
+		auto &os((*st.files)[window]);
+		if (class_index != st.first_rows[window].size()) return 1;
+		st.first_rows[window].push_back(first_row);
+		os << '>' << (*st.ids)[first_row] << '\n';                             // the record regions_sink writes for that row
+		os.write(bytes, std::streamsize(length));
+		os << '\n';
+		st.bytes += length;
+		return os.good() ? 0 : 1;
+	}
 }
 
 
-void output::output_regions(variant_graph const &graph, std::vector<output_region> const &regions, std::size_t regions_per_pass)
+void output::output_regions(variant_graph const &graph, std::vector<output_region> const &regions, std::size_t regions_per_pass, bool distinct, bool verbose)
 {
 	row_set const rows(a2m_rows(graph));
 	v2m_row_batch batch{};
@@ -600,8 +621,32 @@ void output::output_regions(variant_graph const &graph, std::vector<output_regio
 			files[k].open(name, std::ios::binary | std::ios::trunc);
 			if (!files[k]) throw std::runtime_error("unable to open " + name + " for writing");
 		}
-		regions_state st{&files, &slot_offset, &rows.ids, first + n == regions.size() ? m_delegate : nullptr};
-		m_gpu.check(v2m_splice_window_set(m_gpu.get(), &batch, m_should_output_unaligned ? V2M_SPLICE_UNALIGNED : 0u, regions_sink, &st));
+		if (distinct) {
+			std::uint64_t const n_rows(batch.n_rows);
+			std::vector<std::uint32_t> class_of(std::max<std::uint64_t>(1, n_rows * n)), n_classes(n);
+			distinct_state st{&files, &rows.ids, std::vector<std::vector<std::uint64_t>>(n), 0};
+			m_gpu.check(v2m_splice_window_set_distinct(m_gpu.get(), &batch, m_should_output_unaligned ? V2M_SPLICE_UNALIGNED : 0u, distinct_sink, &st, class_of.data(), n_classes.data()));
+			std::uint64_t n_distinct(0);
+			for (std::size_t k(0); k < n; ++k) {
+				std::string const name(regions[first + k].name + ".classes.tsv");
+				std::ofstream tsv(name, std::ios::binary | std::ios::trunc);
+				if (!tsv) throw std::runtime_error("unable to open " + name + " for writing");
+				for (std::uint64_t r(0); r < n_rows; ++r) {
+					std::uint32_t const c(class_of[r * n + k]);
+					tsv << rows.ids[r] << '\t' << rows.ids[st.first_rows[k].at(c)] << '\t' << c << '\n';
+				}
+				tsv.close();
+				if (!tsv) throw std::runtime_error("error while writing " + name);
+				n_distinct += n_classes[k];
+			}
+			if (verbose)
+				std::cerr << "\n  regions " << first << ".." << first + n - 1 << ": " << n_rows * n << " pieces, " << n_distinct << " distinct pieces, " << st.bytes << " bytes over the link" << std::flush;
+			if (m_delegate && first + n == regions.size()) m_delegate->handled_sequences(u32(n_rows));
+		}
+		else {
+			regions_state st{&files, &slot_offset, &rows.ids, first + n == regions.size() ? m_delegate : nullptr};
+			m_gpu.check(v2m_splice_window_set(m_gpu.get(), &batch, m_should_output_unaligned ? V2M_SPLICE_UNALIGNED : 0u, regions_sink, &st));
+		}
 		for (std::size_t k(0); k < n; ++k) {
 			files[k].close();
 			if (!files[k]) throw std::runtime_error("error while writing " + regions[first + k].name + suffix);

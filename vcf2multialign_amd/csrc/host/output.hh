@@ -84,7 +84,12 @@ public:
 	// identifiers) cut to the region's columns -- byte for byte what output_a2m() writes under that region's column window.  The
 	// regions of a pass are one window set (include/v2m_hip.h, "window sets") spliced in one call; a pass holds at most
 	// regions_per_pass regions (as many files are open at once), more regions take more passes.  First context only.
-	void output_regions(variant_graph const &graph, std::vector<output_region> const &regions, std::size_t regions_per_pass);
+	// distinct (--distinct): a region's file holds one record per distinct body, in the order of first occurrence -- the plain file
+	// without every record whose body occurred earlier in it --, and `name` + ".classes.tsv" one line per row: its identifier, the
+	// identifier of the first row with the same body, and that body's index in the file.  The duplicates are found on the device
+	// (v2m_splice_window_set_distinct) and only the distinct bodies come to the host; verbose prints per pass the pieces, the distinct
+	// pieces and the bytes that crossed the link to stderr.
+	void output_regions(variant_graph const &graph, std::vector<output_region> const &regions, std::size_t regions_per_pass, bool distinct = false, bool verbose = false);
 	virtual void output_a2m(variant_graph const &graph, std::ostream &stream) = 0;
 
 	// --output-chain: one chain per output row (chain_text above: the reference as target, the row as query) into `path`, from

@@ -2848,4 +2848,146 @@ __global__ __launch_bounds__(256) void scan_window_set_kernel(
 	}
 }
 
+// ---------------------------------------------------------------------------------------------
+// Distinct pieces of a window set (v2m_splice_window_set_distinct): a key per (row, window) piece of a slice's records, the new
+// representatives copied into the pool, and every other piece compared with its candidate's pool entry.
+//
+// A piece is lengths[k] defined bytes from a slot that starts 16-byte aligned; what follows them up to the end of the slot's last
+// 16-byte chunk is clobbered (aligned mode) or stale (unaligned mode), and then the next slot begins.  All three kernels read a piece
+// in 16-byte chunks with one exception: when at most 8 bytes of the piece lie in its last chunk, only that chunk's first 8-byte word is
+// loaded, so no load reaches past the length rounded up to 8, and the word that holds the piece's end is masked.
+//
+// One wave takes one work item, kDistinctWaves items a workgroup; no LDS, no barrier (a wave without an item just leaves).
+// ---------------------------------------------------------------------------------------------
+constexpr int kDistinctThreads = 256;
+constexpr int kDistinctWaves = kDistinctThreads / kWave;
+constexpr u32 kDistinctChunkBytes = 8192;    // a long piece is hashed, gathered and verified in chunks of this many bytes, a wave each
+constexpr u32 kDistinctLongBytes = 16384;    // windows longer than this are long: their pieces' keys are summed from chunks by atomic add
+
+// A piece's bytes [begin, end) for one wave's item list: `src` and `dst` are byte offsets (multiples of 16) into the records and
+// into the pool, `index` the pair whose flag a mismatch sets (verify only).
+struct __attribute__((aligned(8))) piece_item {
+	u64 src;
+	u64 dst;
+	u32 len;
+	u32 index;
+};
+
+__device__ __forceinline__ u64 low_bytes_mask(u32 n_bytes)   // 1 <= n_bytes <= 7
+{
+	return (1ULL << (8 * n_bytes)) - 1;
+}
+
+// The two 8-byte words of the 16-byte chunk at p + off of a piece of len bytes (off a multiple of 16, off < len), the bytes past the
+// piece's end as zeros; returns whether the second word holds any byte of the piece.
+__device__ __forceinline__ bool load_piece_chunk(char const *__restrict__ p, u32 off, u32 len, u64 &lo, u64 &hi)
+{
+	u32 const left = len - off;
+	if (left <= 8) {
+		lo = *(u64 const *) (p + off);
+		if (left < 8) lo &= low_bytes_mask(left);
+		hi = 0;
+		return false;
+	}
+	vec4u const v = *(vec4u const *) (p + off);
+	lo = (u64) v.x | (u64) v.y << 32;
+	hi = (u64) v.z | (u64) v.w << 32;
+	if (left < 16) hi &= low_bytes_mask(left - 8);
+	return true;
+}
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 acc)
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) {
+		u32 const lo = __shfl_down((u32) acc, d, kWave);
+		u32 const hi = __shfl_down((u32) (acc >> 32), d, kWave);
+		acc += ((u64) hi << 32) | lo;
+	}
+	return acc;
+}
+
+// keys[row][k] = the checksum of checksum_rows_kernel (include/v2m_hip.h, "verification helper") of piece (row, k).  Window k has
+// first_item[k + 1] - first_item[k] items per row: one when it is at most kDistinctLongBytes long (the wave hashes the whole piece and
+// stores the key), else one per kDistinctChunkBytes of the window's length (the wave adds its chunk's partial sum to the key, which the
+// host has zeroed; chunks past a shorter unaligned piece's end add nothing).  lengths[row * len_stride + k]: len_stride = n_windows for a
+// slice's [rows][n_windows] table, 0 for one length per window.
+__global__ __launch_bounds__(kDistinctThreads) void hash_pieces_kernel(
+	char const *__restrict__ records, u64 record_pitch, u32 n_windows, u32 const *__restrict__ slot_offset /* [n_windows] */,
+	u32 const *__restrict__ lengths, u32 len_stride, u32 const *__restrict__ first_item /* [n_windows + 1] */,
+	unsigned long long *__restrict__ keys /* [n_rows][n_windows] */)
+{
+	u32 const lane = threadIdx.x & (kWave - 1);
+	u32 const items_per_row = first_item[n_windows];
+	u64 const row = blockIdx.y;               // (grid: the row's items in x, kDistinctWaves a workgroup; rows in y)
+	u32 const c = blockIdx.x * kDistinctWaves + (threadIdx.x >> 6);
+	if (c >= items_per_row) return;
+	u32 lo_k = 0, hi_k = n_windows;          // the window with first_item[k] <= c < first_item[k + 1]
+	if (items_per_row == n_windows) lo_k = c;   // (no long window: an item a window)
+	else while (hi_k - lo_k > 1) {
+		u32 const mid = lo_k + (hi_k - lo_k) / 2;
+		if (first_item[mid] <= c) lo_k = mid; else hi_k = mid;
+	}
+	u32 const k = lo_k;
+	u32 const j = c - first_item[k];
+	bool const chunked = first_item[k + 1] - first_item[k] > 1;
+	u32 const len = lengths[(u64) row * len_stride + k];
+	u32 const begin = chunked ? j * kDistinctChunkBytes : 0;
+	u32 end = len;
+	if (chunked && end - (begin < end ? begin : end) > kDistinctChunkBytes) end = begin + kDistinctChunkBytes;
+	char const *const p = records + row * record_pitch + slot_offset[k];
+	u64 acc = 0;
+	for (u32 off = begin + lane * 16; off < end; off += kWave * 16) {
+		u64 lo, hi;
+		bool const two = load_piece_chunk(p, off, len, lo, hi);
+		u64 const w = off / 8;
+		acc += mix64((w + 1) * kGolden ^ lo);
+		if (two) acc += mix64((w + 2) * kGolden ^ hi);
+	}
+	acc = wave_sum_u64(acc);
+	if (0 != lane) return;
+	if (0 == j) acc += mix64(len);
+	unsigned long long *const key = keys + row * n_windows + k;
+	if (!chunked) *key = acc;
+	else if (acc) atomicAdd(key, (unsigned long long) acc);
+}
+
+// Copies each item's len bytes from records + src to pool + dst: whole 16-byte chunks, then the last bytes one by one, so that the
+// pool entry gets exactly the piece's defined bytes and nothing past them is read.
+__global__ __launch_bounds__(kDistinctThreads) void gather_pieces_kernel(
+	char const *__restrict__ records, piece_item const *__restrict__ items, u64 n_items, char *__restrict__ pool)
+{
+	u32 const lane = threadIdx.x & (kWave - 1);
+	u64 const i = (u64) blockIdx.x * kDistinctWaves + (threadIdx.x >> 6);
+	if (i >= n_items) return;
+	piece_item const it = items[i];
+	char const *const s = records + it.src;
+	char *const d = pool + it.dst;
+	u32 const whole = it.len & ~15u;
+	for (u32 off = lane * 16; off < whole; off += kWave * 16)
+		*(vec4u *) (d + off) = *(vec4u const *) (s + off);
+	if (whole + lane < it.len) d[whole + lane] = s[whole + lane];
+}
+
+// Compares each item's len bytes at records + src with those at pool + dst and sets flags[index] when they differ (the host has
+// zeroed the flags; the items of a long pair all name its flag and all write the same value).
+__global__ __launch_bounds__(kDistinctThreads) void verify_pieces_kernel(
+	char const *__restrict__ records, char const *__restrict__ pool, piece_item const *__restrict__ items, u64 n_items, u32 *__restrict__ flags)
+{
+	u32 const lane = threadIdx.x & (kWave - 1);
+	u64 const i = (u64) blockIdx.x * kDistinctWaves + (threadIdx.x >> 6);
+	if (i >= n_items) return;
+	piece_item const it = items[i];
+	char const *const a = records + it.src;
+	char const *const b = pool + it.dst;
+	u64 diff = 0;
+	for (u32 off = lane * 16; off < it.len; off += kWave * 16) {
+		u64 alo, ahi, blo, bhi;
+		load_piece_chunk(a, off, it.len, alo, ahi);
+		load_piece_chunk(b, off, it.len, blo, bhi);
+		diff |= (alo ^ blo) | (ahi ^ bhi);
+	}
+	if (__any(0 != diff) && 0 == lane) flags[it.index] = 1;
+}
+
 } // namespace v2m

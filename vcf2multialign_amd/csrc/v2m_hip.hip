@@ -23,6 +23,7 @@
 #include <vector>
 
 #include <type_traits>
+#include <unordered_map>
 
 #include "../../include/v2m_hip.h"
 #include "kernels.hpp"
@@ -216,6 +217,10 @@ struct v2m_ctx {
 	bool has_set{}, set_call{};
 	scratch_buf d_set_tile_offsets, d_set_lengths[2];   // unaligned: the tiles' destinations; [rows][n_windows] lengths of a slice, two in turn (s & 1)
 	int set_lengths_slot{};
+	// distinct pieces (v2m_splice_window_set_distinct): a slice's keys, the windows' item table and lengths, a round's gather or verify
+	// items and its flags, with their pinned staging (keys and lengths down, items up, flags down); the pool belongs to the call
+	scratch_buf d_distinct_keys, d_distinct_windows, d_distinct_items, d_distinct_flags;
+	pinned_buf h_distinct_keys, h_distinct_items, h_distinct_flags;
 
 	// paths_by_chrom_copy_and_edge
 	u64 const *d_paths{};
@@ -1171,17 +1176,18 @@ int check_batch(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags)
 // How a row call cuts its batch into slices: row pitch, rows per slice, slice count and the bytes of a slice's rows.  Slices of
 // 512 MB; of 128 MB for batches of less than 8 GB (a founder run's 26 rows): a gigabyte of pinned memory takes 0.15 s to set up and as
 // long to give back, which a run of a second notices (config 4 end to end: 1.39 -> 1.22 s).  max_rows_per_slice: a limit of the
-// caller's (BGZF's member slots).
+// caller's (BGZF's member slots); table_bytes_per_row: what a row takes in device tables beside its bytes, counted against the slot
+// (the distinct call's keys, lengths, pairs and flags).
 struct slice_plan { u64 pitch, rows_per_slice, n_slices, slot_bytes; };
 
-slice_plan plan_slices(v2m_ctx const *ctx, u64 n_rows, bool unaligned, u64 max_rows_per_slice = ~u64(0))
+slice_plan plan_slices(v2m_ctx const *ctx, u64 n_rows, bool unaligned, u64 max_rows_per_slice = ~u64(0), u64 table_bytes_per_row = 0)
 {
 	slice_plan p;
 	p.pitch = ctx->set_call ? ctx->set.pitch : unaligned ? ((v2m_max_unaligned_length(ctx) + 255) & ~u64(255)) : v2m_min_row_pitch(ctx);
 	char const *const slot_env(std::getenv("V2M_RING_SLOT_BYTES"));   // test knob: force small slices
 	u64 const slot_default(n_rows * p.pitch < (u64(8) << 30) ? (u64(128) << 20) : (u64(512) << 20));
 	u64 const slot_target((slot_env && *slot_env) ? std::strtoull(slot_env, nullptr, 10) : slot_default);
-	p.rows_per_slice = std::max<u64>(1, std::min<u64>({n_rows, slot_target / p.pitch, max_rows_per_slice}));
+	p.rows_per_slice = std::max<u64>(1, std::min<u64>({n_rows, slot_target / (p.pitch + table_bytes_per_row), max_rows_per_slice}));
 	p.n_slices = (n_rows + p.rows_per_slice - 1) / p.rows_per_slice;
 	p.slot_bytes = p.rows_per_slice * p.pitch;
 	return p;
@@ -2301,6 +2307,277 @@ int v2m_splice_window_set_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32
 		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	}
 	return V2M_OK;
+}
+
+
+// ---- distinct pieces of a window set ----------------------------------------------------------------
+
+namespace {
+
+u64 env_u64(char const *name, u64 fallback)
+{
+	char const *const e(std::getenv(name));
+	return (e && *e) ? std::strtoull(e, nullptr, 10) : fallback;
+}
+
+// A class of one window: its first row, its bytes' place in the pool, its number within the window (given when its slice is done)
+// and the next class of the same window with the same key and length (a key collision).
+struct distinct_class {
+	u64 first_row, pool_offset;
+	u32 window, length, index, next;
+};
+
+struct distinct_key {
+	u64 key;
+	u32 window, length;
+	bool operator==(distinct_key const &o) const { return key == o.key && window == o.window && length == o.length; }
+};
+
+struct distinct_key_hash {
+	std::size_t operator()(distinct_key const &k) const { return std::size_t(v2m::mix64(k.key ^ (u64(k.window) << 32 | k.length) * v2m::kGolden)); }
+};
+
+constexpr u32 kNoClass = ~u32(0);
+
+// The slices of the set calls, with the records staying in the device slot: per slice the keys of its pieces come to the host, which
+// looks every piece up per (window, key, length) in a table that lives for the call -- a piece with an unknown key becomes a class's
+// representative and is gathered into the pool, every other piece is verified byte for byte against its candidate's pool entry; a
+// mismatch (a key collision) moves the piece on to the next class with that key, or makes it a representative in the next round.
+// The classes a slice has added leave for the host in one copy of the slice's pool bytes on the copy stream, and are handed to the
+// sink while the next slice's kernels run.
+int distinct_run(v2m_ctx *ctx, v2m_row_batch const *rows, bool unaligned, v2m_distinct_sink_fn sink, void *user, u32 *class_of_out, u32 *n_classes_out)
+{
+	auto const &set(ctx->set);
+	u64 const W(set.n_windows), n_rows(rows->n_rows);
+	u64 const hash_bits(std::min<u64>(64, env_u64("V2M_DISTINCT_HASH_BITS", 64)));   // test knob: fewer bits, more collisions, the same classes
+	u64 const key_mask(hash_bits >= 64 ? ~u64(0) : (u64(1) << hash_bits) - 1);
+	std::size_t free_bytes(0), total_bytes(0);
+	V2M_HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
+	u64 const pool_limit(std::min<u64>(env_u64("V2M_DISTINCT_POOL_BYTES", u64(4) << 30), free_bytes));
+
+	// the items of a row in hash_pieces_kernel, and the windows' lengths for aligned mode
+	std::vector<u32> window_table(2 * W + 1);
+	std::vector<u64> slot_offset(W);
+	u64 items_per_row(0), slots_end(0);
+	for (u64 k(0); k < W; ++k) {
+		window_table[k] = u32(items_per_row);
+		u32 const len(set.lengths[k]);
+		slot_offset[k] = slots_end;
+		slots_end += (u64(len) + 15) & ~u64(15);
+		items_per_row += len <= v2m::kDistinctLongBytes ? 1 : (len + v2m::kDistinctChunkBytes - 1) / v2m::kDistinctChunkBytes;
+		window_table[W + 1 + k] = len;
+	}
+	if (items_per_row >= 0xFFFFFFFFull) return fail(ctx, V2M_ERR_UNSUPPORTED, "the window set has too many chunks (%llu) for one set: split it", (unsigned long long) items_per_row);
+	window_table[W] = u32(items_per_row);
+	if (int const rc = upload_vec(ctx, ctx->d_distinct_windows, window_table)) return rc;
+	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the upload reads this call's vector)
+	u32 const *const d_first_item(ctx->d_distinct_windows.as<u32>());
+	u32 const *const d_window_lengths(d_first_item + W + 1);
+
+	// per piece 8 bytes of key and 4 of length, and a round's item (24) and flag (4)
+	slice_plan const p(plan_slices(ctx, n_rows, unaligned, ~u64(0), 40 * W));
+	if (int const rc = ensure_host_slots(ctx, 2, 0)) return rc;
+
+	std::vector<distinct_class> classes;
+	std::unordered_map<distinct_key, u32, distinct_key_hash> heads;
+	std::vector<u32> n_classes(W, 0);
+	scratch_buf pool;
+	u64 pool_used(0);
+	struct delivery { std::vector<u32> ids; u64 pool_begin{}; bool pending{}; } deliveries[2];
+
+	auto const grow_pool([&](u64 keep) -> int {
+		if (pool_used > pool_limit)
+			return fail(ctx, V2M_ERR_OUT_OF_MEMORY, "the distinct pieces need %llu bytes so far, more than the pool may hold: V2M_DISTINCT_POOL_BYTES is %llu (default 4 GiB, clamped to the free device memory)",
+				(unsigned long long) pool_used, (unsigned long long) pool_limit);
+		if (pool_used <= pool.bytes) return V2M_OK;
+		scratch_buf bigger;
+		V2M_HIP_TRY(ctx, bigger.dev_buf::ensure(std::min(pool_limit, std::max<u64>({pool_used, 2 * u64(pool.bytes), u64(1) << 20}))));
+		if (keep) {
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(bigger.p, pool.p, keep, hipMemcpyDeviceToDevice, ctx->stream));
+			V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		}
+		std::swap(pool.p, bigger.p);
+		std::swap(pool.bytes, bigger.bytes);
+		return V2M_OK;
+	});
+
+	auto const deliver([&](delivery &d, v2m_row_hold &slot) -> int {
+		if (!d.pending) return V2M_OK;
+		d.pending = false;
+		V2M_HIP_TRY(ctx, hipEventSynchronize(slot.copied));
+		char const *const base(slot.host.as<char>());
+		for (u32 const id : d.ids) {
+			distinct_class const &c(classes[id]);
+			if (sink(user, c.window, c.index, c.first_row, c.length ? base + (c.pool_offset - d.pool_begin) : "", c.length))
+				return fail(ctx, V2M_ERR_SINK, "sink aborted at class %u of window %u", c.index, c.window);
+		}
+		return V2M_OK;
+	});
+
+	auto const push_items([&](std::vector<v2m::piece_item> &items, u64 src, u64 dst, u32 len, u32 index) {
+		for (u32 at(0); at < len; at += v2m::kDistinctChunkBytes)
+			items.push_back({src + at, dst + at, std::min(v2m::kDistinctChunkBytes, len - at), index});
+	});
+
+	std::vector<u32> piece_class, pending, next_pending, pair_piece, slice_new;
+	std::vector<v2m::piece_item> gather_items, verify_items;
+
+	auto const slice([&](u64 s) -> int {
+		u64 const r0(s * p.rows_per_slice), r1(std::min(n_rows, r0 + p.rows_per_slice)), nr(r1 - r0), n_pieces(nr * W);
+		V2M_HIP_TRY(ctx, ctx->ring[0].ensure(p.slot_bytes));   // (the slice takes its device slot: refilled in the checked build)
+		char *const d_records(ctx->ring[0].as<char>());
+		ctx->set_lengths_slot = 0;
+		if (int const rc = unaligned ? splice_unaligned_slice(ctx, rows, r0, r1, d_records, p.pitch) : splice_aligned_slice(ctx, rows, r0, r1, d_records, p.pitch))
+			return rc;
+		V2M_HIP_TRY(ctx, ctx->d_distinct_keys.ensure(n_pieces * 8));
+		V2M_HIP_TRY(ctx, hipMemsetAsync(ctx->d_distinct_keys.p, 0, n_pieces * 8, ctx->stream));
+		u32 const *const d_lengths(unaligned ? ctx->d_set_lengths[0].as<u32>() : d_window_lengths);
+		{
+			timed_launch tl(ctx, V2M_KERNEL_DISTINCT_HASH);
+			u64 const rows_per_launch(32768);   // (the grid's y)
+			for (u64 b(0); b < nr; b += rows_per_launch) {
+				u64 const n(std::min(rows_per_launch, nr - b));
+				hipLaunchKernelGGL(v2m::hash_pieces_kernel, dim3(unsigned((items_per_row + v2m::kDistinctWaves - 1) / v2m::kDistinctWaves), unsigned(n)), dim3(v2m::kDistinctThreads), 0, ctx->stream,
+					d_records + b * p.pitch, p.pitch, u32(W), set.d_slot_offset32.as<u32>(), unaligned ? d_lengths + b * W : d_lengths, unaligned ? u32(W) : 0u,
+					d_first_item, ctx->d_distinct_keys.as<unsigned long long>() + b * W);
+			}
+		}
+		V2M_HIP_TRY(ctx, hipGetLastError());
+		V2M_HIP_TRY(ctx, ctx->h_distinct_keys.ensure(n_pieces * 12));
+		V2M_POISON_HOST(ctx->h_distinct_keys.p, n_pieces * 12);
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_distinct_keys.p, ctx->d_distinct_keys.p, n_pieces * 8, hipMemcpyDeviceToHost, ctx->stream));
+		if (unaligned)
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_distinct_keys.as<char>() + n_pieces * 8, d_lengths, n_pieces * 4, hipMemcpyDeviceToHost, ctx->stream));
+		// the previous slice's classes go to the sink under this slice's kernels
+		if (s >= 1) if (int const rc = deliver(deliveries[(s - 1) & 1], *ctx->host_slots[(s - 1) & 1])) return rc;
+		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		u64 const *const keys(ctx->h_distinct_keys.as<u64>());
+		u32 const *const slice_lengths(reinterpret_cast<u32 const *>(ctx->h_distinct_keys.as<char>() + n_pieces * 8));
+		auto const length_of([&](u64 i) { return unaligned ? slice_lengths[i] : set.lengths[i % W]; });
+		auto const record_offset([&](u64 i) { return (i / W) * p.pitch + slot_offset[i % W]; });
+
+		u64 const slice_pool_begin(pool_used);
+		piece_class.assign(n_pieces, kNoClass);
+		slice_new.clear();
+		pending.clear();
+		auto const new_class([&](u64 i, u32 len) -> u32 {
+			u32 const id(u32(classes.size()));
+			classes.push_back({r0 + i / W, pool_used, u32(i % W), len, 0, kNoClass});
+			if (len) push_items(gather_items, record_offset(i), pool_used, len, 0);
+			pool_used += (u64(len) + 15) & ~u64(15);
+			slice_new.push_back(id);
+			piece_class[i] = id;
+			return id;
+		});
+		auto const try_class([&](u64 i, u32 len, u32 candidate) {
+			piece_class[i] = candidate;
+			if (0 == len) return;   // (all empty pieces of a window are one class)
+			push_items(verify_items, record_offset(i), classes[candidate].pool_offset, len, u32(pair_piece.size()));
+			pair_piece.push_back(u32(i));
+		});
+		for (u64 round(0);; ++round) {
+			gather_items.clear(); verify_items.clear(); pair_piece.clear();
+			u64 const round_pool_begin(pool_used);
+			if (0 == round) {
+				for (u64 i(0); i < n_pieces; ++i) {
+					u32 const len(length_of(i));
+					auto const found(heads.find({keys[i] & key_mask, u32(i % W), len}));
+					if (heads.end() == found) heads.insert({{keys[i] & key_mask, u32(i % W), len}, new_class(i, len)});
+					else try_class(i, len, found->second);
+				}
+			}
+			else {
+				for (u32 const i : pending) {   // in piece order: an earlier piece of the same bytes becomes the representative first
+					u32 const len(length_of(i));
+					u32 const tried(piece_class[i]);
+					if (kNoClass == classes[tried].next) { u32 const id(new_class(i, len)); classes[tried].next = id; }
+					else try_class(i, len, classes[tried].next);
+				}
+			}
+			if (classes.size() >= kNoClass) return fail(ctx, V2M_ERR_UNSUPPORTED, "too many distinct pieces in one call");
+			if (int const rc = grow_pool(round_pool_begin)) return rc;
+			if (verify_items.empty() && gather_items.empty()) break;
+			u64 const n_gather(gather_items.size()), n_verify(verify_items.size()), n_pairs(pair_piece.size());
+			V2M_HIP_TRY(ctx, ctx->h_distinct_items.ensure((n_gather + n_verify) * sizeof(v2m::piece_item)));
+			V2M_HIP_TRY(ctx, ctx->d_distinct_items.ensure((n_gather + n_verify) * sizeof(v2m::piece_item)));
+			v2m::piece_item *const h_items(ctx->h_distinct_items.as<v2m::piece_item>());
+			std::copy(gather_items.begin(), gather_items.end(), h_items);
+			std::copy(verify_items.begin(), verify_items.end(), h_items + n_gather);
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_distinct_items.p, h_items, (n_gather + n_verify) * sizeof(v2m::piece_item), hipMemcpyHostToDevice, ctx->stream));
+			v2m::piece_item const *const d_items(ctx->d_distinct_items.as<v2m::piece_item>());
+			if (n_gather) {
+				timed_launch tl(ctx, V2M_KERNEL_DISTINCT_GATHER);
+				for (u64 b(0); b < n_gather; b += u64(1) << 32) {
+					u64 const n(std::min<u64>(u64(1) << 32, n_gather - b));
+					hipLaunchKernelGGL(v2m::gather_pieces_kernel, dim3(unsigned((n + v2m::kDistinctWaves - 1) / v2m::kDistinctWaves)), dim3(v2m::kDistinctThreads), 0, ctx->stream,
+						d_records, d_items + b, n, pool.as<char>());
+				}
+			}
+			if (n_verify) {
+				V2M_HIP_TRY(ctx, ctx->d_distinct_flags.ensure(n_pairs * 4));
+				V2M_HIP_TRY(ctx, ctx->h_distinct_flags.ensure(n_pairs * 4));
+				V2M_POISON_HOST(ctx->h_distinct_flags.p, n_pairs * 4);
+				V2M_HIP_TRY(ctx, hipMemsetAsync(ctx->d_distinct_flags.p, 0, n_pairs * 4, ctx->stream));
+				{
+					timed_launch tl(ctx, V2M_KERNEL_DISTINCT_VERIFY);
+					for (u64 b(0); b < n_verify; b += u64(1) << 32) {
+						u64 const n(std::min<u64>(u64(1) << 32, n_verify - b));
+						hipLaunchKernelGGL(v2m::verify_pieces_kernel, dim3(unsigned((n + v2m::kDistinctWaves - 1) / v2m::kDistinctWaves)), dim3(v2m::kDistinctThreads), 0, ctx->stream,
+							d_records, pool.as<char>(), d_items + n_gather + b, n, ctx->d_distinct_flags.as<u32>());
+					}
+				}
+				V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_distinct_flags.p, ctx->d_distinct_flags.p, n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
+			}
+			V2M_HIP_TRY(ctx, hipGetLastError());
+			V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			next_pending.clear();
+			u32 const *const flags(ctx->h_distinct_flags.as<u32>());
+			for (u64 j(0); j < n_pairs; ++j) if (flags[j]) next_pending.push_back(pair_piece[j]);
+			pending.swap(next_pending);
+			if (pending.empty()) break;
+		}
+
+		// the slice's classes in the order of their first rows (a later round's class may begin before an earlier round's): their numbers
+		std::sort(slice_new.begin(), slice_new.end(), [&](u32 a, u32 b) {
+			return classes[a].first_row != classes[b].first_row ? classes[a].first_row < classes[b].first_row : classes[a].window < classes[b].window; });
+		for (u32 const id : slice_new) classes[id].index = n_classes[classes[id].window]++;
+		for (u64 i(0); i < n_pieces; ++i) class_of_out[r0 * W + i] = classes[piece_class[i]].index;
+		if (sink && !slice_new.empty()) {
+			delivery &d(deliveries[s & 1]);
+			v2m_row_hold &slot(*ctx->host_slots[s & 1]);
+			u64 const bytes(pool_used - slice_pool_begin);
+			V2M_HIP_TRY(ctx, slot.host.ensure(bytes));
+			V2M_POISON_HOST(slot.host.p, bytes);
+			if (bytes) V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, pool.as<char>() + slice_pool_begin, bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
+			V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
+			d.ids = slice_new;
+			d.pool_begin = slice_pool_begin;
+			d.pending = true;
+		}
+		return V2M_OK;
+	});
+
+	int rc(V2M_OK);
+	for (u64 s(0); s < p.n_slices && V2M_OK == rc; ++s) rc = slice(s);
+	if (V2M_OK == rc && p.n_slices) rc = deliver(deliveries[(p.n_slices - 1) & 1], *ctx->host_slots[(p.n_slices - 1) & 1]);
+	// leave both streams idle whatever happened (the pool goes with the call)
+	(void) hipStreamSynchronize(ctx->stream);
+	(void) hipStreamSynchronize(ctx->copy_stream);
+	if (V2M_OK == rc && n_classes_out) std::copy(n_classes.begin(), n_classes.end(), n_classes_out);
+	return rc;
+}
+
+} // namespace
+
+int v2m_splice_window_set_distinct(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_distinct_sink_fn sink, void *user, uint32_t *class_of_out, uint32_t *n_classes_out)
+{
+	if (int const rc = check_set_call(ctx, rows, flags)) return rc;
+	if (!class_of_out) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "class_of_out is NULL");
+	if (n_classes_out) std::fill(n_classes_out, n_classes_out + ctx->set.n_windows, 0u);
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	scoped_set_call const in_set(ctx);
+	return distinct_run(ctx, rows, flags & V2M_SPLICE_UNALIGNED, sink, user, class_of_out, n_classes_out);
 }
 
 
