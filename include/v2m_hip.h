@@ -377,26 +377,43 @@ int v2m_splice_window_set_distinct(v2m_ctx *ctx, const v2m_row_batch *rows, uint
  * reference or inside a label is a byte, not padding.  The column's class:
  *   ref and row -> M     row only -> I     ref only -> D     neither -> none (the column is skipped)
  * The row's ops are the run-length encoding of the classes of its non-skipped columns, in column order; skipped columns do not break
- * a run.  Op codes are BAM's: M = 0, I = 1, D = 2.  Codes 7 and 8 stay free for a later '=' / 'X' split: M covers match and mismatch.
+ * a run.  Op codes are BAM's: M = 0, I = 1, D = 2.  With flags = 0, M covers match and mismatch; V2M_OPS_SPLIT_MATCH (below) splits it
+ * into BAM's '=' (7) and 'X' (8).
  * Guarantees: no op has length 0; no two neighbouring ops have the same code; the lengths of M and D sum to the reference length;
  * those of M and I to the row's unaligned length (what v2m_splice_rows_device reports for the row with V2M_SPLICE_UNALIGNED, passed
  * to the sink as row_length); the REF row (V2M_PLOIDY_MAX, no cuts) is the single op M R (no op for an empty reference); rows with
  * cuts follow the same rule on the row they would splice.
  * Rows arrive in batch order, one call per row, on the calling thread; `ops` is library-owned and valid during the call only; a
- * non-zero return ends the call with V2M_ERR_SINK.  Synchronous.  flags must be 0.  Errors as for v2m_splice_rows: V2M_ERR_STATE
+ * non-zero return ends the call with V2M_ERR_SINK.  Synchronous.  flags must be 0 or V2M_OPS_SPLIT_MATCH, anything else is
+ * V2M_ERR_INVALID_ARGUMENT.  Errors as for v2m_splice_rows: V2M_ERR_STATE
  * before an upload, V2M_ERR_PRECONDITION for bad cuts; a graph with a NUL byte is refused as V2M_SPLICE_UNALIGNED refuses it.
  * The ops always describe the WHOLE row: a column window or window set in force is neither used nor disturbed.
  * A row's first op is never I: column 0 holds the first reference byte (node 0 sits at reference and aligned position 0), so its class is M or D.
  * The call works through the batch in slices of as many rows as keep the per-row tables of its first two passes (three words per tile
  * and the effective-edge words) within 256 MiB of device memory; a slice is counted once and its rows' records (12 bytes per op) come to
  * the host in pieces of consecutive rows that fit 64 MiB of device and of pinned memory each (V2M_OPS_SLICE_BYTES overrides the 64 MiB, a
- * test knob; a single row goes through whatever it takes). */
+ * test knob; a single row goes through whatever it takes).
+ *
+ * V2M_OPS_SPLIT_MATCH: every column of class M gets a further fact, eq.  The REF row's byte is the 0-padded template's byte at that
+ * column, the row's byte the built row's byte there (a reference byte, or a label byte over it); eq holds when the two are equal AFTER
+ * FOLDING ASCII LETTERS TO ONE CASE, and only those: bytes a and b are equal when a == b, or when (a ^ b) == 0x20 and (a | 0x20) lies
+ * in 'a'..'z'.  So 'a' over 'A' is '=' (a soft-masked reference under an upper-case ALT is no mismatch); '@' / '`', '[' / '{' and
+ * 0xC4 / 0xE4 are 'X'; 'N' over 'A' is 'X' (no IUPAC semantics); a literal '-' over a literal '-' is '='.  The column's class is then
+ * '=' (V2M_OP_EQ), 'X' (V2M_OP_X), I, D or none, and the ops are the run-length encoding over the non-skipped columns exactly as above:
+ * skipped columns do not break a run here either, and V2M_OP_M does not occur.  Guarantees: no op has length 0; no two neighbouring
+ * ops have the same code; the lengths of =, X and D sum to the reference length, those of =, X and I to the row's unaligned length;
+ * REPLACING 7 AND 8 BY 0 AND MERGING EQUAL NEIGHBOURS GIVES EXACTLY THE OPS OF flags = 0 FOR THE SAME ROW; the REF row is the single op
+ * = R; rows with cuts follow the row they would splice.  Everything else above holds unchanged: whole rows only, windows and window
+ * sets untouched, NUL bytes refused, the sink and error rules, the slices. */
 typedef struct v2m_aln_op { uint32_t op; uint32_t length; } v2m_aln_op;
 #define V2M_OP_M 0u
 #define V2M_OP_I 1u
 #define V2M_OP_D 2u
+#define V2M_OP_EQ 7u
+#define V2M_OP_X 8u
+#define V2M_OPS_SPLIT_MATCH 0x4u
 typedef int (*v2m_ops_sink_fn)(void *user, uint64_t row_index, const v2m_aln_op *ops, uint64_t n_ops, uint64_t row_length /* unaligned length */);
-int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 */, v2m_ops_sink_fn sink, void *user);
+int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_OPS_SPLIT_MATCH */, v2m_ops_sink_fn sink, void *user);
 
 /* ---- founder search: the chunk walks ---------------------------------- */
 

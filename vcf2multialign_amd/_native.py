@@ -36,6 +36,8 @@ KERNEL_NAMES = ["transpose_bits_kernel", "resolve_effective_edges_kernel", "spli
 DISTINCT_CHUNK_BYTES = 8192
 DISTINCT_LONG_BYTES = 16384
 OP_M, OP_I, OP_D = 0, 1, 2   # v2m_aln_op.op (BAM's codes)
+OP_EQ, OP_X = 7, 8           # with OPS_SPLIT_MATCH, in place of OP_M
+OPS_SPLIT_MATCH = 0x4        # v2m_row_ops flag: M split into = and X (letters compare without case)
 ABI_VERSION = 5
 
 

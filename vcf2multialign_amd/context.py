@@ -385,9 +385,10 @@ class Context:
 			d_out, row_pitch, lengths.ctypes.data if want_lengths and rows.n_rows else None))
 		return lengths
 
-	def row_ops(self, rows):
+	def row_ops(self, rows, split_match=False):
 		"""v2m_row_ops: per row ((n, 2) uint32 array of (op, length) with op 0 = M, 1 = I, 2 = D; the row's unaligned length) -- the row's
-		alignment to the reference, always of the whole row whatever column window or window set is in force."""
+		alignment to the reference, always of the whole row whatever column window or window set is in force.  split_match
+		(V2M_OPS_SPLIT_MATCH): 7 = '=' and 8 = X in place of M -- the row's byte equals the REF row's, letters compared without case, or not."""
 		if not isinstance(rows, RowBatch):
 			rows = RowBatch(rows)
 		collected, error = [], []
@@ -401,7 +402,7 @@ class Context:
 				error.append(e)
 				return 1
 
-		rc = self._lib.v2m_row_ops(self._h, C.byref(rows.struct), 0, N.OPS_SINK_FN(_cb), None)
+		rc = self._lib.v2m_row_ops(self._h, C.byref(rows.struct), N.OPS_SPLIT_MATCH if split_match else 0, N.OPS_SINK_FN(_cb), None)
 		if error:
 			raise error[0]
 		self._check(rc)

@@ -432,4 +432,19 @@ int64_t v2mh_chain_text(v2m_aln_op const *ops, uint64_t n_ops, char const *t_nam
 	}
 }
 
+// paf_text() of output.hh (no GPU), handed over as v2mh_chain_text hands over a chain: 0 for ops without any = / X (no line), -1 with a
+// message in err for ops that are none of =, X, I, D.
+int64_t v2mh_paf_text(v2m_aln_op const *ops, uint64_t n_ops, char const *t_name, uint64_t t_size, char const *q_name, uint64_t q_size,
+	char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		std::string const text(vh::paf_text(ops, n_ops, t_name, t_size, q_name, q_size));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
 } // extern "C"

@@ -52,6 +52,7 @@ struct options {
 	char const *region{};                 // --region=START-END: 1-based inclusive positions on the reference sequence
 	std::uint64_t region_start{}, region_end{};
 	char const *output_chain{};           // --output-chain=FILE: one UCSC chain per output row (reference -> row), from v2m_row_ops
+	char const *output_paf{};             // --output-paf=FILE: one PAF line with an =/X/I/D cigar per output row, from v2m_row_ops with V2M_OPS_SPLIT_MATCH
 	char const *regions_file{};           // --regions-file=FILE.bed: one output file per BED region, all spliced as one window set per pass
 	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
 	std::vector<int> devices{0};
@@ -98,6 +99,12 @@ void usage()
 		"                                     query; names as --output-sequences-separate forms them) that maps reference positions\n"
 		"                                     to positions in the --unaligned sequence, e.g. for liftOver or CrossMap.  The REF row\n"
 		"                                     has no chain.  Alone or beside -s / --output-sequences-separate; not with --region,\n"
+		"                                     --regions-file or several --device entries\n"
+		"      --output-paf=FILE              Write one PAF line per output sequence (the sequence as query, the reference as target;\n"
+		"                                     names as for --output-chain) with the number of matching bytes, NM and the extended\n"
+		"                                     CIGAR (cg:Z: in = X I D, as minimap2 --eqx -c writes it): where the sequence differs\n"
+		"                                     from the reference.  Letters compare without case.  The REF row has no line.  Alone\n"
+		"                                     or beside -s / --output-sequences-separate / --output-chain; not with --region,\n"
 		"                                     --regions-file or several --device entries\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
@@ -285,7 +292,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -297,7 +304,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct}, {"output-paf", required_argument, nullptr, o_output_paf},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -346,6 +353,7 @@ int main(int argc, char **argv)
 			case o_regions_file: opt.regions_file = optarg; break;
 			case o_output_chain: opt.output_chain = optarg; break;
 			case o_distinct: opt.distinct = true; break;
+			case o_output_paf: opt.output_paf = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -381,6 +389,11 @@ int main(int argc, char **argv)
 		// a chain describes whole rows, from one context that holds every chromosome copy
 		char const *const other(opt.region ? "--region" : opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
 		if (other) { std::cerr << "ERROR: --output-chain cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+	}
+	if (opt.output_paf) {
+		// as for a chain: whole rows, one context
+		char const *const other(opt.region ? "--region" : opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
+		if (other) { std::cerr << "ERROR: --output-paf cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
 	}
 	if (opt.region && !parse_region(opt.region, opt.region_start, opt.region_end)) {
 		std::cerr << "ERROR: --region must be START-END with 1 <= START <= END (1-based, inclusive), got \"" << opt.region << "\".\n";
@@ -600,9 +613,17 @@ int main(int argc, char **argv)
 				output.output_separate(graph, !opt.separate_plain);
 				std::cerr << " Done.\n";
 			}
-			if (opt.output_chain) {
+			if (opt.output_chain && opt.output_paf) {   // one pass over the rows, with the split; the chains from the ops folded back
+				std::cerr << "Outputting chains and PAF..." << std::flush;
+				output.output_chain_and_paf(graph, opt.output_chain, opt.output_paf);
+				std::cerr << " Done.\n";
+			} else if (opt.output_chain) {
 				std::cerr << "Outputting chains..." << std::flush;
 				output.output_chain(graph, opt.output_chain);
+				std::cerr << " Done.\n";
+			} else if (opt.output_paf) {
+				std::cerr << "Outputting PAF..." << std::flush;
+				output.output_paf(graph, opt.output_paf);
 				std::cerr << " Done.\n";
 			}
 		});

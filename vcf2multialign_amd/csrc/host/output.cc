@@ -842,8 +842,52 @@ std::string chain_text(v2m_aln_op const *ops, u64 n_ops, std::string const &t_na
 }
 
 
+// --- PAF (--output-paf) -----------------------------------------------------------------------------------------
+std::string paf_text(v2m_aln_op const *ops, u64 n_ops, std::string const &t_name, u64 t_size, std::string const &q_name, u64 q_size)
+{
+	auto const aligned([](v2m_aln_op const &op) { return V2M_OP_EQ == op.op || V2M_OP_X == op.op; });
+	u64 first(n_ops), last(0);
+	for (u64 i(0); i < n_ops; ++i) {
+		if (!aligned(ops[i]) && V2M_OP_I != ops[i].op && V2M_OP_D != ops[i].op)
+			throw std::invalid_argument("alignment op code " + std::to_string(ops[i].op) + " is none of =, X, I, D (ops made with V2M_OPS_SPLIT_MATCH)");
+		if (!aligned(ops[i])) continue;
+		if (n_ops == first) first = i;
+		last = i;
+	}
+	if (n_ops == first) return std::string();
+	u64 t_start(0), q_start(0), t_end(t_size), q_end(q_size);
+	for (u64 i(0); i < first; ++i) (V2M_OP_D == ops[i].op ? t_start : q_start) += ops[i].length;
+	for (u64 i(last + 1); i < n_ops; ++i) (V2M_OP_D == ops[i].op ? t_end : q_end) -= ops[i].length;
+	u64 n_eq(0), block_len(0);
+	std::string cigar;
+	for (u64 i(first); i <= last; ++i) {
+		block_len += ops[i].length;
+		if (V2M_OP_EQ == ops[i].op) n_eq += ops[i].length;
+		cigar += std::to_string(ops[i].length);
+		cigar += V2M_OP_EQ == ops[i].op ? '=' : V2M_OP_X == ops[i].op ? 'X' : V2M_OP_I == ops[i].op ? 'I' : 'D';
+	}
+	return q_name + '\t' + std::to_string(q_size) + '\t' + std::to_string(q_start) + '\t' + std::to_string(q_end) + "\t+\t"
+		+ t_name + '\t' + std::to_string(t_size) + '\t' + std::to_string(t_start) + '\t' + std::to_string(t_end) + '\t'
+		+ std::to_string(n_eq) + '\t' + std::to_string(block_len) + "\t255\tNM:i:" + std::to_string(block_len - n_eq) + "\tcg:Z:" + cigar + '\n';
+}
+
+
+std::vector<v2m_aln_op> fold_split_ops(v2m_aln_op const *ops, u64 n_ops)
+{
+	std::vector<v2m_aln_op> folded;
+	folded.reserve(n_ops);
+	for (u64 i(0); i < n_ops; ++i) {
+		u32 const op(V2M_OP_EQ == ops[i].op || V2M_OP_X == ops[i].op ? V2M_OP_M : ops[i].op);
+		if (!folded.empty() && folded.back().op == op) folded.back().length += ops[i].length;
+		else folded.push_back(v2m_aln_op{op, ops[i].length});
+	}
+	return folded;
+}
+
+
 namespace {
-	struct chain_state { std::ostream *stream; std::vector<std::string> const *names; std::string const *t_name; std::exception_ptr error; };
+	// chain and paf: either may be null; with paf the ops are split ones, and the chain is made from them folded back
+	struct chain_state { std::ostream *chain, *paf; std::vector<std::string> const *names; std::string const *t_name; std::exception_ptr error; };
 
 	int chain_sink(void *user, uint64_t row, v2m_aln_op const *ops, uint64_t n_ops, uint64_t row_length)
 	{
@@ -851,10 +895,22 @@ namespace {
 		try {
 			u64 t_size(0);
 			for (u64 i(0); i < n_ops; ++i) if (V2M_OP_I != ops[i].op) t_size += ops[i].length;
-			std::string const text(chain_text(ops, n_ops, *st.t_name, t_size, (*st.names)[row], row_length, row + 1));
-			if (text.empty()) std::fprintf(stderr, "Warning: %s shares no column with the reference; it gets no chain.\n", (*st.names)[row].c_str());
-			else st.stream->write(text.data(), std::streamsize(text.size()));
-			return st.stream->good() ? 0 : 1;
+			if (st.chain) {
+				std::vector<v2m_aln_op> folded;
+				if (st.paf) folded = fold_split_ops(ops, n_ops);
+				std::string const text(st.paf ? chain_text(folded.data(), folded.size(), *st.t_name, t_size, (*st.names)[row], row_length, row + 1)
+					: chain_text(ops, n_ops, *st.t_name, t_size, (*st.names)[row], row_length, row + 1));
+				if (text.empty()) std::fprintf(stderr, "Warning: %s shares no column with the reference; it gets no chain.\n", (*st.names)[row].c_str());
+				else st.chain->write(text.data(), std::streamsize(text.size()));
+				if (!st.chain->good()) return 1;
+			}
+			if (st.paf) {
+				std::string const text(paf_text(ops, n_ops, *st.t_name, t_size, (*st.names)[row], row_length));
+				if (text.empty()) std::fprintf(stderr, "Warning: %s shares no column with the reference; it gets no PAF line.\n", (*st.names)[row].c_str());
+				else st.paf->write(text.data(), std::streamsize(text.size()));
+				if (!st.paf->good()) return 1;
+			}
+			return 0;
 		} catch (...) {   // nothing may cross the C boundary
 			st.error = std::current_exception();
 			return 1;
@@ -869,10 +925,11 @@ void output::output_chain(variant_graph const &graph, std::ostream &stream)
 }
 
 
-void output::write_chains(variant_graph const &graph, std::function<std::ostream &()> const &open)
+void output::write_chains(variant_graph const &graph, std::function<std::ostream &()> const &open_chain, std::function<std::ostream &()> const &open_paf)
 {
-	if (!m_more_gpus.empty()) throw std::runtime_error("--output-chain needs every chromosome copy on one GPU context");
-	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-chain needs every chromosome copy on one GPU context");
+	char const *const what(open_chain ? "--output-chain" : "--output-paf");
+	if (!m_more_gpus.empty()) throw std::runtime_error(std::string(what) + " needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error(std::string(what) + " needs every chromosome copy on one GPU context");
 	row_set const all(chain_rows(graph));
 	std::string const t_name(prefixed("REF", '.'));
 	auto const has_space([](std::string const &s) { return std::any_of(s.begin(), s.end(), [](char c) { return std::isspace(static_cast<unsigned char>(c)); }); });
@@ -900,8 +957,8 @@ void output::write_chains(variant_graph const &graph, std::function<std::ostream
 		batch.cut_nodes = rows.cut_nodes.data();
 		batch.cut_copies = rows.cut_copies.data();
 	}
-	chain_state st{&open(), &rows.ids, &t_name, nullptr};
-	int const rc(v2m_row_ops(m_gpu.get(), &batch, 0, chain_sink, &st));
+	chain_state st{open_chain ? &open_chain() : nullptr, open_paf ? &open_paf() : nullptr, &rows.ids, &t_name, nullptr};
+	int const rc(v2m_row_ops(m_gpu.get(), &batch, open_paf ? V2M_OPS_SPLIT_MATCH : 0, chain_sink, &st));
 	if (st.error) std::rethrow_exception(st.error);
 	m_gpu.check(rc);
 }
@@ -917,6 +974,53 @@ void output::output_chain(variant_graph const &graph, char const *path)
 	});
 	stream.flush();
 	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+}
+
+
+void output::output_paf(variant_graph const &graph, std::ostream &stream)
+{
+	write_chains(graph, {}, [&stream]() -> std::ostream & { return stream; });
+}
+
+
+void output::output_chain_and_paf(variant_graph const &graph, std::ostream &chain_stream, std::ostream &paf_stream)
+{
+	write_chains(graph, [&chain_stream]() -> std::ostream & { return chain_stream; }, [&paf_stream]() -> std::ostream & { return paf_stream; });
+}
+
+
+namespace {
+	std::function<std::ostream &()> opener(std::ofstream &stream, char const *path)
+	{
+		return [&stream, path]() -> std::ostream & {
+			stream.open(path, std::ios::binary | std::ios::trunc);
+			if (!stream) throw std::runtime_error(std::string("unable to open ") + path + " for writing");
+			return stream;
+		};
+	}
+
+	void finish(std::ofstream &stream, char const *path)
+	{
+		stream.flush();
+		if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+	}
+}
+
+
+void output::output_paf(variant_graph const &graph, char const *path)
+{
+	std::ofstream stream;
+	write_chains(graph, {}, opener(stream, path));
+	finish(stream, path);
+}
+
+
+void output::output_chain_and_paf(variant_graph const &graph, char const *chain_path, char const *paf_path)
+{
+	std::ofstream chain_stream, paf_stream;
+	write_chains(graph, opener(chain_stream, chain_path), opener(paf_stream, paf_path));
+	finish(chain_stream, chain_path);
+	finish(paf_stream, paf_path);
 }
 
 

@@ -45,6 +45,18 @@ struct output_region {
 // Ops without any M give the empty string (no chain).  Throws std::invalid_argument for an op code other than M, I, D.
 std::string chain_text(v2m_aln_op const *ops, u64 n_ops, std::string const &t_name, u64 t_size, std::string const &q_name, u64 q_size, u64 id);
 
+// One PAF line (the row as query, the reference as target) from a row's SPLIT alignment ops (V2M_OPS_SPLIT_MATCH: =, X, I, D), as
+// minimap2 --eqx -c writes it: a pure function of its arguments.  Tab-separated, ending in '\n':
+//   q_name q_size qStart qEnd + t_name t_size tStart tEnd n_eq block_len 255 NM:i:<n> cg:Z:<cigar>
+// Leading and trailing I / D ops move qStart / tStart and qEnd / tEnd inward, as in chain_text; the cigar is the ops from the first to
+// the last = / X op inclusive, each <length><=|X|I|D>; n_eq = the summed = lengths, block_len = the summed lengths of the cigar's ops,
+// NM = block_len - n_eq.  Ops without any = / X give the empty string (no line).  Throws std::invalid_argument for an op code other
+// than =, X, I, D: a caller that passes M has not asked for the split.
+std::string paf_text(v2m_aln_op const *ops, u64 n_ops, std::string const &t_name, u64 t_size, std::string const &q_name, u64 q_size);
+
+// Split ops folded back to those of flags = 0: = and X become M, equal neighbours merge.
+std::vector<v2m_aln_op> fold_split_ops(v2m_aln_op const *ops, u64 n_ops);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -100,6 +112,15 @@ public:
 	void output_chain(variant_graph const &graph, char const *path);
 	void output_chain(variant_graph const &graph, std::ostream &stream);
 
+	// --output-paf: one PAF line per output row (paf_text above) from v2m_row_ops with V2M_OPS_SPLIT_MATCH; the rows, their names and
+	// the whitespace check are output_chain's.  The REF row has no line; a row without any = / X op gets none and a warning on stderr.
+	void output_paf(variant_graph const &graph, char const *path);
+	void output_paf(variant_graph const &graph, std::ostream &stream);
+	// Both files from ONE pass over the rows, with the split: the chains are made from the ops folded back (fold_split_ops) and are
+	// byte for byte those of output_chain().
+	void output_chain_and_paf(variant_graph const &graph, char const *chain_path, char const *paf_path);
+	void output_chain_and_paf(variant_graph const &graph, std::ostream &chain_stream, std::ostream &paf_stream);
+
 protected:
 	struct row_set {
 		std::vector<std::string> ids;           // FASTA identifiers (a2m) or file names (separate)
@@ -117,7 +138,8 @@ protected:
 	void write_a2m(row_set const &rows, std::ostream &stream);
 	void write_a2m_sharded(row_set const &rows, char const *dst_name);
 	virtual row_set a2m_rows(variant_graph const &graph) = 0;
-	void write_chains(variant_graph const &graph, std::function<std::ostream &()> const &open);   // `open` is called once the names are checked
+	// `open_chain` / `open_paf` (either may be empty, not both) are called once the names are checked; with open_paf the rows go through v2m_row_ops with the split
+	void write_chains(variant_graph const &graph, std::function<std::ostream &()> const &open_chain, std::function<std::ostream &()> const &open_paf = {});
 	virtual row_set chain_rows(variant_graph const &graph) = 0;   // the rows of a2m_rows() under the names of output_separate()
 	void write_separate(row_set const &rows);
 	std::string prefixed(std::string const &name, char sep) const;

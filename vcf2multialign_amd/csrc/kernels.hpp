@@ -2453,8 +2453,10 @@ __global__ __launch_bounds__(256) void scan_tile_counts_kernel(u32 *__restrict__
 // tile is 16 slots of 1 KiB, slot k * 4 + wave = that wave's chunks of round k, so what is carried from column to
 // column (the class of the last non-skipped column; the running counts) is one wave scan per slot plus a carry over
 // the 16 slots, as in the stream-out.
+// With V2M_OPS_SPLIT_MATCH the class has a third bit, ne: both lower bits set and the row's byte differs from the REF row's
+// (mismatch_byte_bits) -- 3 = '=', 7 = 'X' -- and the *_eqx_kernel forms of the three passes carry it wherever a class is carried.
 // ---------------------------------------------------------------------------------------------
-struct row_op_record { u32 cls, ref_pos, row_pos; };   // cls: ref | row << 1
+struct row_op_record { u32 cls, ref_pos, row_pos; };   // cls: ref | row << 1 (| ne << 2 from the _eqx kernels)
 
 // Bit i set for every non-zero byte i of the 16-B chunk.
 __device__ __forceinline__ u32 nonzero_byte_bits(vec4u const v)
@@ -2468,13 +2470,33 @@ __device__ __forceinline__ u32 nonzero_byte_bits(vec4u const v)
 	return bits;
 }
 
+// Bit i set for every byte i at which the two 16-B chunks differ under the split's rule (include/v2m_hip.h, V2M_OPS_SPLIT_MATCH):
+// equal bytes, or two bytes that differ in bit 5 only and are an ASCII letter, compare equal.
+__device__ __forceinline__ u32 mismatch_byte_bits(vec4u const a, vec4u const b)
+{
+	u32 bits = 0;
+#pragma unroll
+	for (int d = 0; d < 4; ++d) {
+		u32 const x = a[d] ^ b[d];
+		u32 const v = a[d] | 0x20202020u, low = v & 0x7F7F7F7Fu;
+		// bit 7 per byte of v in 'a'..'z': low + 0x1F carries into bit 7 from 0x61 on, low + 0x05 from 0x7B on; bit 7 of v itself rules the byte out
+		u32 const letter = (low + 0x1F1F1F1Fu) & ~(low + 0x05050505u) & ~v;
+		// a byte differs when x has a bit other than bit 5, or has bit 5 (moved to bit 7 by << 2) and the byte is no letter
+		u32 const keep = (~zero_bytes_mask(x & 0xDFDFDFDFu) | ((x << 2) & ~letter)) & 0x80808080u;   // bits 7, 15, 23, 31
+		bits |= (((keep >> 7) | (keep >> 14) | (keep >> 21) | (keep >> 28)) & 0xFu) << (4 * d);
+	}
+	return bits;
+}
+
 constexpr int kOpsSlots = kChunksPerThread * (kSpliceThreads / 64);   // 16
 
-template <bool kEmit>
+// kSplit (V2M_OPS_SPLIT_MATCH): a third class bit, ne -- both lower bits set and the row's byte differs from the REF row's --, carried wherever
+// a class is carried: class 3 is '=', 7 is 'X'.  The kSplit = false instantiations are the kernels as they were.
+template <bool kEmit, bool kSplit>
 __device__ __forceinline__ void row_ops_tiles(
 	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
 	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
-	u32 *__restrict__ tile_info /* [n_rows][n_tiles]; count: written (breakpoints | first class << 16 | last class << 18); emit: the carry into the tile */,
+	u32 *__restrict__ tile_info /* [n_rows][n_tiles]; count: written (breakpoints | first class << 16 | last class << 18, with kSplit << 19); emit: the carry into the tile */,
 	u32 n_tiles, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run,
 	u32 const *__restrict__ op_offsets /* [n_rows][n_tiles] */, u32 const *__restrict__ tile_ref_before /* [n_tiles] */,
 	u32 const *__restrict__ tile_row_before /* [n_rows][n_tiles] */, u64 const *__restrict__ op_base /* [n_rows] */,
@@ -2528,21 +2550,27 @@ __device__ __forceinline__ void row_ops_tiles(
 		// per chunk: the row's bits, the class of its last non-skipped column, and (from ballots, no LDS) that of the last
 		// non-skipped column of the wave's earlier chunks of the same slot
 		u32 row_bits[kChunksPerThread], wave_carry[kChunksPerThread];
+		u32 ne_bits[kSplit ? kChunksPerThread : 1];   // kSplit: the M columns whose two bytes differ
 #pragma unroll
 		for (int k = 0; k < kChunksPerThread; ++k) {
-			row_bits[k] = nonzero_byte_bits(lds[t + kSpliceThreads * k]);
+			vec4u const mine = lds[t + kSpliceThreads * k];
+			row_bits[k] = nonzero_byte_bits(mine);
+			if constexpr (kSplit) ne_bits[k] = mismatch_byte_bits(pristine[k], mine) & ref_bits[k] & row_bits[k];
 			u32 const live = ref_bits[k] | row_bits[k];
 			u32 last = 0;
 			if (live) {
 				u32 const top = 31u - (u32) __builtin_clz(live);
 				last = ((ref_bits[k] >> top) & 1u) | (((row_bits[k] >> top) & 1u) << 1);
+				if constexpr (kSplit) last |= ((ne_bits[k] >> top) & 1u) << 2;
 			}
 			u64 const b0 = __ballot(last & 1u), b1 = __ballot(last & 2u);
-			u64 const any = b0 | b1, before = any & below_lanes;
+			u64 const b2 = kSplit ? __ballot(last & 4u) : 0ULL;
+			u64 const any = b0 | b1, before = any & below_lanes;   // (bit 2 is set only beside the two lower ones)
 			u32 carry = 0;
 			if (before) {
 				u32 const p = 63u - (u32) __builtin_clzll(before);
 				carry = (u32) ((b0 >> p) & 1u) | ((u32) ((b1 >> p) & 1u) << 1);
+				if constexpr (kSplit) carry |= (u32) ((b2 >> p) & 1u) << 2;
 			}
 			wave_carry[k] = carry;
 			if (0 == lane) {
@@ -2550,6 +2578,7 @@ __device__ __forceinline__ void row_ops_tiles(
 				if (any) {
 					u32 const p = 63u - (u32) __builtin_clzll(any);
 					slot_class = (u32) ((b0 >> p) & 1u) | ((u32) ((b1 >> p) & 1u) << 1);
+					if constexpr (kSplit) slot_class |= (u32) ((b2 >> p) & 1u) << 2;
 				}
 				slot_last[k * kWaves + wave] = slot_class;
 			}
@@ -2573,17 +2602,22 @@ __device__ __forceinline__ void row_ops_tiles(
 			// bit i of prev_ref / prev_row: the bit of the last non-skipped column before column i (known[i]: there is one), filled forward over the skipped columns
 			u32 known = ((live << 1) | (carry ? 1u : 0u)) & 0xFFFFu;
 			u32 prev_ref = ((ref_bits[k] << 1) | (carry & 1u)) & 0xFFFFu;
-			u32 prev_row = ((row_bits[k] << 1) | (carry >> 1)) & 0xFFFFu;
+			u32 prev_row = ((row_bits[k] << 1) | (kSplit ? (carry >> 1) & 1u : carry >> 1)) & 0xFFFFu;
+			u32 prev_ne = kSplit ? ((ne_bits[kSplit ? k : 0] << 1) | (carry >> 2)) & 0xFFFFu : 0u;
 #pragma unroll
 			for (int d = 1; d < 16; d <<= 1) {
 				prev_ref |= (prev_ref << d) & ~known & 0xFFFFu;
 				prev_row |= (prev_row << d) & ~known & 0xFFFFu;
+				if constexpr (kSplit) prev_ne |= (prev_ne << d) & ~known & 0xFFFFu;
 				known |= (known << d) & 0xFFFFu;
 			}
 			breaks[k] = live & ((ref_bits[k] ^ prev_ref) | (row_bits[k] ^ prev_row));
+			if constexpr (kSplit) breaks[k] |= live & (ne_bits[k] ^ prev_ne);
 			if (!kEmit && live && 0 == carry) {   // (one chunk per tile at most: the first one with a non-skipped column)
 				u32 const low = (u32) __builtin_ctz(live);
-				first_class = ((ref_bits[k] >> low) & 1u) | (((row_bits[k] >> low) & 1u) << 1);
+				u32 first = ((ref_bits[k] >> low) & 1u) | (((row_bits[k] >> low) & 1u) << 1);
+				if constexpr (kSplit) first |= ((ne_bits[k] >> low) & 1u) << 2;
+				first_class = first;
 			}
 		}
 
@@ -2599,7 +2633,7 @@ __device__ __forceinline__ void row_ops_tiles(
 				u32 total = 0;
 #pragma unroll
 				for (int wv = 0; wv < kWaves; ++wv) total += wave_sums[wv];
-				tile_info[(u64) row * n_tiles + tile] = total | first_class << 16 | tile_last << 18;   // total <= kTileBytes = 1 << 14
+				tile_info[(u64) row * n_tiles + tile] = total | first_class << 16 | tile_last << (kSplit ? 19 : 18);   // total <= kTileBytes = 1 << 14
 			}
 		} else {
 			// running counts before every chunk: breakpoints | reference bytes << 16 (each at most kTileBytes in a tile) and row bytes
@@ -2639,6 +2673,7 @@ __device__ __forceinline__ void row_ops_tiles(
 					u32 const i = (u32) __builtin_ctz(b), lower = (1u << i) - 1u;
 					row_op_record rec;
 					rec.cls = ((ref_bits[k] >> i) & 1u) | (((row_bits[k] >> i) & 1u) << 1);
+					if constexpr (kSplit) rec.cls |= ((ne_bits[k] >> i) & 1u) << 2;
 					rec.ref_pos = ref_before_tile + (before_a >> 16) + (u32) __builtin_popcount(ref_bits[k] & lower);
 					rec.row_pos = row_before_tile + before_b + (u32) __builtin_popcount(row_bits[k] & lower);
 					u64 const at = first_op + (before_a & 0xFFFFu) + (u32) __builtin_popcount(breaks[k] & lower);
@@ -2655,7 +2690,7 @@ __global__ __launch_bounds__(kSpliceThreads) void count_row_ops_kernel(
 	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
 	u32 *__restrict__ tile_info /* [n_rows][n_tiles] */, u32 n_tiles, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
 {
-	row_ops_tiles<false>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_info, n_tiles, n_rows, rows_per_group, n_groups, tile_run,
+	row_ops_tiles<false, false>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_info, n_tiles, n_rows, rows_per_group, n_groups, tile_run,
 		nullptr, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
@@ -2666,7 +2701,28 @@ __global__ __launch_bounds__(kSpliceThreads) void emit_row_ops_kernel(
 	u32 const *__restrict__ op_offsets, u32 const *__restrict__ tile_ref_before, u32 const *__restrict__ tile_row_before, u64 const *__restrict__ op_base,
 	row_op_record *__restrict__ out, u64 out_capacity)
 {
-	row_ops_tiles<true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_info, n_tiles, n_rows, rows_per_group, n_groups, tile_run,
+	row_ops_tiles<true, false>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_info, n_tiles, n_rows, rows_per_group, n_groups, tile_run,
+		op_offsets, tile_ref_before, tile_row_before, op_base, out, out_capacity);
+}
+
+// The kSplit = true instantiations (V2M_OPS_SPLIT_MATCH).
+__global__ __launch_bounds__(kSpliceThreads) void count_row_ops_eqx_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 *__restrict__ tile_info /* [n_rows][n_tiles] */, u32 n_tiles, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run)
+{
+	row_ops_tiles<false, true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_info, n_tiles, n_rows, rows_per_group, n_groups, tile_run,
+		nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+}
+
+__global__ __launch_bounds__(kSpliceThreads) void emit_row_ops_eqx_kernel(
+	vec4u const *__restrict__ tmpl0, u64 const *__restrict__ eff, u64 eff_words_per_row,
+	tile_tables tt, edge_patch const *__restrict__ patches, char const *__restrict__ labels,
+	u32 *__restrict__ tile_info /* [n_rows][n_tiles]: the carry into each tile (pass 2) */, u32 n_tiles, u32 n_rows, u32 rows_per_group, u32 n_groups, u32 tile_run,
+	u32 const *__restrict__ op_offsets, u32 const *__restrict__ tile_ref_before, u32 const *__restrict__ tile_row_before, u64 const *__restrict__ op_base,
+	row_op_record *__restrict__ out, u64 out_capacity)
+{
+	row_ops_tiles<true, true>(tmpl0, eff, eff_words_per_row, tt, patches, labels, tile_info, n_tiles, n_rows, rows_per_group, n_groups, tile_run,
 		op_offsets, tile_ref_before, tile_row_before, op_base, out, out_capacity);
 }
 
@@ -2737,6 +2793,76 @@ __global__ __launch_bounds__(256) void scan_row_ops_kernel(u32 *__restrict__ til
 	}
 	if (t == 0) n_ops[blockIdx.x] = carry_s[0];
 }
+
+// Pass 2 for the split (V2M_OPS_SPLIT_MATCH): the same scan over three-bit classes -- first class << 16, last class << 19, a third ballot.
+// Written out beside scan_row_ops_kernel and not as a second instantiation of one body: a kernel that merely calls a shared
+// __forceinline__ body compiles to 28 VGPRs where the kernel above has 25, and the existing kernels stay what they are.
+__global__ __launch_bounds__(256) void scan_row_ops_eqx_kernel(u32 *__restrict__ tile_info, u32 *__restrict__ op_offsets, u32 n_tiles, u32 *__restrict__ n_ops)
+{
+	__shared__ u32 wave_sums[4];
+	__shared__ u32 wave_last[4];
+	__shared__ u32 carry_s[2];   // ops so far, class of the last non-skipped column so far
+	V2M_POISON_LDS(wave_sums);
+	V2M_POISON_LDS(wave_last);
+	V2M_POISON_LDS(carry_s);
+	u32 *const info = tile_info + (u64) blockIdx.x * n_tiles;
+	u32 *const offsets = op_offsets + (u64) blockIdx.x * n_tiles;
+	int const t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	if (t == 0) { carry_s[0] = 0; carry_s[1] = 0; }
+	__syncthreads();
+	for (u32 base = 0; base < n_tiles; base += 256) {
+		u32 const i = base + t;
+		u32 const mine = i < n_tiles ? info[i] : 0u;
+		u32 const breaks = mine & 0xFFFFu, first = (mine >> 16) & 7u, last = (mine >> 19) & 7u;
+		u64 const b0 = __ballot(last & 1u), b1 = __ballot(last & 2u), b2 = __ballot(last & 4u);
+		u64 const any = b0 | b1, before = any & ((1ULL << lane) - 1);
+		u32 wave_carry = 0;
+		if (before) {
+			u32 const p = 63u - (u32) __builtin_clzll(before);
+			wave_carry = (u32) ((b0 >> p) & 1u) | ((u32) ((b1 >> p) & 1u) << 1) | ((u32) ((b2 >> p) & 1u) << 2);
+		}
+		if (0 == lane) {
+			u32 c = 0;
+			if (any) {
+				u32 const p = 63u - (u32) __builtin_clzll(any);
+				c = (u32) ((b0 >> p) & 1u) | ((u32) ((b1 >> p) & 1u) << 1) | ((u32) ((b2 >> p) & 1u) << 2);
+			}
+			wave_last[wave] = c;
+		}
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		__syncthreads();
+		u32 carry = carry_s[1], block_last = carry_s[1];
+#pragma unroll
+		for (int wv = 0; wv < 4; ++wv) {
+			u32 const c = wave_last[wv];
+			if (c) { if (wv < wave) carry = c; block_last = c; }
+		}
+		if (wave_carry) carry = wave_carry;
+		u32 const ops = breaks - ((breaks && first == carry) ? 1u : 0u);
+		u32 const incl = wave_inclusive_scan_u32(ops);
+		if (lane == 63) wave_sums[wave] = incl;
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		__syncthreads();
+		u32 ops_before = carry_s[0], total = 0;
+#pragma unroll
+		for (int wv = 0; wv < 4; ++wv) {
+			u32 const ws = wave_sums[wv];
+			if (wv < wave) ops_before += ws;
+			total += ws;
+		}
+		if (i < n_tiles) {
+			info[i] = carry;
+			offsets[i] = ops_before + incl - ops;
+		}
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		__syncthreads();
+		if (t == 0) { carry_s[0] += total; carry_s[1] = block_last; }
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		__syncthreads();
+	}
+	if (t == 0) n_ops[blockIdx.x] = carry_s[0];
+}
+
 
 // Non-zero bytes of every tile of the 0-padded template (one workgroup per tile): scan_tile_counts_kernel over them as one "row" gives
 // the reference bytes before each tile, the table pass 3 starts its reference positions from.

@@ -2951,7 +2951,8 @@ u64 ops_slice_budget()
 // Passes 1 and 2 for rows [row_begin, row_end) of the batch over the whole view: effective edges, the unaligned tile offsets and row lengths
 // (count_unaligned_kernel + scan_tile_counts_kernel, as the unaligned splice has them), breakpoints per row tile, op offsets and carried
 // classes.  Leaves the rows' op counts (u32) and lengths (u64) in ctx->h_ops_stage, in that order, and returns their sum in *total_ops.
-int row_ops_count_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row_end, u64 *total_ops)
+// split (V2M_OPS_SPLIT_MATCH): the _eqx kernels, timed under the same ids.
+int row_ops_count_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, u64 row_end, bool split, u64 *total_ops)
 {
 	u64 const n_rows(row_end - row_begin);
 	row_view &v(ctx->whole);
@@ -2978,13 +2979,13 @@ int row_ops_count_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, 
 	}
 	{
 		timed_launch tl(ctx, V2M_KERNEL_ROW_OPS_COUNT);
-		hipLaunchKernelGGL(v2m::count_row_ops_kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+		hipLaunchKernelGGL(split ? v2m::count_row_ops_eqx_kernel : v2m::count_row_ops_kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
 			v.d_template0.as<v2m::vec4u>(), d_eff, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
 			ctx->d_ops_info.as<u32>(), v.n_tiles, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run);
 	}
 	{
 		timed_launch tl(ctx, V2M_KERNEL_ROW_OPS_SCAN);
-		hipLaunchKernelGGL(v2m::scan_row_ops_kernel, dim3(unsigned(n_rows)), dim3(256), 0, ctx->stream,
+		hipLaunchKernelGGL(split ? v2m::scan_row_ops_eqx_kernel : v2m::scan_row_ops_kernel, dim3(unsigned(n_rows)), dim3(256), 0, ctx->stream,
 			ctx->d_ops_info.as<u32>(), ctx->d_ops_offsets.as<u32>(), v.n_tiles, ctx->d_ops_counts.as<u32>());
 	}
 	V2M_HIP_TRY(ctx, hipGetLastError());
@@ -3004,7 +3005,7 @@ int row_ops_count_slice(v2m_ctx *ctx, v2m_row_batch const *rows, u64 row_begin, 
 // Pass 3 for rows [piece_begin, piece_end) of the slice of slice_rows rows that row_ops_count_slice has just counted (slice_begin = the slice's
 // first row in the batch), and those rows to the sink.  The slice's tables are indexed by row, so a piece needs nothing counted again: it takes
 // them from its first row on.
-int row_ops_emit_piece(v2m_ctx *ctx, u64 slice_begin, u64 slice_rows, u64 piece_begin, u64 piece_end, v2m_ops_sink_fn sink, void *user)
+int row_ops_emit_piece(v2m_ctx *ctx, u64 slice_begin, u64 slice_rows, u64 piece_begin, u64 piece_end, bool split, v2m_ops_sink_fn sink, void *user)
 {
 	u64 const n_rows(piece_end - piece_begin);
 	row_view &v(ctx->whole);
@@ -3028,7 +3029,7 @@ int row_ops_emit_piece(v2m_ctx *ctx, u64 slice_begin, u64 slice_rows, u64 piece_
 		u64 const first_cell(piece_begin * v.n_tiles);
 		{
 			timed_launch tl(ctx, V2M_KERNEL_ROW_OPS_EMIT);
-			hipLaunchKernelGGL(v2m::emit_row_ops_kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
+			hipLaunchKernelGGL(split ? v2m::emit_row_ops_eqx_kernel : v2m::emit_row_ops_kernel, dim3(unsigned(g.n_blocks)), dim3(v2m::kSpliceThreads), 0, ctx->stream,
 				v.d_template0.as<v2m::vec4u>(), ctx->d_eff.as<u64>() - v.words.restart + piece_begin * v.words.stride, v.words.stride, tt, ctx->d_patches.as<v2m::edge_patch>(), ctx->d_labels.as<char>(),
 				ctx->d_ops_info.as<u32>() + first_cell, v.n_tiles, u32(n_rows), g.rows_per_group, g.n_groups, g.tile_run,
 				ctx->d_ops_offsets.as<u32>() + first_cell, ctx->d_ops_ref_before.as<u32>(), ctx->d_tile_counts.as<u32>() + first_cell, ctx->d_ops_base.as<u64>(),
@@ -3039,7 +3040,8 @@ int row_ops_emit_piece(v2m_ctx *ctx, u64 slice_begin, u64 slice_rows, u64 piece_
 		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		records = ctx->h_ops_out.as<v2m::row_op_record>();
 	}
-	// an op runs to the next breakpoint, the last one to the row's end (reference length, row length): in reference bytes for M and D, in row bytes for I
+	// an op runs to the next breakpoint, the last one to the row's end (reference length, row length): in reference bytes for M (split: = and X)
+	// and D, in row bytes for I.  Class 3 is M without the split and = with it; class 7 (X) comes from the _eqx kernels only.
 	for (u64 r(0); r < n_rows; ++r) {
 		u64 const n(counts[r]);
 		ctx->ops_row.resize(n);
@@ -3048,7 +3050,7 @@ int row_ops_emit_piece(v2m_ctx *ctx, u64 slice_begin, u64 slice_rows, u64 piece_
 			bool const last(i + 1 == n);
 			u64 const next_ref(last ? ctx->ref_len : records[bases[r] + i + 1].ref_pos), next_row(last ? lengths[r] : records[bases[r] + i + 1].row_pos);
 			bool const insertion(2 == rec.cls);
-			ctx->ops_row[i].op = 3 == rec.cls ? V2M_OP_M : insertion ? V2M_OP_I : V2M_OP_D;
+			ctx->ops_row[i].op = 3 == rec.cls ? (split ? V2M_OP_EQ : V2M_OP_M) : 7 == rec.cls ? V2M_OP_X : insertion ? V2M_OP_I : V2M_OP_D;
 			ctx->ops_row[i].length = u32(insertion ? next_row - rec.row_pos : next_ref - rec.ref_pos);
 		}
 		u64 const row(slice_begin + piece_begin + r);
@@ -3063,7 +3065,8 @@ int row_ops_emit_piece(v2m_ctx *ctx, u64 slice_begin, u64 slice_rows, u64 piece_
 int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_ops_sink_fn sink, void *user)
 {
 	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
-	if (flags) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "v2m_row_ops takes no flags (got 0x%x)", flags);
+	if (flags & ~V2M_OPS_SPLIT_MATCH) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "v2m_row_ops takes 0 or V2M_OPS_SPLIT_MATCH as flags (got 0x%x)", flags);
+	bool const split(flags & V2M_OPS_SPLIT_MATCH);
 	if (int const rc = check_batch(ctx, rows, V2M_SPLICE_UNALIGNED)) return rc;   // (the ops are read off the unaligned kernels' 0-padded rows: a NUL byte refuses as there)
 	if (!sink) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "sink is NULL");
 	if (0 == rows->n_rows) return V2M_OK;
@@ -3099,12 +3102,12 @@ int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_ops
 	for (u64 r0(0); r0 < rows->n_rows; r0 += want) {
 		u64 const n(std::min<u64>(want, rows->n_rows - r0));
 		u64 total_ops(0);
-		if (int const rc = row_ops_count_slice(ctx, rows, r0, r0 + n, &total_ops)) return rc;
+		if (int const rc = row_ops_count_slice(ctx, rows, r0, r0 + n, split, &total_ops)) return rc;
 		u32 const *const counts(ctx->h_ops_stage.as<u32>());
 		for (u64 p0(0); p0 < n;) {
 			u64 p1(p0 + 1), piece_ops(counts[p0]);
 			while (p1 < n && piece_ops + counts[p1] <= budget_ops) piece_ops += counts[p1++];
-			if (int const rc = row_ops_emit_piece(ctx, r0, n, p0, p1, sink, user)) return rc;
+			if (int const rc = row_ops_emit_piece(ctx, r0, n, p0, p1, split, sink, user)) return rc;
 			p0 = p1;
 		}
 	}

@@ -69,6 +69,8 @@ def _load():
 		L.v2mh_columns_of_reference_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, _u64p, _u64p]
 		L.v2mh_chain_text.restype = C.c_int64
 		L.v2mh_chain_text.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_paf_text.restype = C.c_int64
+		L.v2mh_paf_text.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -97,6 +99,23 @@ def chain_text(ops, t_name, t_size, q_name, q_size, chain_id):
 		raise ValueError(err.value.decode())
 	dst = C.create_string_buffer(max(1, n))
 	if n != L.v2mh_chain_text(*args, dst, n, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:n]
+
+
+def paf_text(ops, t_name, t_size, q_name, q_size):
+	"""The host library's PAF formatter (csrc/host/output.cc: paf_text; no GPU): the PAF line, as bytes, of the SPLIT alignment ops `ops`
+	((n, 2) of (op, length), 7 = '=', 8 = X, 1 = I, 2 = D) with the reference as target and the row as query; b"" for ops without any
+	= / X.  ValueError for any other op code (0 = M: ops made without split_match)."""
+	a = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1, 2)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (a.ctypes.data if a.size else None, a.shape[0], str(t_name).encode(), int(t_size), str(q_name).encode(), int(q_size))
+	n = L.v2mh_paf_text(*args, None, 0, err, len(err))
+	if n < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, n))
+	if n != L.v2mh_paf_text(*args, dst, n, err, len(err)):
 		raise ValueError(err.value.decode())
 	return dst.raw[:n]
 

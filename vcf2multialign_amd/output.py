@@ -45,6 +45,22 @@ class Output:
 			written += 1 if text else 0
 		return written
 
+	def _write_paf(self, stream, names, rows):
+		"""One PAF line per row (the row as query, the reference as target) from Context.row_ops(split_match=True), formatted by the host
+		library (host.paf_text); rows, names and the whitespace check are those of _write_chains.  Returns the number of lines written."""
+		from . import host
+		keep = [(n, r) for n, r in zip(names, rows) if not (isinstance(r, int) and r == PLOIDY_MAX)]
+		for name in [self._chain_name("REF")] + [n for n, _ in keep]:
+			if any(c.isspace() for c in name):
+				raise ValueError("the sequence name %r holds whitespace, which a PAF line cannot" % name)
+		written = 0
+		for (name, _), (ops, length) in zip(keep, self.ctx.row_ops(RowBatch([r for _, r in keep]), split_match=True)):
+			t_size = int(ops[ops[:, 0] != 1, 1].astype("u8").sum())
+			text = host.paf_text(ops, self._chain_name("REF"), t_size, name, length)
+			stream.write(text)
+			written += 1 if text else 0
+		return written
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -94,6 +110,15 @@ class HaplotypeOutput(Output):
 				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
 		return self._write_chains(stream, names, rows)
 
+	def output_paf(self, graph, stream):
+		"""--output-paf: one PAF line with an = / X / I / D cigar for each row output_chain gives a chain."""
+		names, rows = [], []
+		for sample_idx, sample in enumerate(graph.sample_names):
+			for chr_copy_idx in range(graph.sample_ploidy(sample_idx)):
+				names.append(self._chain_name("%s.%d" % (sample, 1 + chr_copy_idx)))
+				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
+		return self._write_paf(stream, names, rows)
+
 
 class FounderSequenceGreedyOutput(Output):
 	"""The output half of founder_sequence_greedy_output (output.hh:81-130): given cut positions and the
@@ -123,3 +148,14 @@ class FounderSequenceGreedyOutput(Output):
 			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
 			rows.append(list(zip(cut_positions[:-1], col)))
 		return self._write_chains(stream, names, rows)
+
+	def output_paf(self, graph, cut_positions, assigned_samples_column_major, stream):
+		"""--output-paf for the founder rows of output_a2m."""
+		n_rows = len(cut_positions) - 1
+		n_founders = len(assigned_samples_column_major) // n_rows if n_rows else 0
+		names, rows = [], []
+		for col_idx in range(n_founders):
+			names.append(self._chain_name(str(1 + col_idx)))
+			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
+			rows.append(list(zip(cut_positions[:-1], col)))
+		return self._write_paf(stream, names, rows)
