@@ -38,7 +38,8 @@
  * v2m_bgzf_scan and v2m_bgzf_decompress (with V2M_KERNEL_INFLATE), and v2m_vcf_scan (with V2M_KERNEL_VCF): a caller probes for them by symbol.
  * The window-set calls (v2m_window_set_layout, v2m_set_window_set, v2m_splice_window_set[_device]) were added the same way, and so was
  * v2m_row_ops (with v2m_aln_op, v2m_ops_sink_fn and the V2M_KERNEL_ROW_OPS_* ids), and v2m_splice_window_set_distinct (with
- * v2m_distinct_sink_fn and the V2M_KERNEL_DISTINCT_* ids).
+ * v2m_distinct_sink_fn and the V2M_KERNEL_DISTINCT_* ids), and v2m_column_counts / v2m_column_counts_device (with v2m_column_count,
+ * v2m_column_counts_sink_fn, the V2M_COUNTS_* flags and the V2M_KERNEL_COLUMN_* ids).
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -415,6 +416,53 @@ typedef struct v2m_aln_op { uint32_t op; uint32_t length; } v2m_aln_op;
 typedef int (*v2m_ops_sink_fn)(void *user, uint64_t row_index, const v2m_aln_op *ops, uint64_t n_ops, uint64_t row_length /* unaligned length */);
 int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_OPS_SPLIT_MATCH */, v2m_ops_sink_fn sink, void *user);
 
+/* ---- column counts ------------------------------------------------------------------------------
+ *
+ * The alignment by column: for every column of the view, how many rows of the batch hold which base there.  The view is the whole row,
+ * or the column window of v2m_set_column_window (a window set in force is ignored, as the row calls ignore it); it has
+ * L = v2m_window_length() columns.  Only the aligned form exists: the flag bits 0x1, 0x2 and 0x4 are V2M_ERR_INVALID_ARGUMENT.
+ * For column i of the view, count[c][i] is the number of batch rows whose aligned byte b at that column is of class c:
+ *   c = 0 .. 3  A, C, G, T: (b | 0x20) == 'a', 'c', 'g', 't'.  Exactly the two ASCII letters match: 0x41 and 0x61 are A, 0xC1 and 0xE1 are not.
+ *   c = 4       N: (b | 0x20) == 'n'
+ *   c = 5       gap: b == '-' exactly (0x0D is no gap), whether the '-' is the walk's padding or a literal byte of the reference or of a
+ *               label: the counts describe the bytes the A2M file holds
+ *   c = 6       other: n_rows minus the sum of the six.  Derived, never stored.
+ * Rows may repeat in a batch and every occurrence counts; a row with cuts counts as the row it splices.  n_rows < 2^32 - 1 as for every
+ * row call, so no count overflows.  A column is VARIABLE when none of the seven classes holds all n_rows rows (a column where every row
+ * is "other" is not variable; with n_rows <= 1 no column is).
+ *
+ * Device form.  d_counts is u32[V2M_COUNT_CLASSES][plane_pitch], 16-byte aligned; plane_pitch % 4 == 0 and plane_pitch >= (L + 3) & ~3.
+ * Element i < L of plane c is overwritten with count[c][i] -- with V2M_COUNTS_ACCUMULATE it is added to; elements L ..< (L + 3) & ~3 are
+ * written as 0, or left alone under V2M_COUNTS_ACCUMULATE; nothing beyond them is touched.
+ * Sink form.  One record per column (flags = 0) or per variable column (V2M_COUNTS_VARIABLE_ONLY), in ascending column order; `column`
+ * is absolute (the view's begin + i).  Records arrive in blocks of at most V2M_COLUMN_COUNTS_BLOCK_BYTES (environment, read per call;
+ * default 64 MiB; a test knob like V2M_OPS_SLICE_BYTES), on the calling thread, in library-owned pinned memory valid during the call
+ * only; the sink is never called with n = 0; a non-zero return ends the call with V2M_ERR_SINK.
+ * Errors as for the row calls: V2M_ERR_INVALID_ARGUMENT for NULL pointers, unknown flags, a misaligned d_counts or a bad pitch,
+ * V2M_ERR_STATE without a graph, V2M_ERR_PRECONDITION for bad cuts.  n_rows == 0 returns V2M_OK and touches nothing.  Both synchronous.
+ * The column window and the window set are left as they were.
+ * How: the batch goes through one device slot in row slices (as v2m_splice_window_set_distinct's does); per slice the aligned splice,
+ * then column_counts_kernel adds the slice's rows into the table (d_counts, or a context-owned one of 6 * L * 4 bytes); a call of
+ * many slices of few rows each (whole rows of a hundred million columns) carries the kernel's byte-wide counters from slice to slice in
+ * a context-owned stage of 6 bytes per column and widens them into the table before they would pass 255 rows.  The sink form then selects per column range (count_variable_columns_kernel, scan_tile_counts_kernel, emit_column_counts_kernel), a range's
+ * records crossing the link while the sink has the previous range's. */
+#define V2M_COUNT_CLASSES 6
+#define V2M_COUNTS_VARIABLE_ONLY 0x8u
+#define V2M_COUNTS_ACCUMULATE    0x10u
+
+typedef struct {
+	uint64_t column;                      /* absolute aligned column */
+	uint32_t count[V2M_COUNT_CLASSES];
+} v2m_column_count;                       /* 32 bytes */
+
+typedef int (*v2m_column_counts_sink_fn)(void *user, const v2m_column_count *cols, uint64_t n);
+
+int v2m_column_counts(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_COUNTS_VARIABLE_ONLY */,
+                      v2m_column_counts_sink_fn sink, void *user);
+
+int v2m_column_counts_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_COUNTS_ACCUMULATE */,
+                             void *d_counts, uint64_t plane_pitch);
+
 /* ---- founder search: the chunk walks ---------------------------------- */
 
 /* The edge-by-edge part of find_initial_cut_positions_lambda_min (libvcf2multialign/find_cut_positions.cc:126-176): the pBWT
@@ -652,6 +700,13 @@ enum {
 	V2M_KERNEL_DISTINCT_GATHER = 13, /* gather_pieces_kernel */
 	V2M_KERNEL_DISTINCT_VERIFY = 14, /* verify_pieces_kernel */
 	V2M_KERNEL_END = 15
+};
+/* The passes of v2m_column_counts[_device], added behind those in the same way (V2M_KERNEL_END keeps its value; V2M_KERNEL_LIMIT
+ * bounds what v2m_profile_get accepts). */
+enum {
+	V2M_KERNEL_COLUMN_COUNTS = 15,  /* column_counts_kernel, one launch per slice */
+	V2M_KERNEL_COLUMN_SELECT = 16,  /* count_variable_columns_kernel + scan_tile_counts_kernel + emit_column_counts_kernel, one group per column range */
+	V2M_KERNEL_LIMIT = 17
 };
 
 /* When enabled, every launch of the kernels above is bracketed by HIP events on the ctx's

@@ -31,6 +31,18 @@ KERNEL_DISTINCT_HASH, KERNEL_DISTINCT_GATHER, KERNEL_DISTINCT_VERIFY = 12, 13, 1
 KERNEL_NAMES = ["transpose_bits_kernel", "resolve_effective_edges_kernel", "splice_aligned_kernel", "splice_unaligned_kernel", "expand_reference_row_kernel", "count_unaligned_kernel",
 	"bgzf_deflate_kernel", "bgzf_inflate_kernel", "vcf_scan_kernels", "count_row_ops_kernel", "scan_row_ops_kernel", "emit_row_ops_kernel",
 	"hash_pieces_kernel", "gather_pieces_kernel", "verify_pieces_kernel"]
+# the passes of v2m_column_counts[_device], behind V2M_KERNEL_END (KERNEL_NAMES keeps the ids below it; KERNEL_LIMIT bounds profile_get)
+KERNEL_COLUMN_COUNTS, KERNEL_COLUMN_SELECT, KERNEL_LIMIT = 15, 16, 17
+COLUMN_KERNEL_NAMES = {KERNEL_COLUMN_COUNTS: "column_counts_kernel", KERNEL_COLUMN_SELECT: "emit_column_counts_kernel"}
+COUNT_CLASSES = 6                # v2m_column_count.count: A, C, G, T, N, gap ("other" is n_rows minus their sum)
+COUNTS_VARIABLE_ONLY = 0x8       # v2m_column_counts flag: only the columns no class holds all rows of
+COUNTS_ACCUMULATE = 0x10         # v2m_column_counts_device flag: add to the table instead of overwriting it
+# csrc/kernels.hpp: kCountColumns (columns per workgroup of column_counts_kernel), kCountRun (rows between two flushes of its byte
+# lanes), kSelectColumns (columns per workgroup of the selection); csrc/v2m_hip.hip: kColumnCountsMinRows (the least rows of a row group)
+COUNT_COLUMNS = 4096
+COUNT_RUN = 255
+SELECT_COLUMNS = 256
+COLUMN_COUNTS_MIN_ROWS = 32
 # csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
 # kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
 DISTINCT_CHUNK_BYTES = 8192
@@ -83,6 +95,8 @@ HOLD_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint
 WINDOW_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32))   # v2m_window_sink_fn
 DISTINCT_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64)   # v2m_distinct_sink_fn
 OPS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_ops_sink_fn
+COLUMN_COUNT_DTYPE = [("column", "<u8"), ("count", "<u4", (6,))]   # v2m_column_count
+COLUMN_COUNTS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_column_counts_sink_fn
 TRIALS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_trials_sink
 
 # every symbol include/v2m_hip.h declares: (restype, argtypes)
@@ -118,6 +132,8 @@ SIGNATURES = {
 	"v2m_row_release": (None, [C.c_void_p]),
 	"v2m_splice_rows_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
 	"v2m_row_ops": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, OPS_SINK_FN, C.c_void_p]),
+	"v2m_column_counts": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, COLUMN_COUNTS_SINK_FN, C.c_void_p]),
+	"v2m_column_counts_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -408,6 +408,37 @@ class Context:
 		self._check(rc)
 		return collected
 
+	def column_counts(self, rows, variable_only=False):
+		"""v2m_column_counts: (columns u64[n], counts u32[n, 6]) -- per column of the view in force (the whole row, or the column window)
+		how many rows of the batch hold A, C, G, T, N (either case) or '-' there; `columns` are absolute and ascend.  variable_only
+		(V2M_COUNTS_VARIABLE_ONLY): only the columns where no class -- "other", rows minus the six, included -- holds every row."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		blocks, error = [], []
+
+		def _cb(_user, records, n):
+			try:
+				blocks.append(np.frombuffer(C.string_at(records, 32 * n), dtype=np.dtype(N.COLUMN_COUNT_DTYPE)).copy())
+				return 0
+			except BaseException as e:  # propagate through the C frame as V2M_ERR_SINK
+				error.append(e)
+				return 1
+
+		rc = self._lib.v2m_column_counts(self._h, C.byref(rows.struct), N.COUNTS_VARIABLE_ONLY if variable_only else 0, N.COLUMN_COUNTS_SINK_FN(_cb), None)
+		if error:
+			raise error[0]
+		self._check(rc)
+		self.column_count_blocks = [len(b) for b in blocks]   # the sizes of the blocks the records arrived in
+		records = np.concatenate(blocks) if blocks else np.zeros(0, dtype=np.dtype(N.COLUMN_COUNT_DTYPE))
+		return records["column"].copy(), records["count"].copy()
+
+	def column_counts_device(self, rows, ptr, plane_pitch, accumulate=False):
+		"""v2m_column_counts_device: the counts into device memory at `ptr`, u32[6][plane_pitch] (16-byte aligned, plane_pitch a multiple
+		of 4 and at least the view's length rounded up to 4); accumulate (V2M_COUNTS_ACCUMULATE) adds to what is there."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		self._check(self._lib.v2m_column_counts_device(self._h, C.byref(rows.struct), N.COUNTS_ACCUMULATE if accumulate else 0, ptr, plane_pitch))
+
 	def bgzf_compress(self, data):
 		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
 		src = bytes(data)

@@ -447,4 +447,19 @@ int64_t v2mh_paf_text(v2m_aln_op const *ops, uint64_t n_ops, char const *t_name,
 	}
 }
 
+// column_counts_text() of output.hh (no GPU), handed over as v2mh_chain_text hands over a chain; -1 with a message in err on failure.
+int64_t v2mh_column_counts_text(uint64_t n_rows, v2m_column_count const *records, uint64_t n_records,
+	uint64_t const *reference_positions, uint64_t const *aligned_positions, uint64_t node_count,
+	char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		std::string const text(vh::column_counts_text(n_rows, records, n_records, reference_positions, aligned_positions, node_count));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
 } // extern "C"

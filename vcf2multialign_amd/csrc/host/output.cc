@@ -1024,6 +1024,124 @@ void output::output_chain_and_paf(variant_graph const &graph, char const *chain_
 }
 
 
+// --- column counts (--output-column-counts) ---------------------------------------------------------------------
+namespace {
+	// One line per record, appended to `text`.  `node` carries the graph position from one record to the next (records ascend; a
+	// record that does not is looked up afresh).
+	void append_column_count_lines(std::string &text, u64 n_rows, v2m_column_count const *records, u64 n_records,
+		u64 const *reference_positions, u64 const *aligned_positions, u64 node_count, u64 &node)
+	{
+		for (u64 i(0); i < n_records; ++i) {
+			v2m_column_count const &rec(records[i]);
+			// the last node n with aligned_positions[n] <= column
+			if (node >= node_count || aligned_positions[node] > rec.column)
+			{
+				u64 const above(u64(std::upper_bound(aligned_positions, aligned_positions + node_count, rec.column) - aligned_positions));
+				node = above ? above - 1 : 0;
+			}
+			while (node + 1 < node_count && aligned_positions[node + 1] <= rec.column) ++node;
+			text += std::to_string(rec.column);
+			text += '\t';
+			bool has_ref(false);
+			if (node + 1 < node_count && aligned_positions[node] <= rec.column) {
+				u64 const k(rec.column - aligned_positions[node]);
+				if (k < reference_positions[node + 1] - reference_positions[node]) {
+					text += std::to_string(reference_positions[node] + k + 1);
+					has_ref = true;
+				}
+			}
+			if (!has_ref) text += '.';   // the REF row has padding there
+			u64 sum(0);
+			for (u32 const c : rec.count) {
+				text += '\t';
+				text += std::to_string(c);
+				sum += c;
+			}
+			text += '\t';
+			text += std::to_string(n_rows - sum);
+			text += '\n';
+		}
+	}
+
+	std::string column_counts_header(u64 n_rows)
+	{
+		return "#rows\t" + std::to_string(n_rows) + "\n#column\tref_pos\tA\tC\tG\tT\tN\tgap\tother\n";
+	}
+
+	struct column_counts_state {
+		std::ostream *stream;
+		u64 n_rows, n_records, n_variable, node;
+		variant_graph const *graph;
+		std::string text;
+		std::exception_ptr error;
+	};
+
+	int column_counts_sink(void *user, v2m_column_count const *records, uint64_t n)
+	{
+		auto &st(*static_cast<column_counts_state *>(user));
+		try {
+			st.text.clear();
+			append_column_count_lines(st.text, st.n_rows, records, n, st.graph->reference_positions.data(), st.graph->aligned_positions.data(), st.graph->node_count(), st.node);
+			st.stream->write(st.text.data(), std::streamsize(st.text.size()));
+			st.n_records += n;
+			for (u64 i(0); i < n; ++i) {   // (variable: none of the seven classes holds every row)
+				u64 sum(0), most(0);
+				for (u32 const c : records[i].count) { sum += c; most = std::max<u64>(most, c); }
+				if (std::max(most, st.n_rows - sum) != st.n_rows) ++st.n_variable;
+			}
+			return st.stream->good() ? 0 : 1;
+		} catch (...) {   // nothing may cross the C boundary
+			st.error = std::current_exception();
+			return 1;
+		}
+	}
+}
+
+
+std::string column_counts_text(u64 n_rows, v2m_column_count const *records, u64 n_records, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count)
+{
+	std::string text(column_counts_header(n_rows));
+	u64 node(0);
+	append_column_count_lines(text, n_rows, records, n_records, reference_positions, aligned_positions, node_count, node);
+	return text;
+}
+
+
+void output::output_column_counts(variant_graph const &graph, std::ostream &stream, bool all_columns, bool verbose)
+{
+	if (!m_more_gpus.empty()) throw std::runtime_error("--output-column-counts needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-column-counts needs every chromosome copy on one GPU context");
+	row_set const rows(a2m_rows(graph));
+	v2m_row_batch batch{};
+	batch.n_rows = rows.copy_index.size();
+	batch.copy_index = rows.copy_index.data();
+	if (rows.any_cuts) {
+		batch.cut_offsets = rows.cut_offsets.data();
+		batch.cut_nodes = rows.cut_nodes.data();
+		batch.cut_copies = rows.cut_copies.data();
+	}
+	std::string const header(column_counts_header(batch.n_rows));
+	stream.write(header.data(), std::streamsize(header.size()));
+	column_counts_state st{&stream, batch.n_rows, 0, 0, 0, &graph, {}, nullptr};
+	int const rc(v2m_column_counts(m_gpu.get(), &batch, all_columns ? 0 : V2M_COUNTS_VARIABLE_ONLY, column_counts_sink, &st));
+	if (st.error) std::rethrow_exception(st.error);
+	m_gpu.check(rc);
+	if (verbose)
+		std::fprintf(stderr, "Column counts: %llu rows, %llu columns, %llu variable.\n", (unsigned long long) batch.n_rows, (unsigned long long) v2m_window_length(m_gpu.get()),
+			(unsigned long long) st.n_variable);
+}
+
+
+void output::output_column_counts(variant_graph const &graph, char const *path, bool all_columns, bool verbose)
+{
+	std::ofstream stream(path, std::ios::binary | std::ios::trunc);
+	if (!stream) throw std::runtime_error(std::string("unable to open ") + path + " for writing");
+	output_column_counts(graph, stream, all_columns, verbose);
+	stream.flush();
+	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+}
+
+
 // --- haplotype_output (haplotype_output.cc:38-132) ------------------------------------------------------------
 output::row_set haplotype_output::rows_for(variant_graph const &graph, char sep, char const *suffix)
 {

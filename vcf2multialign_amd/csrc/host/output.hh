@@ -57,6 +57,15 @@ std::string paf_text(v2m_aln_op const *ops, u64 n_ops, std::string const &t_name
 // Split ops folded back to those of flags = 0: = and X become M, equal neighbours merge.
 std::vector<v2m_aln_op> fold_split_ops(v2m_aln_op const *ops, u64 n_ops);
 
+// The TSV of column counts (include/v2m_hip.h, "column counts"): a pure function of its arguments.
+//   #rows<TAB><n_rows>
+//   #column<TAB>ref_pos<TAB>A<TAB>C<TAB>G<TAB>T<TAB>N<TAB>gap<TAB>other
+//   one line per record: the 0-based aligned column; the 1-based reference position whose byte the REF row holds there -- with n the
+//   last node with aligned_positions[n] <= column and k = column - aligned_positions[n]: reference_positions[n] + k + 1 when
+//   k < reference_positions[n + 1] - reference_positions[n], else `.` (the REF row has padding there) --; the six counts; other =
+//   n_rows minus their sum.
+std::string column_counts_text(u64 n_rows, v2m_column_count const *records, u64 n_records, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -120,6 +129,12 @@ public:
 	// byte for byte those of output_chain().
 	void output_chain_and_paf(variant_graph const &graph, char const *chain_path, char const *paf_path);
 	void output_chain_and_paf(variant_graph const &graph, std::ostream &chain_stream, std::ostream &paf_stream);
+
+	// --output-column-counts: column_counts_text above for the rows of the A2M output (REF first, unless omitted) over the view in force
+	// (--region: the window's columns, reported as absolute), from v2m_column_counts on the first context, which must hold every
+	// copy.  Variable columns only unless all_columns; verbose prints the rows, columns and variable columns to stderr.
+	void output_column_counts(variant_graph const &graph, char const *path, bool all_columns = false, bool verbose = false);
+	void output_column_counts(variant_graph const &graph, std::ostream &stream, bool all_columns = false, bool verbose = false);
 
 protected:
 	struct row_set {

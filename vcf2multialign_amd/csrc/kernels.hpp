@@ -2952,6 +2952,217 @@ __global__ __launch_bounds__(256) void checksum_rows_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
+// Column counts (v2m_column_counts[_device], include/v2m_hip.h "column counts"): per column of the view how many of a slice's spliced
+// rows hold A, C, G, T, N (either case) or '-' there.  counts is u32[kCountClasses][plane_pitch]; class 6, "other", is rows - sum.
+//
+// column_counts_kernel: blockIdx.x = a block of kCountColumns columns, blockIdx.y = a group of rows_per_group rows.  A lane owns the
+// 16-byte chunk `blockIdx.x * 256 + threadIdx.x` of every row of its group (a wave reads 1 KiB contiguous bytes per row) and keeps,
+// per class and 32-bit word of the chunk, four byte-lane counters: the word (folded to lower case for the letters, raw for the
+// gap) XOR the class byte replicated has a zero byte exactly where the row's byte is of the class, zero_bytes_mask >> 7 is a 1 in
+// those byte lanes.  A byte lane holds 255, so after at most kCountRun rows the 24 registers are widened and added to the planes: with
+// atomics when the launch has several row groups (two workgroups then meet on an element; integer adds, so the result is exact and
+// independent of their order; zero addends are skipped, and in most columns five of the six are zero), else with 16-byte
+// read-modify-writes.  Bytes of a row at or beyond `length` (the last chunk's tail: whatever the splice left there) are masked to 0,
+// which is of no class.  Elements at or beyond `length` rounded up to 4 are never touched.  No LDS, no barrier.
+// kStaged: see column_counts_kernel below.
+// ---------------------------------------------------------------------------------------------
+constexpr int kCountClasses = 6;
+constexpr int kCountThreads = 256;
+constexpr u32 kCountColumns = kCountThreads * 16;   // columns per workgroup (4096)
+constexpr u32 kCountRun = 255;                      // rows between two flushes of the byte lanes
+
+__device__ __forceinline__ void column_counts_add(u32 (&acc)[kCountClasses][4], vec4u v, vec4u keep)
+{
+	u32 const x[4] = {v.x & keep.x, v.y & keep.y, v.z & keep.z, v.w & keep.w};
+#pragma unroll
+	for (int w = 0; w < 4; ++w) {
+		u32 const lower = x[w] | 0x20202020u;
+		acc[0][w] += zero_bytes_mask(lower ^ 0x61616161u) >> 7;   // a
+		acc[1][w] += zero_bytes_mask(lower ^ 0x63636363u) >> 7;   // c
+		acc[2][w] += zero_bytes_mask(lower ^ 0x67676767u) >> 7;   // g
+		acc[3][w] += zero_bytes_mask(lower ^ 0x74747474u) >> 7;   // t
+		acc[4][w] += zero_bytes_mask(lower ^ 0x6E6E6E6Eu) >> 7;   // n
+		acc[5][w] += zero_bytes_mask(x[w] ^ 0x2D2D2D2Du) >> 7;    // '-', the raw byte
+	}
+}
+
+// The bytes of the chunk at `column` that lie inside the view, as a mask per word.
+__device__ __forceinline__ vec4u column_counts_keep(u64 left)
+{
+	vec4u keep;
+	keep.x = left >= 4 ? ~0u : (1u << (8 * (u32) left)) - 1u;
+	keep.y = left >= 8 ? ~0u : left <= 4 ? 0u : (1u << (8 * (u32) (left - 4))) - 1u;
+	keep.z = left >= 12 ? ~0u : left <= 8 ? 0u : (1u << (8 * (u32) (left - 8))) - 1u;
+	keep.w = left >= 16 ? ~0u : left <= 12 ? 0u : (1u << (8 * (u32) (left - 12))) - 1u;
+	return keep;
+}
+
+// A lane's byte lanes widened and added to the planes; `left` = length - column.
+__device__ __forceinline__ void column_counts_flush(u32 const (&acc)[kCountClasses][4], u32 *__restrict__ counts, u64 plane_pitch, u64 column, u64 left, u32 use_atomics)
+{
+#pragma unroll
+	for (int c = 0; c < kCountClasses; ++c) {
+		u32 *const plane = counts + (u64) c * plane_pitch + column;
+		if (0 == (acc[c][0] | acc[c][1] | acc[c][2] | acc[c][3])) continue;   // (no row of the run has the class in these 16 columns: N and the gap, mostly)
+#pragma unroll
+		for (int w = 0; w < 4; ++w) {
+			if ((u64) (4 * w) >= left) continue;   // (whole words beyond `length` rounded up to 4 stay as they are)
+			u32 const a = acc[c][w];
+			if (use_atomics) {
+				if (a & 0xFFu) atomicAdd(plane + 4 * w, a & 0xFFu);
+				if (a & 0xFF00u) atomicAdd(plane + 4 * w + 1, (a >> 8) & 0xFFu);
+				if (a & 0xFF0000u) atomicAdd(plane + 4 * w + 2, (a >> 16) & 0xFFu);
+				if (a >> 24) atomicAdd(plane + 4 * w + 3, a >> 24);
+			}
+			else {
+				vec4u sum = *(vec4u const *) (plane + 4 * w);
+				sum.x += a & 0xFFu; sum.y += (a >> 8) & 0xFFu; sum.z += (a >> 16) & 0xFFu; sum.w += a >> 24;
+				*(vec4u *) (plane + 4 * w) = sum;
+			}
+		}
+	}
+}
+
+// kStaged (the staged form: one row group, and the host keeps the rows added since the last widening at kCountRun or fewer): the
+// byte lanes are not flushed but carried from launch to launch in `stage`, vec4u[kCountClasses][stage_chunks] -- a lane's 24 registers
+// as they are, 96 bytes per 16 columns where the planes take 384 -- and widen_column_counts_kernel adds them to the planes.
+template <bool kStaged>
+__global__ __launch_bounds__(kCountThreads) void column_counts_kernel(
+	char const *__restrict__ rows, u64 row_pitch, u32 n_rows, u32 rows_per_group, u64 length,
+	u32 *__restrict__ counts, u64 plane_pitch, u32 use_atomics, vec4u *__restrict__ stage, u64 stage_chunks)
+{
+	u64 const chunk = (u64) blockIdx.x * kCountThreads + threadIdx.x;
+	u64 const column = chunk * 16;
+	if (column >= length) return;
+	u32 const row_begin = blockIdx.y * rows_per_group;
+	u32 const row_end = n_rows - row_begin < rows_per_group ? n_rows : row_begin + rows_per_group;
+	u64 const left = length - column;   // bytes of the chunk inside the view, when fewer than 16
+	vec4u const keep = column_counts_keep(left);
+	char const *const base = rows + column;
+	for (u32 r = row_begin; r < row_end;) {
+		u32 const run_end = row_end - r < kCountRun ? row_end : r + kCountRun;
+		u32 acc[kCountClasses][4] = {};
+		if constexpr (kStaged) {
+#pragma unroll
+			for (int c = 0; c < kCountClasses; ++c) {
+				vec4u const carried = stage[(u64) c * stage_chunks + chunk];
+				acc[c][0] = carried.x; acc[c][1] = carried.y; acc[c][2] = carried.z; acc[c][3] = carried.w;
+			}
+		}
+		for (; r + 4 <= run_end; r += 4) {
+			vec4u const v0 = *(vec4u const *) (base + (u64) r * row_pitch);
+			vec4u const v1 = *(vec4u const *) (base + (u64) (r + 1) * row_pitch);
+			vec4u const v2 = *(vec4u const *) (base + (u64) (r + 2) * row_pitch);
+			vec4u const v3 = *(vec4u const *) (base + (u64) (r + 3) * row_pitch);
+			column_counts_add(acc, v0, keep);
+			column_counts_add(acc, v1, keep);
+			column_counts_add(acc, v2, keep);
+			column_counts_add(acc, v3, keep);
+		}
+		for (; r < run_end; ++r)
+			column_counts_add(acc, *(vec4u const *) (base + (u64) r * row_pitch), keep);
+		if constexpr (kStaged) {
+#pragma unroll
+			for (int c = 0; c < kCountClasses; ++c) {
+				vec4u const carried = {acc[c][0], acc[c][1], acc[c][2], acc[c][3]};
+				stage[(u64) c * stage_chunks + chunk] = carried;
+			}
+			return;   // (the host gives a staged launch at most kCountRun rows)
+		}
+		column_counts_flush(acc, counts, plane_pitch, column, left, use_atomics);
+	}
+}
+
+// The staged byte lanes added to the planes and cleared: a lane a chunk, plain 16-byte read-modify-writes.
+__global__ __launch_bounds__(kCountThreads) void widen_column_counts_kernel(vec4u *__restrict__ stage, u64 stage_chunks, u64 length, u32 *__restrict__ counts, u64 plane_pitch)
+{
+	u64 const chunk = (u64) blockIdx.x * kCountThreads + threadIdx.x;
+	u64 const column = chunk * 16;
+	if (column >= length) return;
+	u32 acc[kCountClasses][4];
+	vec4u const zero = {0, 0, 0, 0};
+#pragma unroll
+	for (int c = 0; c < kCountClasses; ++c) {
+		vec4u const carried = stage[(u64) c * stage_chunks + chunk];
+		acc[c][0] = carried.x; acc[c][1] = carried.y; acc[c][2] = carried.z; acc[c][3] = carried.w;
+		stage[(u64) c * stage_chunks + chunk] = zero;
+	}
+	column_counts_flush(acc, counts, plane_pitch, column, length - column, 0u);
+}
+
+// The column selection of v2m_column_counts over columns [col_begin, col_end) of the view, in blocks of kSelectColumns columns, a lane a
+// column.  A column is selected when variable_only is 0, or when none of the seven classes holds all n_rows rows.
+//   count_variable_columns_kernel   the selected columns of every block; scan_tile_counts_kernel over them as one "row" gives each
+//                                   block's first rank and the total
+//   emit_column_counts_kernel       the selection again; a selected column's record {view_begin + column, its six counts} goes to its
+//                                   rank, when that lies within `capacity`
+constexpr int kSelectColumns = 256;
+
+struct column_count_record { u64 column; u32 count[kCountClasses]; };
+static_assert(sizeof(column_count_record) == 32, "v2m_column_count is 32 bytes");
+
+__device__ __forceinline__ bool column_selected(u32 const *__restrict__ counts, u64 plane_pitch, u64 column, u32 n_rows, u32 variable_only, u32 (&c)[kCountClasses])
+{
+	u32 sum = 0, most = 0;
+#pragma unroll
+	for (int k = 0; k < kCountClasses; ++k) {
+		c[k] = counts[(u64) k * plane_pitch + column];
+		sum += c[k];
+		most = c[k] > most ? c[k] : most;
+	}
+	u32 const other = n_rows - sum;
+	most = other > most ? other : most;
+	return !variable_only || most != n_rows;
+}
+
+__global__ __launch_bounds__(kSelectColumns) void count_variable_columns_kernel(
+	u32 const *__restrict__ counts, u64 plane_pitch, u64 col_begin, u64 col_end, u32 n_rows, u32 variable_only, u32 *__restrict__ block_counts)
+{
+	__shared__ u32 wave_sums[kSelectColumns / 64];
+	V2M_POISON_LDS(wave_sums);
+	int const t = threadIdx.x;
+	u64 const column = col_begin + (u64) blockIdx.x * kSelectColumns + t;
+	u32 c[kCountClasses];
+	u32 mine = column < col_end && column_selected(counts, plane_pitch, column, n_rows, variable_only, c) ? 1u : 0u;
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d, kWave);
+	if ((t & 63) == 0) wave_sums[t >> 6] = mine;
+	__syncthreads();
+	if (0 == t) {
+		u32 total = 0;
+#pragma unroll
+		for (int wv = 0; wv < kSelectColumns / 64; ++wv) total += wave_sums[wv];
+		block_counts[blockIdx.x] = total;
+	}
+}
+
+__global__ __launch_bounds__(kSelectColumns) void emit_column_counts_kernel(
+	u32 const *__restrict__ counts, u64 plane_pitch, u64 col_begin, u64 col_end, u64 view_begin, u32 n_rows, u32 variable_only,
+	u32 const *__restrict__ block_offsets, column_count_record *__restrict__ records, u64 capacity)
+{
+	__shared__ u32 wave_sums[kSelectColumns / 64];
+	V2M_POISON_LDS(wave_sums);
+	int const t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	u64 const column = col_begin + (u64) blockIdx.x * kSelectColumns + t;
+	u32 c[kCountClasses] = {};
+	u32 const mine = column < col_end && column_selected(counts, plane_pitch, column, n_rows, variable_only, c) ? 1u : 0u;
+	u32 const incl = wave_inclusive_scan_u32(mine);
+	if (lane == 63) wave_sums[wave] = incl;
+	__syncthreads();
+	u64 rank = (u64) block_offsets[blockIdx.x] + incl - mine;
+#pragma unroll
+	for (int wv = 0; wv < kSelectColumns / 64; ++wv) if (wv < wave) rank += wave_sums[wv];
+	if (mine && rank < capacity) {
+		u64 const absolute = view_begin + column;
+		vec4u *const dst = (vec4u *) (records + rank);
+		vec4u const head = {(u32) absolute, (u32) (absolute >> 32), c[0], c[1]};
+		vec4u const tail = {c[2], c[3], c[4], c[5]};
+		dst[0] = head;
+		dst[1] = tail;
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
 // Window sets: the scan of scan_tile_counts_kernel segmented at each window's first tile.  From a row's exclusive prefix sums over
 // all tiles of the set (tile_prefix, with the row's total in row_totals): the destination of tile t in the record, slot_offset[k] +
 // the bytes of window k's tiles before t, and the length of every (row, window) piece.  One workgroup per row.

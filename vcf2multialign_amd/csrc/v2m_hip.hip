@@ -181,7 +181,7 @@ struct v2m_ctx {
 
 	// profiling
 	bool profiling{};
-	std::vector<event_pair> events[V2M_KERNEL_END];
+	std::vector<event_pair> events[V2M_KERNEL_LIMIT];
 	std::vector<event_pair> free_events;
 
 	// graph
@@ -258,6 +258,10 @@ struct v2m_ctx {
 	scratch_buf d_ops_info, d_ops_offsets, d_ops_counts, d_ops_base, d_ops_out;
 	pinned_buf h_ops_stage, h_ops_out;
 	std::vector<v2m_aln_op> ops_row;
+	// column counts (v2m_column_counts): the sink form's table, the staged byte lanes of a call whose slices hold few rows, a column
+	// range's block counts and total, its records (two, used in turn) and the total's pinned staging (two likewise)
+	scratch_buf d_column_table, d_column_stage, d_column_blocks, d_column_total, d_column_records[2];
+	pinned_buf h_column_total;
 	// pinned slots: the rows of v2m_splice_rows[_held] (a slot is kept until the sink has released its rows); slots 0 and 1 also stage
 	// the BGZF members and v2m_upload_path_blocks' columns
 	held_ring_state held_state;
@@ -3115,6 +3119,182 @@ int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_ops
 }
 
 
+// ---- column counts ---------------------------------------------------------------------------------
+
+namespace {
+
+// What both column-count calls ask of their arguments, in check_batch's order; `allowed` is the call's one flag.
+int check_column_counts(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, u32 allowed, char const *name)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!rows) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "rows is NULL");
+	if (flags & ~allowed) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s takes 0 or 0x%x as flags (got 0x%x): only the aligned form exists", name, allowed, flags);
+	return check_batch(ctx, rows, 0);
+}
+
+// The rows of a launch of column_counts_kernel are spread over row groups so that a short view under many rows still fills the device: as many groups as
+// bring the launch to about four workgroups per compute unit, of at least kColumnCountsMinRows rows and -- so that a group flushes its byte
+// lanes once -- at most kCountRun.  V2M_COLUMN_COUNTS_ROWS_PER_GROUP overrides (a test knob, read per call: the kernel takes any value).
+constexpr u64 kColumnCountsMinRows = 32;
+
+u64 column_counts_rows_per_group(v2m_ctx const *ctx, u64 n_rows, u64 column_blocks)
+{
+	u64 const forced(env_u64("V2M_COLUMN_COUNTS_ROWS_PER_GROUP", 0));
+	u64 const want_groups((4 * u64(ctx->n_cus) + column_blocks - 1) / column_blocks);
+	u64 const spread(std::min<u64>(v2m::kCountRun, std::max<u64>(kColumnCountsMinRows, (n_rows + want_groups - 1) / want_groups)));
+	return std::max<u64>({1, forced ? forced : spread, (n_rows + 65534) / 65535});   // (the grid's y)
+}
+
+// Adds the counts of the batch's rows over the view in force to the table: the batch in row slices through one device slot, per slice
+// the aligned splice and column_counts_kernel.  Queues only; the caller synchronises.
+// Staged form: when the call takes several slices and a full slice is one row group of at most kCountRun rows -- whole rows of a hundred
+// million columns come five to a slice -- a slice would read and write 24 bytes of table per column for its few bytes of rows.  The
+// kernel then carries its byte lanes from slice to slice in ctx->d_column_stage (6 bytes per column), and widen_column_counts_kernel
+// adds them to the table before the rows since the last widening would exceed kCountRun, and after the last slice.
+// V2M_COLUMN_COUNTS_STAGE=0 turns it off (measurement).
+int column_counts_accumulate(v2m_ctx *ctx, v2m_row_batch const *rows, u32 *d_table, u64 plane_pitch)
+{
+	u64 const L(ctx->view().length());
+	if (0 == L) return V2M_OK;
+	slice_plan const p(plan_slices(ctx, rows->n_rows, false));
+	u64 const column_blocks((L + v2m::kCountColumns - 1) / v2m::kCountColumns), chunks((L + 15) / 16);
+	bool const staged(p.n_slices > 1 && p.rows_per_slice <= v2m::kCountRun && column_counts_rows_per_group(ctx, p.rows_per_slice, column_blocks) >= p.rows_per_slice
+		&& 0 != env_u64("V2M_COLUMN_COUNTS_STAGE", 1));
+	v2m::vec4u *d_stage(nullptr);
+	if (staged) {
+		V2M_HIP_TRY(ctx, ctx->d_column_stage.ensure(V2M_COUNT_CLASSES * chunks * 16));
+		d_stage = ctx->d_column_stage.as<v2m::vec4u>();
+		V2M_HIP_TRY(ctx, hipMemsetAsync(d_stage, 0, V2M_COUNT_CLASSES * chunks * 16, ctx->stream));
+	}
+	auto const widen([&] {
+		hipLaunchKernelGGL(v2m::widen_column_counts_kernel, dim3(unsigned(column_blocks)), dim3(v2m::kCountThreads), 0, ctx->stream, d_stage, chunks, L, d_table, plane_pitch);
+	});
+	u64 staged_rows(0);
+	for (u64 s(0); s < p.n_slices; ++s) {
+		u64 const r0(s * p.rows_per_slice), r1(std::min(rows->n_rows, r0 + p.rows_per_slice)), nr(r1 - r0);
+		V2M_HIP_TRY(ctx, ctx->ring[0].ensure(p.slot_bytes));   // (the slice takes its device slot: refilled in the checked build)
+		char *const d_rows(ctx->ring[0].as<char>());
+		if (int const rc = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch)) return rc;
+		u64 const per_group(staged ? nr : column_counts_rows_per_group(ctx, nr, column_blocks));
+		u64 const groups((nr + per_group - 1) / per_group);
+		{
+			timed_launch tl(ctx, V2M_KERNEL_COLUMN_COUNTS);
+			if (staged && staged_rows + nr > v2m::kCountRun) { widen(); staged_rows = 0; }
+			hipLaunchKernelGGL(staged ? v2m::column_counts_kernel<true> : v2m::column_counts_kernel<false>, dim3(unsigned(column_blocks), unsigned(groups)), dim3(v2m::kCountThreads), 0, ctx->stream,
+				d_rows, p.pitch, u32(nr), u32(std::min<u64>(per_group, nr)), L, d_table, plane_pitch, groups > 1 ? 1u : 0u, d_stage, chunks);
+			staged_rows += nr;
+			if (staged && s + 1 == p.n_slices) widen();
+		}
+		V2M_HIP_TRY(ctx, hipGetLastError());
+	}
+	return V2M_OK;
+}
+
+// Elements [0, (L + 3) & ~3) of every plane to 0.
+int column_counts_zero(v2m_ctx *ctx, u32 *d_table, u64 plane_pitch, u64 L)
+{
+	if (0 == L) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipMemset2DAsync(d_table, plane_pitch * 4, 0, ((L + 3) & ~u64(3)) * 4, V2M_COUNT_CLASSES, ctx->stream));
+	return V2M_OK;
+}
+
+} // namespace
+
+int v2m_column_counts_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, void *d_counts, uint64_t plane_pitch)
+{
+	if (int const rc = check_column_counts(ctx, rows, flags, V2M_COUNTS_ACCUMULATE, "v2m_column_counts_device")) return rc;
+	if (!d_counts) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_counts is NULL");
+	if (reinterpret_cast<uintptr_t>(d_counts) & 15) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_counts must be 16-byte aligned");
+	u64 const L(ctx->view().length());
+	if ((plane_pitch & 3) || plane_pitch < ((L + 3) & ~u64(3)))
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "plane_pitch %llu must be a multiple of 4 and at least %llu", (unsigned long long) plane_pitch, (unsigned long long) ((L + 3) & ~u64(3)));
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	u32 *const table(static_cast<u32 *>(d_counts));
+	int rc(V2M_OK);
+	if (!(flags & V2M_COUNTS_ACCUMULATE)) rc = column_counts_zero(ctx, table, plane_pitch, L);
+	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, table, plane_pitch);
+	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
+	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
+	return rc;
+}
+
+int v2m_column_counts(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_column_counts_sink_fn sink, void *user)
+{
+	if (int const rc = check_column_counts(ctx, rows, flags, V2M_COUNTS_VARIABLE_ONLY, "v2m_column_counts")) return rc;
+	if (!sink) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "sink is NULL");
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	u64 const L(ctx->view().length()), view_begin(ctx->view().begin), n_rows(rows->n_rows);
+	if (0 == L) return V2M_OK;
+	u64 const pitch((L + 3) & ~u64(3));
+	u32 const variable_only((flags & V2M_COUNTS_VARIABLE_ONLY) ? 1u : 0u);
+	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(V2M_COUNT_CLASSES * pitch * 4));
+	u32 *const table(ctx->d_column_table.as<u32>());
+	if (int const rc = column_counts_zero(ctx, table, pitch, L)) return rc;
+
+	// Column ranges whose records fit the block budget even when every column is selected; range k's records go to record buffer and
+	// pinned slot k & 1, and the sink has range k - 1 while range k's kernels run.
+	u64 const range_columns(std::max<u64>(1, std::min<u64>(L, env_u64("V2M_COLUMN_COUNTS_BLOCK_BYTES", u64(64) << 20) / sizeof(v2m_column_count))));
+	u64 const n_ranges((L + range_columns - 1) / range_columns);
+	u64 const range_blocks((range_columns + v2m::kSelectColumns - 1) / v2m::kSelectColumns);
+	struct delivery { u64 n{}; bool pending{}; } deliveries[2];
+	auto const deliver([&](delivery &d, v2m_row_hold &slot) -> int {
+		if (!d.pending) return V2M_OK;
+		d.pending = false;
+		V2M_HIP_TRY(ctx, hipEventSynchronize(slot.copied));
+		if (sink(user, slot.host.as<v2m_column_count>(), d.n)) return fail(ctx, V2M_ERR_SINK, "sink aborted");
+		return V2M_OK;
+	});
+	auto const range([&](u64 k) -> int {
+		u64 const c0(k * range_columns), c1(std::min(L, c0 + range_columns));
+		u32 const blocks(u32((c1 - c0 + v2m::kSelectColumns - 1) / v2m::kSelectColumns));
+		V2M_HIP_TRY(ctx, ctx->d_column_records[k & 1].ensure(range_columns * sizeof(v2m_column_count)));
+		auto *const d_records(ctx->d_column_records[k & 1].as<v2m::column_count_record>());
+		{
+			timed_launch tl(ctx, V2M_KERNEL_COLUMN_SELECT);
+			hipLaunchKernelGGL(v2m::count_variable_columns_kernel, dim3(blocks), dim3(v2m::kSelectColumns), 0, ctx->stream,
+				table, pitch, c0, c1, u32(n_rows), variable_only, ctx->d_column_blocks.as<u32>());
+			hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->d_column_blocks.as<u32>(), blocks, ctx->d_column_total.as<u64>());
+			hipLaunchKernelGGL(v2m::emit_column_counts_kernel, dim3(blocks), dim3(v2m::kSelectColumns), 0, ctx->stream,
+				table, pitch, c0, c1, view_begin, u32(n_rows), variable_only, ctx->d_column_blocks.as<u32>(), d_records, range_columns);
+		}
+		V2M_HIP_TRY(ctx, hipGetLastError());
+		u64 *const h_total(ctx->h_column_total.as<u64>() + (k & 1));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(h_total, ctx->d_column_total.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+		if (k >= 1) if (int const rc = deliver(deliveries[(k - 1) & 1], *ctx->host_slots[(k - 1) & 1])) return rc;
+		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		u64 const n(*h_total);
+		if (n > c1 - c0) return fail(ctx, V2M_ERR_HIP, "the column selection counted %llu of %llu columns", (unsigned long long) n, (unsigned long long) (c1 - c0));
+		if (0 == n) return V2M_OK;
+		v2m_row_hold &slot(*ctx->host_slots[k & 1]);
+		V2M_HIP_TRY(ctx, slot.host.ensure(n * sizeof(v2m_column_count)));
+		V2M_POISON_HOST(slot.host.p, n * sizeof(v2m_column_count));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, d_records, n * sizeof(v2m_column_count), hipMemcpyDeviceToHost, ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
+		deliveries[k & 1].n = n;
+		deliveries[k & 1].pending = true;
+		return V2M_OK;
+	});
+
+	int rc(column_counts_accumulate(ctx, rows, table, pitch));
+	if (V2M_OK == rc) rc = ensure_host_slots(ctx, 2, 0);
+	if (V2M_OK == rc) {
+		hipError_t st(ctx->d_column_blocks.ensure(std::max<u64>(range_blocks * sizeof(u32), 16)));
+		if (hipSuccess == st) st = ctx->d_column_total.ensure(sizeof(u64));
+		if (hipSuccess == st) st = ctx->h_column_total.ensure(2 * sizeof(u64));
+		if (hipSuccess != st) rc = fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "column counts: %s", hipGetErrorString(st));
+	}
+	if (V2M_OK == rc) V2M_POISON_HOST(ctx->h_column_total.p, 2 * sizeof(u64));
+	for (u64 k(0); k < n_ranges && V2M_OK == rc; ++k) rc = range(k);
+	if (V2M_OK == rc) rc = deliver(deliveries[(n_ranges - 1) & 1], *ctx->host_slots[(n_ranges - 1) & 1]);
+	// leave both streams idle whatever happened
+	(void) hipStreamSynchronize(ctx->stream);
+	(void) hipStreamSynchronize(ctx->copy_stream);
+	return rc;
+}
+
+
 // ---- output buffers ------------------------------------------------------------------------------
 
 namespace {
@@ -3789,7 +3969,7 @@ int v2m_profile_reset(v2m_ctx *ctx)
 int v2m_profile_get(v2m_ctx *ctx, int kernel, uint64_t *launches_out, double *total_ms_out)
 {
 	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
-	if (kernel < 0 || kernel >= V2M_KERNEL_END) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown kernel id %d", kernel);
+	if (kernel < 0 || kernel >= V2M_KERNEL_LIMIT) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown kernel id %d", kernel);
 	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	double total(0);
 	for (auto const &e : ctx->events[kernel]) {
@@ -3805,7 +3985,7 @@ int v2m_profile_get(v2m_ctx *ctx, int kernel, uint64_t *launches_out, double *to
 int v2m_profile_get_launches(v2m_ctx *ctx, int kernel, double *ms_out, uint64_t capacity, uint64_t *launches_out)
 {
 	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
-	if (kernel < 0 || kernel >= V2M_KERNEL_END) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown kernel id %d", kernel);
+	if (kernel < 0 || kernel >= V2M_KERNEL_LIMIT) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "unknown kernel id %d", kernel);
 	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	auto const &ev(ctx->events[kernel]);
 	for (u64 i(0); i < ev.size() && i < capacity && ms_out; ++i) {

@@ -7,6 +7,7 @@ import stat
 
 import numpy as np
 
+from . import _native
 from . import build as _build
 
 _u64p = C.POINTER(C.c_uint64)
@@ -71,6 +72,8 @@ def _load():
 		L.v2mh_chain_text.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_paf_text.restype = C.c_int64
 		L.v2mh_paf_text.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_column_counts_text.restype = C.c_int64
+		L.v2mh_column_counts_text.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -116,6 +119,32 @@ def paf_text(ops, t_name, t_size, q_name, q_size):
 		raise ValueError(err.value.decode())
 	dst = C.create_string_buffer(max(1, n))
 	if n != L.v2mh_paf_text(*args, dst, n, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:n]
+
+
+def column_counts_text(n_rows, columns, counts, reference_positions, aligned_positions):
+	"""The host library's column-count formatter (csrc/host/output.cc: column_counts_text; no GPU): the TSV, as bytes, of the records
+	(columns[i], counts[i, 0..6)) of a batch of n_rows rows over the graph whose node arrays are given."""
+	columns = np.ascontiguousarray(columns, dtype=np.uint64).reshape(-1)
+	counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1, 6)
+	if columns.shape[0] != counts.shape[0]:
+		raise ValueError("columns and counts differ in length")
+	records = np.zeros(columns.shape[0], dtype=np.dtype(_native.COLUMN_COUNT_DTYPE))
+	records["column"] = columns
+	records["count"] = counts
+	ref = np.ascontiguousarray(reference_positions, dtype=np.uint64)
+	aln = np.ascontiguousarray(aligned_positions, dtype=np.uint64)
+	if ref.shape != aln.shape:
+		raise ValueError("reference_positions and aligned_positions differ in length")
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (int(n_rows), records.ctypes.data if records.size else None, records.shape[0], ref.ctypes.data if ref.size else None, aln.ctypes.data if aln.size else None, ref.shape[0])
+	n = L.v2mh_column_counts_text(*args, None, 0, err, len(err))
+	if n < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, n))
+	if n != L.v2mh_column_counts_text(*args, dst, n, err, len(err)):
 		raise ValueError(err.value.decode())
 	return dst.raw[:n]
 

@@ -61,6 +61,20 @@ class Output:
 			written += 1 if text else 0
 		return written
 
+	def _write_column_counts(self, stream, rows, graph, all_columns):
+		"""--output-column-counts: the TSV of host.column_counts_text for `rows` (those of output_a2m) from Context.column_counts, over the
+		region's columns when there is one (reported as absolute); variable columns only unless all_columns.  Returns the number of lines."""
+		from . import host
+		if self.region is not None:
+			self.ctx.set_column_window(*columns_of_reference_range(graph.reference_positions, graph.aligned_positions, *self.region))
+		try:
+			columns, counts = self.ctx.column_counts(RowBatch(rows), variable_only=not all_columns)
+		finally:
+			if self.region is not None:
+				self.ctx.set_column_window(0, self.ctx.aligned_length)
+		stream.write(host.column_counts_text(len(rows), columns, counts, graph.reference_positions, graph.aligned_positions))
+		return len(columns)
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -101,6 +115,14 @@ class HaplotypeOutput(Output):
 		self._write_rows(stream, ids, rows, graph)
 		return len(rows)
 
+	def output_column_counts(self, graph, stream, all_columns=False):
+		"""--output-column-counts for the rows of output_a2m (REF first, unless omitted)."""
+		rows = [PLOIDY_MAX] if self.should_output_reference else []
+		for sample_idx in range(len(graph.sample_names)):
+			for chr_copy_idx in range(graph.sample_ploidy(sample_idx)):
+				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
+		return self._write_column_counts(stream, rows, graph, all_columns)
+
 	def output_chain(self, graph, stream):
 		"""--output-chain: the chains of the rows of output_a2m (without REF), named as one file per sequence would be."""
 		names, rows = [], []
@@ -137,6 +159,16 @@ class FounderSequenceGreedyOutput(Output):
 			rows.append(list(zip(cut_positions[:-1], col)))               # delegate: switch copy at each cut node (:106-114)
 		self._write_rows(stream, ids, rows, graph)
 		return len(rows)
+
+	def output_column_counts(self, graph, cut_positions, assigned_samples_column_major, stream, all_columns=False):
+		"""--output-column-counts for the rows of output_a2m (REF first, unless omitted, then the founder rows)."""
+		n_rows = len(cut_positions) - 1
+		n_founders = len(assigned_samples_column_major) // n_rows if n_rows else 0
+		rows = [PLOIDY_MAX] if self.should_output_reference else []
+		for col_idx in range(n_founders):
+			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
+			rows.append(list(zip(cut_positions[:-1], col)))
+		return self._write_column_counts(stream, rows, graph, all_columns)
 
 	def output_chain(self, graph, cut_positions, assigned_samples_column_major, stream):
 		"""--output-chain for the founder rows of output_a2m."""

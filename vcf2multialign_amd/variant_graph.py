@@ -48,6 +48,19 @@ class VariantGraph:
 		"""The column window [col(s), col(e)) of the 0-based half-open reference range [s, e) (see columns_of_reference_range)."""
 		return columns_of_reference_range(self.reference_positions, self.aligned_positions, s, e)
 
+	def reference_position_of_column(self, column):
+		"""The 1-based reference position whose byte the REF row holds at aligned column `column`, or None where it holds padding (or
+		the column lies outside the row): with n the last node with aligned_positions[n] <= column and k = column - aligned_positions[n],
+		reference_positions[n] + k + 1 when k < reference_positions[n + 1] - reference_positions[n] (csrc/host/output.cc: column_counts_text)."""
+		column = int(column)
+		n = int(np.searchsorted(self.aligned_positions, np.uint64(column), side="right")) - 1 if column >= 0 else -1
+		if n < 0 or n + 1 >= self.node_count:
+			return None
+		k = column - int(self.aligned_positions[n])
+		if k < int(self.reference_positions[n + 1]) - int(self.reference_positions[n]):
+			return int(self.reference_positions[n]) + k + 1
+		return None
+
 	# variant_graph.hh:73-74
 	def sample_ploidy(self, sample_idx):
 		return int(self.ploidy_csum[sample_idx + 1]) - int(self.ploidy_csum[sample_idx])
