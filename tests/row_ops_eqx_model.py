@@ -7,7 +7,8 @@ them.  TEST INFRASTRUCTURE ONLY.
   paf_text            the PAF line of a row, written from the PAF specification (the twelve mandatory columns, NM:i: and cg:Z: as minimap2
                       --eqx -c writes them);
   the eqx graphs      seam_graphs.Builder graphs whose bytes are then chosen (retouch(): '=' or 'X' per label byte, or literal bytes on both
-                      sides), which put '=' / 'X' runs at the ops kernels' seams, and reach(), which recomputes from the model what each places."""
+                      sides), which put '=' / 'X' runs at the ops kernels' seams, and reach(), which recomputes from the model what each places;
+  the scan graphs     row_ops_model's scan graphs retouched, and scan_reach() over the split classes."""
 
 import functools
 
@@ -419,6 +420,47 @@ def reach(sg, rows=None):
 				if np.any(cls[lo:hi] == CLS_X):
 					out.add("X_in_edge_from_the_crossing_list")
 	return out
+
+
+# ---- the scan graphs -------------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def scan_graph(which):
+	"""The scan graphs of row_ops_model.py (0: scan_waves, 1 and 2: scan_block_0 and _1) with the bytes of their substitution sites chosen:
+	every byte of the runs across the seams and of the one-byte sites either side of the skipped stretches differs from the reference
+	(X), and the M columns of the dense tiles alternate between '=' and X."""
+	sg = M.scan_graphs()[which]
+	return retouch(sg, sg.name + "_eqx", sg.notes["eqx_plan"])
+
+
+def scan_graphs():
+	return [scan_graph(i) for i in range(len(M.scan_graphs()))]
+
+
+def scan_reach(sg, rows=None):
+	"""row_ops_model.scan_reach over the split classes."""
+	T = sgs.kernel_constants().kTileBytes
+	n_tiles = -(-sg.length // T)
+	out = set()
+	for row in (sg.rows if rows is None else rows):
+		cls = np.zeros(n_tiles * T, dtype=np.uint8)
+		cls[:sg.length] = seam_classes(sg, row)
+		M.scan_reach_classes(cls, T, "_DI=___X", out)
+		if len(seam_ops(sg, row)[0]) > 65535:
+			out.add("row_with_more_than_65535_ops")
+	return out
+
+
+SCAN_REACHED_BY = {
+	"scan_waves_eqx": {"wave_seam_merge_=", "wave_seam_merge_X", "wave_seam_merge_D", "wave_seam_break", "block_seam_merge_=", "block_seam_merge_X", "block_seam_merge_D",
+		"block_seam_break", "skipped_wave_equal", "skipped_wave_different", "carried_D_through_skipped_wave", "carried_X_through_skipped_wave", "D_skipped_wave_M",
+		"skipped_from_lane_0", "skipped_up_to_lane_63", "dense_tile_last_of_wave", "dense_tile_first_of_wave", "dense_tile_last_of_block", "dense_tile_first_of_block",
+		"row_with_more_than_65535_ops", "empty_tile_count_at_wave_seam"},
+	"scan_block_0_eqx": {"skipped_block_equal", "skipped_block_different", "carried_D_through_skipped_block", "carried_X_through_skipped_block", "D_skipped_block_M",
+		"wave_seam_merge_I", "empty_tile_count_at_block_seam"},
+	"scan_block_1_eqx": {"skipped_block_equal", "skipped_block_different", "skipped_block_into_later_wave", "carried_D_through_skipped_block",
+		"carried_X_through_skipped_block", "D_skipped_block_M", "wave_seam_merge_I", "block_seam_merge_I", "empty_tile_count_at_block_seam", "empty_tile_count_at_wave_seam"},
+}
 
 
 REACHED_BY = {

@@ -8,7 +8,9 @@
                       to a million nodes; their bytes are ACGT / acgt, so padding is exactly the '-' columns of the model's rows);
   chain_text          the UCSC chain of a row, written from the format's description;
   the ops graphs      hand-made graphs (seam_graphs.Builder) that put runs, breakpoints and skipped stretches at the ops kernels' seams, and
-                      reach(), which recomputes from the masks -- with the constants of csrc/kernels.hpp -- what each graph is meant to place."""
+                      reach(), which recomputes from the masks -- with the constants of csrc/kernels.hpp -- what each graph is meant to place;
+  the scan graphs     graphs of 513 to 578 tiles that put runs, dense tiles and all-skipped stretches at the seams of the one-workgroup scan
+                      kernels (a scan wave is 64 tiles, a scan block 256), and scan_reach(), reach()'s vectorised counterpart for them."""
 
 import functools
 
@@ -393,6 +395,206 @@ def reach(sg, rows=None):
 			if np.all(tile[tile != 0] == 2) and tile_live.size and t > 0 and not empty[t]:
 				out.add("tile_is_one_I_run")
 	return out
+
+
+# ---- graphs for the scan kernels' seams --------------------------------------------------------------------------------------------------
+# scan_row_ops_kernel, scan_row_ops_eqx_kernel and scan_tile_counts_kernel walk a row's tiles in rounds of 256, one tile per thread: tile i is
+# lane i % 64 of scan wave (i % 256) / 64 of scan block i / 256.  The graphs below put runs, dense tiles and all-skipped stretches at those
+# seams.  Their substitution sites make no difference to the unsplit ops; row_ops_eqx_model.scan_graph() gives the same graphs with the
+# bytes of those sites chosen (notes["eqx_plan"]), so that one Builder layout serves both class sets.
+
+SCAN_WAVE, SCAN_BLOCK = 64, 256          # tiles per scan wave and per scan block (a round of the scan kernels)
+
+
+def _seam_site(b, column, n=40):
+	"""n reference bytes, half of them either side of `column`, under two edges: a label of one byte (the row is M, then a D run across
+	the column) and one of n bytes (M all along; an X run once row_ops_eqx_model has chosen its bytes)."""
+	b.ref_to(column - n // 2)
+	return b.add_site([1, n], n, n)
+
+
+def _stretch(b, first_tile, end_column, T, insertion=True, back=5, ahead=5):
+	"""An all-padding stretch from column 0 of first_tile to end_column: the reference byte on the last column of the tile before it, padding
+	up to end_column, a one-column substitution site there.  Edges, by name: DD a deletion from `back` columns before the stretch to `ahead`
+	columns after it (D ... skipped ... D); DM one that ends on the first column after it (D ... skipped ... M); ins an insertion that fills
+	the stretch (an I run through every tile of it); sub / after one-byte labels on the reference byte before and on the one after."""
+	begin = first_tile * T - 1
+	b.ref_to(begin - back)
+	b.add_ref(back)
+	e = {"DD": b.edge(begin - back, end_column + ahead, 0), "DM": b.edge(begin - back, end_column, 0)}
+	span = end_column - begin
+	got = b.add_site([span, 1] if insertion else [1], span)
+	e["sub"] = got[-1]
+	if insertion:
+		e["ins"] = got[0]
+	e["after"] = b.add_site([1], 1, 1)[0]
+	b.add_ref(ahead + 3)
+	return e
+
+
+@functools.lru_cache(maxsize=None)
+def scan_wave_graph():
+	"""513 tiles and a few columns, every scan block live:
+	  tiles 63, 64, 255, 256     every column a breakpoint (M I M I ...): the last and first tile of a scan wave and of a scan block;
+	  127|128 and 511|512        a D run and a substituted run across a wave seam and across a block seam;
+	  tiles 192 ... 196 (+ 100 columns)  all padding: a skipped stretch that begins at lane 0 of a wave and ends inside it;
+	  tiles 320 ... 383          all padding: one whole scan wave, from its lane 0 to its lane 63, with live waves before and after it in the block.
+	Copies: 0 every dense tile (65 536 ops from them), the insertion over the skipped wave, the substituted runs; 1 dense tiles 63 and 256, D
+	either side of the skipped wave, the D runs across the seams; 2 dense tiles 64 and 255, D before the skipped wave and M after it; 3 - 5 the
+	one-byte substitutions either side of the skipped wave: both, the later, the earlier; 6 those either side of the shorter stretch."""
+	K = sgs.kernel_constants()
+	T = K.kTileBytes
+	b = sgs.Builder(9600)
+	dense = {}
+	b.ref_to(63 * T)
+	dense[63] = b.add_sites(T // 2, 2, 1, 2)
+	dense[64] = b.add_sites(T // 2, 2, 1, 2)
+	b.add_ref(9)
+	dw, xw = _seam_site(b, 128 * T)
+	s2 = _stretch(b, 192, 197 * T + 100, T, insertion=False)
+	b.ref_to(255 * T)
+	dense[255] = b.add_sites(T // 2, 2, 1, 2)
+	dense[256] = b.add_sites(T // 2, 2, 1, 2)
+	b.add_ref(9)
+	s1 = _stretch(b, 320, 384 * T, T)
+	db, xb = _seam_site(b, 512 * T)
+	b.add_ref(700)
+	all_of = lambda t: list(range(dense[t], dense[t] + T // 2))
+	copies = [
+		all_of(63) + all_of(64) + [xw] + all_of(255) + all_of(256) + [s1["ins"], xb],
+		all_of(63) + [dw] + all_of(256) + [s1["DD"], db],
+		all_of(64) + all_of(255) + [s1["DM"]],
+		[s1["sub"], s1["after"]],
+		[s1["after"]],
+		[s1["sub"], dw],
+		[s2["sub"], s2["after"], xb],
+	]
+	sg = b.finish([sorted(c) for c in copies], "scan_waves")
+	x_edges = [xw, xb, s1["sub"], s1["after"], s2["sub"], s2["after"]]
+	plan = {e: "X" * int(sg.label_len[e]) for e in x_edges}
+	for t in dense:                                       # the M columns of the dense tiles: = X = X ...
+		plan.update({e: "=X"[(e - dense[t]) & 1] for e in all_of(t)})
+	sg.notes.update(dense=dense, stretches={"wave": s1, "lane_0": s2}, seams={"wave": (dw, xw), "block": (db, xb)}, eqx_plan=plan, skipped=[(192, 197), (320, 384)])
+	sg.notes["windows"] = [
+		("begins_in_skipped_wave", 330 * T + 77, 420 * T + 5),                  # the window's first 53 tiles hold no byte
+		("empty_then_full_at_its_tile_256", 128 * T, 400 * T),                   # its tiles 192 ... 255 are the skipped wave, its tile 256 is full
+	]
+	return sg
+
+
+@functools.lru_cache(maxsize=None)
+def scan_block_graph(extra_waves):
+	"""Scan block 0 live, then all padding from tile 256 on: one whole scan block (extra_waves = 0: the first live tile is tile 512, lane 0 of
+	wave 0 of the next block) or a scan block and the first wave of the next (extra_waves = 1: tile 576, in wave 1, which gets its carry past a
+	zero entry of its own block).  Copies: 0 the insertion over the stretch (an I run across three wave seams and, with extra_waves, the block
+	seam 511|512); 1 D either side; 2 D before and M after; 3 - 5 the one-byte substitutions either side: both, the later, the earlier."""
+	K = sgs.kernel_constants()
+	T = K.kTileBytes
+	b = sgs.Builder(9610 + extra_waves)
+	s = _stretch(b, SCAN_BLOCK, (2 * SCAN_BLOCK + extra_waves * SCAN_WAVE) * T, T)
+	b.add_ref(T + 300)                                      # the first tile after the stretch is full
+	sg = b.finish([[s["ins"]], [s["DD"]], [s["DM"]], [s["sub"], s["after"]], [s["after"]], [s["sub"]]], "scan_block_%d" % extra_waves)
+	sg.notes.update(stretches={"block": s}, eqx_plan={s["sub"]: "X", s["after"]: "X"}, skipped=[(SCAN_BLOCK, 2 * SCAN_BLOCK + extra_waves * SCAN_WAVE)])
+	sg.notes["windows"] = [
+		("begins_in_skipped_block", 300 * T + 123, sg.length),
+		("empty_then_full_at_its_tile_256", (SCAN_BLOCK + extra_waves * SCAN_WAVE) * T, sg.length),      # every tile of it up to 255 is empty
+	]
+	return sg
+
+
+def scan_graphs():
+	return [scan_wave_graph(), scan_block_graph(0), scan_block_graph(1)]
+
+
+def tile_ends(cls, n_tiles, T):
+	"""Per tile the first and the last non-zero class (0: the tile is all skipped), and the last non-zero class at or before each tile's
+	end (0: none yet): the carry the scan hands to the next tile."""
+	per_tile = cls.reshape(n_tiles, T)
+	mask = per_tile != 0
+	live = mask.any(axis=1)
+	rows = np.arange(n_tiles)
+	first = np.where(live, per_tile[rows, mask.argmax(axis=1)], 0)
+	last = np.where(live, per_tile[rows, T - 1 - mask[:, ::-1].argmax(axis=1)], 0)
+	at = np.maximum.accumulate(np.where(live, rows, -1))
+	carried = np.where(at >= 0, last[np.maximum(at, 0)], 0)
+	return first, last, carried, live, per_tile
+
+
+def scan_reach_classes(cls, T, names, out):
+	"""What one row's classes (0 = skipped; padded to whole tiles) place at the scan kernels' seams.  names: class code -> letter."""
+	n_tiles = cls.size // T
+	first, last, carried, live, per_tile = tile_ends(cls, n_tiles, T)
+	bytes_in = (per_tile >= 2).sum(axis=1)                    # the row's bytes: classes with the row bit (2, 3, 7)
+	for t in range(SCAN_WAVE, n_tiles, SCAN_WAVE):
+		where = "block" if 0 == t % SCAN_BLOCK else "wave"
+		if live[t - 1] and live[t]:
+			out.add("%s_seam_merge_%s" % (where, names[int(first[t])]) if last[t - 1] == first[t] else "%s_seam_break" % where)
+		if (0 == bytes_in[t - 1] and T == bytes_in[t]) or (T == bytes_in[t - 1] and 0 == bytes_in[t]):
+			out.add("empty_tile_count_at_%s_seam" % where)
+	# a dense tile: no column skipped, every column's class differs from the one before it
+	for t in np.flatnonzero(per_tile.all(axis=1) & (per_tile[:, 1:] != per_tile[:, :-1]).all(axis=1)).tolist():
+		for name, hit in (("dense_tile_last_of_wave", t % SCAN_WAVE == SCAN_WAVE - 1 and t % SCAN_BLOCK != SCAN_BLOCK - 1), ("dense_tile_first_of_wave", t % SCAN_WAVE == 0 and t % SCAN_BLOCK != 0),
+				("dense_tile_last_of_block", t % SCAN_BLOCK == SCAN_BLOCK - 1), ("dense_tile_first_of_block", t % SCAN_BLOCK == 0 and t > 0)):
+			if hit:
+				out.add(name)
+	# maximal runs of all-skipped tiles with live tiles either side
+	edges = np.flatnonzero(np.diff(np.r_[True, live, True].astype(np.int8)))
+	for a, z in zip(edges[0::2].tolist(), edges[1::2].tolist()):          # tiles [a, z) are skipped
+		if 0 == a or z >= n_tiles:
+			continue
+		before, after = int(carried[a - 1]), int(first[z])
+		same = "equal" if before == after else "different"
+		w0, w1 = -(-a // SCAN_WAVE), z // SCAN_WAVE                          # whole scan waves [w0, w1) lie inside
+		whole_blocks = [k for k in range(-(-a // SCAN_BLOCK), z // SCAN_BLOCK)]
+		for w in range(w0, w1):
+			blk = w // 4
+			if live[blk * SCAN_BLOCK:w * SCAN_WAVE].any() and live[(w + 1) * SCAN_WAVE:(blk + 1) * SCAN_BLOCK].any():
+				out.add("skipped_wave_" + same)
+				if before == after and names[before] in "DX":
+					out.add("carried_%s_through_skipped_wave" % names[before])
+				if names[before] == "D" and names[after] in "M=":
+					out.add("D_skipped_wave_M")
+		if whole_blocks:
+			out.add("skipped_block_" + same)
+			if before == after and names[before] in "DX":
+				out.add("carried_%s_through_skipped_block" % names[before])
+			if names[before] == "D" and names[after] in "M=":
+				out.add("D_skipped_block_M")
+			if z // SCAN_BLOCK == whole_blocks[-1] + 1 and z % SCAN_BLOCK >= SCAN_WAVE:
+				out.add("skipped_block_into_later_wave")
+		if 0 == a % SCAN_WAVE and z % SCAN_WAVE and z // SCAN_WAVE == a // SCAN_WAVE:
+			out.add("skipped_from_lane_0")                                   # the first live tile of the wave has no live lane before it
+		if 0 == z % SCAN_WAVE and z % SCAN_BLOCK:
+			out.add("skipped_up_to_lane_63")                                 # lane 0 of the next wave looks at the waves before it
+	return out
+
+
+def scan_reach(sg, rows=None):
+	"""What the rows of a scan graph place, recomputed from the masks: a set of names.  Vectorised per row (reach() slices per tile and row,
+	which takes minutes on graphs of 600 tiles)."""
+	T = sgs.kernel_constants().kTileBytes
+	n_tiles = -(-sg.length // T)
+	out = set()
+	for row in (sg.rows if rows is None else rows):
+		ref_is_base, row_is_base = seam_masks(sg, row)
+		cls = np.zeros(n_tiles * T, dtype=np.uint8)
+		cls[:sg.length] = classes(ref_is_base, row_is_base)
+		scan_reach_classes(cls, T, "_DIM", out)
+		if len(seam_ops(sg, row)[0]) > 65535:
+			out.add("row_with_more_than_65535_ops")
+	return out
+
+
+SCAN_REACHED_BY = {
+	"scan_waves": {"wave_seam_merge_M", "wave_seam_merge_D", "wave_seam_break", "block_seam_merge_M", "block_seam_merge_D", "block_seam_break",
+		"skipped_wave_equal", "skipped_wave_different", "carried_D_through_skipped_wave", "D_skipped_wave_M", "skipped_from_lane_0", "skipped_up_to_lane_63",
+		"dense_tile_last_of_wave", "dense_tile_first_of_wave", "dense_tile_last_of_block", "dense_tile_first_of_block", "row_with_more_than_65535_ops",
+		"empty_tile_count_at_wave_seam"},
+	"scan_block_0": {"skipped_block_equal", "skipped_block_different", "carried_D_through_skipped_block", "D_skipped_block_M", "wave_seam_merge_I",
+		"empty_tile_count_at_block_seam"},
+	"scan_block_1": {"skipped_block_equal", "skipped_block_different", "skipped_block_into_later_wave", "carried_D_through_skipped_block", "D_skipped_block_M",
+		"wave_seam_merge_I", "block_seam_merge_I", "empty_tile_count_at_block_seam", "empty_tile_count_at_wave_seam"},
+}
 
 
 REACHED_BY = {

@@ -70,6 +70,63 @@ def test_what_the_graphs_mean_in_ops():
 	assert E.seam_ops(long, 0)[0][1::2].tolist() == [[E.OP_X, 1]] * 3
 
 
+# what the scan graphs have to place between them under the split, by the names of scan_reach()
+SCAN_WANTED = {
+	"wave_seam_merge_=", "wave_seam_merge_X", "wave_seam_merge_I", "wave_seam_merge_D", "wave_seam_break",
+	"block_seam_merge_=", "block_seam_merge_X", "block_seam_merge_I", "block_seam_merge_D", "block_seam_break",
+	"skipped_wave_equal", "skipped_wave_different", "skipped_block_equal", "skipped_block_different", "skipped_block_into_later_wave",
+	"skipped_from_lane_0", "skipped_up_to_lane_63",
+	"carried_D_through_skipped_wave", "carried_D_through_skipped_block", "carried_X_through_skipped_wave", "carried_X_through_skipped_block",
+	"D_skipped_wave_M", "D_skipped_block_M",
+	"dense_tile_last_of_wave", "dense_tile_first_of_wave", "dense_tile_last_of_block", "dense_tile_first_of_block", "row_with_more_than_65535_ops",
+	"empty_tile_count_at_wave_seam", "empty_tile_count_at_block_seam",
+}
+
+
+def test_the_scan_graphs_place_what_they_are_meant_to_under_the_split():
+	K = sgs.kernel_constants()
+	T = K.kTileBytes
+	union = set()
+	for sg, plain in zip(E.scan_graphs(), M.scan_graphs()):
+		got = E.scan_reach(sg)
+		assert E.SCAN_REACHED_BY[sg.name] <= got, (sg.name, sorted(E.SCAN_REACHED_BY[sg.name] - got))
+		union |= E.SCAN_REACHED_BY[sg.name]
+		assert 513 <= -(-sg.length // T) <= 640 and len(sg.rows) <= 8
+		R = int(sg.kept.sum())
+		for row in sg.rows:
+			ops, length = E.seam_ops(sg, row)
+			E.check_invariants(ops, R, length, is_ref_row=row == PLOIDY_MAX)
+			assert np.array_equal(E.fold(ops), M.seam_ops(sg, row)[0]) and np.array_equal(E.fold(ops), M.seam_ops(plain, row)[0]), (sg.name, row)
+	assert SCAN_WANTED <= union, sorted(SCAN_WANTED - union)
+	# the unsplit model of the retouched graph's arrays is the walk's
+	sg = E.scan_graph(2)
+	for row in (0, 3):
+		assert np.array_equal(E.model_ops(sg.g, row)[0], E.seam_ops(sg, row)[0])
+
+
+def test_what_the_scan_graphs_mean_in_split_ops():
+	"""Written down by hand: X ... a skipped block (and a wave) ... X is one X op of length 2."""
+	T = sgs.kernel_constants().kTileBytes
+	eq, x, d = E.OP_EQ, E.OP_X, E.OP_D
+	for which, extra in ((1, 0), (2, 1)):
+		sg = E.scan_graph(which)
+		R = 256 * T + 1 + 8 + T + 300
+		assert int(sg.kept.sum()) == R
+		assert E.seam_ops(sg, PLOIDY_MAX)[0].tolist() == [[eq, R]]
+		assert E.seam_ops(sg, 1)[0].tolist() == [[eq, 256 * T - 6], [d, 11], [eq, R - 256 * T - 5]]          # D ... skipped ... D
+		assert E.seam_ops(sg, 2)[0].tolist() == [[eq, 256 * T - 6], [d, 6], [eq, R - 256 * T]]               # D ... skipped ... =
+		assert E.seam_ops(sg, 3)[0].tolist() == [[eq, 256 * T - 1], [x, 2], [eq, T + 308]]                   # X ... skipped ... X
+		assert E.seam_ops(sg, 4)[0].tolist() == [[eq, 256 * T], [x, 1], [eq, T + 308]]                       # = ... skipped ... X
+		assert E.seam_ops(sg, 5)[0].tolist() == [[eq, 256 * T - 1], [x, 1], [eq, T + 309]]                   # X ... skipped ... =
+	sg = E.scan_graph(0)
+	ops = E.seam_ops(sg, 0)[0]
+	assert len(ops) > 65535 and ops[:5, 0].tolist() == [eq, E.OP_I, x, E.OP_I, eq]                       # the dense tiles: = I X I = I ...
+	ops = E.seam_ops(sg, 3)[0]                                                                        # X ... a skipped wave ... X
+	assert ops[:, 0].tolist() == [eq, x, eq] and ops[1, 1] == 2
+	ops = E.seam_ops(sg, 6)[0]                                                                        # X ... skipped from lane 0 ... X, then the X run across 511|512
+	assert ops.tolist()[1:] == [[x, 2], [eq, ops[2, 1]], [x, 40], [eq, 700]]
+
+
 def all_seam_graphs():
 	return E.eqx_graphs() + M.ops_seam_graphs()
 

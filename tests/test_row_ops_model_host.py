@@ -1,5 +1,5 @@
 """The model of the row alignment ops (tests/row_ops_model.py) against the oracle, the host library's chain formatter against the model's, and
-what the ops seam graphs place.  No GPU."""
+what the ops seam graphs and the scan graphs place.  No GPU."""
 
 import json
 import os
@@ -87,6 +87,101 @@ def test_the_ops_graphs_place_what_they_are_meant_to():
 		rows = M.many_rows(M.boundary_graph(), n)
 		assert len(rows) == n and rows.count(PLOIDY_MAX) >= 4 and len(set(rows)) == 5
 	assert (K.kGroupRowsLds + 1, 2 * K.kGroupRowsLds + 1) == (17, 33)
+
+
+# ---- the scan graphs -----------------------------------------------------------------------------------------------------------------
+
+# what the graphs for the scan kernels' seams have to place between them, by the names of scan_reach()
+SCAN_WANTED = {
+	"wave_seam_merge_M", "wave_seam_merge_I", "wave_seam_merge_D", "wave_seam_break", "block_seam_merge_M", "block_seam_merge_I", "block_seam_merge_D", "block_seam_break",
+	"skipped_wave_equal", "skipped_wave_different", "skipped_block_equal", "skipped_block_different", "skipped_block_into_later_wave",
+	"skipped_from_lane_0", "skipped_up_to_lane_63",
+	"carried_D_through_skipped_wave", "carried_D_through_skipped_block", "D_skipped_wave_M", "D_skipped_block_M",
+	"dense_tile_last_of_wave", "dense_tile_first_of_wave", "dense_tile_last_of_block", "dense_tile_first_of_block", "row_with_more_than_65535_ops",
+	"empty_tile_count_at_wave_seam", "empty_tile_count_at_block_seam",
+}
+
+
+def test_scan_reach_on_hand_made_classes():
+	"""scan_reach_classes on class rows written out here: a tile is 4 columns, so tile i is columns [4 i, 4 i + 4)."""
+	def row(*pieces):
+		cls = np.zeros(4 * 600, dtype=np.uint8)
+		for first_tile, codes in pieces:
+			cls[4 * first_tile:4 * first_tile + len(codes)] = codes
+		return cls
+	live = [3] * (4 * 600)
+	assert M.scan_reach_classes(row((0, live)), 4, "_DIM", set()) == {"wave_seam_merge_M", "block_seam_merge_M"}
+	# tiles 64 ... 127 skipped, D before and D after: one whole wave of block 0, from lane 0 to lane 63
+	got = M.scan_reach_classes(row((0, [3] * 255 + [1]), (128, [1, 3] + [3] * 400)), 4, "_DIM", set())
+	assert {"skipped_wave_equal", "carried_D_through_skipped_wave", "skipped_up_to_lane_63"} <= got and "skipped_wave_different" not in got and "skipped_from_lane_0" not in got
+	# tiles 63 ... 127 skipped, M before and I after: wave 1 is skipped whole, and no live tile stands at either side of the seam 63|64
+	got = M.scan_reach_classes(row((0, [3] * 252), (128, [2] * 8)), 4, "_DIM", set())
+	assert "skipped_wave_different" in got and "wave_seam_break" not in got
+	# tiles 0 ... 63 live, 64 ... 255 skipped: no live tile after wave 1 in block 0
+	got = M.scan_reach_classes(row((0, [3] * 256), (256, [3] * 8)), 4, "_DIM", set())
+	assert not {"skipped_wave_equal", "skipped_block_equal"} & got
+	# block 1 skipped, tile 512 live; then with wave 0 of block 2 as well
+	got = M.scan_reach_classes(row((0, [3] * 1024), (512, [3] * 8)), 4, "_DIM", set())
+	assert "skipped_block_equal" in got and "skipped_block_into_later_wave" not in got and "empty_tile_count_at_block_seam" in got
+	got = M.scan_reach_classes(row((0, [3] * 1023 + [1]), (576, [3] * 8)), 4, "_DIM", set())
+	assert {"skipped_block_different", "skipped_block_into_later_wave", "D_skipped_block_M", "empty_tile_count_at_wave_seam"} <= got and "skipped_block_equal" not in got
+	# tiles 192 ... 196 skipped: from lane 0 of wave 3, which has live lanes after them
+	got = M.scan_reach_classes(row((0, [3] * 768), (197, [3] * 40)), 4, "_DIM", set())
+	assert "skipped_from_lane_0" in got and "skipped_wave_equal" not in got
+	# dense tiles 63 and 256: M I D M | ... ; tile 64 with a skipped column is not dense
+	got = M.scan_reach_classes(row((0, live), (63, [3, 2, 1, 3]), (64, [2, 0, 2, 3]), (256, [2, 3, 2, 3])), 4, "_DIM", set())
+	assert {"dense_tile_last_of_wave", "dense_tile_first_of_block"} <= got and not {"dense_tile_first_of_wave", "dense_tile_last_of_block"} & got
+	assert "wave_seam_break" in got and "block_seam_break" in got
+
+
+def test_the_scan_graphs_place_what_they_are_meant_to():
+	K = sgs.kernel_constants()
+	T = K.kTileBytes
+	union = set()
+	for sg in M.scan_graphs():
+		got = M.scan_reach(sg)
+		assert M.SCAN_REACHED_BY[sg.name] <= got, (sg.name, sorted(M.SCAN_REACHED_BY[sg.name] - got))
+		union |= M.SCAN_REACHED_BY[sg.name]
+		assert 513 <= -(-sg.length // T) <= 640 and len(sg.rows) <= 8
+		R = int(sg.kept.sum())
+		for row in sg.rows:
+			ops, length = M.seam_ops(sg, row)
+			M.check_invariants(ops, R, length, is_ref_row=row == PLOIDY_MAX)
+			# the builder's description and the walk over the graph's arrays agree
+			_, ref_is_base, row_is_base = M.column_walk(sg.g, copy_index=row)
+			assert np.array_equal(ref_is_base, sg.kept) and np.array_equal(row_is_base, M.seam_masks(sg, row)[1]), (sg.name, row)
+		for start, end in sg.notes["skipped"]:
+			assert not sg.kept[start * T:end * T].any() and sg.kept[start * T - 1]
+	assert SCAN_WANTED <= union, sorted(SCAN_WANTED - union)
+
+
+def test_what_the_scan_graphs_mean_in_ops():
+	"""The op lists written down by hand, so that model and kernel cannot be wrong together."""
+	T = sgs.kernel_constants().kTileBytes
+	m, i, d = M.OP_M, M.OP_I, M.OP_D
+	for extra in (0, 1):
+		sg = M.scan_block_graph(extra)
+		n_skipped = 256 + 64 * extra
+		R = 256 * T + 1 + 8 + T + 300                    # block 0; after the stretch its substitution site and 8 columns; the tail
+		assert int(sg.kept.sum()) == R and sg.length == (256 + n_skipped) * T + 1 + 8 + T + 300
+		want = {
+			PLOIDY_MAX: [[m, R]],
+			0: [[m, 256 * T], [i, n_skipped * T], [m, 1 + 8 + T + 300]],              # the label's first byte lies over the reference byte
+			1: [[m, 256 * T - 6], [d, 6 + 5], [m, R - 256 * T - 5]],                  # D ... skipped ... D: one op
+			2: [[m, 256 * T - 6], [d, 6], [m, R - 256 * T]],
+			3: [[m, R]], 4: [[m, R]], 5: [[m, R]],                                   # M ... a skipped block ... M: one op
+		}
+		for row in sg.rows:
+			assert M.seam_ops(sg, row)[0].tolist() == want[row], (sg.name, row)
+	sg = M.scan_wave_graph()
+	ops = M.seam_ops(sg, 0)[0]
+	assert len(ops) == 4 * T + 3 and ops[0].tolist() == [m, 63 * T + 1] and ops[1:2 * T, 1].max() == 1          # tiles 63 and 64: ops 1 ... 32 767 of one column each
+	assert ops[2 * T - 1].tolist() == [i, 1] and ops[2 * T].tolist() == [m, 190 * T - 5 * T - 100 + 1]         # then the M run up to tile 255: 190 tiles less the stretch of 5 tiles and 100 columns
+	for row in (3, 4, 6):
+		assert M.seam_ops(sg, row)[0].tolist() == [[m, int(sg.kept.sum())]]
+	# copy 5, the D run across 127|128: 63 full tiles, two dense ones with a reference byte on every other column, then up to 20 columns before tile 128
+	before = 63 * T + T + (63 * T - 20)
+	assert M.seam_ops(sg, 5)[0].tolist() == [[m, before + 1], [d, 39], [m, int(sg.kept.sum()) - before - 40]]
 
 
 # ---- the chain formatter -------------------------------------------------------------------------------------------------------------
