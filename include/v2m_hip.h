@@ -39,7 +39,8 @@
  * The window-set calls (v2m_window_set_layout, v2m_set_window_set, v2m_splice_window_set[_device]) were added the same way, and so was
  * v2m_row_ops (with v2m_aln_op, v2m_ops_sink_fn and the V2M_KERNEL_ROW_OPS_* ids), and v2m_splice_window_set_distinct (with
  * v2m_distinct_sink_fn and the V2M_KERNEL_DISTINCT_* ids), and v2m_column_counts / v2m_column_counts_device (with v2m_column_count,
- * v2m_column_counts_sink_fn, the V2M_COUNTS_* flags and the V2M_KERNEL_COLUMN_* ids).
+ * v2m_column_counts_sink_fn, the V2M_COUNTS_* flags and the V2M_KERNEL_COLUMN_* ids), and v2m_pair_distances / v2m_pair_distances_device
+ * (with v2m_pair_distances_info, V2M_DIST_ACGT_ONLY and V2M_PAIR_DISTANCES_MAX_ROWS; no kernel ids: the info carries their times).
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -462,6 +463,62 @@ int v2m_column_counts(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /*
 
 int v2m_column_counts_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_COUNTS_ACCUMULATE */,
                              void *d_counts, uint64_t plane_pitch);
+
+/* ---- pair distances -----------------------------------------------------------------------------
+ *
+ * The alignment by pair of rows: an n_rows x n_rows matrix of how many columns of the view two rows of the batch differ in -- what
+ * snp-dists prints, and what neighbour joining and clustering start from.  The view is that of the column counts: the whole row, or the
+ * column window of v2m_set_column_window (a window set in force is ignored); L = v2m_window_length() columns.  The class of an aligned
+ * byte is exactly the column counts' (above): 0-3 A, C, G, T; 4 N; 5 gap ('-' exactly); 6 other.
+ *   flags = 0             dist[i][j] = the columns where the class of batch row i differs from that of batch row j.  All "other" bytes are
+ *                         one class: 'R' against 'Y' counts as equal, and so does 'a' against 'A'.
+ *   V2M_DIST_ACGT_ONLY    dist[i][j] = the columns where both classes are in 0-3 and differ (snp-dists' default).
+ * Every other flag bit -- 0x1, 0x2, 0x4, 0x8 and 0x10 included -- is V2M_ERR_INVALID_ARGUMENT.
+ * Rows may repeat: their distance is 0 and both entries exist; a row with cuts counts as the row it splices.  The matrix is symmetric
+ * with a zero diagonal, and both triangles are written.  n_rows <= V2M_PAIR_DISTANCES_MAX_ROWS (32 768: 4 GiB of matrix); more rows, or
+ * L >= 2^32, is V2M_ERR_UNSUPPORTED with a message that names the limit, before any device work.
+ *
+ * Device form.  d_dist is u32[n_rows][pitch], 16-byte aligned, pitch % 4 == 0 and pitch >= n_rows.  Elements [i][j < n_rows] are
+ * overwritten (not added to); nothing else is touched.
+ * Host form.  dist is u32[n_rows][n_rows] in host memory; the matrix is computed into a context-owned device buffer and copied.  info,
+ * which may be NULL, receives n_sites (the VARIABLE columns of the view for this batch, as the column counts define them), n_columns
+ * (L), n_passes, and -- while v2m_profile_enable is on, else 0 -- the times of the call's three stages in ms.  A stage's time is the
+ * time elapsed on the context's stream between events around everything the stage queues (every slice's splice and kernel for the
+ * counts and the pack stage), so it holds the gaps the host's queueing leaves between launches: it bounds the stage's kernel time from
+ * above and is not a sum of kernel times.  That is how the stages are timed: they have no V2M_KERNEL_* ids, and V2M_KERNEL_LIMIT
+ * keeps its value.
+ * Errors as for the column counts: V2M_ERR_INVALID_ARGUMENT for NULL pointers, unknown flags, a misaligned d_dist or a bad pitch,
+ * V2M_ERR_STATE without a graph, V2M_ERR_PRECONDITION for bad cuts.  n_rows == 0 returns V2M_OK and touches nothing (info included);
+ * L == 0 writes zeros.  Both forms are synchronous.  The column window and the window set are left as they were, and so is what
+ * v2m_column_counts returns afterwards.
+ * How: a column where one class holds every row adds 0 to every pair under both definitions, so only the variable columns -- the
+ * sites -- count.  (1) The column counts of the batch into the context's table, as v2m_column_counts makes them, and the selection
+ * of the variable columns into a site list (emit_site_columns_kernel).  (2) A second pass over the same row slices: per slice the
+ * aligned splice, then pack_sites_kernel gathers the rows' bytes at the sites into three bit planes of 3-bit class codes.  (3)
+ * pair_distances_kernel: XOR + popcount over the planes, a workgroup a tile of 64 x 64 rows of the upper triangle (the mirror entry is
+ * written too), the site words through LDS in chunks of 8; with few rows the site words are split over the grid and the parts meet
+ * by integer atomicAdd on a zeroed matrix.  The planes take 3 * n_rows * n_sites / 8 bytes; V2M_PAIR_DISTANCES_PLANE_BYTES
+ * (environment, read per call; default 16 GiB; a test knob like V2M_COLUMN_COUNTS_BLOCK_BYTES) bounds them: sites that do not fit
+ * are taken in ranges of whole chunks, each range repeating (2) and (3) and adding into the matrix; n_passes counts the ranges.
+ * V2M_PAIR_DISTANCES_PARTS (environment, read once per call; a test knob as well) overrides the number of parts the site words of a
+ * launch of pair_distances_kernel are split into: the parts hold ceil(chunks / parts) chunks each and the last one the remainder. */
+#define V2M_DIST_ACGT_ONLY 0x20u
+#define V2M_PAIR_DISTANCES_MAX_ROWS 32768u
+
+typedef struct {
+	uint64_t n_sites;     /* variable columns of the view for this batch */
+	uint64_t n_columns;   /* L */
+	uint64_t n_passes;    /* site ranges the plane budget made (0 when there was no site) */
+	double counts_ms;     /* column counts + site selection: stream time elapsed over the stage, see above */
+	double pack_ms;       /* splices of the second pass + pack_sites_kernel: likewise */
+	double pairs_ms;      /* pair_distances_kernel (with the zeroing of the matrix, where the parts meet by atomics) */
+} v2m_pair_distances_info;    /* 48 bytes */
+
+int v2m_pair_distances(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_DIST_ACGT_ONLY */,
+                       uint32_t *dist /* n_rows x n_rows, host */, v2m_pair_distances_info *info /* may be NULL */);
+
+int v2m_pair_distances_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_DIST_ACGT_ONLY */,
+                              void *d_dist, uint64_t pitch);
 
 /* ---- founder search: the chunk walks ---------------------------------- */
 

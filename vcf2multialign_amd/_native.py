@@ -43,6 +43,12 @@ COUNT_COLUMNS = 4096
 COUNT_RUN = 255
 SELECT_COLUMNS = 256
 COLUMN_COUNTS_MIN_ROWS = 32
+# v2m_pair_distances[_device]: the one flag, the row limit, and csrc/distance_kernels.hpp's kPairTile (rows per side of a workgroup's
+# tile) and kPairChunkWords (64-bit site words per LDS chunk); tests/test_pair_distances_host.py holds them to the sources
+DIST_ACGT_ONLY = 0x20
+PAIR_DISTANCES_MAX_ROWS = 32768
+PAIR_TILE = 64
+PAIR_CHUNK_WORDS = 8
 # csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
 # kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
 DISTINCT_CHUNK_BYTES = 8192
@@ -97,6 +103,12 @@ DISTINCT_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_
 OPS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_ops_sink_fn
 COLUMN_COUNT_DTYPE = [("column", "<u8"), ("count", "<u4", (6,))]   # v2m_column_count
 COLUMN_COUNTS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_column_counts_sink_fn
+
+
+class PairDistancesInfo(C.Structure):   # v2m_pair_distances_info
+	_fields_ = [("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("n_passes", C.c_uint64), ("counts_ms", C.c_double), ("pack_ms", C.c_double), ("pairs_ms", C.c_double)]
+
+
 TRIALS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_trials_sink
 
 # every symbol include/v2m_hip.h declares: (restype, argtypes)
@@ -134,6 +146,8 @@ SIGNATURES = {
 	"v2m_row_ops": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, OPS_SINK_FN, C.c_void_p]),
 	"v2m_column_counts": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, COLUMN_COUNTS_SINK_FN, C.c_void_p]),
 	"v2m_column_counts_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64]),
+	"v2m_pair_distances": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.POINTER(PairDistancesInfo)]),
+	"v2m_pair_distances_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -439,6 +439,30 @@ class Context:
 			rows = RowBatch(rows)
 		self._check(self._lib.v2m_column_counts_device(self._h, C.byref(rows.struct), N.COUNTS_ACCUMULATE if accumulate else 0, ptr, plane_pitch))
 
+	def pair_distances(self, rows, acgt_only=False, info=False):
+		"""v2m_pair_distances: np.uint32[n, n], the number of columns of the view in force (the whole row, or the column window) in which
+		two rows of the batch differ by class (A, C, G, T, N, gap, other) -- with acgt_only (V2M_DIST_ACGT_ONLY) the columns where both hold
+		one of A, C, G, T and differ.  With info=True: (matrix, dict of v2m_pair_distances_info's fields)."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = int(rows.struct.n_rows)
+		dist = np.zeros(max(1, n * n), dtype=np.uint32)   # (never a NULL pointer: no rows is no error)
+		record = N.PairDistancesInfo()
+		self._check(self._lib.v2m_pair_distances(self._h, C.byref(rows.struct), N.DIST_ACGT_ONLY if acgt_only else 0, dist.ctypes.data, C.byref(record)))
+		dist = dist[:n * n].reshape(n, n)
+		if n == 0:
+			record.n_columns = self.window_length   # (with no rows the call returns before it writes the info)
+		if info:
+			return dist, {name: getattr(record, name) for name, _ in N.PairDistancesInfo._fields_}
+		return dist
+
+	def pair_distances_device(self, rows, ptr, pitch, acgt_only=False):
+		"""v2m_pair_distances_device: the matrix into device memory at `ptr`, u32[n][pitch] (16-byte aligned, pitch a multiple of 4 and at
+		least n); elements [i][j < n] are overwritten, nothing else is touched."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		self._check(self._lib.v2m_pair_distances_device(self._h, C.byref(rows.struct), N.DIST_ACGT_ONLY if acgt_only else 0, ptr, pitch))
+
 	def bgzf_compress(self, data):
 		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
 		src = bytes(data)

@@ -462,4 +462,21 @@ int64_t v2mh_column_counts_text(uint64_t n_rows, v2m_column_count const *records
 	}
 }
 
+// distances_text() of output.hh (no GPU), handed over as v2mh_column_counts_text hands over its table; ids are n NUL-terminated
+// strings; -1 with a message in err on failure.
+int64_t v2mh_distances_text(char const *const *ids, uint64_t n_rows, uint32_t const *dist, uint64_t n_columns, uint64_t n_sites, int acgt_only,
+	char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		std::vector<std::string> names;
+		for (uint64_t i(0); i < n_rows; ++i) names.emplace_back(ids[i]);
+		std::string const text(vh::distances_text(names, dist, n_columns, n_sites, 0 != acgt_only));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
 } // extern "C"

@@ -55,6 +55,8 @@ struct options {
 	char const *output_paf{};             // --output-paf=FILE: one PAF line with an =/X/I/D cigar per output row, from v2m_row_ops with V2M_OPS_SPLIT_MATCH
 	char const *regions_file{};           // --regions-file=FILE.bed: one output file per BED region, all spliced as one window set per pass
 	char const *output_column_counts{};   // --output-column-counts=FILE: base counts per variable alignment column, from v2m_column_counts
+	char const *output_distances{};       // --output-distances=FILE: the matrix of pairwise distances between the output rows, from v2m_pair_distances
+	bool acgt_only{};                     // --acgt-only (with --output-distances): only columns where both rows hold A, C, G or T count
 	bool all_columns{};                   // --all-columns (with --output-column-counts): every column, not only the variable ones
 	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
 	std::vector<int> devices{0};
@@ -115,6 +117,14 @@ void usage()
 		"                                     says; --region restricts the columns.  Alone or beside -s / --output-sequences-separate /\n"
 		"                                     --output-chain / --output-paf; not with --regions-file or several --device entries\n"
 		"      --all-columns                  With --output-column-counts: write every column, not only the variable ones\n"
+		"      --output-distances=FILE        Write a TSV with the matrix of pairwise distances between the output sequences (REF first,\n"
+		"                                     unless --omit-reference), as snp-dists writes it: a `#rows` line, a header line with the\n"
+		"                                     sequence names (those of --output-paf), then one line per sequence.  A distance is the\n"
+		"                                     number of alignment columns in which two sequences differ by class (A, C, G, T, N -- either\n"
+		"                                     case --, gap, other), counted on the GPU.  Always of the aligned form, whatever --unaligned\n"
+		"                                     says; --region restricts the columns.  Alone or beside the other outputs; not with\n"
+		"                                     --regions-file or several --device entries\n"
+		"      --acgt-only                    With --output-distances: count only the columns where both sequences hold A, C, G or T\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -301,7 +311,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -313,7 +323,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct}, {"output-paf", required_argument, nullptr, o_output_paf}, {"output-column-counts", required_argument, nullptr, o_output_column_counts}, {"all-columns", no_argument, nullptr, o_all_columns},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct}, {"output-paf", required_argument, nullptr, o_output_paf}, {"output-column-counts", required_argument, nullptr, o_output_column_counts}, {"all-columns", no_argument, nullptr, o_all_columns}, {"output-distances", required_argument, nullptr, o_output_distances}, {"acgt-only", no_argument, nullptr, o_acgt_only},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -365,6 +375,8 @@ int main(int argc, char **argv)
 			case o_output_paf: opt.output_paf = optarg; break;
 			case o_output_column_counts: opt.output_column_counts = optarg; break;
 			case o_all_columns: opt.all_columns = true; break;
+			case o_output_distances: opt.output_distances = optarg; break;
+			case o_acgt_only: opt.acgt_only = true; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -411,6 +423,12 @@ int main(int argc, char **argv)
 		// one table from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
 		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
 		if (other) { std::cerr << "ERROR: --output-column-counts cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+	}
+	if (opt.acgt_only && !opt.output_distances) { std::cerr << "ERROR: --acgt-only requires --output-distances.\n"; return EXIT_FAILURE; }
+	if (opt.output_distances) {
+		// one matrix from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
+		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
+		if (other) { std::cerr << "ERROR: --output-distances cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
 	}
 	if (opt.region && !parse_region(opt.region, opt.region_start, opt.region_end)) {
 		std::cerr << "ERROR: --region must be START-END with 1 <= START <= END (1-based, inclusive), got \"" << opt.region << "\".\n";
@@ -646,6 +664,11 @@ int main(int argc, char **argv)
 			if (opt.output_column_counts) {
 				std::cerr << "Outputting column counts..." << std::flush;
 				output.output_column_counts(graph, opt.output_column_counts, opt.all_columns, opt.verbose);
+				std::cerr << " Done.\n";
+			}
+			if (opt.output_distances) {
+				std::cerr << "Outputting distances..." << std::flush;
+				output.output_distances(graph, opt.output_distances, opt.acgt_only, opt.verbose);
 				std::cerr << " Done.\n";
 			}
 		});

@@ -1142,6 +1142,59 @@ void output::output_column_counts(variant_graph const &graph, char const *path, 
 }
 
 
+// --- pair distances (--output-distances) ------------------------------------------------------------------------
+std::string distances_text(std::vector<std::string> const &ids, std::uint32_t const *dist, u64 n_columns, u64 n_sites, bool acgt_only)
+{
+	u64 const n(ids.size());
+	for (auto const &id : ids)
+		if (std::string::npos != id.find_first_of("\t\n\r")) throw std::runtime_error("the sequence name \"" + id + "\" holds a tab or a line break, which a cell of the distance table cannot");
+	std::string text("#rows\t" + std::to_string(n) + "\tcolumns\t" + std::to_string(n_columns) + "\tsites\t" + std::to_string(n_sites) + "\tmodel\t" + (acgt_only ? "acgt" : "all") + "\nid");
+	for (auto const &id : ids) { text += '\t'; text += id; }
+	text += '\n';
+	for (u64 i(0); i < n; ++i) {
+		text += ids[i];
+		for (u64 j(0); j < n; ++j) { text += '\t'; text += std::to_string(dist[i * n + j]); }
+		text += '\n';
+	}
+	return text;
+}
+
+
+void output::output_distances(variant_graph const &graph, std::ostream &stream, bool acgt_only, bool verbose)
+{
+	if (!m_more_gpus.empty()) throw std::runtime_error("--output-distances needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-distances needs every chromosome copy on one GPU context");
+	row_set const rows(chain_rows(graph));   // (the rows of a2m_rows() under the names --output-paf writes)
+	v2m_row_batch batch{};
+	batch.n_rows = rows.copy_index.size();
+	batch.copy_index = rows.copy_index.data();
+	if (rows.any_cuts) {
+		batch.cut_offsets = rows.cut_offsets.data();
+		batch.cut_nodes = rows.cut_nodes.data();
+		batch.cut_copies = rows.cut_copies.data();
+	}
+	std::vector<std::uint32_t> dist(std::max<std::size_t>(1, std::size_t(batch.n_rows) * batch.n_rows));
+	v2m_pair_distances_info info{};
+	info.n_columns = v2m_window_length(m_gpu.get());
+	m_gpu.check(v2m_pair_distances(m_gpu.get(), &batch, acgt_only ? V2M_DIST_ACGT_ONLY : 0, dist.data(), &info));
+	std::string const text(distances_text(rows.ids, dist.data(), info.n_columns, info.n_sites, acgt_only));
+	stream.write(text.data(), std::streamsize(text.size()));
+	if (verbose)
+		std::fprintf(stderr, "Distances: %llu rows, %llu columns, %llu sites, %llu passes.\n", (unsigned long long) batch.n_rows, (unsigned long long) info.n_columns,
+			(unsigned long long) info.n_sites, (unsigned long long) info.n_passes);
+}
+
+
+void output::output_distances(variant_graph const &graph, char const *path, bool acgt_only, bool verbose)
+{
+	std::ofstream stream(path, std::ios::binary | std::ios::trunc);
+	if (!stream) throw std::runtime_error(std::string("unable to open ") + path + " for writing");
+	output_distances(graph, stream, acgt_only, verbose);
+	stream.flush();
+	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+}
+
+
 // --- haplotype_output (haplotype_output.cc:38-132) ------------------------------------------------------------
 output::row_set haplotype_output::rows_for(variant_graph const &graph, char sep, char const *suffix)
 {

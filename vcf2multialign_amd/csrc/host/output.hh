@@ -66,6 +66,13 @@ std::vector<v2m_aln_op> fold_split_ops(v2m_aln_op const *ops, u64 n_ops);
 //   n_rows minus their sum.
 std::string column_counts_text(u64 n_rows, v2m_column_count const *records, u64 n_records, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count);
 
+// The TSV of pair distances (include/v2m_hip.h, "pair distances"), as snp-dists writes its matrix: a pure function of its arguments.
+//   #rows<TAB><n><TAB>columns<TAB><n_columns><TAB>sites<TAB><n_sites><TAB>model<TAB>all|acgt
+//   id<TAB><ids[0]><TAB>...<TAB><ids[n - 1]>
+//   one line per sequence: its id, then its n distances (dist is n x n, row-major)
+// An id that holds a tab or a line break is refused.
+std::string distances_text(std::vector<std::string> const &ids, std::uint32_t const *dist, u64 n_columns, u64 n_sites, bool acgt_only);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -135,6 +142,12 @@ public:
 	// copy.  Variable columns only unless all_columns; verbose prints the rows, columns and variable columns to stderr.
 	void output_column_counts(variant_graph const &graph, char const *path, bool all_columns = false, bool verbose = false);
 	void output_column_counts(variant_graph const &graph, std::ostream &stream, bool all_columns = false, bool verbose = false);
+
+	// --output-distances: distances_text above for the rows of the A2M output (REF first, unless omitted) under the names --output-paf
+	// writes, over the view in force (--region: the window's columns), from v2m_pair_distances on the first context, which must hold
+	// every copy.  acgt_only: V2M_DIST_ACGT_ONLY; verbose prints the rows, columns, sites and passes to stderr.
+	void output_distances(variant_graph const &graph, char const *path, bool acgt_only = false, bool verbose = false);
+	void output_distances(variant_graph const &graph, std::ostream &stream, bool acgt_only = false, bool verbose = false);
 
 protected:
 	struct row_set {

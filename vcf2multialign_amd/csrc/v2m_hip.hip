@@ -30,6 +30,7 @@
 #include "founder_kernels.hpp"
 #include "bgzf_kernels.hpp"
 #include "vcf_kernels.hpp"
+#include "distance_kernels.hpp"
 
 using v2m::u32;
 using v2m::u64;
@@ -262,6 +263,8 @@ struct v2m_ctx {
 	// range's block counts and total, its records (two, used in turn) and the total's pinned staging (two likewise)
 	scratch_buf d_column_table, d_column_stage, d_column_blocks, d_column_total, d_column_records[2];
 	pinned_buf h_column_total;
+	// pair distances (v2m_pair_distances): the site list, a pass's bit planes, and the host form's matrix
+	scratch_buf d_dist_sites, d_dist_planes, d_dist_matrix;
 	// pinned slots: the rows of v2m_splice_rows[_held] (a slot is kept until the sink has released its rows); slots 0 and 1 also stage
 	// the BGZF members and v2m_upload_path_blocks' columns
 	held_ring_state held_state;
@@ -3292,6 +3295,212 @@ int v2m_column_counts(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v
 	(void) hipStreamSynchronize(ctx->stream);
 	(void) hipStreamSynchronize(ctx->copy_stream);
 	return rc;
+}
+
+
+// ---- pair distances (distance_kernels.hpp) ---------------------------------------------------------
+
+namespace {
+
+// The three stages of a pair-distance call, timed with events of their own while profiling is on (they have no V2M_KERNEL_* ids):
+// a stage's segments are bracketed as they are queued and summed after the call's last synchronisation.  A segment is one event pair
+// around everything the stage queues -- the counts and the pack segment span every slice -- so a figure is time elapsed on the stream,
+// with whatever gaps the host's queueing leaves between the launches, not summed kernel time.
+struct stage_times {
+	enum { counts, pack, pairs, n_stages };
+	struct segment { int stage; hipEvent_t begin, end; };
+	v2m_ctx *ctx;
+	std::vector<segment> segments;
+	explicit stage_times(v2m_ctx *c) : ctx(c) {}
+	stage_times(stage_times const &) = delete;
+	~stage_times() { for (auto &s : segments) { (void) hipEventDestroy(s.begin); (void) hipEventDestroy(s.end); } }
+	void begin(int stage)
+	{
+		if (!ctx->profiling) return;
+		segment s{stage, nullptr, nullptr};
+		if (hipSuccess != hipEventCreate(&s.begin)) return;
+		if (hipSuccess != hipEventCreate(&s.end)) { (void) hipEventDestroy(s.begin); return; }
+		(void) hipEventRecord(s.begin, ctx->stream);
+		segments.push_back(s);
+	}
+	void end() { if (ctx->profiling && !segments.empty()) (void) hipEventRecord(segments.back().end, ctx->stream); }
+	// after the stream is idle
+	void sum(double (&ms)[n_stages]) const
+	{
+		for (auto const &s : segments) {
+			float t(0);
+			if (hipSuccess == hipEventElapsedTime(&t, s.begin, s.end)) ms[s.stage] += double(t);
+		}
+	}
+};
+
+int check_pair_distances(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, char const *name)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!rows) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "rows is NULL");
+	if (flags & ~u32(V2M_DIST_ACGT_ONLY)) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s takes 0 or 0x%x as flags (got 0x%x)", name, V2M_DIST_ACGT_ONLY, flags);
+	if (int const rc = check_batch(ctx, rows, 0)) return rc;
+	if (rows->n_rows > V2M_PAIR_DISTANCES_MAX_ROWS)
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes at most V2M_PAIR_DISTANCES_MAX_ROWS = %u rows (got %llu)", name, V2M_PAIR_DISTANCES_MAX_ROWS, (unsigned long long) rows->n_rows);
+	if (ctx->view().length() >= (u64(1) << 32))
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes a view of fewer than 2^32 columns (got %llu)", name, (unsigned long long) ctx->view().length());
+	return V2M_OK;
+}
+
+// The parts the site chunks of a launch of pair_distances_kernel are split into: with few tile pairs, as many as bring the launch to
+// about four workgroups per compute unit.  Returns the chunks of a part.  forced_parts: V2M_PAIR_DISTANCES_PARTS, which overrides the
+// number of parts asked for (a test knob, read once per call: the kernel takes any split), or 0.
+u64 pair_chunks_per_part(v2m_ctx const *ctx, u64 tile_pairs, u64 n_chunks, u64 forced)
+{
+	u64 const spread((4 * u64(ctx->n_cus) + tile_pairs - 1) / tile_pairs);
+	u64 const want_parts(std::max<u64>(1, std::min<u64>({n_chunks, forced ? forced : spread, 65535})));
+	return (n_chunks + want_parts - 1) / want_parts;
+}
+
+// Queues and completes the call: the matrix of the batch over the view in force into d_dist (u32[n_rows][pitch]).  n_rows >= 1.
+int pair_distances_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, u32 *d_dist, u64 pitch, v2m_pair_distances_info *info)
+{
+	u64 const L(ctx->view().length()), n(rows->n_rows);
+	stage_times times(ctx);
+	v2m_pair_distances_info out{};
+	out.n_columns = L;
+	auto const zeros([&]() -> int {
+		V2M_HIP_TRY(ctx, hipMemset2DAsync(d_dist, pitch * 4, 0, n * 4, n, ctx->stream));
+		return V2M_OK;
+	});
+	auto const finish([&](int rc) -> int {
+		hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
+		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
+		if (V2M_OK == rc && info) {
+			double ms[stage_times::n_stages] = {};
+			times.sum(ms);
+			out.counts_ms = ms[stage_times::counts]; out.pack_ms = ms[stage_times::pack]; out.pairs_ms = ms[stage_times::pairs];
+			*info = out;
+		}
+		return rc;
+	});
+	if (0 == L) return finish(zeros());
+
+	// (1) the counts and the site list
+	u64 const table_pitch((L + 3) & ~u64(3));
+	u64 const select_blocks((L + v2m::kSelectColumns - 1) / v2m::kSelectColumns);
+	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(V2M_COUNT_CLASSES * table_pitch * 4));
+	V2M_HIP_TRY(ctx, ctx->d_column_blocks.ensure(std::max<u64>(select_blocks * sizeof(u32), 16)));
+	V2M_HIP_TRY(ctx, ctx->d_column_total.ensure(sizeof(u64)));
+	V2M_HIP_TRY(ctx, ctx->h_column_total.ensure(2 * sizeof(u64)));
+	V2M_POISON_HOST(ctx->h_column_total.p, 2 * sizeof(u64));
+	u32 *const table(ctx->d_column_table.as<u32>());
+	times.begin(stage_times::counts);
+	int rc(column_counts_zero(ctx, table, table_pitch, L));
+	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, table, table_pitch);
+	if (V2M_OK != rc) return finish(rc);
+	hipLaunchKernelGGL(v2m::count_variable_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+		table, table_pitch, u64(0), L, u32(n), 1u, ctx->d_column_blocks.as<u32>());
+	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->d_column_blocks.as<u32>(), u32(select_blocks), ctx->d_column_total.as<u64>());
+	times.end();
+	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: the site selection did not launch"));
+	if (hipSuccess != hipMemcpyAsync(ctx->h_column_total.p, ctx->d_column_total.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
+		|| hipSuccess != hipStreamSynchronize(ctx->stream))
+		return finish(fail(ctx, V2M_ERR_HIP, "pair distances: the site count did not arrive"));
+	u64 const V(*ctx->h_column_total.as<u64>());
+	if (V > L) return finish(fail(ctx, V2M_ERR_HIP, "the site selection counted %llu of %llu columns", (unsigned long long) V, (unsigned long long) L));
+	out.n_sites = V;
+	if (0 == V) return finish(zeros());
+	{
+		hipError_t const st(ctx->d_dist_sites.ensure(V * sizeof(u32)));
+		if (hipSuccess != st) return finish(fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "pair distances: the site list: %s", hipGetErrorString(st)));
+	}
+	u32 *const sites(ctx->d_dist_sites.as<u32>());
+	times.begin(stage_times::counts);
+	hipLaunchKernelGGL(v2m::emit_site_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+		table, table_pitch, L, u32(n), ctx->d_column_blocks.as<u32>(), sites, V);
+	times.end();
+	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: emit_site_columns_kernel did not launch"));
+
+	// the passes: ranges of whole chunks whose planes fit the budget
+	u64 const n_tiles((n + v2m::kPairTile - 1) / v2m::kPairTile), n_pad(n_tiles * v2m::kPairTile), tile_pairs(n_tiles * (n_tiles + 1) / 2);
+	u64 const chunk_sites(64 * u64(v2m::kPairChunkWords)), n_chunks((V + chunk_sites - 1) / chunk_sites);
+	u64 const chunk_bytes(u64(v2m::kPairChunkWords) * 3 * n_pad * sizeof(u64));
+	u64 const pass_chunks(std::max<u64>(1, std::min<u64>(n_chunks, env_u64("V2M_PAIR_DISTANCES_PLANE_BYTES", u64(16) << 30) / chunk_bytes)));
+	u64 const n_passes((n_chunks + pass_chunks - 1) / pass_chunks);
+	out.n_passes = n_passes;
+	u64 const forced_parts(env_u64("V2M_PAIR_DISTANCES_PARTS", 0));
+	bool const atomics(n_passes > 1 || pair_chunks_per_part(ctx, tile_pairs, pass_chunks, forced_parts) < pass_chunks);
+	slice_plan const p(plan_slices(ctx, n, false));
+	if (atomics) {
+		times.begin(stage_times::pairs);
+		rc = zeros();
+		times.end();
+		if (V2M_OK != rc) return finish(rc);
+	}
+	for (u64 pass(0); pass < n_passes; ++pass) {
+		u64 const c0(pass * pass_chunks), c1(std::min(n_chunks, c0 + pass_chunks)), chunks(c1 - c0);
+		u64 const site_begin(c0 * chunk_sites), site_end(std::min(V, c1 * chunk_sites));
+		{
+			hipError_t const st(ctx->d_dist_planes.ensure(pass_chunks * chunk_bytes));   // (refilled per pass in the checked build)
+			if (hipSuccess != st) return finish(fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "pair distances: %llu bytes of planes: %s", (unsigned long long) (pass_chunks * chunk_bytes), hipGetErrorString(st)));
+		}
+		u64 *const planes(ctx->d_dist_planes.as<u64>());
+		// (2) the planes of the pass: zeroed (padding sites and rows hold code 0), then packed slice by slice
+		times.begin(stage_times::pack);
+		if (hipSuccess != hipMemsetAsync(planes, 0, chunks * chunk_bytes, ctx->stream)) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: the planes could not be zeroed"));
+		u64 const pack_blocks((site_end - site_begin + v2m::kPackThreads - 1) / v2m::kPackThreads);
+		for (u64 s(0); s < p.n_slices; ++s) {
+			u64 const r0(s * p.rows_per_slice), r1(std::min(n, r0 + p.rows_per_slice)), nr(r1 - r0);
+			{
+				hipError_t const st(ctx->ring[0].ensure(p.slot_bytes));
+				if (hipSuccess != st) return finish(fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "pair distances: the row slot: %s", hipGetErrorString(st)));
+			}
+			char *const d_rows(ctx->ring[0].as<char>());
+			if (V2M_OK != (rc = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch))) return finish(rc);
+			// row groups: with few site blocks, as many as bring the launch to about four workgroups per compute unit, of at least 16 rows
+			u64 const want_groups((4 * u64(ctx->n_cus) + pack_blocks - 1) / pack_blocks);
+			u64 const per_group(std::max<u64>({16, (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}));
+			u64 const groups((nr + per_group - 1) / per_group);
+			hipLaunchKernelGGL(v2m::pack_sites_kernel, dim3(unsigned(pack_blocks), unsigned(groups)), dim3(v2m::kPackThreads), 0, ctx->stream,
+				d_rows, p.pitch, u32(nr), u32(per_group), u32(r0), sites, site_begin, site_end, planes, n_pad);
+			if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pack_sites_kernel did not launch"));
+		}
+		times.end();
+		// (3) the pairs
+		u64 const per_part(pair_chunks_per_part(ctx, tile_pairs, chunks, forced_parts)), parts((chunks + per_part - 1) / per_part);
+		times.begin(stage_times::pairs);
+		hipLaunchKernelGGL((flags & V2M_DIST_ACGT_ONLY) ? v2m::pair_distances_kernel<true> : v2m::pair_distances_kernel<false>,
+			dim3(unsigned(tile_pairs), 1, unsigned(parts)), dim3(v2m::kPairThreads), 0, ctx->stream,
+			planes, n_pad, u32(chunks), u32(per_part), u32(n_tiles), u32(n), d_dist, pitch, atomics ? 1u : 0u);
+		times.end();
+		if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pair_distances_kernel did not launch"));
+		if (pass + 1 < n_passes && hipSuccess != hipStreamSynchronize(ctx->stream))   // (the planes are reused, and refilled in the checked build)
+			return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pass %llu failed", (unsigned long long) pass));
+	}
+	return finish(V2M_OK);
+}
+
+} // namespace
+
+int v2m_pair_distances_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, void *d_dist, uint64_t pitch)
+{
+	if (int const rc = check_pair_distances(ctx, rows, flags, "v2m_pair_distances_device")) return rc;
+	if (!d_dist) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_dist is NULL");
+	if (reinterpret_cast<uintptr_t>(d_dist) & 15) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_dist must be 16-byte aligned");
+	if ((pitch & 3) || pitch < rows->n_rows)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "pitch %llu must be a multiple of 4 and at least n_rows = %llu", (unsigned long long) pitch, (unsigned long long) rows->n_rows);
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	return pair_distances_run(ctx, rows, flags, static_cast<u32 *>(d_dist), pitch, nullptr);
+}
+
+int v2m_pair_distances(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, uint32_t *dist, v2m_pair_distances_info *info)
+{
+	if (int const rc = check_pair_distances(ctx, rows, flags, "v2m_pair_distances")) return rc;
+	if (!dist) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "dist is NULL");
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	u64 const n(rows->n_rows), pitch((n + 3) & ~u64(3));
+	V2M_HIP_TRY(ctx, ctx->d_dist_matrix.ensure(n * pitch * 4));
+	if (int const rc = pair_distances_run(ctx, rows, flags, ctx->d_dist_matrix.as<u32>(), pitch, info)) return rc;
+	V2M_HIP_TRY(ctx, hipMemcpy2D(dist, n * 4, ctx->d_dist_matrix.p, pitch * 4, n * 4, n, hipMemcpyDeviceToHost));
+	return V2M_OK;
 }
 
 

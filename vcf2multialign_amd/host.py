@@ -74,6 +74,8 @@ def _load():
 		L.v2mh_paf_text.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_column_counts_text.restype = C.c_int64
 		L.v2mh_column_counts_text.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_distances_text.restype = C.c_int64
+		L.v2mh_distances_text.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -147,6 +149,27 @@ def column_counts_text(n_rows, columns, counts, reference_positions, aligned_pos
 	if n != L.v2mh_column_counts_text(*args, dst, n, err, len(err)):
 		raise ValueError(err.value.decode())
 	return dst.raw[:n]
+
+
+def distances_text(ids, dist, n_columns, n_sites, acgt_only=False):
+	"""The host library's distance formatter (csrc/host/output.cc: distances_text; no GPU): the TSV, as bytes, of the matrix dist[n, n]
+	of the sequences named `ids` over n_columns columns of which n_sites are variable."""
+	names = [i if isinstance(i, bytes) else str(i).encode() for i in ids]
+	n = len(names)
+	dist = np.ascontiguousarray(dist, dtype=np.uint32).reshape(n, n)
+	if any(b"\0" in i for i in names):
+		raise ValueError("a sequence name holds a NUL byte")
+	array = (C.c_char_p * max(1, n))(*names)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (array, n, dist.ctypes.data if dist.size else None, int(n_columns), int(n_sites), 1 if acgt_only else 0)
+	size = L.v2mh_distances_text(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != L.v2mh_distances_text(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
 
 
 def write_cut_positions(path, cut_positions, min_distance, score):

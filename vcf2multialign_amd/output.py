@@ -75,6 +75,20 @@ class Output:
 		stream.write(host.column_counts_text(len(rows), columns, counts, graph.reference_positions, graph.aligned_positions))
 		return len(columns)
 
+	def _write_distances(self, stream, ids, rows, graph, acgt_only):
+		"""--output-distances: the TSV of host.distances_text for `rows` (those of output_a2m, named as --output-paf names them) from
+		Context.pair_distances, over the region's columns when there is one.  Returns the info of the call."""
+		from . import host
+		if self.region is not None:
+			self.ctx.set_column_window(*columns_of_reference_range(graph.reference_positions, graph.aligned_positions, *self.region))
+		try:
+			dist, info = self.ctx.pair_distances(RowBatch(rows), acgt_only=acgt_only, info=True)
+		finally:
+			if self.region is not None:
+				self.ctx.set_column_window(0, self.ctx.aligned_length)
+		stream.write(host.distances_text(ids, dist, info["n_columns"], info["n_sites"], acgt_only))
+		return info
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -123,6 +137,15 @@ class HaplotypeOutput(Output):
 				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
 		return self._write_column_counts(stream, rows, graph, all_columns)
 
+	def output_distances(self, graph, stream, acgt_only=False):
+		"""--output-distances for the rows of output_a2m (REF first, unless omitted), named as one file per sequence would be."""
+		ids, rows = ([self._chain_name("REF")], [PLOIDY_MAX]) if self.should_output_reference else ([], [])
+		for sample_idx in range(len(graph.sample_names)):
+			for chr_copy_idx in range(graph.sample_ploidy(sample_idx)):
+				ids.append(self._chain_name("%s.%d" % (graph.sample_names[sample_idx], 1 + chr_copy_idx)))
+				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
+		return self._write_distances(stream, ids, rows, graph, acgt_only)
+
 	def output_chain(self, graph, stream):
 		"""--output-chain: the chains of the rows of output_a2m (without REF), named as one file per sequence would be."""
 		names, rows = [], []
@@ -169,6 +192,17 @@ class FounderSequenceGreedyOutput(Output):
 			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
 			rows.append(list(zip(cut_positions[:-1], col)))
 		return self._write_column_counts(stream, rows, graph, all_columns)
+
+	def output_distances(self, graph, cut_positions, assigned_samples_column_major, stream, acgt_only=False):
+		"""--output-distances for the rows of output_a2m (REF first, unless omitted, then the founder rows)."""
+		n_rows = len(cut_positions) - 1
+		n_founders = len(assigned_samples_column_major) // n_rows if n_rows else 0
+		ids, rows = ([self._chain_name("REF")], [PLOIDY_MAX]) if self.should_output_reference else ([], [])
+		for col_idx in range(n_founders):
+			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
+			ids.append(self._chain_name(str(1 + col_idx)))
+			rows.append(list(zip(cut_positions[:-1], col)))
+		return self._write_distances(stream, ids, rows, graph, acgt_only)
 
 	def output_chain(self, graph, cut_positions, assigned_samples_column_major, stream):
 		"""--output-chain for the founder rows of output_a2m."""
