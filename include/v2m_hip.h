@@ -40,7 +40,8 @@
  * v2m_row_ops (with v2m_aln_op, v2m_ops_sink_fn and the V2M_KERNEL_ROW_OPS_* ids), and v2m_splice_window_set_distinct (with
  * v2m_distinct_sink_fn and the V2M_KERNEL_DISTINCT_* ids), and v2m_column_counts / v2m_column_counts_device (with v2m_column_count,
  * v2m_column_counts_sink_fn, the V2M_COUNTS_* flags and the V2M_KERNEL_COLUMN_* ids), and v2m_pair_distances / v2m_pair_distances_device
- * (with v2m_pair_distances_info, V2M_DIST_ACGT_ONLY and V2M_PAIR_DISTANCES_MAX_ROWS; no kernel ids: the info carries their times).
+ * (with v2m_pair_distances_info, V2M_DIST_ACGT_ONLY and V2M_PAIR_DISTANCES_MAX_ROWS; no kernel ids: the info carries their times), and
+ * v2m_variable_sites / v2m_variable_sites_device (with v2m_variable_sites_info, the two sink types and V2M_SITES_SNP; no kernel ids either).
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -519,6 +520,63 @@ int v2m_pair_distances(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /
 
 int v2m_pair_distances_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_DIST_ACGT_ONLY */,
                               void *d_dist, uint64_t pitch);
+
+/* ---- variable sites -----------------------------------------------------------------------------
+ *
+ * The alignment reduced to its variable columns: the rows of the batch, cut down to the selected columns of the view -- the FASTA
+ * snp-sites makes from a multi-FASTA, and what IQ-TREE, RAxML, FastTree and Gubbins read.  The view is that of the column counts: the
+ * whole row, or the column window of v2m_set_column_window (a window set in force is ignored); L = v2m_window_length() columns.  The
+ * selection is decided from the column counts of the batch alone (classes as above: 0-3 A, C, G, T; 4 N; 5 gap; 6 other):
+ *   flags = 0        the VARIABLE columns exactly as the column counts define them: none of the seven classes holds all n_rows rows.
+ *                    These are the sites of v2m_pair_distances with flags 0 (its info's n_sites).
+ *   V2M_SITES_SNP    the columns where at least two of the four classes A, C, G, T have a non-zero count (snp-sites' default rule):
+ *                    exactly the columns that can add to a V2M_DIST_ACGT_ONLY distance.  Columns that vary only by gap, N or "other"
+ *                    -- above all the padding columns of inserted ALT alleles -- are left out.
+ * Every other flag bit -- 0x1, 0x2, 0x4, 0x8, 0x10 and 0x20 included -- is V2M_ERR_INVALID_ARGUMENT.  With n_rows <= 1 there is no
+ * site.  The bytes delivered are the bytes the A2M file holds at those columns, unchanged: case, '-', 'N' and every other byte as they
+ * are.  Rows may repeat; a row with cuts is the row it splices.  L >= 2^32 is V2M_ERR_UNSUPPORTED with a message that names the limit,
+ * before any device work.  V is the number of selected columns.
+ *
+ * Device form.  d_bytes is u8[n_rows][pitch], 16-byte aligned, pitch % 16 == 0; d_columns, which may be NULL, is u32[pitch] and
+ * receives the selected columns relative to the view, ascending; *n_sites receives V.  If V > pitch the call fails with
+ * V2M_ERR_INVALID_ARGUMENT and a message that names V: *n_sites is set, nothing is written to either buffer, and the caller sizes its
+ * buffers and calls again.  Otherwise bytes [r][s < V] and d_columns[s < V] are overwritten, bytes [r][V ..< (V + 3) & ~3] are
+ * written as 0 (a lane stores whole words), and nothing else is touched.
+ * Host form.  columns_sink is called once, before any row, with the ABSOLUTE aligned columns, ascending (as v2m_column_count.column
+ * is absolute); rows_sink then receives blocks of consecutive batch rows in batch order: row first_row + r of the batch is the
+ * n_sites bytes at bytes + r * pitch.  That memory is library-owned pinned memory, valid during the call only, on the calling thread.
+ * Neither sink is ever called with zero sites or zero rows; a non-zero return stops the call with V2M_ERR_SINK; either may be NULL,
+ * and a NULL sink's deliveries are skipped.  info, which may be NULL, receives n_sites (V), n_columns (L) and -- while
+ * v2m_profile_enable is on, else 0 -- the stream time elapsed over the call's two stages in ms, timed as the pair distances' stages
+ * are (above): no V2M_KERNEL_* ids, V2M_KERNEL_LIMIT keeps its value.
+ * Errors as for the pair distances: V2M_ERR_INVALID_ARGUMENT for NULL rows or n_sites, unknown flags, a misaligned d_bytes or a bad
+ * pitch, V2M_ERR_STATE without a graph, V2M_ERR_PRECONDITION for bad cuts.  n_rows == 0 returns V2M_OK and touches nothing (*n_sites
+ * and info included).  Both forms are synchronous.  The column window and the window set are left as they were, and so is what
+ * v2m_column_counts returns afterwards.
+ * How: (1) the column counts of the batch into the context's table, as v2m_column_counts makes them, and the selection into a site
+ * list: count_variable_columns_kernel / emit_site_columns_kernel for flags 0, count_snp_columns_kernel / emit_snp_columns_kernel for
+ * V2M_SITES_SNP, scan_tile_counts_kernel between them.  (2) A second pass over the same row slices: per slice the aligned splice, then
+ * gather_sites_kernel reads the rows' bytes at the sites -- a lane four sites, one 4-byte store per row -- into d_bytes (device form)
+ * or into one of two context-owned buffers, from which the slice crosses the link on the copy stream into one of two pinned slots and
+ * reaches rows_sink while the next slice is spliced and gathered. */
+#define V2M_SITES_SNP 0x40u
+
+typedef struct {
+	uint64_t n_sites;     /* V: the selected columns of the view for this batch */
+	uint64_t n_columns;   /* L */
+	double counts_ms;     /* column counts + site selection: stream time elapsed over the stage */
+	double gather_ms;     /* splices of the second pass + gather_sites_kernel: likewise, summed over the slices */
+} v2m_variable_sites_info;    /* 32 bytes */
+
+typedef int (*v2m_site_columns_sink_fn)(void *user, const uint64_t *columns, uint64_t n_sites);
+typedef int (*v2m_site_rows_sink_fn)(void *user, uint64_t first_row, uint64_t n_rows, const char *bytes, uint64_t pitch, uint64_t n_sites);
+
+int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_SITES_SNP */,
+                       v2m_site_columns_sink_fn columns_sink /* may be NULL */, v2m_site_rows_sink_fn rows_sink /* may be NULL */, void *user,
+                       v2m_variable_sites_info *info /* may be NULL */);
+
+int v2m_variable_sites_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_SITES_SNP */,
+                              void *d_columns /* may be NULL */, void *d_bytes, uint64_t pitch, uint64_t *n_sites);
 
 /* ---- founder search: the chunk walks ---------------------------------- */
 

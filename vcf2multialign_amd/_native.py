@@ -49,6 +49,12 @@ DIST_ACGT_ONLY = 0x20
 PAIR_DISTANCES_MAX_ROWS = 32768
 PAIR_TILE = 64
 PAIR_CHUNK_WORDS = 8
+# v2m_variable_sites[_device]: the one flag, and csrc/site_kernels.hpp's kGatherSites (sites a lane owns), kGatherThreads (lanes of a
+# workgroup) and kGatherMinGroupRows (the fewest rows of a row group); tests/test_variable_sites_host.py holds them to the sources
+SITES_SNP = 0x40
+GATHER_SITES = 4
+GATHER_THREADS = 256
+GATHER_MIN_GROUP_ROWS = 16
 # csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
 # kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
 DISTINCT_CHUNK_BYTES = 8192
@@ -108,7 +114,12 @@ COLUMN_COUNTS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 class PairDistancesInfo(C.Structure):   # v2m_pair_distances_info
 	_fields_ = [("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("n_passes", C.c_uint64), ("counts_ms", C.c_double), ("pack_ms", C.c_double), ("pairs_ms", C.c_double)]
 
+class VariableSitesInfo(C.Structure):   # v2m_variable_sites_info
+	_fields_ = [("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("counts_ms", C.c_double), ("gather_ms", C.c_double)]
 
+
+SITE_COLUMNS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_site_columns_sink_fn
+SITE_ROWS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_site_rows_sink_fn
 TRIALS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_trials_sink
 
 # every symbol include/v2m_hip.h declares: (restype, argtypes)
@@ -148,6 +159,8 @@ SIGNATURES = {
 	"v2m_column_counts_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64]),
 	"v2m_pair_distances": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.POINTER(PairDistancesInfo)]),
 	"v2m_pair_distances_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64]),
+	"v2m_variable_sites": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, SITE_COLUMNS_SINK_FN, SITE_ROWS_SINK_FN, C.c_void_p, C.POINTER(VariableSitesInfo)]),
+	"v2m_variable_sites_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -463,6 +463,65 @@ class Context:
 			rows = RowBatch(rows)
 		self._check(self._lib.v2m_pair_distances_device(self._h, C.byref(rows.struct), N.DIST_ACGT_ONLY if acgt_only else 0, ptr, pitch))
 
+	def variable_sites(self, rows, snp_only=False, info=False):
+		"""v2m_variable_sites: (columns np.uint64[V], bytes np.uint8[n, V]) -- the rows of the batch cut down to the variable columns of
+		the view in force (the whole row, or the column window), byte for byte; `columns` are absolute and ascend.  snp_only
+		(V2M_SITES_SNP): only the columns where at least two of A, C, G, T occur.  With info=True: (columns, bytes, dict of
+		v2m_variable_sites_info's fields).  self.variable_sites_blocks: the (first_row, n_rows) of the blocks the rows arrived in."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = int(rows.struct.n_rows)
+		columns, blocks, error = [], [], []
+
+		def _columns(_user, cols, n_sites):
+			try:
+				columns.append(np.frombuffer(C.string_at(cols, 8 * n_sites), dtype=np.uint64).copy())
+				return 0
+			except BaseException as e:  # propagate through the C frame as V2M_ERR_SINK
+				error.append(e)
+				return 1
+
+		def _rows(_user, first_row, n_rows, data, pitch, n_sites):
+			try:
+				if not columns:
+					raise AssertionError("rows before the columns")
+				a = np.frombuffer(C.string_at(data, (n_rows - 1) * pitch + n_sites), dtype=np.uint8)
+				a = np.lib.stride_tricks.as_strided(a, shape=(n_rows, n_sites), strides=(pitch, 1)).copy()
+				blocks.append((int(first_row), a))
+				return 0
+			except BaseException as e:
+				error.append(e)
+				return 1
+
+		record = N.VariableSitesInfo()
+		rc = self._lib.v2m_variable_sites(self._h, C.byref(rows.struct), N.SITES_SNP if snp_only else 0, N.SITE_COLUMNS_SINK_FN(_columns), N.SITE_ROWS_SINK_FN(_rows), None, C.byref(record))
+		if error:
+			raise error[0]
+		self._check(rc)
+		if len(columns) > 1:
+			raise AssertionError("the columns arrived %d times" % len(columns))
+		self.variable_sites_blocks = [(first, len(a)) for first, a in blocks]
+		cols = columns[0] if columns else np.zeros(0, dtype=np.uint64)
+		data = np.concatenate([a for _, a in blocks]) if blocks else np.zeros((n, 0), dtype=np.uint8)
+		if n == 0:
+			record.n_columns = self.window_length   # (with no rows the call returns before it writes the info)
+		if info:
+			return cols, data, {name: getattr(record, name) for name, _ in N.VariableSitesInfo._fields_}
+		return cols, data
+
+	def variable_sites_device(self, rows, ptr, pitch, columns_ptr=None, snp_only=False):
+		"""v2m_variable_sites_device: the rows' bytes at the sites into device memory at `ptr`, u8[n][pitch] (16-byte aligned, pitch a
+		multiple of 16), and the view-relative columns into u32[pitch] at `columns_ptr` when given.  Returns V, the number of sites; with
+		V > pitch the call raises (self.variable_sites_count then holds V) and has written nothing."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		count = C.c_uint64(0)
+		self.variable_sites_count = None
+		rc = self._lib.v2m_variable_sites_device(self._h, C.byref(rows.struct), N.SITES_SNP if snp_only else 0, columns_ptr, ptr, pitch, C.byref(count))
+		self.variable_sites_count = int(count.value)
+		self._check(rc)
+		return int(count.value)
+
 	def bgzf_compress(self, data):
 		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
 		src = bytes(data)

@@ -479,4 +479,19 @@ int64_t v2mh_distances_text(char const *const *ids, uint64_t n_rows, uint32_t co
 	}
 }
 
+// site_positions_text() of output.hh (no GPU), handed over as v2mh_column_counts_text hands over its table; -1 with a message in err
+// on failure.
+int64_t v2mh_site_positions_text(uint64_t const *columns, uint64_t n_sites, uint64_t const *reference_positions, uint64_t const *aligned_positions, uint64_t node_count,
+	char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		std::string const text(vh::site_positions_text(columns, n_sites, reference_positions, aligned_positions, node_count));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
 } // extern "C"

@@ -57,6 +57,9 @@ struct options {
 	char const *output_column_counts{};   // --output-column-counts=FILE: base counts per variable alignment column, from v2m_column_counts
 	char const *output_distances{};       // --output-distances=FILE: the matrix of pairwise distances between the output rows, from v2m_pair_distances
 	bool acgt_only{};                     // --acgt-only (with --output-distances): only columns where both rows hold A, C, G or T count
+	char const *output_variable_sites{};  // --output-variable-sites=FILE: the output rows cut down to the variable columns, as FASTA, from v2m_variable_sites
+	char const *output_site_positions{};  // --output-site-positions=FILE (with --output-variable-sites): the column and the reference position of every site
+	bool snp_sites{};                     // --snp-sites (with --output-variable-sites): only columns where at least two of A, C, G, T occur
 	bool all_columns{};                   // --all-columns (with --output-column-counts): every column, not only the variable ones
 	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
 	std::vector<int> devices{0};
@@ -125,6 +128,16 @@ void usage()
 		"                                     says; --region restricts the columns.  Alone or beside the other outputs; not with\n"
 		"                                     --regions-file or several --device entries\n"
 		"      --acgt-only                    With --output-distances: count only the columns where both sequences hold A, C, G or T\n"
+		"      --output-variable-sites=FILE   Write a FASTA file with the output sequences (REF first, unless --omit-reference) cut down\n"
+		"                                     to the variable alignment columns, gathered on the GPU: the -s file with every sequence\n"
+		"                                     line reduced to the columns in which the sequences differ by class (A, C, G, T, N --\n"
+		"                                     either case --, gap, other), as snp-sites makes it from a multi-FASTA.  Always of the\n"
+		"                                     aligned form, whatever --unaligned says; --region restricts the columns.  Alone or beside\n"
+		"                                     the other outputs; not with --regions-file or several --device entries\n"
+		"      --snp-sites                    With --output-variable-sites: keep only the columns where at least two of A, C, G, T\n"
+		"                                     occur (snp-sites' rule); columns that vary only by gap, N or other bytes are left out\n"
+		"      --output-site-positions=FILE   With --output-variable-sites: write one line per kept column, `column<TAB>reference\n"
+		"                                     position` (the first two fields of its --output-column-counts line)\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -311,7 +324,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -323,7 +336,7 @@ int main(int argc, char **argv)
 		{"ref-mismatch-handling", required_argument, nullptr, o_mismatch}, {"include-samples", required_argument, nullptr, o_include},
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
-		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct}, {"output-paf", required_argument, nullptr, o_output_paf}, {"output-column-counts", required_argument, nullptr, o_output_column_counts}, {"all-columns", no_argument, nullptr, o_all_columns}, {"output-distances", required_argument, nullptr, o_output_distances}, {"acgt-only", no_argument, nullptr, o_acgt_only},
+		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct}, {"output-paf", required_argument, nullptr, o_output_paf}, {"output-column-counts", required_argument, nullptr, o_output_column_counts}, {"all-columns", no_argument, nullptr, o_all_columns}, {"output-distances", required_argument, nullptr, o_output_distances}, {"acgt-only", no_argument, nullptr, o_acgt_only}, {"output-variable-sites", required_argument, nullptr, o_output_variable_sites}, {"snp-sites", no_argument, nullptr, o_snp_sites}, {"output-site-positions", required_argument, nullptr, o_output_site_positions},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -377,6 +390,9 @@ int main(int argc, char **argv)
 			case o_all_columns: opt.all_columns = true; break;
 			case o_output_distances: opt.output_distances = optarg; break;
 			case o_acgt_only: opt.acgt_only = true; break;
+			case o_output_variable_sites: opt.output_variable_sites = optarg; break;
+			case o_snp_sites: opt.snp_sites = true; break;
+			case o_output_site_positions: opt.output_site_positions = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -429,6 +445,13 @@ int main(int argc, char **argv)
 		// one matrix from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
 		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
 		if (other) { std::cerr << "ERROR: --output-distances cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+	}
+	if (opt.snp_sites && !opt.output_variable_sites) { std::cerr << "ERROR: --snp-sites requires --output-variable-sites.\n"; return EXIT_FAILURE; }
+	if (opt.output_site_positions && !opt.output_variable_sites) { std::cerr << "ERROR: --output-site-positions requires --output-variable-sites.\n"; return EXIT_FAILURE; }
+	if (opt.output_variable_sites) {
+		// one set of sites from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
+		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
+		if (other) { std::cerr << "ERROR: --output-variable-sites cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
 	}
 	if (opt.region && !parse_region(opt.region, opt.region_start, opt.region_end)) {
 		std::cerr << "ERROR: --region must be START-END with 1 <= START <= END (1-based, inclusive), got \"" << opt.region << "\".\n";
@@ -669,6 +692,11 @@ int main(int argc, char **argv)
 			if (opt.output_distances) {
 				std::cerr << "Outputting distances..." << std::flush;
 				output.output_distances(graph, opt.output_distances, opt.acgt_only, opt.verbose);
+				std::cerr << " Done.\n";
+			}
+			if (opt.output_variable_sites) {
+				std::cerr << "Outputting variable sites..." << std::flush;
+				output.output_variable_sites(graph, opt.output_variable_sites, opt.snp_sites, opt.output_site_positions, opt.verbose);
 				std::cerr << " Done.\n";
 			}
 		});

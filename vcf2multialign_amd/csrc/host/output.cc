@@ -1028,29 +1028,35 @@ void output::output_chain_and_paf(variant_graph const &graph, char const *chain_
 namespace {
 	// One line per record, appended to `text`.  `node` carries the graph position from one record to the next (records ascend; a
 	// record that does not is looked up afresh).
+	// The first two fields of a line: the column and the reference position the REF row holds there ('.' where it holds padding).
+	void append_column_and_position(std::string &text, u64 column, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count, u64 &node)
+	{
+		// the last node n with aligned_positions[n] <= column
+		if (node >= node_count || aligned_positions[node] > column)
+		{
+			u64 const above(u64(std::upper_bound(aligned_positions, aligned_positions + node_count, column) - aligned_positions));
+			node = above ? above - 1 : 0;
+		}
+		while (node + 1 < node_count && aligned_positions[node + 1] <= column) ++node;
+		text += std::to_string(column);
+		text += '\t';
+		bool has_ref(false);
+		if (node + 1 < node_count && aligned_positions[node] <= column) {
+			u64 const k(column - aligned_positions[node]);
+			if (k < reference_positions[node + 1] - reference_positions[node]) {
+				text += std::to_string(reference_positions[node] + k + 1);
+				has_ref = true;
+			}
+		}
+		if (!has_ref) text += '.';   // the REF row has padding there
+	}
+
 	void append_column_count_lines(std::string &text, u64 n_rows, v2m_column_count const *records, u64 n_records,
 		u64 const *reference_positions, u64 const *aligned_positions, u64 node_count, u64 &node)
 	{
 		for (u64 i(0); i < n_records; ++i) {
 			v2m_column_count const &rec(records[i]);
-			// the last node n with aligned_positions[n] <= column
-			if (node >= node_count || aligned_positions[node] > rec.column)
-			{
-				u64 const above(u64(std::upper_bound(aligned_positions, aligned_positions + node_count, rec.column) - aligned_positions));
-				node = above ? above - 1 : 0;
-			}
-			while (node + 1 < node_count && aligned_positions[node + 1] <= rec.column) ++node;
-			text += std::to_string(rec.column);
-			text += '\t';
-			bool has_ref(false);
-			if (node + 1 < node_count && aligned_positions[node] <= rec.column) {
-				u64 const k(rec.column - aligned_positions[node]);
-				if (k < reference_positions[node + 1] - reference_positions[node]) {
-					text += std::to_string(reference_positions[node] + k + 1);
-					has_ref = true;
-				}
-			}
-			if (!has_ref) text += '.';   // the REF row has padding there
+			append_column_and_position(text, rec.column, reference_positions, aligned_positions, node_count, node);
 			u64 sum(0);
 			for (u32 const c : rec.count) {
 				text += '\t';
@@ -1192,6 +1198,109 @@ void output::output_distances(variant_graph const &graph, char const *path, bool
 	output_distances(graph, stream, acgt_only, verbose);
 	stream.flush();
 	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+}
+
+
+// --- variable sites (--output-variable-sites) ---------------------------------------------------------------------
+std::string site_positions_text(u64 const *columns, u64 n_sites, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count)
+{
+	std::string text;
+	u64 node(0);
+	for (u64 i(0); i < n_sites; ++i) {
+		append_column_and_position(text, columns[i], reference_positions, aligned_positions, node_count, node);
+		text += '\n';
+	}
+	return text;
+}
+
+
+namespace {
+	struct variable_sites_state {
+		std::ostream *stream;
+		std::ostream *positions;
+		std::vector<std::string> const *ids;
+		variant_graph const *graph;
+		u64 next_row;
+		std::exception_ptr error;
+	};
+
+	int variable_sites_columns_sink(void *user, uint64_t const *columns, uint64_t n_sites)
+	{
+		auto &st(*static_cast<variable_sites_state *>(user));
+		if (!st.positions) return 0;
+		try {
+			std::string const text(site_positions_text(columns, n_sites, st.graph->reference_positions.data(), st.graph->aligned_positions.data(), st.graph->node_count()));
+			st.positions->write(text.data(), std::streamsize(text.size()));
+			return st.positions->good() ? 0 : 1;
+		} catch (...) {   // nothing may cross the C boundary
+			st.error = std::current_exception();
+			return 1;
+		}
+	}
+
+	int variable_sites_rows_sink(void *user, uint64_t first_row, uint64_t n_rows, char const *bytes, uint64_t pitch, uint64_t n_sites)
+	{
+		auto &st(*static_cast<variable_sites_state *>(user));
+		try {
+			if (first_row != st.next_row) throw std::runtime_error("the rows of the variable sites arrived out of order");
+			for (u64 r(0); r < n_rows; ++r) {
+				*st.stream << '>' << (*st.ids)[first_row + r] << '\n';   // as a2m_sink writes a row
+				st.stream->write(bytes + r * pitch, std::streamsize(n_sites));
+				*st.stream << '\n';
+			}
+			st.next_row = first_row + n_rows;
+			return st.stream->good() ? 0 : 1;
+		} catch (...) {
+			st.error = std::current_exception();
+			return 1;
+		}
+	}
+}
+
+
+void output::output_variable_sites(variant_graph const &graph, std::ostream &stream, bool snp_only, std::ostream *positions, bool verbose)
+{
+	if (!m_more_gpus.empty()) throw std::runtime_error("--output-variable-sites needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-variable-sites needs every chromosome copy on one GPU context");
+	row_set const rows(a2m_rows(graph));   // (the rows and the names of the -s file)
+	v2m_row_batch batch{};
+	batch.n_rows = rows.copy_index.size();
+	batch.copy_index = rows.copy_index.data();
+	if (rows.any_cuts) {
+		batch.cut_offsets = rows.cut_offsets.data();
+		batch.cut_nodes = rows.cut_nodes.data();
+		batch.cut_copies = rows.cut_copies.data();
+	}
+	variable_sites_state st{&stream, positions, &rows.ids, &graph, 0, nullptr};
+	v2m_variable_sites_info info{};
+	info.n_columns = v2m_window_length(m_gpu.get());
+	int const rc(v2m_variable_sites(m_gpu.get(), &batch, snp_only ? V2M_SITES_SNP : 0, variable_sites_columns_sink, variable_sites_rows_sink, &st, &info));
+	if (st.error) std::rethrow_exception(st.error);
+	m_gpu.check(rc);
+	if (0 == info.n_sites)   // no site, no delivery: every sequence line is empty
+		for (auto const &id : rows.ids) stream << '>' << id << "\n\n";
+	if (verbose)
+		std::fprintf(stderr, "Variable sites: %llu rows, %llu columns, %llu sites.\n", (unsigned long long) batch.n_rows, (unsigned long long) info.n_columns,
+			(unsigned long long) info.n_sites);
+}
+
+
+void output::output_variable_sites(variant_graph const &graph, char const *path, bool snp_only, char const *positions_path, bool verbose)
+{
+	std::ofstream stream(path, std::ios::binary | std::ios::trunc);
+	if (!stream) throw std::runtime_error(std::string("unable to open ") + path + " for writing");
+	std::ofstream positions;
+	if (positions_path) {
+		positions.open(positions_path, std::ios::binary | std::ios::trunc);
+		if (!positions) throw std::runtime_error(std::string("unable to open ") + positions_path + " for writing");
+	}
+	output_variable_sites(graph, stream, snp_only, positions_path ? &positions : nullptr, verbose);
+	stream.flush();
+	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+	if (positions_path) {
+		positions.flush();
+		if (!positions) throw std::runtime_error(std::string("error while writing ") + positions_path);
+	}
 }
 
 

@@ -73,6 +73,11 @@ std::string column_counts_text(u64 n_rows, v2m_column_count const *records, u64 
 // An id that holds a tab or a line break is refused.
 std::string distances_text(std::vector<std::string> const &ids, std::uint32_t const *dist, u64 n_columns, u64 n_sites, bool acgt_only);
 
+// The --output-site-positions file of the variable sites (include/v2m_hip.h, "variable sites"): one line per site,
+//   <column><TAB><reference position | .>
+// the first two fields of that column's line of column_counts_text, made by the same code.
+std::string site_positions_text(u64 const *columns, u64 n_sites, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -148,6 +153,13 @@ public:
 	// every copy.  acgt_only: V2M_DIST_ACGT_ONLY; verbose prints the rows, columns, sites and passes to stderr.
 	void output_distances(variant_graph const &graph, char const *path, bool acgt_only = false, bool verbose = false);
 	void output_distances(variant_graph const &graph, std::ostream &stream, bool acgt_only = false, bool verbose = false);
+
+	// --output-variable-sites: a FASTA file of the rows of the A2M output (REF first, unless omitted) under the names the -s file gives
+	// them, every sequence line cut down to the selected columns of the view in force (--region: the window's columns): the -s file
+	// with only its variable columns, from v2m_variable_sites on the first context, which must hold every copy.  snp_only:
+	// V2M_SITES_SNP; positions: site_positions_text above goes there; verbose prints the rows, columns and sites to stderr.
+	void output_variable_sites(variant_graph const &graph, char const *path, bool snp_only = false, char const *positions_path = nullptr, bool verbose = false);
+	void output_variable_sites(variant_graph const &graph, std::ostream &stream, bool snp_only = false, std::ostream *positions = nullptr, bool verbose = false);
 
 protected:
 	struct row_set {

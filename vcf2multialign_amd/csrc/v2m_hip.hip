@@ -31,6 +31,7 @@
 #include "bgzf_kernels.hpp"
 #include "vcf_kernels.hpp"
 #include "distance_kernels.hpp"
+#include "site_kernels.hpp"
 
 using v2m::u32;
 using v2m::u64;
@@ -265,6 +266,9 @@ struct v2m_ctx {
 	pinned_buf h_column_total;
 	// pair distances (v2m_pair_distances): the site list, a pass's bit planes, and the host form's matrix
 	scratch_buf d_dist_sites, d_dist_planes, d_dist_matrix;
+	// variable sites (v2m_variable_sites): the site list, the host form's gathered slices (two, used in turn), the list's pinned staging
+	scratch_buf d_site_columns, d_site_bytes[2];
+	pinned_buf h_site_columns;
 	// pinned slots: the rows of v2m_splice_rows[_held] (a slot is kept until the sink has released its rows); slots 0 and 1 also stage
 	// the BGZF members and v2m_upload_path_blocks' columns
 	held_ring_state held_state;
@@ -3501,6 +3505,216 @@ int v2m_pair_distances(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 	if (int const rc = pair_distances_run(ctx, rows, flags, ctx->d_dist_matrix.as<u32>(), pitch, info)) return rc;
 	V2M_HIP_TRY(ctx, hipMemcpy2D(dist, n * 4, ctx->d_dist_matrix.p, pitch * 4, n * 4, n, hipMemcpyDeviceToHost));
 	return V2M_OK;
+}
+
+
+// ---- variable sites (site_kernels.hpp) -------------------------------------------------------------
+
+namespace {
+
+int check_variable_sites(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, char const *name)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!rows) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "rows is NULL");
+	if (flags & ~u32(V2M_SITES_SNP)) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s takes 0 or 0x%x as flags (got 0x%x)", name, V2M_SITES_SNP, flags);
+	if (int const rc = check_batch(ctx, rows, 0)) return rc;
+	if (ctx->view().length() >= (u64(1) << 32))
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes a view of fewer than 2^32 columns (got %llu)", name, (unsigned long long) ctx->view().length());
+	return V2M_OK;
+}
+
+// Stage (1): the counts of the batch over the view in force and the selection into ctx->d_site_columns (u32[V], readable up to
+// (V + 3) & ~3 entries).  Completes on the stream; V to n_sites.  n_rows >= 1, L >= 1.
+int variable_sites_select(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, stage_times &times, u64 &n_sites)
+{
+	u64 const L(ctx->view().length()), n(rows->n_rows);
+	bool const snp(flags & V2M_SITES_SNP);
+	u64 const table_pitch((L + 3) & ~u64(3));
+	u64 const select_blocks((L + v2m::kSelectColumns - 1) / v2m::kSelectColumns);
+	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(V2M_COUNT_CLASSES * table_pitch * 4));
+	V2M_HIP_TRY(ctx, ctx->d_column_blocks.ensure(std::max<u64>(select_blocks * sizeof(u32), 16)));
+	V2M_HIP_TRY(ctx, ctx->d_column_total.ensure(sizeof(u64)));
+	V2M_HIP_TRY(ctx, ctx->h_column_total.ensure(2 * sizeof(u64)));
+	V2M_POISON_HOST(ctx->h_column_total.p, 2 * sizeof(u64));
+	u32 *const table(ctx->d_column_table.as<u32>());
+	u32 *const blocks(ctx->d_column_blocks.as<u32>());
+	times.begin(stage_times::counts);
+	int rc(column_counts_zero(ctx, table, table_pitch, L));
+	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, table, table_pitch);
+	if (V2M_OK != rc) return rc;
+	if (snp)
+		hipLaunchKernelGGL(v2m::count_snp_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream, table, table_pitch, L, blocks);
+	else
+		hipLaunchKernelGGL(v2m::count_variable_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+			table, table_pitch, u64(0), L, u32(n), 1u, blocks);
+	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, blocks, u32(select_blocks), ctx->d_column_total.as<u64>());
+	times.end();
+	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "variable sites: the site selection did not launch");
+	if (hipSuccess != hipMemcpyAsync(ctx->h_column_total.p, ctx->d_column_total.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
+		|| hipSuccess != hipStreamSynchronize(ctx->stream))
+		return fail(ctx, V2M_ERR_HIP, "variable sites: the site count did not arrive");
+	u64 const V(*ctx->h_column_total.as<u64>());
+	if (V > L) return fail(ctx, V2M_ERR_HIP, "the site selection counted %llu of %llu columns", (unsigned long long) V, (unsigned long long) L);
+	n_sites = V;
+	if (0 == V) return V2M_OK;
+	{
+		hipError_t const st(ctx->d_site_columns.ensure(((V + 3) & ~u64(3)) * sizeof(u32)));
+		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "variable sites: the site list: %s", hipGetErrorString(st));
+	}
+	u32 *const sites(ctx->d_site_columns.as<u32>());
+	times.begin(stage_times::counts);
+	if (snp)
+		hipLaunchKernelGGL(v2m::emit_snp_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream, table, table_pitch, L, blocks, sites, V);
+	else
+		hipLaunchKernelGGL(v2m::emit_site_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+			table, table_pitch, L, u32(n), blocks, sites, V);
+	times.end();
+	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "variable sites: the site list did not launch");
+	return V2M_OK;
+}
+
+// Stage (2) for rows [r0, r1) of the batch: the aligned splice into ring slot 0, then gather_sites_kernel into out, where batch row r
+// lands at out + (r - out_first_row) * out_pitch.  Queues only.
+int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_plan const &p, u64 r0, u64 r1, u64 V, char *out, u64 out_first_row, u64 out_pitch, stage_times &times)
+{
+	u64 const nr(r1 - r0);
+	{
+		hipError_t const st(ctx->ring[0].ensure(p.slot_bytes));   // (the slice takes its device slot: refilled in the checked build)
+		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "variable sites: the row slot: %s", hipGetErrorString(st));
+	}
+	char *const d_rows(ctx->ring[0].as<char>());
+	times.begin(stage_times::pack);   // (the second pass's stage, as the pair distances number it)
+	if (int const rc = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch)) return rc;
+	// row groups by pack_sites_kernel's rule: with few site blocks, as many as bring the launch to about four workgroups per compute
+	// unit, of at least kGatherMinGroupRows rows
+	u64 const block_sites(u64(v2m::kGatherThreads) * v2m::kGatherSites);
+	u64 const site_blocks((V + block_sites - 1) / block_sites);
+	u64 const want_groups((4 * u64(ctx->n_cus) + site_blocks - 1) / site_blocks);
+	u64 const per_group(std::max<u64>({u64(v2m::kGatherMinGroupRows), (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}));
+	u64 const groups((nr + per_group - 1) / per_group);
+	hipLaunchKernelGGL(v2m::gather_sites_kernel, dim3(unsigned(site_blocks), unsigned(groups)), dim3(v2m::kGatherThreads), 0, ctx->stream,
+		d_rows, p.pitch, u32(nr), u32(per_group), r0 - out_first_row, ctx->d_site_columns.as<u32>(), V, out, out_pitch);
+	times.end();
+	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "variable sites: gather_sites_kernel did not launch");
+	return V2M_OK;
+}
+
+void variable_sites_report(stage_times const &times, u64 V, u64 L, v2m_variable_sites_info *info)
+{
+	if (!info) return;
+	double ms[stage_times::n_stages] = {};
+	times.sum(ms);
+	*info = v2m_variable_sites_info{V, L, ms[stage_times::counts], ms[stage_times::pack]};
+}
+
+} // namespace
+
+int v2m_variable_sites_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, void *d_columns, void *d_bytes, uint64_t pitch, uint64_t *n_sites)
+{
+	if (int const rc = check_variable_sites(ctx, rows, flags, "v2m_variable_sites_device")) return rc;
+	if (!d_bytes) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_bytes is NULL");
+	if (!n_sites) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "n_sites is NULL");
+	if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_bytes must be 16-byte aligned");
+	if (reinterpret_cast<uintptr_t>(d_columns) & 3) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_columns must be 4-byte aligned");
+	if (pitch & 15) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "pitch %llu must be a multiple of 16", (unsigned long long) pitch);
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	u64 const L(ctx->view().length()), n(rows->n_rows);
+	stage_times times(ctx);
+	u64 V(0);
+	int rc(0 == L ? V2M_OK : variable_sites_select(ctx, rows, flags, times, V));
+	if (V2M_OK == rc) {
+		*n_sites = V;
+		if (V > pitch)
+			rc = fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%llu sites do not fit a pitch of %llu: size the buffers for n_sites = %llu and call again",
+				(unsigned long long) V, (unsigned long long) pitch, (unsigned long long) V);
+	}
+	if (V2M_OK == rc && V) {
+		if (d_columns && hipSuccess != hipMemcpyAsync(d_columns, ctx->d_site_columns.p, V * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream))
+			rc = fail(ctx, V2M_ERR_HIP, "variable sites: the site list could not be copied");
+		slice_plan const p(plan_slices(ctx, n, false));
+		for (u64 s(0); s < p.n_slices && V2M_OK == rc; ++s)
+			rc = variable_sites_gather_slice(ctx, rows, p, s * p.rows_per_slice, std::min(n, (s + 1) * p.rows_per_slice), V, static_cast<char *>(d_bytes), 0, pitch, times);
+	}
+	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
+	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
+	return rc;
+}
+
+int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_site_columns_sink_fn columns_sink, v2m_site_rows_sink_fn rows_sink, void *user,
+	v2m_variable_sites_info *info)
+{
+	if (int const rc = check_variable_sites(ctx, rows, flags, "v2m_variable_sites")) return rc;
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	u64 const L(ctx->view().length()), view_begin(ctx->view().begin), n(rows->n_rows);
+	stage_times times(ctx);
+	u64 V(0);
+	auto const finish([&](int rc) -> int {
+		// leave both streams idle whatever happened
+		hipError_t const st(hipStreamSynchronize(ctx->stream));
+		(void) hipStreamSynchronize(ctx->copy_stream);
+		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
+		if (V2M_OK == rc) variable_sites_report(times, V, L, info);
+		return rc;
+	});
+	if (0 == L) return finish(V2M_OK);
+	if (int const rc = variable_sites_select(ctx, rows, flags, times, V)) return finish(rc);
+	if (0 == V) return finish(V2M_OK);
+
+	// the site list: over the link as it is, widened to absolute columns on the host
+	if (columns_sink) {
+		if (hipSuccess != ctx->h_site_columns.ensure(V * sizeof(u32))) return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "variable sites: %llu bytes of pinned site list", (unsigned long long) (V * sizeof(u32))));
+		V2M_POISON_HOST(ctx->h_site_columns.p, V * sizeof(u32));
+		if (hipSuccess != hipMemcpyAsync(ctx->h_site_columns.p, ctx->d_site_columns.p, V * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream)
+			|| hipSuccess != hipStreamSynchronize(ctx->stream))
+			return finish(fail(ctx, V2M_ERR_HIP, "variable sites: the site list did not arrive"));
+		std::vector<u64> absolute(V);
+		u32 const *const relative(ctx->h_site_columns.as<u32>());
+		for (u64 i(0); i < V; ++i) absolute[i] = view_begin + relative[i];
+		if (columns_sink(user, absolute.data(), V)) return finish(fail(ctx, V2M_ERR_SINK, "sink aborted"));
+	}
+	if (!rows_sink) return finish(V2M_OK);
+
+	// Slice k is gathered into d_site_bytes[k & 1], crosses the link on the copy stream into pinned slot k & 1, and reaches the sink
+	// while slice k + 1 is spliced and gathered.  Both buffers of slice k are free again when slice k - 2 has been handed over,
+	// which waits for its copy on the host before slice k - 1 is queued.
+	slice_plan const p(plan_slices(ctx, n, false));
+	u64 const out_pitch((V + 15) & ~u64(15)), slice_bytes(p.rows_per_slice * out_pitch);
+	if (int const rc = ensure_host_slots(ctx, std::min<u64>(2, p.n_slices), slice_bytes)) return finish(rc);
+	auto const first_row([&](u64 s) { return s * p.rows_per_slice; });
+	auto const end_row([&](u64 s) { return std::min(n, (s + 1) * p.rows_per_slice); });
+	auto const issue([&](u64 s) -> int {
+		int const b(int(s & 1));
+		v2m_row_hold &slot(*ctx->host_slots[b]);
+		u64 const r0(first_row(s)), r1(end_row(s));
+		{
+			hipError_t const st(ctx->d_site_bytes[b].ensure(slice_bytes));   // (refilled per slice in the checked build)
+			if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "variable sites: %llu bytes of sites: %s", (unsigned long long) slice_bytes, hipGetErrorString(st));
+		}
+		V2M_POISON_HOST(slot.host.p, slice_bytes);
+		if (int const rc = variable_sites_gather_slice(ctx, rows, p, r0, r1, V, ctx->d_site_bytes[b].as<char>(), r0, out_pitch, times)) return rc;
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, ctx->d_site_bytes[b].p, (r1 - r0) * out_pitch, hipMemcpyDeviceToHost, ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
+		return V2M_OK;
+	});
+	auto const hand_over([&](u64 s) -> int {
+		v2m_row_hold &slot(*ctx->host_slots[s & 1]);
+		V2M_HIP_TRY(ctx, hipEventSynchronize(slot.copied));
+		if (rows_sink(user, first_row(s), end_row(s) - first_row(s), slot.host.as<char>(), out_pitch, V)) return fail(ctx, V2M_ERR_SINK, "sink aborted");
+		return V2M_OK;
+	});
+	int rc(V2M_OK);
+	u64 launched(0);
+	for (u64 s(0); s < p.n_slices && V2M_OK == rc; ++s) {
+		if (V2M_OK != (rc = issue(s))) break;
+		launched = s + 1;
+		if (s >= 1) rc = hand_over(s - 1);   // its copy ran under this slice's kernels
+	}
+	if (V2M_OK == rc && launched) rc = hand_over(launched - 1);
+	return finish(rc);
 }
 
 

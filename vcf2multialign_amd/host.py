@@ -76,6 +76,8 @@ def _load():
 		L.v2mh_column_counts_text.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_distances_text.restype = C.c_int64
 		L.v2mh_distances_text.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_site_positions_text.restype = C.c_int64
+		L.v2mh_site_positions_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -168,6 +170,24 @@ def distances_text(ids, dist, n_columns, n_sites, acgt_only=False):
 		raise ValueError(err.value.decode())
 	dst = C.create_string_buffer(max(1, size))
 	if size != L.v2mh_distances_text(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
+
+
+def site_positions_text(columns, reference_positions, aligned_positions):
+	"""The host library's formatter of --output-site-positions (csrc/host/output.cc: site_positions_text; no GPU): one line per absolute
+	aligned column, `column<TAB>reference position`, as bytes -- the first two fields of column_counts_text's line for that column."""
+	columns = np.ascontiguousarray(columns, dtype=np.uint64)
+	ref = np.ascontiguousarray(reference_positions, dtype=np.uint64)
+	aln = np.ascontiguousarray(aligned_positions, dtype=np.uint64)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (columns.ctypes.data if len(columns) else None, len(columns), ref.ctypes.data, aln.ctypes.data, len(aln))
+	size = L.v2mh_site_positions_text(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != L.v2mh_site_positions_text(*args, dst, size, err, len(err)):
 		raise ValueError(err.value.decode())
 	return dst.raw[:size]
 

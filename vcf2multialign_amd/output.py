@@ -89,6 +89,26 @@ class Output:
 		stream.write(host.distances_text(ids, dist, info["n_columns"], info["n_sites"], acgt_only))
 		return info
 
+	def _write_variable_sites(self, stream, ids, rows, graph, snp_only, positions):
+		"""--output-variable-sites: the FASTA of `rows` (those of output_a2m, under its names) cut down to the variable columns from
+		Context.variable_sites, over the region's columns when there is one; `positions`, a stream, receives host.site_positions_text.
+		Returns the info of the call."""
+		from . import host
+		if self.region is not None:
+			self.ctx.set_column_window(*columns_of_reference_range(graph.reference_positions, graph.aligned_positions, *self.region))
+		try:
+			columns, data, info = self.ctx.variable_sites(RowBatch(rows), snp_only=snp_only, info=True)
+		finally:
+			if self.region is not None:
+				self.ctx.set_column_window(0, self.ctx.aligned_length)
+		for name, body in zip(ids, data):
+			stream.write(b">" + name.encode() + b"\n")
+			stream.write(body.tobytes())
+			stream.write(b"\n")
+		if positions is not None:
+			positions.write(host.site_positions_text(columns, graph.reference_positions, graph.aligned_positions))
+		return info
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -145,6 +165,15 @@ class HaplotypeOutput(Output):
 				ids.append(self._chain_name("%s.%d" % (graph.sample_names[sample_idx], 1 + chr_copy_idx)))
 				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
 		return self._write_distances(stream, ids, rows, graph, acgt_only)
+
+	def output_variable_sites(self, graph, stream, snp_only=False, positions=None):
+		"""--output-variable-sites (with --snp-sites and --output-site-positions) for the rows of output_a2m under its names."""
+		ids, rows = ([self._fasta_id("REF")], [PLOIDY_MAX]) if self.should_output_reference else ([], [])
+		for sample_idx, sample in enumerate(graph.sample_names):
+			for chr_copy_idx in range(graph.sample_ploidy(sample_idx)):
+				ids.append(self._fasta_id("%s-%d" % (sample, 1 + chr_copy_idx)))
+				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
+		return self._write_variable_sites(stream, ids, rows, graph, snp_only, positions)
 
 	def output_chain(self, graph, stream):
 		"""--output-chain: the chains of the rows of output_a2m (without REF), named as one file per sequence would be."""
@@ -203,6 +232,17 @@ class FounderSequenceGreedyOutput(Output):
 			ids.append(self._chain_name(str(1 + col_idx)))
 			rows.append(list(zip(cut_positions[:-1], col)))
 		return self._write_distances(stream, ids, rows, graph, acgt_only)
+
+	def output_variable_sites(self, graph, cut_positions, assigned_samples_column_major, stream, snp_only=False, positions=None):
+		"""--output-variable-sites for the rows of output_a2m (REF first, unless omitted, then the founder rows) under its names."""
+		n_rows = len(cut_positions) - 1
+		n_founders = len(assigned_samples_column_major) // n_rows if n_rows else 0
+		ids, rows = ([self._fasta_id("REF")], [PLOIDY_MAX]) if self.should_output_reference else ([], [])
+		for col_idx in range(n_founders):
+			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
+			ids.append(self._fasta_id(str(1 + col_idx)))
+			rows.append(list(zip(cut_positions[:-1], col)))
+		return self._write_variable_sites(stream, ids, rows, graph, snp_only, positions)
 
 	def output_chain(self, graph, cut_positions, assigned_samples_column_major, stream):
 		"""--output-chain for the founder rows of output_a2m."""
