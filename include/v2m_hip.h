@@ -578,6 +578,93 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /
 int v2m_variable_sites_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_SITES_SNP */,
                               void *d_columns /* may be NULL */, void *d_bytes, uint64_t pitch, uint64_t *n_sites);
 
+/* ---- site LD ------------------------------------------------------------------------------------
+ *
+ * The alignment by pair of columns: linkage disequilibrium between nearby biallelic sites of the batch's rows, the four integer counts
+ * that r^2 is made of, as plink --r2 reports it for phased haplotypes.  The view is that of the column counts: the whole row, or the
+ * column window of v2m_set_column_window (a window set in force is ignored); L = v2m_window_length() columns.  Classes as above: 0-3 A,
+ * C, G, T; 4 N; 5 gap; 6 other.
+ * Sites.  Decided from the column counts of the batch alone: a column is a site when exactly two of the classes A, C, G, T have a
+ * non-zero count and both counts are >= min_allele_count (>= 1).  lo < hi are those two classes.  At a site a row is CALLED when its
+ * class is lo or hi and CARRIES when it is hi; rows of any other class (N, gap, other; case is ignored as the classes ignore it) are
+ * missing there.  V is the number of sites, ascending by column; with n_rows <= 1, V = 0.
+ * Pairs.  (s, t), site indices with s < t, t - s <= window_sites (1 ... V2M_SITE_LD_MAX_WINDOW) and, unless window_columns is 0,
+ * column[t] - column[s] <= window_columns: the candidates.  Over the batch rows (a repeated row counts every time; a row with cuts is the
+ * row it splices):
+ *   n      rows called at both sites          n_a    rows called at both that carry at s
+ *   n_ab   rows that carry at both            n_b    rows called at both that carry at t
+ * D = n n_ab - n_a n_b and den = n_a (n - n_a) n_b (n - n_b).  A pair is REPORTED iff den != 0 and D^2 min_r2_den >= min_r2_num den:
+ * compared exactly in integers (n_rows <= V2M_SITE_LD_MAX_ROWS = 32 768 keeps D^2 and den inside 64 bits; the two products are taken
+ * 128 bits wide), never in floating point; 1 <= min_r2_den <= 1 000 000 and 0 <= min_r2_num <= min_r2_den.  Reported pairs are
+ * delivered ascending by (s, t).  r^2 = D^2 / den as a floating-point number appears only where a caller prints it.
+ *
+ * Host form.  sites_sink is called once with all V site records, before any pair.  pairs_sink then receives blocks of reported pairs in
+ * order.  Both get library-owned pinned memory valid during the call only, and neither is ever called with n = 0.  Either sink may be NULL; a
+ * non-zero return is V2M_ERR_SINK.  info, which may be NULL, receives V, L, the reported pairs, the candidates, and -- while
+ * v2m_profile_enable is on, else 0 -- the stream time elapsed over the three stages, timed as the pair distances' stages are.
+ * Device form.  d_sites (v2m_ld_site[site_capacity]) and d_pairs (v2m_ld_pair[pair_capacity]) are 16-byte aligned; d_pairs may be
+ * NULL with pair_capacity 0, to ask for the counts only (then nothing is written to either buffer unless the call succeeds, which it
+ * does only when no pair is reported).  *n_sites and *n_pairs receive V and the number of reported pairs.  When V > site_capacity or
+ * the reported pairs exceed pair_capacity the call fails with V2M_ERR_INVALID_ARGUMENT, a message that names both numbers, both
+ * outputs set and nothing written; otherwise exactly records [0, V) and [0, n_pairs) are written.
+ * Errors, worded and ordered as for v2m_variable_sites: V2M_ERR_INVALID_ARGUMENT for NULL rows or params, parameters out of range, NULL
+ * outputs or misaligned buffers; V2M_ERR_UNSUPPORTED, with a message that names the limit, for more rows than V2M_SITE_LD_MAX_ROWS,
+ * L >= 2^32 (both before any device work) or planes beyond the budget (below; before any device work beyond the counts);
+ * V2M_ERR_STATE without a graph; V2M_ERR_PRECONDITION for bad cuts.  n_rows == 0 returns V2M_OK and touches nothing.  Both forms are
+ * synchronous.  The column window and the window set are left as they were, and so is what v2m_column_counts returns afterwards.
+ * How (csrc/ld_kernels.hpp).  (1) The column counts into the context's table; count_ld_columns_kernel / scan_tile_counts_kernel /
+ * emit_ld_columns_kernel make the site list and the records.  (2) A second pass over the row slices: per slice the aligned splice, then
+ * ld_pack_kernel ORs the rows' called and carries bits into two bit planes by site over rows, u64[row word][2][V rounded up to 64],
+ * 16 * V_pad * ceil(n_rows / 64) bytes.  V2M_SITE_LD_PLANE_BYTES (environment, read per call; default 16 GiB) bounds them: beyond it
+ * the call is V2M_ERR_UNSUPPORTED with the bytes needed in the message.  (3) ld_pairs_kernel<false>, a workgroup a tile of 64 x 64
+ * sites of the band, AND + popcount with the row words through LDS, counts the reported pairs per (site, tile);
+ * scan_tile_counts_kernel turns the counts of a strip of 64 sites into offsets; ld_pairs_kernel<true> computes the tiles that hold a
+ * pair again and writes every pair at its rank: the order (s, t) with no sort.  The host form emits ranges of whole strips whose
+ * records fit V2M_SITE_LD_BLOCK_BYTES (environment, read per call; default 64 MiB, at least one strip) into two buffers in turn; a
+ * range crosses the link on the copy stream while the next is emitted.  No V2M_KERNEL_* ids: V2M_KERNEL_LIMIT keeps its value. */
+#define V2M_SITE_LD_MAX_WINDOW 4096u
+#define V2M_SITE_LD_MAX_ROWS 32768u
+
+typedef struct {
+	uint32_t window_sites;       /* 1 ... V2M_SITE_LD_MAX_WINDOW */
+	uint32_t min_allele_count;   /* >= 1 */
+	uint32_t min_r2_num;         /* 0 ... min_r2_den */
+	uint32_t min_r2_den;         /* 1 ... 1 000 000 */
+	uint64_t window_columns;     /* 0: no limit */
+} v2m_site_ld_params;    /* 24 bytes */
+
+typedef struct {
+	uint64_t column;             /* absolute aligned column */
+	uint32_t class_lo, class_hi; /* the two classes, lo < hi, of 0-3 */
+	uint32_t count_lo, count_hi; /* their counts over the batch */
+} v2m_ld_site;           /* 24 bytes */
+
+typedef struct {
+	uint32_t site_a, site_b;     /* s < t: indices into the site records */
+	uint32_t n, n_a, n_b, n_ab;
+} v2m_ld_pair;           /* 24 bytes */
+
+typedef struct {
+	uint64_t n_sites;     /* V */
+	uint64_t n_columns;   /* L */
+	uint64_t n_pairs;     /* reported pairs */
+	uint64_t n_candidates;/* pairs that satisfy the two window limits */
+	double counts_ms;     /* column counts + site selection: stream time elapsed over the stage */
+	double pack_ms;       /* splices of the second pass + ld_pack_kernel */
+	double pairs_ms;      /* ld_pairs_kernel<false>, the scan, ld_pairs_kernel<true> */
+} v2m_site_ld_info;      /* 56 bytes */
+
+typedef int (*v2m_ld_sites_sink_fn)(void *user, const v2m_ld_site *sites, uint64_t n);
+typedef int (*v2m_ld_pairs_sink_fn)(void *user, const v2m_ld_pair *pairs, uint64_t n);
+
+int v2m_site_ld(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_site_ld_params *params,
+                v2m_ld_sites_sink_fn sites_sink /* may be NULL */, v2m_ld_pairs_sink_fn pairs_sink /* may be NULL */, void *user,
+                v2m_site_ld_info *info /* may be NULL */);
+
+int v2m_site_ld_device(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_site_ld_params *params,
+                       void *d_sites, uint64_t site_capacity, void *d_pairs /* may be NULL with capacity 0 */, uint64_t pair_capacity,
+                       uint64_t *n_sites, uint64_t *n_pairs);
+
 /* ---- founder search: the chunk walks ---------------------------------- */
 
 /* The edge-by-edge part of find_initial_cut_positions_lambda_min (libvcf2multialign/find_cut_positions.cc:126-176): the pBWT

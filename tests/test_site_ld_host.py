@@ -1,0 +1,339 @@
+"""The model of the site LD (tests/site_ld_model.py) held to identities it must satisfy, its corpus held to the seams it is there for, the
+host library's text against the model's, the header, the Python surface and the driver's argument errors.  No GPU."""
+
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import column_counts_model as CM
+import pair_distances_model as PM
+import site_ld_model as LM
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CLI = os.path.join(ROOT, "vcf2multialign_amd", "bin", "vcf2multialign")
+FIX = os.path.join(HERE, "golden", "reference-fixtures", "variant-graph")
+T, CHUNK = LM.kernel_constants()
+
+
+def _header():
+	with open(os.path.join(ROOT, "include", "v2m_hip.h")) as f:
+		return f.read()
+
+
+@pytest.fixture(scope="module")
+def modelled():
+	"""[(item, classes, site records, pairs of every candidate, reported)] of the corpus."""
+	out = []
+	for item in LM.corpus():
+		cls = PM.classes(CM.matrix(item.g, item.rows, item.window))
+		records, pairs, keep = LM.evaluate(cls, item.params, item.window[0] if item.window else 0)
+		out.append((item, cls, records, pairs, keep))
+	return out
+
+
+def den_of(p):
+	return LM.d_and_den(p["n"], p["n_a"], p["n_b"], p["n_ab"])[1]
+
+
+# ---- the model -------------------------------------------------------------------------------------------------------------------------------
+
+def test_count_identities(modelled):
+	for item, cls, records, pairs, keep in modelled:
+		n_rows = len(item.rows)
+		for p in pairs:
+			assert p["n_ab"] <= min(p["n_a"], p["n_b"]) <= max(p["n_a"], p["n_b"]) <= p["n"] <= n_rows, (item.name, p)
+			assert p["site_a"] < p["site_b"] <= p["site_a"] + item.params.window_sites
+		assert np.array_equal(pairs[["site_a", "site_b"]], np.sort(pairs[["site_a", "site_b"]], order=["site_a", "site_b"]))      # ascending by (s, t)
+		if len(records):
+			assert (np.diff(records["column"].astype(np.int64)) > 0).all() and (records["class_lo"] < records["class_hi"]).all() and (records["class_hi"] < 4).all()
+			assert (np.minimum(records["count_lo"], records["count_hi"]) >= item.params.min_allele_count).all()
+		if n_rows <= 1:
+			assert len(records) == 0
+		assert LM.expected(item)[2] == len(pairs)
+
+
+def test_swapping_the_alleles_changes_no_report(modelled):
+	"""With lo and hi exchanged at a site, n_a becomes n - n_a (or n_b, n - n_b) and n_ab follows; D changes its sign at most and den
+	stays: the reported set is the same."""
+	for item, cls, records, pairs, keep in modelled:
+		if not len(records):
+			continue
+		called, carries = LM.planes(cls, records, item.window[0] if item.window else 0)
+		flipped = carries.copy()
+		flipped[:, ::2] = called[:, ::2] & ~carries[:, ::2]
+		n, n_a, n_b, n_ab = LM.pair_counts(called, flipped)
+		again = np.array([LM.is_reported(n[s, t], n_a[s, t], n_b[s, t], n_ab[s, t], item.params.min_r2) for s, t in pairs[["site_a", "site_b"]].tolist()], dtype=bool)
+		assert np.array_equal(again, keep), item.name
+
+
+def test_without_missing_data_every_row_is_called():
+	choice = (LM.random_graph(40, seed=2).choice != 0).astype(np.int64)      # the missing bytes turned into the other base
+	choice[:, 7] = 0
+	choice[0, 7] = 1
+	g = LM.graph_from_choice(choice, name="complete")
+	rows = list(range(LM.N_COPIES))
+	records, pairs, _ = LM.evaluate(PM.classes(CM.matrix(g, rows)), LM.Params(min_r2=(0, 1)))
+	assert len(records) == 40 and len(pairs) == 40 * 39 // 2 and (pairs["n"] == len(rows)).all()
+	assert np.array_equal(records["count_lo"] + records["count_hi"], np.full(40, len(rows)))
+
+
+def test_the_numbers_of_the_sites_graph():
+	"""pair_distances_model.sites_graph(40, 12, 11) with all 12 copies: 25 sites among 44 columns, 140 reported pairs at r^2 >= 1/5 (139
+	of them with missing rows), 8 of them exactly on the threshold, and no pair with den = 0."""
+	item = next(i for i in LM.corpus() if i.name == "pm_sites")
+	records, reported, n_candidates, L = LM.expected(item)
+	assert (len(records), L, len(reported), n_candidates) == (25, 44, 140, 300)
+	assert sum(1 for p in reported if p["n"] < 12) == 139
+	assert sum(1 for p in reported if 5 * LM.d_and_den(p["n"], p["n_a"], p["n_b"], p["n_ab"])[0] ** 2 == den_of(p)) == 8
+	_, pairs, _ = LM.evaluate(PM.classes(CM.matrix(item.g, item.rows)), item.params)
+	assert all(den_of(p) for p in pairs)
+
+
+def test_the_ld_graph():
+	records, pairs, keep = LM.evaluate(PM.classes(CM.matrix(LM.ld_graph(), LM.LD_ROWS)), LM.Params(min_r2=(1, 1)))
+	by = {(int(p["site_a"]), int(p["site_b"])): p for p in pairs}
+	assert len(records) == 7
+	for s, t in ((0, 1), (0, 2), (1, 2)):      # perfect LD, with D of either sign
+		d, den = LM.d_and_den(*[by[s, t][k] for k in ("n", "n_a", "n_b", "n_ab")])
+		assert d * d == den != 0
+	assert LM.d_and_den(*[by[0, 1][k] for k in ("n", "n_a", "n_b", "n_ab")])[0] > 0 > LM.d_and_den(*[by[0, 2][k] for k in ("n", "n_a", "n_b", "n_ab")])[0]
+	assert {(int(p["site_a"]), int(p["site_b"])) for p in pairs[keep]} == {(0, 1), (0, 2), (1, 2)}
+	for s in (0, 1, 2):                        # the rows called at both sites are monomorphic at s
+		assert den_of(by[s, 4]) == 0 and by[s, 4]["n"] == 4
+	assert LM.d_and_den(*[by[0, 5][k] for k in ("n", "n_a", "n_b", "n_ab")])[0] == 0 != den_of(by[0, 5])
+	# one row apart; at site 3 the reference's T is hi, so the five rows that keep the reference carry: D = 8 - 20, r^2 = 144 / 240 = 3 / 5
+	assert tuple(int(by[0, 3][k]) for k in ("n", "n_a", "n_b", "n_ab")) == (8, 4, 5, 1) and LM.lowest_terms(by[0, 3]) == (3, 5)
+	assert by[0, 6]["n"] < 8
+
+
+# ---- the corpus cannot hide a failure --------------------------------------------------------------------------------------------------------
+
+def test_the_corpus_holds_what_it_is_for(modelled):
+	by_name = {item.name: (item, cls, records, pairs, keep) for item, cls, records, pairs, keep in modelled}
+	# reported and unreported candidates, ties, den = 0 and missing rows
+	assert any(keep.any() and not keep.all() for _, _, _, _, keep in modelled)
+	ties = den0 = missing = 0
+	for item, cls, records, pairs, keep in modelled:
+		num, den = item.params.min_r2
+		for p, k in zip(pairs, keep):
+			d, dn = LM.d_and_den(p["n"], p["n_a"], p["n_b"], p["n_ab"])
+			ties += int(dn != 0 and num and d * d * den == num * dn)
+			den0 += int(dn == 0)
+			missing += int(k and p["n"] < len(item.rows))
+	assert ties > 20 and den0 > 20 and missing > 100, (ties, den0, missing)
+	# a tie of each graph under a threshold of its own, strictly inside (0, 1)
+	for name, g, rows in (("ld_graph", LM.ld_graph(), LM.LD_ROWS), ("random_40", LM.random_graph(40, seed=2), LM.all_rows(LM.random_graph(40, seed=2)))):
+		num, den = LM.tie_threshold(g, rows)
+		assert 0 < num < den and math.gcd(num, den) == 1
+		item, _, _, pairs, keep = by_name["%s_r2_%d_%d" % (name, num, den)]
+		on = [k for p, k in zip(pairs, keep) if den_of(p) and LM.lowest_terms(p) == (num, den)]
+		assert on and all(on)
+		assert {"%s_r2_0_1" % name, "%s_r2_1_1" % name, "%s_r2_1_5" % name} <= set(by_name)
+	assert by_name["random_40_r2_0_1"][4].sum() > by_name["random_40_r2_1_5"][4].sum() > by_name["random_40_r2_27_55"][4].sum() > 0 == by_name["random_40_r2_1_1"][4].sum()
+	assert by_name["ld_graph_r2_1_1"][4].sum() == 3
+	# the site counts
+	counts = {len(records) for _, _, records, _, _ in modelled}
+	assert {0, 1, 2, T - 1, T, T + 1, 2 * T + 1} <= counts
+	for V in LM.site_counts():
+		assert len(by_name["sites_%d" % V][2]) == V
+	# the band: every size, each excluding what the next one takes in until the window holds every site
+	sizes = LM.window_sizes()
+	assert {1, T - 1, T, T + 1, LM.MAX_WINDOW} <= set(sizes)
+	taken = [len(by_name["window_sites_%d" % w][3]) for w in sizes]
+	V = len(by_name["window_sites_1"][2])
+	assert V == 2 * T + 1 and taken[0] == V - 1 and taken == sorted(taken) and len(set(taken[:5])) == 5 and taken[-1] == taken[-2] == V * (V - 1) // 2
+	assert [int(by_name["window_sites_%d" % w][4].sum()) for w in sizes] == sorted(int(by_name["window_sites_%d" % w][4].sum()) for w in sizes)
+	# the row counts, a repeated row and rows with cuts
+	rows = {len(item.rows) for item, *_ in modelled}
+	assert {1, 2, 63, 64, 65, 64 * CHUNK - 1, 64 * CHUNK, 64 * CHUNK + 1, 128 * CHUNK + 1} <= rows
+	item = by_name["rows_%d" % (128 * CHUNK + 1)][0]
+	assert sum(isinstance(r, list) for r in item.rows[:20]) == 3 and item.rows[3] == item.rows[13] == 3
+	assert len(by_name["rows_1"][2]) == 0 and 0 < len(by_name["rows_2"][2]) < len(by_name["rows_63"][2]) == T + 1
+	# the column distance: the exact one of a pair, and one less, which excludes that pair and others; both limits together
+	a, b, c = (by_name[n] for n in ("window_columns_18", "window_columns_17", "window_columns_and_sites"))
+	cols = a[2]["column"].astype(np.int64)
+	assert int(cols[9] - cols[3]) == 18 == a[0].params.window_columns
+	in_a, in_b = {(int(p["site_a"]), int(p["site_b"])) for p in a[3]}, {(int(p["site_a"]), int(p["site_b"])) for p in b[3]}
+	assert (3, 9) in in_a and (3, 9) not in in_b and in_b < in_a
+	assert all(cols[t] - cols[s] <= 18 for s, t in in_a) and (3, 10) not in in_a
+	in_c = {(int(p["site_a"]), int(p["site_b"])) for p in c[3]}
+	assert in_c < in_a and all(t - s <= 4 for s, t in in_c) and any(t - s > 4 for s, t in in_a)
+	# the allele count excludes sites
+	one, two = by_name["min_count_1"], by_name["min_count_2"]
+	assert len(two[2]) < len(one[2]) and set(two[2]["column"].tolist()) < set(one[2]["column"].tolist())
+	assert (np.minimum(one[2]["count_lo"], one[2]["count_hi"]) == 1).any() and (np.minimum(two[2]["count_lo"], two[2]["count_hi"]) >= 2).all()
+	# sites whose REFERENCE carries (hi), in either case
+	item, cls, records, _, _ = by_name["sites_%d" % T]
+	ref_cls = PM.classes(np.frombuffer(item.g.ref.encode() if isinstance(item.g.ref, str) else item.g.ref, dtype=np.uint8))
+	hi_is_ref = records["class_hi"] == ref_cls[records["column"].astype(np.int64)]
+	assert hi_is_ref.any() and not hi_is_ref.all()
+	# the hostile bytes: every class and case decides a call somewhere
+	for s in CM.HOSTILE_SHIFTS:
+		assert len(by_name["hostile_%d" % s][2]) == 1
+	assert len(by_name["all_other"][2]) == 0
+
+
+def test_the_windows(modelled):
+	g = LM.window_graph()
+	whole = LM.sites(PM.classes(CM.matrix(g, LM.all_rows(g))))["column"].astype(np.int64).tolist()
+	ws = [item.window for item, *_ in modelled if item.window]
+	assert ws == LM.windows()
+	assert {b % 4 for b, _ in ws} == {e % 4 for _, e in ws} == {0, 1, 2, 3}
+	assert any(b in whole for b, e in ws) and any(e - 1 in whole for b, e in ws) and sum(1 for b, e in ws if not any(b <= c < e for c in whole)) >= 2
+	for item, cls, records, pairs, keep in modelled:
+		if item.window:
+			b, e = item.window
+			assert records["column"].astype(np.int64).tolist() == [c for c in whole if b <= c < e]      # absolute columns
+
+
+# ---- the text --------------------------------------------------------------------------------------------------------------------------------
+
+def test_site_ld_text():
+	from vcf2multialign_amd import host
+	for name in ("ld_graph_r2_0_1", "random_40_r2_1_5", "window_columns_17", "min_count_2", "hostile_1", "all_other"):
+		item = next(i for i in LM.corpus() if i.name == name)
+		records, pairs, _, L = LM.expected(item)
+		got = host.site_ld_text(len(item.rows), L, records, pairs, item.g.reference_positions, item.g.aligned_positions, **item.params.kwargs())
+		want = LM.text(item.g, len(item.rows), L, records, pairs, item.params)
+		assert got == want, (name, got.decode(), want.decode())
+		assert got == LM.file_text(item.g, item.rows, item.window, item.params)
+		lines = got.decode().splitlines()
+		assert len(lines) == 2 + len(pairs) and lines[1] == "#column_a\tpos_a\tcolumn_b\tpos_b\tn\tn_a\tn_b\tn_ab\tr2"
+	# r2: the quotient of the two integers as doubles, six decimals
+	item = next(i for i in LM.corpus() if i.name == "ld_graph_r2_0_1")
+	records, pairs, _, L = LM.expected(item)
+	text = host.site_ld_text(8, L, records, pairs, item.g.reference_positions, item.g.aligned_positions, min_r2=(0, 1)).decode().splitlines()[2:]
+	r2 = {tuple(int(x) for x in (line.split("\t")[0], line.split("\t")[2])): line.split("\t")[-1] for line in text}
+	cols = [int(c) for c in records["column"]]
+	assert r2[cols[0], cols[1]] == "1.000000" and r2[cols[0], cols[3]] == "0.600000" and r2[cols[0], cols[5]] == "0.000000"
+	# a padding column has no reference position
+	g = PM.row_count_graph()
+	item = next(i for i in LM.corpus() if i.name == "pm_sites")
+	records, pairs, _, L = LM.expected(item)
+	got = host.site_ld_text(12, L, records, pairs, g.reference_positions, g.aligned_positions, window_sites=LM.MAX_WINDOW)
+	assert got == LM.text(g, 12, L, records, pairs, item.params)
+	# a pair the library never reports is refused
+	bad = np.array([(0, 1, 4, 0, 2, 0)], dtype=LM.PAIR_DTYPE)
+	with pytest.raises(ValueError):
+		host.site_ld_text(8, L, records, bad, g.reference_positions, g.aligned_positions)
+	with pytest.raises(ValueError):
+		host.site_ld_text(8, L, records[:1], pairs[:1], g.reference_positions, g.aligned_positions)
+
+
+def test_parse_decimal_fraction():
+	from vcf2multialign_amd import host
+	for text, want in (("0", (0, 1)), ("1", (1, 1)), ("0.2", (1, 5)), ("0.20", (1, 5)), ("0.", (0, 1)), ("1.000000", (1, 1)), ("0.000001", (1, 1000000)),
+			("0.999999", (999999, 1000000)), ("0.05", (1, 20)), ("00.5", (1, 2)), ("0.3", (3, 10)), ("0.1", (1, 10))):
+		assert host.parse_decimal_fraction(text) == want, text
+	for text in ("", ".", ".5", "1.000001", "2", "0.0000001", "-0.1", "+0.1", "0.1e0", "1e-1", "0,2", " 0.2", "0.2 ", "0x1", "nan", "0..1", "12345678"):
+		with pytest.raises(ValueError):
+			host.parse_decimal_fraction(text)
+
+
+# ---- the header and the library --------------------------------------------------------------------------------------------------------------
+
+def test_header_constants_and_prototypes():
+	from vcf2multialign_amd import _native as N
+	header = _header()
+	assert re.search(r"#define V2M_SITE_LD_MAX_WINDOW\s+4096u", header) and N.SITE_LD_MAX_WINDOW == 4096 == LM.MAX_WINDOW
+	assert re.search(r"#define V2M_SITE_LD_MAX_ROWS\s+32768u", header) and N.SITE_LD_MAX_ROWS == 32768
+	assert "#define V2M_ABI_VERSION 5" in header and "V2M_KERNEL_END = 15" in header and "V2M_KERNEL_LIMIT = 17" in header
+	assert N.ABI_VERSION == 5 and N.KERNEL_LIMIT == 17
+	assert header.index("---- variable sites") < header.index("---- site LD") < header.index("---- founder search")
+	assert re.search(r"\bint v2m_site_ld\(v2m_ctx \*ctx, const v2m_row_batch \*rows, const v2m_site_ld_params \*params,\s*v2m_ld_sites_sink_fn sites_sink[^;]*?,"
+		r"\s*v2m_ld_pairs_sink_fn pairs_sink[^;]*?, void \*user,\s*v2m_site_ld_info \*info", header)
+	assert re.search(r"\bint v2m_site_ld_device\(v2m_ctx \*ctx, const v2m_row_batch \*rows, const v2m_site_ld_params \*params,\s*void \*d_sites, uint64_t site_capacity, "
+		r"void \*d_pairs[^;]*?, uint64_t pair_capacity,\s*uint64_t \*n_sites, uint64_t \*n_pairs\)", header)
+	assert re.search(r"typedef int \(\*v2m_ld_sites_sink_fn\)\(void \*user, const v2m_ld_site \*sites, uint64_t n\);", header)
+	assert re.search(r"typedef int \(\*v2m_ld_pairs_sink_fn\)\(void \*user, const v2m_ld_pair \*pairs, uint64_t n\);", header)
+	for name in ("v2m_site_ld", "v2m_site_ld_device"):
+		assert name in N.SIGNATURES
+
+	def fields(struct):
+		body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, header).group(1)
+		body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+		return [name.strip() for decl in re.findall(r"\w+\s+([\w\s,]+);", body) for name in decl.split(",")]
+
+	assert fields("v2m_site_ld_params") == [f for f, _ in N.SiteLdParams._fields_] == ["window_sites", "min_allele_count", "min_r2_num", "min_r2_den", "window_columns"]
+	assert fields("v2m_ld_site") == [f for f, *_ in N.LD_SITE_DTYPE] == list(LM.SITE_DTYPE.names)
+	assert fields("v2m_ld_pair") == [f for f, *_ in N.LD_PAIR_DTYPE] == list(LM.PAIR_DTYPE.names)
+	assert fields("v2m_site_ld_info") == [f for f, _ in N.SiteLdInfo._fields_] == ["n_sites", "n_columns", "n_pairs", "n_candidates", "counts_ms", "pack_ms", "pairs_ms"]
+	assert (C.sizeof(N.SiteLdParams), np.dtype(N.LD_SITE_DTYPE).itemsize, np.dtype(N.LD_PAIR_DTYPE).itemsize, C.sizeof(N.SiteLdInfo)) == (24, 24, 24, 56)
+	assert (N.LD_TILE, N.LD_CHUNK_WORDS) == LM.kernel_constants()
+
+
+def test_exported_symbols():
+	from vcf2multialign_amd import build
+	hip = C.CDLL(build.LIB_PATH)
+	for name in ("v2m_site_ld", "v2m_site_ld_device"):
+		assert hasattr(hip, name), name
+	host = C.CDLL(build.HOST_LIB_PATH)
+	assert hasattr(host, "v2mh_site_ld_text") and hasattr(host, "v2mh_parse_decimal_fraction")
+	out = subprocess.run(["nm", "-D", "--defined-only", build.LIB_PATH], stdout=subprocess.PIPE, check=True).stdout.decode()
+	assert " T v2m_site_ld\n" in out and " T v2m_site_ld_device\n" in out
+
+
+def test_the_kernels_are_in_the_library_source():
+	with open(LM.LD_KERNELS_HPP) as f:
+		text = f.read()
+	for kernel in ("count_ld_columns_kernel", "emit_ld_columns_kernel", "ld_pack_kernel", "ld_pairs_kernel"):
+		assert re.search(r"__global__[^;{]*\b%s\(" % kernel, text), kernel
+	assert text.count("__shared__") == text.count("V2M_POISON_LDS(") == 6         # every LDS object goes through V2M_POISON_LDS
+	assert "__umul64hi" in text and "double" not in text and "float" not in text  # the threshold is compared in integers
+	with open(os.path.join(ROOT, "vcf2multialign_amd", "csrc", "v2m_hip.hip")) as f:
+		library = f.read()
+	assert library.index('#include "site_kernels.hpp"') < library.index('#include "ld_kernels.hpp"')
+	# the band's tiles per strip, which the corpus' window sizes are chosen for
+	assert "(u64(prm.window_sites) + v2m::kLdTile - 1) / v2m::kLdTile + 1" in library
+	from vcf2multialign_amd import build
+	assert LM.LD_KERNELS_HPP in build.deps("HIP_DEPS")
+
+
+def test_python_surface():
+	import inspect
+	import vcf2multialign_amd as v
+	from vcf2multialign_amd import host
+	assert list(inspect.signature(v.Context.site_ld).parameters)[:7] == ["self", "rows", "window_sites", "window_columns", "min_r2", "min_allele_count", "info"]
+	assert inspect.signature(v.Context.site_ld).parameters["min_r2"].default == (1, 5)
+	assert list(inspect.signature(v.Context.site_ld_device).parameters) == ["self", "rows", "sites_ptr", "site_capacity", "pairs_ptr", "pair_capacity", "window_sites", "window_columns", "min_r2", "min_allele_count"]
+	assert list(inspect.signature(v.HaplotypeOutput.output_ld).parameters) == ["self", "graph", "stream", "window_sites", "window_columns", "min_r2", "min_allele_count"]
+	assert list(inspect.signature(v.FounderSequenceGreedyOutput.output_ld).parameters) == ["self", "graph", "cut_positions", "assigned_samples_column_major", "stream", "window_sites", "window_columns", "min_r2", "min_allele_count"]
+	assert callable(host.site_ld_text) and callable(host.parse_decimal_fraction)
+
+
+# ---- the driver's argument errors (reported before a device is opened) ---------------------------------------------------------------------
+
+def _run(args, cwd=None):
+	assert os.path.exists(CLI), "build the host driver first (__graft_entry__.build())"
+	return subprocess.run([CLI] + args, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+
+
+def test_cli_argument_errors(tmp_path):
+	fa, vcf = os.path.join(FIX, "test-4.fa"), os.path.join(FIX, "test-4.vcf")
+	bed = tmp_path / "r.bed"
+	bed.write_text("1\t0\t4\n")
+	common = ["-H", "-r", fa, "-a", vcf, "-c", "1"]
+	out = "--output-ld=" + str(tmp_path / "x.tsv")
+	for extra, what in ((["--regions-file=" + str(bed)], "--regions-file"), (["--device=0,0"], "more than one --device entry")):
+		r = _run(common + [out] + extra, cwd=str(tmp_path))
+		assert r.returncode != 0
+		assert ("ERROR: --output-ld cannot be combined with %s.\n" % what).encode() in r.stderr, r.stderr.decode()
+	for option in ("--ld-window=5", "--ld-window-columns=5", "--ld-min-r2=0.5", "--ld-min-count=2"):
+		r = _run(common + [option, "-s", str(tmp_path / "x.a2m")], cwd=str(tmp_path))
+		assert r.returncode != 0 and ("ERROR: %s requires --output-ld.\n" % option.split("=")[0]).encode() in r.stderr, r.stderr.decode()
+	for option in ("--ld-window=0", "--ld-window=4097", "--ld-window=x", "--ld-window=-1", "--ld-window-columns=1.5", "--ld-window-columns=", "--ld-min-count=0", "--ld-min-count=two",
+			"--ld-min-r2=1.1", "--ld-min-r2=0.0000001", "--ld-min-r2=-0.1", "--ld-min-r2=1e-1", "--ld-min-r2=.5", "--ld-min-r2="):
+		r = _run(common + [out, option], cwd=str(tmp_path))
+		assert r.returncode != 0 and ("ERROR: %s must be " % option.split("=")[0]).encode() in r.stderr, (option, r.stderr.decode())
+	assert not (tmp_path / "x.tsv").exists() and not (tmp_path / "x.a2m").exists()
+	r = _run(["--help"])
+	text = r.stdout + r.stderr
+	assert r.returncode == 0
+	for option in (b"--output-ld=FILE", b"--ld-window=SITES", b"--ld-window-columns=N", b"--ld-min-r2=DECIMAL", b"--ld-min-count=N"):
+		assert option in text

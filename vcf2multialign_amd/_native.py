@@ -55,6 +55,12 @@ SITES_SNP = 0x40
 GATHER_SITES = 4
 GATHER_THREADS = 256
 GATHER_MIN_GROUP_ROWS = 16
+# v2m_site_ld[_device]: the limits, and csrc/ld_kernels.hpp's kLdTile (sites per side of a workgroup's tile) and kLdChunkWords (64-row
+# words per LDS chunk); tests/test_site_ld_host.py holds them to the sources
+SITE_LD_MAX_WINDOW = 4096
+SITE_LD_MAX_ROWS = 32768
+LD_TILE = 64
+LD_CHUNK_WORDS = 8
 # csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
 # kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
 DISTINCT_CHUNK_BYTES = 8192
@@ -118,6 +124,17 @@ class VariableSitesInfo(C.Structure):   # v2m_variable_sites_info
 	_fields_ = [("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("counts_ms", C.c_double), ("gather_ms", C.c_double)]
 
 
+class SiteLdParams(C.Structure):   # v2m_site_ld_params
+	_fields_ = [("window_sites", C.c_uint32), ("min_allele_count", C.c_uint32), ("min_r2_num", C.c_uint32), ("min_r2_den", C.c_uint32), ("window_columns", C.c_uint64)]
+
+class SiteLdInfo(C.Structure):   # v2m_site_ld_info
+	_fields_ = [("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("n_pairs", C.c_uint64), ("n_candidates", C.c_uint64),
+		("counts_ms", C.c_double), ("pack_ms", C.c_double), ("pairs_ms", C.c_double)]
+
+
+LD_SITE_DTYPE = [("column", "<u8"), ("class_lo", "<u4"), ("class_hi", "<u4"), ("count_lo", "<u4"), ("count_hi", "<u4")]   # v2m_ld_site
+LD_PAIR_DTYPE = [("site_a", "<u4"), ("site_b", "<u4"), ("n", "<u4"), ("n_a", "<u4"), ("n_b", "<u4"), ("n_ab", "<u4")]   # v2m_ld_pair
+LD_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_ld_sites_sink_fn, v2m_ld_pairs_sink_fn
 SITE_COLUMNS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_site_columns_sink_fn
 SITE_ROWS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_site_rows_sink_fn
 TRIALS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_trials_sink
@@ -161,6 +178,8 @@ SIGNATURES = {
 	"v2m_pair_distances_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_uint64]),
 	"v2m_variable_sites": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, SITE_COLUMNS_SINK_FN, SITE_ROWS_SINK_FN, C.c_void_p, C.POINTER(VariableSitesInfo)]),
 	"v2m_variable_sites_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+	"v2m_site_ld": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.POINTER(SiteLdParams), LD_SINK_FN, LD_SINK_FN, C.c_void_p, C.POINTER(SiteLdInfo)]),
+	"v2m_site_ld_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.POINTER(SiteLdParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p, _u64p]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

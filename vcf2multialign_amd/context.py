@@ -522,6 +522,76 @@ class Context:
 		self._check(rc)
 		return int(count.value)
 
+	@staticmethod
+	def _site_ld_params(window_sites, window_columns, min_r2, min_allele_count):
+		num, den = min_r2
+		return N.SiteLdParams(int(window_sites), int(min_allele_count), int(num), int(den), int(window_columns))
+
+	def site_ld(self, rows, window_sites=1000, window_columns=0, min_r2=(1, 5), min_allele_count=1, info=False, want_sites=True, want_pairs=True):
+		"""v2m_site_ld: (sites, pairs), numpy structured arrays of v2m_ld_site and v2m_ld_pair records -- the biallelic sites of the view
+		in force (the whole row, or the column window) and, of the site pairs (s, t) with t - s <= window_sites and, unless window_columns
+		is 0, a column distance of at most window_columns, those whose r^2 = D^2 / den reaches min_r2 = (numerator, denominator), compared
+		exactly in integers; ascending by (s, t).  With info=True: (sites, pairs, dict of v2m_site_ld_info's fields).  want_sites /
+		want_pairs = False pass a NULL sink.  self.site_ld_blocks: the sizes of the blocks the pairs arrived in."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = int(rows.struct.n_rows)
+		sites, blocks, error = [], [], []
+
+		def _sites(_user, records, count):
+			try:
+				if blocks:
+					raise AssertionError("the sites after a pair")
+				sites.append(np.frombuffer(C.string_at(records, 24 * count), dtype=np.dtype(N.LD_SITE_DTYPE)).copy())
+				return 0
+			except BaseException as e:  # propagate through the C frame as V2M_ERR_SINK
+				error.append(e)
+				return 1
+
+		def _pairs(_user, records, count):
+			try:
+				if count == 0:
+					raise AssertionError("a block of no pairs")
+				blocks.append(np.frombuffer(C.string_at(records, 24 * count), dtype=np.dtype(N.LD_PAIR_DTYPE)).copy())
+				return 0
+			except BaseException as e:
+				error.append(e)
+				return 1
+
+		params = self._site_ld_params(window_sites, window_columns, min_r2, min_allele_count)
+		record = N.SiteLdInfo()
+		no_sink = C.cast(None, N.LD_SINK_FN)
+		rc = self._lib.v2m_site_ld(self._h, C.byref(rows.struct), C.byref(params), N.LD_SINK_FN(_sites) if want_sites else no_sink,
+			N.LD_SINK_FN(_pairs) if want_pairs else no_sink, None, C.byref(record))
+		if error:
+			raise error[0]
+		self._check(rc)
+		if len(sites) > 1:
+			raise AssertionError("the sites arrived %d times" % len(sites))
+		self.site_ld_blocks = [len(b) for b in blocks]
+		site_records = sites[0] if sites else np.zeros(0, dtype=np.dtype(N.LD_SITE_DTYPE))
+		pair_records = np.concatenate(blocks) if blocks else np.zeros(0, dtype=np.dtype(N.LD_PAIR_DTYPE))
+		if n == 0:
+			record.n_columns = self.window_length   # (with no rows the call returns before it writes the info)
+		if info:
+			return site_records, pair_records, {name: getattr(record, name) for name, _ in N.SiteLdInfo._fields_}
+		return site_records, pair_records
+
+	def site_ld_device(self, rows, sites_ptr, site_capacity, pairs_ptr, pair_capacity, window_sites=1000, window_columns=0, min_r2=(1, 5), min_allele_count=1):
+		"""v2m_site_ld_device: the site records into device memory at `sites_ptr` (v2m_ld_site[site_capacity]) and the reported pairs at
+		`pairs_ptr` (v2m_ld_pair[pair_capacity]; None with capacity 0 asks for the counts only), both 16-byte aligned.  Returns
+		(n_sites, n_pairs); when either exceeds its capacity the call raises (self.site_ld_counts then holds both) and has written
+		nothing."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		params = self._site_ld_params(window_sites, window_columns, min_r2, min_allele_count)
+		n_sites, n_pairs = C.c_uint64(0), C.c_uint64(0)
+		self.site_ld_counts = None
+		rc = self._lib.v2m_site_ld_device(self._h, C.byref(rows.struct), C.byref(params), sites_ptr, site_capacity, pairs_ptr, pair_capacity, C.byref(n_sites), C.byref(n_pairs))
+		self.site_ld_counts = (int(n_sites.value), int(n_pairs.value))
+		self._check(rc)
+		return self.site_ld_counts
+
 	def bgzf_compress(self, data):
 		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
 		src = bytes(data)

@@ -494,4 +494,26 @@ int64_t v2mh_site_positions_text(uint64_t const *columns, uint64_t n_sites, uint
 	}
 }
 
+// site_ld_text() of output.hh (no GPU), handed over as v2mh_column_counts_text hands over its table; -1 with a message in err on failure.
+int64_t v2mh_site_ld_text(uint64_t n_rows, uint64_t n_columns, v2m_ld_site const *sites, uint64_t n_sites, v2m_ld_pair const *pairs, uint64_t n_pairs,
+	v2m_site_ld_params const *params, uint64_t const *reference_positions, uint64_t const *aligned_positions, uint64_t node_count,
+	char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		if (!params) throw std::runtime_error("params is NULL");
+		std::string const text(vh::site_ld_text(n_rows, n_columns, sites, n_sites, pairs, n_pairs, *params, reference_positions, aligned_positions, node_count));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
+// parse_decimal_fraction() of output.hh: 1 and the fraction in lowest terms, or 0
+int v2mh_parse_decimal_fraction(char const *text, uint32_t *numerator, uint32_t *denominator)
+{
+	return text && numerator && denominator && vh::parse_decimal_fraction(text, *numerator, *denominator) ? 1 : 0;
+}
+
 } // extern "C"

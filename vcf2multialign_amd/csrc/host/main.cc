@@ -60,6 +60,9 @@ struct options {
 	char const *output_variable_sites{};  // --output-variable-sites=FILE: the output rows cut down to the variable columns, as FASTA, from v2m_variable_sites
 	char const *output_site_positions{};  // --output-site-positions=FILE (with --output-variable-sites): the column and the reference position of every site
 	bool snp_sites{};                     // --snp-sites (with --output-variable-sites): only columns where at least two of A, C, G, T occur
+	char const *output_ld{};              // --output-ld=FILE: linkage disequilibrium between nearby biallelic sites of the output rows, from v2m_site_ld
+	char const *ld_window{}, *ld_window_columns{}, *ld_min_r2{}, *ld_min_count{};   // --ld-window=SITES, --ld-window-columns=N, --ld-min-r2=DECIMAL, --ld-min-count=N (with --output-ld)
+	v2m_site_ld_params ld_params{1000, 1, 1, 5, 0};
 	bool all_columns{};                   // --all-columns (with --output-column-counts): every column, not only the variable ones
 	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
 	std::vector<int> devices{0};
@@ -138,6 +141,20 @@ void usage()
 		"                                     occur (snp-sites' rule); columns that vary only by gap, N or other bytes are left out\n"
 		"      --output-site-positions=FILE   With --output-variable-sites: write one line per kept column, `column<TAB>reference\n"
 		"                                     position` (the first two fields of its --output-column-counts line)\n"
+		"      --output-ld=FILE               Write a TSV with the linkage disequilibrium between nearby biallelic sites of the output\n"
+		"                                     sequences (REF first, unless --omit-reference), as plink --r2 reports it for phased\n"
+		"                                     haplotypes: a `#rows` line, a header line, then per reported pair of sites the column and\n"
+		"                                     reference position of both, the sequences called at both (n), those that carry the\n"
+		"                                     second allele at the first site, at the second, and at both, and r2.  A site is a\n"
+		"                                     column where exactly two of A, C, G, T occur; sequences that hold anything else there are\n"
+		"                                     missing.  Counted on the GPU.  Always of the aligned form, whatever --unaligned says;\n"
+		"                                     --region restricts the columns.  Alone or beside the other outputs; not with\n"
+		"                                     --regions-file or several --device entries\n"
+		"      --ld-window=SITES              With --output-ld: pairs at most SITES sites apart (1 to 4096; default 1000)\n"
+		"      --ld-window-columns=N          With --output-ld: pairs at most N alignment columns apart (default 0: no limit)\n"
+		"      --ld-min-r2=DECIMAL            With --output-ld: report the pairs with r2 >= DECIMAL (0 to 1, at most 6 decimals;\n"
+		"                                     default 0.2), compared exactly\n"
+		"      --ld-min-count=N               With --output-ld: a site's two alleles each occur at least N times (default 1)\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -227,6 +244,15 @@ struct progress_delegate final : vh::output_delegate {
 		if (verbose && 0 == count % 10) std::cerr << "Handled " << count << " sequences...\n";   // main.cc:313-330
 	}
 };
+
+// A decimal count: digits only, at most 18 of them.
+bool parse_count(char const *text, std::uint64_t &out)
+{
+	std::string const t(text);
+	if (t.empty() || t.size() > 18 || std::string::npos != t.find_first_not_of("0123456789")) return false;
+	out = std::stoull(t);
+	return true;
+}
 
 // --region's value: START-END, decimal, 1 <= START <= END (the reference length is checked once the reference is read).
 bool parse_region(char const *text, std::uint64_t &start, std::uint64_t &end)
@@ -324,7 +350,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -337,6 +363,8 @@ int main(int argc, char **argv)
 		{"exclude-samples", required_argument, nullptr, 'x'}, {"device", required_argument, nullptr, o_device}, {"verbose", no_argument, nullptr, o_verbose},
 		{"input-graph", required_argument, nullptr, 'g'}, {"output-graph", required_argument, nullptr, 'f'},
 		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct}, {"output-paf", required_argument, nullptr, o_output_paf}, {"output-column-counts", required_argument, nullptr, o_output_column_counts}, {"all-columns", no_argument, nullptr, o_all_columns}, {"output-distances", required_argument, nullptr, o_output_distances}, {"acgt-only", no_argument, nullptr, o_acgt_only}, {"output-variable-sites", required_argument, nullptr, o_output_variable_sites}, {"snp-sites", no_argument, nullptr, o_snp_sites}, {"output-site-positions", required_argument, nullptr, o_output_site_positions},
+		{"output-ld", required_argument, nullptr, o_output_ld}, {"ld-window", required_argument, nullptr, o_ld_window}, {"ld-window-columns", required_argument, nullptr, o_ld_window_columns},
+		{"ld-min-r2", required_argument, nullptr, o_ld_min_r2}, {"ld-min-count", required_argument, nullptr, o_ld_min_count},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -393,6 +421,11 @@ int main(int argc, char **argv)
 			case o_output_variable_sites: opt.output_variable_sites = optarg; break;
 			case o_snp_sites: opt.snp_sites = true; break;
 			case o_output_site_positions: opt.output_site_positions = optarg; break;
+			case o_output_ld: opt.output_ld = optarg; break;
+			case o_ld_window: opt.ld_window = optarg; break;
+			case o_ld_window_columns: opt.ld_window_columns = optarg; break;
+			case o_ld_min_r2: opt.ld_min_r2 = optarg; break;
+			case o_ld_min_count: opt.ld_min_count = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -452,6 +485,30 @@ int main(int argc, char **argv)
 		// one set of sites from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
 		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
 		if (other) { std::cerr << "ERROR: --output-variable-sites cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+	}
+	for (auto const &[value, name] : {std::pair<char const *, char const *>{opt.ld_window, "--ld-window"}, {opt.ld_window_columns, "--ld-window-columns"}, {opt.ld_min_r2, "--ld-min-r2"}, {opt.ld_min_count, "--ld-min-count"}})
+		if (value && !opt.output_ld) { std::cerr << "ERROR: " << name << " requires --output-ld.\n"; return EXIT_FAILURE; }
+	if (opt.output_ld) {
+		// one set of sites from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
+		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
+		if (other) { std::cerr << "ERROR: --output-ld cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+		std::uint64_t value(0);
+		if (opt.ld_window) {
+			if (!parse_count(opt.ld_window, value) || value < 1 || value > V2M_SITE_LD_MAX_WINDOW) { std::cerr << "ERROR: --ld-window must be a number of sites from 1 to " << V2M_SITE_LD_MAX_WINDOW << ", got \"" << opt.ld_window << "\".\n"; return EXIT_FAILURE; }
+			opt.ld_params.window_sites = std::uint32_t(value);
+		}
+		if (opt.ld_window_columns) {
+			if (!parse_count(opt.ld_window_columns, value)) { std::cerr << "ERROR: --ld-window-columns must be a number of columns, got \"" << opt.ld_window_columns << "\".\n"; return EXIT_FAILURE; }
+			opt.ld_params.window_columns = value;
+		}
+		if (opt.ld_min_count) {
+			if (!parse_count(opt.ld_min_count, value) || value < 1 || value > 0xFFFFFFFFull) { std::cerr << "ERROR: --ld-min-count must be a count of at least 1, got \"" << opt.ld_min_count << "\".\n"; return EXIT_FAILURE; }
+			opt.ld_params.min_allele_count = std::uint32_t(value);
+		}
+		if (opt.ld_min_r2 && !vh::parse_decimal_fraction(opt.ld_min_r2, opt.ld_params.min_r2_num, opt.ld_params.min_r2_den)) {
+			std::cerr << "ERROR: --ld-min-r2 must be a decimal number from 0 to 1 with at most 6 decimals, got \"" << opt.ld_min_r2 << "\".\n";
+			return EXIT_FAILURE;
+		}
 	}
 	if (opt.region && !parse_region(opt.region, opt.region_start, opt.region_end)) {
 		std::cerr << "ERROR: --region must be START-END with 1 <= START <= END (1-based, inclusive), got \"" << opt.region << "\".\n";
@@ -697,6 +754,11 @@ int main(int argc, char **argv)
 			if (opt.output_variable_sites) {
 				std::cerr << "Outputting variable sites..." << std::flush;
 				output.output_variable_sites(graph, opt.output_variable_sites, opt.snp_sites, opt.output_site_positions, opt.verbose);
+				std::cerr << " Done.\n";
+			}
+			if (opt.output_ld) {
+				std::cerr << "Outputting site LD..." << std::flush;
+				output.output_ld(graph, opt.output_ld, opt.ld_params, opt.verbose);
 				std::cerr << " Done.\n";
 			}
 		});

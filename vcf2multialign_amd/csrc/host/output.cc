@@ -1304,6 +1304,123 @@ void output::output_variable_sites(variant_graph const &graph, char const *path,
 }
 
 
+// --- site LD (--output-ld) ----------------------------------------------------------------------------------------
+bool parse_decimal_fraction(char const *text, std::uint32_t &numerator, std::uint32_t &denominator)
+{
+	std::string const s(text);
+	auto const dot(s.find('.'));
+	std::string const whole(s.substr(0, dot)), decimals(std::string::npos == dot ? std::string() : s.substr(dot + 1));
+	if (whole.empty() || whole.size() > 7 || decimals.size() > 6) return false;
+	if (std::string::npos != whole.find_first_not_of("0123456789") || std::string::npos != decimals.find_first_not_of("0123456789")) return false;
+	u64 den(1);
+	for (std::size_t i(0); i < decimals.size(); ++i) den *= 10;
+	u64 num(std::stoull(whole) * den + (decimals.empty() ? 0 : std::stoull(decimals)));
+	if (num > den) return false;
+	u64 a(num), b(den);
+	while (b) { u64 const r(a % b); a = b; b = r; }   // (a = gcd >= 1: den >= 1)
+	numerator = std::uint32_t(num / a);
+	denominator = std::uint32_t(den / a);
+	return true;
+}
+
+
+std::string site_ld_text(u64 n_rows, u64 n_columns, v2m_ld_site const *sites, u64 n_sites, v2m_ld_pair const *pairs, u64 n_pairs, v2m_site_ld_params const &params,
+	u64 const *reference_positions, u64 const *aligned_positions, u64 node_count)
+{
+	std::string text("#rows\t" + std::to_string(n_rows) + "\tcolumns\t" + std::to_string(n_columns) + "\tsites\t" + std::to_string(n_sites) + "\tpairs\t" + std::to_string(n_pairs)
+		+ "\twindow\t" + std::to_string(params.window_sites) + "\twindow_columns\t" + std::to_string(params.window_columns)
+		+ "\tmin_r2\t" + std::to_string(params.min_r2_num) + "/" + std::to_string(params.min_r2_den) + "\tmin_count\t" + std::to_string(params.min_allele_count)
+		+ "\n#column_a\tpos_a\tcolumn_b\tpos_b\tn\tn_a\tn_b\tn_ab\tr2\n");
+	u64 node_a(0), node_b(0);
+	char r2[64];
+	for (u64 i(0); i < n_pairs; ++i) {
+		v2m_ld_pair const &p(pairs[i]);
+		if (p.site_a >= n_sites || p.site_b >= n_sites) throw std::runtime_error("a pair of the site LD names a site beyond the last");
+		std::int64_t const d(std::int64_t(u64(p.n) * p.n_ab) - std::int64_t(u64(p.n_a) * p.n_b));
+		u64 const d2(u64(d * d)), den(u64(p.n_a) * (p.n - p.n_a) * (u64(p.n_b) * (p.n - p.n_b)));
+		if (0 == den) throw std::runtime_error("a pair of the site LD has a denominator of 0");
+		append_column_and_position(text, sites[p.site_a].column, reference_positions, aligned_positions, node_count, node_a);
+		text += '\t';
+		append_column_and_position(text, sites[p.site_b].column, reference_positions, aligned_positions, node_count, node_b);
+		for (u32 const c : {p.n, p.n_a, p.n_b, p.n_ab}) { text += '\t'; text += std::to_string(c); }
+		std::snprintf(r2, sizeof(r2), "\t%.6f\n", double(d2) / double(den));
+		text += r2;
+	}
+	return text;
+}
+
+
+namespace {
+	struct site_ld_state {
+		std::vector<v2m_ld_site> sites;
+		std::vector<v2m_ld_pair> pairs;
+		std::exception_ptr error;
+	};
+
+	int site_ld_sites_sink(void *user, v2m_ld_site const *sites, uint64_t n)
+	{
+		auto &st(*static_cast<site_ld_state *>(user));
+		try {
+			st.sites.assign(sites, sites + n);
+			return 0;
+		} catch (...) {   // nothing may cross the C boundary
+			st.error = std::current_exception();
+			return 1;
+		}
+	}
+
+	int site_ld_pairs_sink(void *user, v2m_ld_pair const *pairs, uint64_t n)
+	{
+		auto &st(*static_cast<site_ld_state *>(user));
+		try {
+			st.pairs.insert(st.pairs.end(), pairs, pairs + n);
+			return 0;
+		} catch (...) {
+			st.error = std::current_exception();
+			return 1;
+		}
+	}
+}
+
+
+void output::output_ld(variant_graph const &graph, std::ostream &stream, v2m_site_ld_params const &params, bool verbose)
+{
+	if (!m_more_gpus.empty()) throw std::runtime_error("--output-ld needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-ld needs every chromosome copy on one GPU context");
+	row_set const rows(a2m_rows(graph));
+	v2m_row_batch batch{};
+	batch.n_rows = rows.copy_index.size();
+	batch.copy_index = rows.copy_index.data();
+	if (rows.any_cuts) {
+		batch.cut_offsets = rows.cut_offsets.data();
+		batch.cut_nodes = rows.cut_nodes.data();
+		batch.cut_copies = rows.cut_copies.data();
+	}
+	site_ld_state st;
+	v2m_site_ld_info info{};
+	info.n_columns = v2m_window_length(m_gpu.get());
+	int const rc(v2m_site_ld(m_gpu.get(), &batch, &params, site_ld_sites_sink, site_ld_pairs_sink, &st, &info));
+	if (st.error) std::rethrow_exception(st.error);
+	m_gpu.check(rc);
+	std::string const text(site_ld_text(batch.n_rows, info.n_columns, st.sites.data(), st.sites.size(), st.pairs.data(), st.pairs.size(), params,
+		graph.reference_positions.data(), graph.aligned_positions.data(), graph.node_count()));
+	stream.write(text.data(), std::streamsize(text.size()));
+	if (verbose)
+		std::fprintf(stderr, "Site LD: %llu rows, %llu columns, %llu sites, %llu candidates, %llu pairs.\n", (unsigned long long) batch.n_rows, (unsigned long long) info.n_columns,
+			(unsigned long long) info.n_sites, (unsigned long long) info.n_candidates, (unsigned long long) info.n_pairs);
+}
+
+
+void output::output_ld(variant_graph const &graph, char const *path, v2m_site_ld_params const &params, bool verbose)
+{
+	std::ofstream stream(path, std::ios::binary | std::ios::trunc);
+	if (!stream) throw std::runtime_error(std::string("unable to open ") + path + " for writing");
+	output_ld(graph, stream, params, verbose);
+	stream.flush();
+	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+}
+
+
 // --- haplotype_output (haplotype_output.cc:38-132) ------------------------------------------------------------
 output::row_set haplotype_output::rows_for(variant_graph const &graph, char sep, char const *suffix)
 {

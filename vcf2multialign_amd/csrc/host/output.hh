@@ -78,6 +78,16 @@ std::string distances_text(std::vector<std::string> const &ids, std::uint32_t co
 // the first two fields of that column's line of column_counts_text, made by the same code.
 std::string site_positions_text(u64 const *columns, u64 n_sites, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count);
 
+// --output-ld's text: a `#rows` line with the figures of the call and its parameters, a header line, then per pair the column and the
+// reference position of both sites (the first two fields of their --output-column-counts lines), n, n_a, n_b, n_ab and r2 =
+// (double) D^2 / (double) den with D^2 and den as 64-bit integers, printed %.6f.  Throws when a pair names a site beyond n_sites or has
+// den = 0 (the library reports no such pair).
+std::string site_ld_text(u64 n_rows, u64 n_columns, v2m_ld_site const *sites, u64 n_sites, v2m_ld_pair const *pairs, u64 n_pairs, v2m_site_ld_params const &params,
+	u64 const *reference_positions, u64 const *aligned_positions, u64 node_count);
+
+// --ld-min-r2's value from its digits, with no floating point: DIGITS[.DIGITS], at most 6 decimals, inside [0, 1]; in lowest terms.
+bool parse_decimal_fraction(char const *text, std::uint32_t &numerator, std::uint32_t &denominator);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -160,6 +170,12 @@ public:
 	// V2M_SITES_SNP; positions: site_positions_text above goes there; verbose prints the rows, columns and sites to stderr.
 	void output_variable_sites(variant_graph const &graph, char const *path, bool snp_only = false, char const *positions_path = nullptr, bool verbose = false);
 	void output_variable_sites(variant_graph const &graph, std::ostream &stream, bool snp_only = false, std::ostream *positions = nullptr, bool verbose = false);
+
+	// --output-ld: site_ld_text above for the rows of the A2M output (REF first, unless omitted), from v2m_site_ld on the first context,
+	// which must hold every copy.  The reported pairs are kept (24 bytes each) until the last has arrived: the first line holds their
+	// number.  verbose prints the rows, columns, sites, candidates and pairs to stderr.
+	void output_ld(variant_graph const &graph, char const *path, v2m_site_ld_params const &params, bool verbose = false);
+	void output_ld(variant_graph const &graph, std::ostream &stream, v2m_site_ld_params const &params, bool verbose = false);
 
 protected:
 	struct row_set {

@@ -32,6 +32,7 @@
 #include "vcf_kernels.hpp"
 #include "distance_kernels.hpp"
 #include "site_kernels.hpp"
+#include "ld_kernels.hpp"
 
 using v2m::u32;
 using v2m::u64;
@@ -269,6 +270,10 @@ struct v2m_ctx {
 	// variable sites (v2m_variable_sites): the site list, the host form's gathered slices (two, used in turn), the list's pinned staging
 	scratch_buf d_site_columns, d_site_bytes[2];
 	pinned_buf h_site_columns;
+	// site LD (v2m_site_ld): the site list and the records, the bit planes, the (site, tile) cells, the strips' totals and bases, the
+	// host form's pairs of a range (two, used in turn), and the pinned staging of the records and of the totals and bases
+	scratch_buf d_ld_sites, d_ld_records, d_ld_planes, d_ld_cells, d_ld_totals, d_ld_bases, d_ld_pairs[2];
+	pinned_buf h_ld_records, h_ld_strips;
 	// pinned slots: the rows of v2m_splice_rows[_held] (a slot is kept until the sink has released its rows); slots 0 and 1 also stage
 	// the BGZF members and v2m_upload_path_blocks' columns
 	held_ring_state held_state;
@@ -3715,6 +3720,285 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 	}
 	if (V2M_OK == rc && launched) rc = hand_over(launched - 1);
 	return finish(rc);
+}
+
+
+// ---- site LD (ld_kernels.hpp) ----------------------------------------------------------------------
+
+namespace {
+
+static_assert(sizeof(v2m_site_ld_params) == 24 && sizeof(v2m_ld_site) == 24 && sizeof(v2m_ld_pair) == 24 && sizeof(v2m_site_ld_info) == 56, "include/v2m_hip.h");
+static_assert(sizeof(v2m_ld_site) == sizeof(v2m::ld_site_record) && sizeof(v2m_ld_pair) == sizeof(v2m::ld_pair_record), "the kernels' records");
+
+int check_site_ld(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params const *params, char const *name)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!rows) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "rows is NULL");
+	if (!params) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "params is NULL");
+	if (params->window_sites < 1 || params->window_sites > V2M_SITE_LD_MAX_WINDOW)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s takes a window_sites of 1 to V2M_SITE_LD_MAX_WINDOW = %u (got %u)", name, V2M_SITE_LD_MAX_WINDOW, params->window_sites);
+	if (params->min_allele_count < 1) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s takes a min_allele_count of at least 1 (got 0)", name);
+	if (params->min_r2_den < 1 || params->min_r2_den > 1000000u || params->min_r2_num > params->min_r2_den)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s takes 1 <= min_r2_den <= 1000000 and min_r2_num <= min_r2_den (got %u / %u)", name, params->min_r2_num, params->min_r2_den);
+	if (int const rc = check_batch(ctx, rows, 0)) return rc;
+	if (rows->n_rows > V2M_SITE_LD_MAX_ROWS)
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes at most V2M_SITE_LD_MAX_ROWS = %u rows (got %llu)", name, V2M_SITE_LD_MAX_ROWS, (unsigned long long) rows->n_rows);
+	if (ctx->view().length() >= (u64(1) << 32))
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes a view of fewer than 2^32 columns (got %llu)", name, (unsigned long long) ctx->view().length());
+	return V2M_OK;
+}
+
+// Where a call's results go: the device form's buffers, or the host form's sinks.
+struct site_ld_dest {
+	bool device;
+	void *d_sites; u64 site_capacity; void *d_pairs; u64 pair_capacity; u64 *n_sites, *n_pairs;
+	v2m_ld_sites_sink_fn sites_sink; v2m_ld_pairs_sink_fn pairs_sink; void *user; v2m_site_ld_info *info;
+};
+
+// The pairs (s, t), s < t < V, within both window limits: on the host, from the records' columns (ascending).
+u64 site_ld_candidates(v2m_ld_site const *sites, u64 V, u64 window_sites, u64 window_columns)
+{
+	u64 total(0), reach(0);
+	for (u64 s(0); s < V; ++s) {
+		u64 last(std::min(V - 1, s + window_sites));
+		if (window_columns) {
+			if (reach < s) reach = s;
+			while (reach + 1 < V && sites[reach + 1].column - sites[s].column <= window_columns) ++reach;
+			last = std::min(last, reach);
+		}
+		total += last - s;
+	}
+	return total;
+}
+
+// Queues and completes the call.  n_rows >= 1.
+int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params const &prm, site_ld_dest const &dest)
+{
+	u64 const L(ctx->view().length()), view_begin(ctx->view().begin), n(rows->n_rows);
+	stage_times times(ctx);
+	v2m_site_ld_info out{};
+	out.n_columns = L;
+	auto const finish([&](int rc) -> int {
+		// leave both streams idle whatever happened
+		hipError_t const st(hipStreamSynchronize(ctx->stream));
+		(void) hipStreamSynchronize(ctx->copy_stream);
+		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
+		if (V2M_OK == rc && dest.info) {
+			double ms[stage_times::n_stages] = {};
+			times.sum(ms);
+			out.counts_ms = ms[stage_times::counts]; out.pack_ms = ms[stage_times::pack]; out.pairs_ms = ms[stage_times::pairs];
+			*dest.info = out;
+		}
+		return rc;
+	});
+	auto const nothing([&]() -> int {
+		if (dest.device) { *dest.n_sites = 0; *dest.n_pairs = 0; }
+		return finish(V2M_OK);
+	});
+	if (0 == L) return nothing();
+
+	// (1) the counts and the number of sites
+	u64 const table_pitch((L + 3) & ~u64(3));
+	u64 const select_blocks((L + v2m::kSelectColumns - 1) / v2m::kSelectColumns);
+	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(V2M_COUNT_CLASSES * table_pitch * 4));
+	V2M_HIP_TRY(ctx, ctx->d_column_blocks.ensure(std::max<u64>(select_blocks * sizeof(u32), 16)));
+	V2M_HIP_TRY(ctx, ctx->d_column_total.ensure(sizeof(u64)));
+	V2M_HIP_TRY(ctx, ctx->h_column_total.ensure(2 * sizeof(u64)));
+	V2M_POISON_HOST(ctx->h_column_total.p, 2 * sizeof(u64));
+	u32 *const table(ctx->d_column_table.as<u32>());
+	u32 *const blocks(ctx->d_column_blocks.as<u32>());
+	times.begin(stage_times::counts);
+	int rc(column_counts_zero(ctx, table, table_pitch, L));
+	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, table, table_pitch);
+	if (V2M_OK != rc) return finish(rc);
+	hipLaunchKernelGGL(v2m::count_ld_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+		table, table_pitch, L, prm.min_allele_count, blocks);
+	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, blocks, u32(select_blocks), ctx->d_column_total.as<u64>());
+	times.end();
+	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "site LD: the site selection did not launch"));
+	if (hipSuccess != hipMemcpyAsync(ctx->h_column_total.p, ctx->d_column_total.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
+		|| hipSuccess != hipStreamSynchronize(ctx->stream))
+		return finish(fail(ctx, V2M_ERR_HIP, "site LD: the site count did not arrive"));
+	u64 const V(*ctx->h_column_total.as<u64>());
+	if (V > L) return finish(fail(ctx, V2M_ERR_HIP, "the site selection counted %llu of %llu columns", (unsigned long long) V, (unsigned long long) L));
+	out.n_sites = V;
+	if (0 == V) return nothing();
+
+	u64 const n_strips((V + v2m::kLdTile - 1) / v2m::kLdTile), v_pad(n_strips * v2m::kLdTile), n_words((n + 63) / 64);
+	u64 const plane_bytes(16 * v_pad * n_words), plane_budget(env_u64("V2M_SITE_LD_PLANE_BYTES", u64(16) << 30));
+	if (plane_bytes > plane_budget)
+		return finish(fail(ctx, V2M_ERR_UNSUPPORTED, "site LD: %llu sites of %llu rows need %llu bytes of planes, beyond V2M_SITE_LD_PLANE_BYTES = %llu",
+			(unsigned long long) V, (unsigned long long) n, (unsigned long long) plane_bytes, (unsigned long long) plane_budget));
+	u64 const n_blocks(std::min<u64>(n_strips, (u64(prm.window_sites) + v2m::kLdTile - 1) / v2m::kLdTile + 1));
+	u64 const strip_cells(u64(v2m::kLdTile) * n_blocks);
+	auto const ensure([&](scratch_buf &b, u64 bytes, char const *what) -> int {
+		hipError_t const st(b.ensure(bytes));
+		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "site LD: %llu bytes of %s: %s", (unsigned long long) bytes, what, hipGetErrorString(st));
+		return V2M_OK;
+	});
+	if (V2M_OK != (rc = ensure(ctx->d_ld_sites, v_pad * sizeof(u32), "site list"))) return finish(rc);
+	if (V2M_OK != (rc = ensure(ctx->d_ld_records, V * sizeof(v2m_ld_site), "site records"))) return finish(rc);
+	if (V2M_OK != (rc = ensure(ctx->d_ld_planes, plane_bytes, "planes"))) return finish(rc);
+	if (V2M_OK != (rc = ensure(ctx->d_ld_cells, n_strips * strip_cells * sizeof(u32), "cells"))) return finish(rc);
+	if (V2M_OK != (rc = ensure(ctx->d_ld_totals, n_strips * sizeof(u64), "strip totals"))) return finish(rc);
+	if (V2M_OK != (rc = ensure(ctx->d_ld_bases, n_strips * sizeof(u64), "strip bases"))) return finish(rc);
+	if (hipSuccess != ctx->h_ld_strips.ensure(2 * n_strips * sizeof(u64))) return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "site LD: %llu bytes of pinned strip totals", (unsigned long long) (2 * n_strips * sizeof(u64))));
+	V2M_POISON_HOST(ctx->h_ld_strips.p, 2 * n_strips * sizeof(u64));
+	u32 *const sites(ctx->d_ld_sites.as<u32>());
+	v2m::ld_site_record *const records(ctx->d_ld_records.as<v2m::ld_site_record>());
+	u64 *const planes(ctx->d_ld_planes.as<u64>());
+	u32 *const cells(ctx->d_ld_cells.as<u32>());
+	u64 *const totals(ctx->d_ld_totals.as<u64>());
+	u64 *const bases(ctx->d_ld_bases.as<u64>());
+	times.begin(stage_times::counts);
+	hipLaunchKernelGGL(v2m::emit_ld_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+		table, table_pitch, L, prm.min_allele_count, view_begin, blocks, sites, records, V);
+	times.end();
+	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "site LD: emit_ld_columns_kernel did not launch"));
+
+	// (2) the planes: zeroed, then ORed into slice by slice
+	slice_plan const p(plan_slices(ctx, n, false));
+	times.begin(stage_times::pack);
+	if (hipSuccess != hipMemsetAsync(planes, 0, plane_bytes, ctx->stream)) return finish(fail(ctx, V2M_ERR_HIP, "site LD: the planes could not be zeroed"));
+	u64 const pack_blocks((V + v2m::kLdPackThreads - 1) / v2m::kLdPackThreads);
+	for (u64 s(0); s < p.n_slices; ++s) {
+		u64 const r0(s * p.rows_per_slice), r1(std::min(n, r0 + p.rows_per_slice)), nr(r1 - r0);
+		if (V2M_OK != (rc = ensure(ctx->ring[0], p.slot_bytes, "row slot"))) return finish(rc);
+		char *const d_rows(ctx->ring[0].as<char>());
+		if (V2M_OK != (rc = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch))) return finish(rc);
+		// word-aligned row groups: with few site blocks, as many as bring the launch to about four workgroups per compute unit
+		u64 const words((r1 - 1) / 64 - r0 / 64 + 1);
+		u64 const want_groups((4 * u64(ctx->n_cus) + pack_blocks - 1) / pack_blocks);
+		u64 const per_group(std::max<u64>(1, (words + want_groups - 1) / want_groups));
+		u64 const groups((words + per_group - 1) / per_group);
+		hipLaunchKernelGGL(v2m::ld_pack_kernel, dim3(unsigned(pack_blocks), unsigned(groups)), dim3(v2m::kLdPackThreads), 0, ctx->stream,
+			d_rows, p.pitch, u32(nr), u32(per_group), u32(r0), sites, records, V, planes, v_pad);
+		if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "site LD: ld_pack_kernel did not launch"));
+	}
+	times.end();
+
+	// (3) the counts of the reported pairs per (site, tile), the offsets within every strip, the strips' totals
+	auto const pairs_launch([&](bool emit, u64 strip_first, u64 strips, u64 out_base, void *d_out) {
+		hipLaunchKernelGGL(emit ? v2m::ld_pairs_kernel<true> : v2m::ld_pairs_kernel<false>, dim3(unsigned(strips), unsigned(n_blocks)), dim3(v2m::kLdThreads), 0, ctx->stream,
+			planes, v_pad, u32(n_words), sites, V, prm.window_sites, prm.window_columns, prm.min_r2_num, prm.min_r2_den,
+			u32(strip_first), u32(n_strips), u32(n_blocks), cells, totals, bases, out_base, static_cast<v2m::ld_pair_record *>(d_out));
+	});
+	times.begin(stage_times::pairs);
+	pairs_launch(false, 0, n_strips, 0, nullptr);
+	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(unsigned(n_strips)), dim3(256), 0, ctx->stream, cells, u32(strip_cells), totals);
+	times.end();
+	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "site LD: ld_pairs_kernel did not launch"));
+	u64 *const h_totals(ctx->h_ld_strips.as<u64>()), *const h_bases(h_totals + n_strips);
+	if (hipSuccess != hipMemcpyAsync(h_totals, totals, n_strips * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
+		|| hipSuccess != hipStreamSynchronize(ctx->stream))
+		return finish(fail(ctx, V2M_ERR_HIP, "site LD: the strip totals did not arrive"));
+	u64 P(0);
+	for (u64 i(0); i < n_strips; ++i) { h_bases[i] = P; P += h_totals[i]; }
+	out.n_pairs = P;
+	if (P && hipSuccess != hipMemcpyAsync(bases, h_bases, n_strips * sizeof(u64), hipMemcpyHostToDevice, ctx->stream))
+		return finish(fail(ctx, V2M_ERR_HIP, "site LD: the strip bases could not be uploaded"));
+
+	if (dest.device) {
+		*dest.n_sites = V;
+		*dest.n_pairs = P;
+		if (V > dest.site_capacity || P > dest.pair_capacity)
+			return finish(fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%llu sites and %llu pairs do not fit capacities of %llu and %llu: size the buffers for them and call again",
+				(unsigned long long) V, (unsigned long long) P, (unsigned long long) dest.site_capacity, (unsigned long long) dest.pair_capacity));
+		if (hipSuccess != hipMemcpyAsync(dest.d_sites, records, V * sizeof(v2m_ld_site), hipMemcpyDeviceToDevice, ctx->stream))
+			return finish(fail(ctx, V2M_ERR_HIP, "site LD: the site records could not be copied"));
+		if (P) {
+			times.begin(stage_times::pairs);
+			pairs_launch(true, 0, n_strips, 0, dest.d_pairs);
+			times.end();
+			if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "site LD: ld_pairs_kernel did not launch"));
+		}
+		return finish(V2M_OK);
+	}
+
+	// the site records: over the link as they are
+	if (dest.sites_sink || dest.info) {
+		if (hipSuccess != ctx->h_ld_records.ensure(V * sizeof(v2m_ld_site))) return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "site LD: %llu bytes of pinned site records", (unsigned long long) (V * sizeof(v2m_ld_site))));
+		V2M_POISON_HOST(ctx->h_ld_records.p, V * sizeof(v2m_ld_site));
+		if (hipSuccess != hipMemcpyAsync(ctx->h_ld_records.p, records, V * sizeof(v2m_ld_site), hipMemcpyDeviceToHost, ctx->stream)
+			|| hipSuccess != hipStreamSynchronize(ctx->stream))
+			return finish(fail(ctx, V2M_ERR_HIP, "site LD: the site records did not arrive"));
+		v2m_ld_site const *const h_sites(ctx->h_ld_records.as<v2m_ld_site>());
+		out.n_candidates = site_ld_candidates(h_sites, V, prm.window_sites, prm.window_columns);
+		if (dest.sites_sink && dest.sites_sink(dest.user, h_sites, V)) return finish(fail(ctx, V2M_ERR_SINK, "sink aborted"));
+	}
+	if (!dest.pairs_sink || 0 == P) return finish(V2M_OK);
+
+	// The ranges: whole strips whose records fit the block, at least one strip; a range without a pair is passed over.  Range k is
+	// emitted into d_ld_pairs[k & 1], crosses the link on the copy stream into pinned slot k & 1, and reaches the sink while range
+	// k + 1 is emitted.  Both buffers of range k are free again when range k - 2 has been handed over, which waits for its copy on
+	// the host before range k - 1 is queued.
+	u64 const block_pairs(std::max<u64>(1, env_u64("V2M_SITE_LD_BLOCK_BYTES", u64(64) << 20) / sizeof(v2m_ld_pair)));
+	struct range { u64 strip_begin, strip_end, base, pairs; };
+	std::vector<range> ranges;
+	u64 most(0);
+	for (u64 i(0); i < n_strips;) {
+		u64 j(i + 1), count(h_totals[i]);
+		while (j < n_strips && count + h_totals[j] <= block_pairs) count += h_totals[j++];
+		if (count) { ranges.push_back(range{i, j, h_bases[i], count}); most = std::max(most, count); }
+		i = j;
+	}
+	if (int const rc2 = ensure_host_slots(ctx, std::min<u64>(2, ranges.size()), most * sizeof(v2m_ld_pair))) return finish(rc2);
+	auto const issue([&](u64 k) -> int {
+		int const b(int(k & 1));
+		range const &g(ranges[k]);
+		v2m_row_hold &slot(*ctx->host_slots[b]);
+		if (int const rc2 = ensure(ctx->d_ld_pairs[b], most * sizeof(v2m_ld_pair), "pairs")) return rc2;   // (refilled per range in the checked build)
+		V2M_POISON_HOST(slot.host.p, g.pairs * sizeof(v2m_ld_pair));
+		times.begin(stage_times::pairs);
+		pairs_launch(true, g.strip_begin, g.strip_end - g.strip_begin, g.base, ctx->d_ld_pairs[b].p);
+		times.end();
+		if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "site LD: ld_pairs_kernel did not launch");
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
+		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, ctx->d_ld_pairs[b].p, g.pairs * sizeof(v2m_ld_pair), hipMemcpyDeviceToHost, ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
+		return V2M_OK;
+	});
+	auto const hand_over([&](u64 k) -> int {
+		v2m_row_hold &slot(*ctx->host_slots[k & 1]);
+		V2M_HIP_TRY(ctx, hipEventSynchronize(slot.copied));
+		if (dest.pairs_sink(dest.user, slot.host.as<v2m_ld_pair>(), ranges[k].pairs)) return fail(ctx, V2M_ERR_SINK, "sink aborted");
+		return V2M_OK;
+	});
+	u64 launched(0);
+	for (u64 k(0); k < ranges.size() && V2M_OK == rc; ++k) {
+		if (V2M_OK != (rc = issue(k))) break;
+		launched = k + 1;
+		if (k >= 1) rc = hand_over(k - 1);   // its copy ran under this range's kernel
+	}
+	if (V2M_OK == rc && launched) rc = hand_over(launched - 1);
+	return finish(rc);
+}
+
+} // namespace
+
+int v2m_site_ld_device(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_site_ld_params *params, void *d_sites, uint64_t site_capacity, void *d_pairs, uint64_t pair_capacity,
+	uint64_t *n_sites, uint64_t *n_pairs)
+{
+	if (int const rc = check_site_ld(ctx, rows, params, "v2m_site_ld_device")) return rc;
+	if (!d_sites) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_sites is NULL");
+	if (!d_pairs && pair_capacity) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_pairs is NULL with a pair_capacity of %llu", (unsigned long long) pair_capacity);
+	if (!n_sites) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "n_sites is NULL");
+	if (!n_pairs) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "n_pairs is NULL");
+	if (reinterpret_cast<uintptr_t>(d_sites) & 15) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_sites must be 16-byte aligned");
+	if (reinterpret_cast<uintptr_t>(d_pairs) & 15) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_pairs must be 16-byte aligned");
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	return site_ld_run(ctx, rows, *params, site_ld_dest{true, d_sites, site_capacity, d_pairs, pair_capacity, n_sites, n_pairs, nullptr, nullptr, nullptr, nullptr});
+}
+
+int v2m_site_ld(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_site_ld_params *params, v2m_ld_sites_sink_fn sites_sink, v2m_ld_pairs_sink_fn pairs_sink, void *user,
+	v2m_site_ld_info *info)
+{
+	if (int const rc = check_site_ld(ctx, rows, params, "v2m_site_ld")) return rc;
+	if (0 == rows->n_rows) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	return site_ld_run(ctx, rows, *params, site_ld_dest{false, nullptr, 0, nullptr, 0, nullptr, nullptr, sites_sink, pairs_sink, user, info});
 }
 
 

@@ -78,6 +78,11 @@ def _load():
 		L.v2mh_distances_text.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_site_positions_text.restype = C.c_int64
 		L.v2mh_site_positions_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_site_ld_text.restype = C.c_int64
+		L.v2mh_site_ld_text.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+			C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_parse_decimal_fraction.restype = C.c_int
+		L.v2mh_parse_decimal_fraction.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -190,6 +195,37 @@ def site_positions_text(columns, reference_positions, aligned_positions):
 	if size != L.v2mh_site_positions_text(*args, dst, size, err, len(err)):
 		raise ValueError(err.value.decode())
 	return dst.raw[:size]
+
+
+def site_ld_text(n_rows, n_columns, sites, pairs, reference_positions, aligned_positions, window_sites=1000, window_columns=0, min_r2=(1, 5), min_allele_count=1):
+	"""The host library's formatter of --output-ld (csrc/host/output.cc: site_ld_text; no GPU): the TSV, as bytes, of the site and pair
+	records of Context.site_ld for n_rows rows over n_columns columns, under the parameters of the call."""
+	from . import _native as N
+	sites = np.ascontiguousarray(sites, dtype=np.dtype(N.LD_SITE_DTYPE))
+	pairs = np.ascontiguousarray(pairs, dtype=np.dtype(N.LD_PAIR_DTYPE))
+	ref = np.ascontiguousarray(reference_positions, dtype=np.uint64)
+	aln = np.ascontiguousarray(aligned_positions, dtype=np.uint64)
+	params = N.SiteLdParams(int(window_sites), int(min_allele_count), int(min_r2[0]), int(min_r2[1]), int(window_columns))
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (int(n_rows), int(n_columns), sites.ctypes.data if len(sites) else None, len(sites), pairs.ctypes.data if len(pairs) else None, len(pairs),
+		C.addressof(params), ref.ctypes.data, aln.ctypes.data, len(aln))
+	size = L.v2mh_site_ld_text(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != L.v2mh_site_ld_text(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
+
+
+def parse_decimal_fraction(text):
+	"""--ld-min-r2's value as (numerator, denominator) in lowest terms, from its digits (csrc/host/output.cc: parse_decimal_fraction);
+	ValueError unless it is DIGITS[.DIGITS] with at most 6 decimals inside [0, 1]."""
+	num, den = C.c_uint32(), C.c_uint32()
+	if not _load().v2mh_parse_decimal_fraction(str(text).encode(), C.byref(num), C.byref(den)):
+		raise ValueError("%r is no decimal number from 0 to 1 with at most 6 decimals" % (text,))
+	return int(num.value), int(den.value)
 
 
 def write_cut_positions(path, cut_positions, min_distance, score):

@@ -109,6 +109,20 @@ class Output:
 			positions.write(host.site_positions_text(columns, graph.reference_positions, graph.aligned_positions))
 		return info
 
+	def _write_ld(self, stream, rows, graph, **params):
+		"""--output-ld: the TSV of host.site_ld_text for `rows` (those of output_a2m) from Context.site_ld, over the region's columns when
+		there is one.  Returns the info of the call."""
+		from . import host
+		if self.region is not None:
+			self.ctx.set_column_window(*columns_of_reference_range(graph.reference_positions, graph.aligned_positions, *self.region))
+		try:
+			sites, pairs, info = self.ctx.site_ld(RowBatch(rows), info=True, **params)
+		finally:
+			if self.region is not None:
+				self.ctx.set_column_window(0, self.ctx.aligned_length)
+		stream.write(host.site_ld_text(len(rows), info["n_columns"], sites, pairs, graph.reference_positions, graph.aligned_positions, **params))
+		return info
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -174,6 +188,14 @@ class HaplotypeOutput(Output):
 				ids.append(self._fasta_id("%s-%d" % (sample, 1 + chr_copy_idx)))
 				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
 		return self._write_variable_sites(stream, ids, rows, graph, snp_only, positions)
+
+	def output_ld(self, graph, stream, window_sites=1000, window_columns=0, min_r2=(1, 5), min_allele_count=1):
+		"""--output-ld (with --ld-window, --ld-window-columns, --ld-min-r2 as a fraction and --ld-min-count) for the rows of output_a2m."""
+		rows = [PLOIDY_MAX] if self.should_output_reference else []
+		for sample_idx in range(len(graph.sample_names)):
+			for chr_copy_idx in range(graph.sample_ploidy(sample_idx)):
+				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
+		return self._write_ld(stream, rows, graph, window_sites=window_sites, window_columns=window_columns, min_r2=min_r2, min_allele_count=min_allele_count)
 
 	def output_chain(self, graph, stream):
 		"""--output-chain: the chains of the rows of output_a2m (without REF), named as one file per sequence would be."""
@@ -243,6 +265,16 @@ class FounderSequenceGreedyOutput(Output):
 			ids.append(self._fasta_id(str(1 + col_idx)))
 			rows.append(list(zip(cut_positions[:-1], col)))
 		return self._write_variable_sites(stream, ids, rows, graph, snp_only, positions)
+
+	def output_ld(self, graph, cut_positions, assigned_samples_column_major, stream, window_sites=1000, window_columns=0, min_r2=(1, 5), min_allele_count=1):
+		"""--output-ld for the rows of output_a2m (REF first, unless omitted, then the founder rows)."""
+		n_rows = len(cut_positions) - 1
+		n_founders = len(assigned_samples_column_major) // n_rows if n_rows else 0
+		rows = [PLOIDY_MAX] if self.should_output_reference else []
+		for col_idx in range(n_founders):
+			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
+			rows.append(list(zip(cut_positions[:-1], col)))
+		return self._write_ld(stream, rows, graph, window_sites=window_sites, window_columns=window_columns, min_r2=min_r2, min_allele_count=min_allele_count)
 
 	def output_chain(self, graph, cut_positions, assigned_samples_column_major, stream):
 		"""--output-chain for the founder rows of output_a2m."""
