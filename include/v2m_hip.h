@@ -41,7 +41,8 @@
  * v2m_distinct_sink_fn and the V2M_KERNEL_DISTINCT_* ids), and v2m_column_counts / v2m_column_counts_device (with v2m_column_count,
  * v2m_column_counts_sink_fn, the V2M_COUNTS_* flags and the V2M_KERNEL_COLUMN_* ids), and v2m_pair_distances / v2m_pair_distances_device
  * (with v2m_pair_distances_info, V2M_DIST_ACGT_ONLY and V2M_PAIR_DISTANCES_MAX_ROWS; no kernel ids: the info carries their times), and
- * v2m_variable_sites / v2m_variable_sites_device (with v2m_variable_sites_info, the two sink types and V2M_SITES_SNP; no kernel ids either).
+ * v2m_variable_sites / v2m_variable_sites_device (with v2m_variable_sites_info, the two sink types and V2M_SITES_SNP; no kernel ids either),
+ * and v2m_nj_tree / v2m_nj_tree_of_distances (with v2m_nj_node, v2m_nj_tree_info, V2M_NJ_NONE and V2M_NJ_MAX_ROWS; no kernel ids).
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -664,6 +665,70 @@ int v2m_site_ld(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_site_ld_param
 int v2m_site_ld_device(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_site_ld_params *params,
                        void *d_sites, uint64_t site_capacity, void *d_pairs /* may be NULL with capacity 0 */, uint64_t pair_capacity,
                        uint64_t *n_sites, uint64_t *n_pairs);
+
+/* ---- neighbour joining --------------------------------------------------------------------------
+ *
+ * The tree of the batch's rows: canonical neighbour joining (Saitou & Nei 1987; Studier & Keppler 1988) on the matrix of the pair
+ * distances, computed where the matrix lies.  This is the library's one floating-point result, and it is defined operation by
+ * operation so that it has exactly one value: all arithmetic is IEEE binary64, round to nearest, every operation rounded on its own
+ * and NEVER contracted into a fused multiply-add.
+ *
+ * Input and node ids.  n >= 3 taxa and the upper triangle d[i][j], i < j, of a u32 matrix; only those elements are read.  Leaves have
+ * ids 0 ... n - 1; the node made at join t (t = 0 ...) has id n + t.  D(a, b) = (double) d to begin with, and R(a) = sum over b of
+ * D(a, b): exact integers below 2^53, so that any order of summation gives the same value -- here, and only here.
+ *
+ * One join, repeated while r > 3 taxa remain:
+ *   1. Q(a, b) = (double) (r - 2) * D(a, b) - (R(a) + R(b)): one product, one sum, one difference.
+ *   2. The pair with the smallest Q; among equal Q the smallest lower id, then the smallest higher id (by id, never by where a taxon
+ *      happens to lie in memory).  a is the lower id, b the higher.
+ *   3. delta = (R(a) - R(b)) / (double) (r - 2);  len_a = 0.5 * (D(a, b) + delta);  len_b = D(a, b) - len_a.  Negative lengths are
+ *      kept, as canonical NJ does.
+ *   4. For every other live k: s = D(a, k) + D(b, k);  D(u, k) = 0.5 * (s - D(a, b));  R(k) = (R(k) - s) + D(u, k).
+ *   5. R(u) = 0.5 * ((R(a) + R(b)) - (double) r * D(a, b)): the closed form, not a sum over k, so that no order of reduction enters.
+ * The last three taxa a < b < c by id:
+ *   len_a = 0.5 * ((D(a, b) + D(a, c)) - D(b, c));  len_b = 0.5 * ((D(a, b) + D(b, c)) - D(a, c));
+ *   len_c = 0.5 * ((D(a, c) + D(b, c)) - D(a, b)).
+ *
+ * Result: n - 2 records.  Records 0 ... n - 4 are the joins in order, with c = V2M_NJ_NONE, len_c = 0 and reserved = 0; the last
+ * record is the trifurcation.
+ *
+ * v2m_nj_tree_of_distances: d_dist is u32[n][pitch] in device memory, 16-byte aligned, pitch % 4 == 0 and pitch >= n, as
+ * v2m_pair_distances_device writes it; it is not modified, and no graph is needed.  v2m_nj_tree: the distances of the batch over the
+ * view in force (flags: 0 or V2M_DIST_ACGT_ONLY, as for the pair distances) go into a context-owned matrix and the tree is built from
+ * it; the column window, the window set and what v2m_column_counts returns afterwards are left as they were.  nodes is host memory
+ * for n - 2 records.  info, which may be NULL, receives n_nodes (n - 2), the pair distances' n_sites, n_columns and n_passes (0 for
+ * v2m_nj_tree_of_distances) and -- while v2m_profile_enable is on, else 0 -- the stream time of the two stages in ms, as the pair
+ * distances define it.  The kernels have no V2M_KERNEL_* ids.
+ * n == 0 returns V2M_OK and touches nothing (info included); n == 1 and n == 2 are V2M_ERR_INVALID_ARGUMENT (there is no tree), and so
+ * are NULL pointers, unknown flags, a misaligned d_dist and a bad pitch; n > V2M_NJ_MAX_ROWS (32 768: 8.6 GB of working matrix) is
+ * V2M_ERR_UNSUPPORTED before any device work.  Rows may repeat (distance 0).  Both calls are synchronous.
+ * How (csrc/nj_kernels.hpp): nj_init_kernel makes the working matrix double[n][n], R and the table of ids; then per join
+ * nj_rowmin_kernel (a wave a row: the row's best (Q, lower id, higher id) over the live taxa, which lie dense in slots 0 ... r - 1)
+ * and nj_join_kernel (one workgroup: the step's pair, the record, D(u, .) and the R updates; u takes one of the two slots and the last
+ * live slot moves into the other); nj_last_kernel writes the trifurcation.  The host sizes every grid from r = n - t and queues all
+ * 2 (n - 3) + 2 launches on the context's stream without a synchronisation in between; the records come back in one copy. */
+#define V2M_NJ_NONE 0xFFFFFFFFu
+#define V2M_NJ_MAX_ROWS 32768u
+
+typedef struct {
+	uint32_t a, b, c, reserved;     /* the joined ids, a < b (< c); c = V2M_NJ_NONE but in the last record */
+	double len_a, len_b, len_c;     /* the branch from the new node to a, b (and c; 0 but in the last record) */
+} v2m_nj_node;           /* 40 bytes */
+
+typedef struct {
+	uint64_t n_nodes;     /* records written: n - 2 */
+	uint64_t n_sites;     /* of the pair distances (v2m_nj_tree) */
+	uint64_t n_columns;   /* likewise: L */
+	uint64_t n_passes;    /* likewise */
+	double distances_ms;  /* the pair distances' three stages together: stream time, see "pair distances" */
+	double tree_ms;       /* nj_init_kernel ... nj_last_kernel: likewise */
+} v2m_nj_tree_info;      /* 48 bytes */
+
+int v2m_nj_tree_of_distances(v2m_ctx *ctx, const void *d_dist, uint64_t n, uint64_t pitch, v2m_nj_node *nodes /* host, n - 2 */,
+                             v2m_nj_tree_info *info /* may be NULL */);
+
+int v2m_nj_tree(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_DIST_ACGT_ONLY */, v2m_nj_node *nodes /* host, n_rows - 2 */,
+                v2m_nj_tree_info *info /* may be NULL */);
 
 /* ---- founder search: the chunk walks ---------------------------------- */
 

@@ -61,6 +61,12 @@ SITE_LD_MAX_WINDOW = 4096
 SITE_LD_MAX_ROWS = 32768
 LD_TILE = 64
 LD_CHUNK_WORDS = 8
+# v2m_nj_tree[_of_distances]: the id that is none, the limit, and csrc/nj_kernels.hpp's kNjRowsPerGroup (rows per workgroup of
+# nj_rowmin_kernel) and kNjJoinThreads (nj_join_kernel's one workgroup); tests/test_nj_tree_host.py holds them to the sources
+NJ_NONE = 0xFFFFFFFF
+NJ_MAX_ROWS = 32768
+NJ_ROWS_PER_GROUP = 8
+NJ_JOIN_THREADS = 256
 # csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
 # kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
 DISTINCT_CHUNK_BYTES = 8192
@@ -135,6 +141,13 @@ class SiteLdInfo(C.Structure):   # v2m_site_ld_info
 LD_SITE_DTYPE = [("column", "<u8"), ("class_lo", "<u4"), ("class_hi", "<u4"), ("count_lo", "<u4"), ("count_hi", "<u4")]   # v2m_ld_site
 LD_PAIR_DTYPE = [("site_a", "<u4"), ("site_b", "<u4"), ("n", "<u4"), ("n_a", "<u4"), ("n_b", "<u4"), ("n_ab", "<u4")]   # v2m_ld_pair
 LD_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_ld_sites_sink_fn, v2m_ld_pairs_sink_fn
+
+
+class NjTreeInfo(C.Structure):   # v2m_nj_tree_info
+	_fields_ = [("n_nodes", C.c_uint64), ("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("n_passes", C.c_uint64), ("distances_ms", C.c_double), ("tree_ms", C.c_double)]
+
+
+NJ_NODE_DTYPE = [("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("reserved", "<u4"), ("len_a", "<f8"), ("len_b", "<f8"), ("len_c", "<f8")]   # v2m_nj_node
 SITE_COLUMNS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_site_columns_sink_fn
 SITE_ROWS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_site_rows_sink_fn
 TRIALS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_trials_sink
@@ -180,6 +193,8 @@ SIGNATURES = {
 	"v2m_variable_sites_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 	"v2m_site_ld": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.POINTER(SiteLdParams), LD_SINK_FN, LD_SINK_FN, C.c_void_p, C.POINTER(SiteLdInfo)]),
 	"v2m_site_ld_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.POINTER(SiteLdParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p, _u64p]),
+	"v2m_nj_tree_of_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(NjTreeInfo)]),
+	"v2m_nj_tree": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.POINTER(NjTreeInfo)]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -592,6 +592,37 @@ class Context:
 		self._check(rc)
 		return self.site_ld_counts
 
+	@staticmethod
+	def _nj_result(n, nodes, record, info):
+		nodes = nodes[:max(0, n - 2)] if n >= 3 else nodes[:0]
+		if info:
+			return nodes, {name: getattr(record, name) for name, _ in N.NjTreeInfo._fields_}
+		return nodes
+
+	def nj_tree(self, rows, acgt_only=False, info=False):
+		"""v2m_nj_tree: the neighbour-joining tree of the batch's rows over the view in force, from their pair distances (acgt_only:
+		V2M_DIST_ACGT_ONLY), as a structured array of the n - 2 v2m_nj_node records (a, b, c, reserved, len_a, len_b, len_c): the joins in
+		order, node n + t made at join t, then the trifurcation.  No rows give no records; one or two raise.  With info=True: (records,
+		dict of v2m_nj_tree_info's fields)."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = int(rows.struct.n_rows)
+		nodes = np.zeros(max(1, n - 2), dtype=np.dtype(N.NJ_NODE_DTYPE))   # (never a NULL pointer: no rows is no error)
+		record = N.NjTreeInfo()
+		self._check(self._lib.v2m_nj_tree(self._h, C.byref(rows.struct), N.DIST_ACGT_ONLY if acgt_only else 0, nodes.ctypes.data, C.byref(record)))
+		if n == 0:
+			record.n_columns = self.window_length   # (with no rows the call returns before it writes the info)
+		return self._nj_result(n, nodes, record, info)
+
+	def nj_tree_of_distances(self, ptr, n, pitch, info=False):
+		"""v2m_nj_tree_of_distances: the tree of the n taxa whose distances lie in device memory at `ptr`, u32[n][pitch] (16-byte aligned,
+		pitch a multiple of 4 and at least n; only the upper triangle is read, nothing is written): the records of nj_tree."""
+		n = int(n)
+		nodes = np.zeros(max(1, n - 2 if n <= N.NJ_MAX_ROWS else 1), dtype=np.dtype(N.NJ_NODE_DTYPE))
+		record = N.NjTreeInfo()
+		self._check(self._lib.v2m_nj_tree_of_distances(self._h, ptr, n, int(pitch), nodes.ctypes.data, C.byref(record)))
+		return self._nj_result(n, nodes, record, info)
+
 	def bgzf_compress(self, data):
 		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
 		src = bytes(data)

@@ -516,4 +516,34 @@ int v2mh_parse_decimal_fraction(char const *text, uint32_t *numerator, uint32_t 
 	return text && numerator && denominator && vh::parse_decimal_fraction(text, *numerator, *denominator) ? 1 : 0;
 }
 
+// nj_tree_cpu() of output.hh (no GPU): the n - 2 records of the tree of dist (u32[n][pitch]) into nodes; 0, or -1 for a NULL pointer,
+// n < 3, pitch < n or no memory.
+int v2mh_nj_tree_cpu(uint32_t const *dist, uint64_t n, uint64_t pitch, v2m_nj_node *nodes)
+{
+	try {
+		if (!dist || !nodes) return -1;
+		vh::nj_tree_cpu(dist, n, pitch, nodes);
+		return 0;
+	} catch (std::exception const &) {
+		return -1;
+	}
+}
+
+// nj_newick_text() of output.hh (no GPU), handed over as v2mh_distances_text hands over its table; labels are n_leaves NUL-terminated
+// strings; -1 with a message in err on failure.
+int64_t v2mh_nj_newick_text(v2m_nj_node const *nodes, uint64_t n_leaves, char const *const *labels, char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		if (!nodes || !labels) throw std::runtime_error("nodes or labels is NULL");
+		std::vector<std::string> names;
+		for (uint64_t i(0); i < n_leaves; ++i) names.emplace_back(labels[i]);
+		std::string const text(vh::nj_newick_text(nodes, n_leaves, names));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
 } // extern "C"

@@ -63,6 +63,8 @@ struct options {
 	char const *output_ld{};              // --output-ld=FILE: linkage disequilibrium between nearby biallelic sites of the output rows, from v2m_site_ld
 	char const *ld_window{}, *ld_window_columns{}, *ld_min_r2{}, *ld_min_count{};   // --ld-window=SITES, --ld-window-columns=N, --ld-min-r2=DECIMAL, --ld-min-count=N (with --output-ld)
 	v2m_site_ld_params ld_params{1000, 1, 1, 5, 0};
+	char const *output_tree{};            // --output-tree=FILE: the neighbour-joining tree of the output rows in Newick form, from v2m_nj_tree
+	bool tree_acgt_only{};                // --tree-acgt-only (with --output-tree): the tree of the distances --acgt-only counts
 	bool all_columns{};                   // --all-columns (with --output-column-counts): every column, not only the variable ones
 	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
 	std::vector<int> devices{0};
@@ -155,6 +157,16 @@ void usage()
 		"      --ld-min-r2=DECIMAL            With --output-ld: report the pairs with r2 >= DECIMAL (0 to 1, at most 6 decimals;\n"
 		"                                     default 0.2), compared exactly\n"
 		"      --ld-min-count=N               With --output-ld: a site's two alleles each occur at least N times (default 1)\n"
+		"      --output-tree=FILE             Write the neighbour-joining tree of the output sequences (REF first, unless\n"
+		"                                     --omit-reference; at least three) in Newick form: canonical NJ on the matrix of\n"
+		"                                     --output-distances, unrooted (the last three nodes meet in a trifurcation), leaves named as\n"
+		"                                     --output-distances names them, branch lengths in columns, negative ones kept.  Distances and\n"
+		"                                     tree are computed on the GPU, in IEEE double precision without fused multiply-adds, ties\n"
+		"                                     broken by node number.  Always of the aligned form, whatever --unaligned says; --region\n"
+		"                                     restricts the columns.  Alone or beside the other outputs; not with --regions-file or\n"
+		"                                     several --device entries\n"
+		"      --tree-acgt-only               With --output-tree: the distances count only the columns where both sequences hold A, C, G\n"
+		"                                     or T (as --acgt-only does for --output-distances)\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -350,7 +362,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_output_tree, o_tree_acgt_only, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -365,6 +377,7 @@ int main(int argc, char **argv)
 		{"output-graphviz", required_argument, nullptr, o_unsupported}, {"output-memory-breakdown", required_argument, nullptr, o_unsupported}, {"pipe", required_argument, nullptr, o_pipe}, {"bgzf", no_argument, nullptr, o_bgzf}, {"region", required_argument, nullptr, o_region}, {"gpu-parse", no_argument, nullptr, o_gpu_parse}, {"regions-file", required_argument, nullptr, o_regions_file}, {"output-chain", required_argument, nullptr, o_output_chain}, {"distinct", no_argument, nullptr, o_distinct}, {"output-paf", required_argument, nullptr, o_output_paf}, {"output-column-counts", required_argument, nullptr, o_output_column_counts}, {"all-columns", no_argument, nullptr, o_all_columns}, {"output-distances", required_argument, nullptr, o_output_distances}, {"acgt-only", no_argument, nullptr, o_acgt_only}, {"output-variable-sites", required_argument, nullptr, o_output_variable_sites}, {"snp-sites", no_argument, nullptr, o_snp_sites}, {"output-site-positions", required_argument, nullptr, o_output_site_positions},
 		{"output-ld", required_argument, nullptr, o_output_ld}, {"ld-window", required_argument, nullptr, o_ld_window}, {"ld-window-columns", required_argument, nullptr, o_ld_window_columns},
 		{"ld-min-r2", required_argument, nullptr, o_ld_min_r2}, {"ld-min-count", required_argument, nullptr, o_ld_min_count},
+		{"output-tree", required_argument, nullptr, o_output_tree}, {"tree-acgt-only", no_argument, nullptr, o_tree_acgt_only},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -426,6 +439,8 @@ int main(int argc, char **argv)
 			case o_ld_window_columns: opt.ld_window_columns = optarg; break;
 			case o_ld_min_r2: opt.ld_min_r2 = optarg; break;
 			case o_ld_min_count: opt.ld_min_count = optarg; break;
+			case o_output_tree: opt.output_tree = optarg; break;
+			case o_tree_acgt_only: opt.tree_acgt_only = true; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -478,6 +493,17 @@ int main(int argc, char **argv)
 		// one matrix from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
 		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
 		if (other) { std::cerr << "ERROR: --output-distances cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+	}
+	if (opt.tree_acgt_only && !opt.output_tree) { std::cerr << "ERROR: --tree-acgt-only requires --output-tree.\n"; return EXIT_FAILURE; }
+	if (opt.output_tree) {
+		// one matrix and one tree from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
+		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
+		if (other) { std::cerr << "ERROR: --output-tree cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+		// the founder rows are counted here; the haplotype rows once the graph is there
+		if (opt.founder_mode && opt.founder_sequences + (opt.omit_reference ? 0 : 1) < 3) {
+			std::cerr << "ERROR: --output-tree needs at least three sequences (got " << opt.founder_sequences + (opt.omit_reference ? 0 : 1) << ").\n";
+			return EXIT_FAILURE;
+		}
 	}
 	if (opt.snp_sites && !opt.output_variable_sites) { std::cerr << "ERROR: --snp-sites requires --output-variable-sites.\n"; return EXIT_FAILURE; }
 	if (opt.output_site_positions && !opt.output_variable_sites) { std::cerr << "ERROR: --output-site-positions requires --output-variable-sites.\n"; return EXIT_FAILURE; }
@@ -634,6 +660,11 @@ int main(int argc, char **argv)
 			if (0 == stats.handled_variants) std::cerr << "WARNING: no variants matched the chromosome identifier \"" << opt.chromosome << "\".\n";
 		}
 
+		if (opt.output_tree && opt.haplotypes && graph.total_chromosome_copies() + (opt.omit_reference ? 0 : 1) < 3) {
+			std::cerr << "ERROR: --output-tree needs at least three sequences (got " << graph.total_chromosome_copies() + (opt.omit_reference ? 0 : 1) << ").\n";
+			return EXIT_FAILURE;
+		}
+
 		if (opt.output_graph) {                                 // main.cc:418-426
 			std::cerr << "Outputting the variant graph..." << std::flush;
 			vh::write_graph(graph, opt.output_graph);
@@ -759,6 +790,11 @@ int main(int argc, char **argv)
 			if (opt.output_ld) {
 				std::cerr << "Outputting site LD..." << std::flush;
 				output.output_ld(graph, opt.output_ld, opt.ld_params, opt.verbose);
+				std::cerr << " Done.\n";
+			}
+			if (opt.output_tree) {
+				std::cerr << "Outputting the tree..." << std::flush;
+				output.output_tree(graph, opt.output_tree, opt.tree_acgt_only, opt.verbose);
 				std::cerr << " Done.\n";
 			}
 		});

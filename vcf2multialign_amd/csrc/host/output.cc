@@ -1421,6 +1421,184 @@ void output::output_ld(variant_graph const &graph, char const *path, v2m_site_ld
 }
 
 
+// --- neighbour joining (--output-tree) ---------------------------------------------------------------------------
+// The header's definition in plain loops.  Every operation of the definition is a statement of its own, and nothing here may be
+// contracted: the host library is built as ISO C++ (-std=c++20, which sets -ffp-contract=off in g++) and without -march, so that the
+// compiler neither fuses a product into a sum nor has an instruction to fuse them with.  The live taxa keep their places in `at`;
+// the new node takes the place of a, and the place of b is dropped from the list of the live ones, which stays in ascending order of
+// place -- the order plays no part: the pair is chosen by (Q, lower id, higher id).
+void nj_tree_cpu(std::uint32_t const *dist, u64 n, u64 pitch, v2m_nj_node *nodes)
+{
+	if (n < 3) throw std::invalid_argument("a neighbour-joining tree needs at least 3 taxa");
+	if (pitch < n) throw std::invalid_argument("the pitch of the distance matrix is smaller than its side");
+	std::vector<double> D(n * n, 0.0), R(n, 0.0);
+	std::vector<std::uint32_t> id(n), live(n);
+	for (u64 i(0); i < n; ++i) {
+		id[i] = std::uint32_t(i);
+		live[i] = std::uint32_t(i);
+		for (u64 j(i + 1); j < n; ++j) {
+			double const d(double(dist[i * pitch + j]));
+			D[i * n + j] = d;
+			D[j * n + i] = d;
+		}
+	}
+	for (u64 i(0); i < n; ++i) {
+		double sum(0.0);   // (exact integers below 2^53: any order)
+		for (u64 j(0); j < n; ++j) sum += D[i * n + j];
+		R[i] = sum;
+	}
+	u64 t(0);
+	for (u64 r(n); r > 3; --r, ++t) {
+		double const factor = double(r - 2);
+		bool have(false);
+		double best_q(0.0);
+		std::uint32_t best_lo(0), best_hi(0);
+		u64 best_x(0), best_y(0);
+		for (u64 x(0); x < r; ++x) {
+			u64 const i(live[x]);
+			double const *const row(&D[i * n]);
+			for (u64 y(x + 1); y < r; ++y) {
+				u64 const j(live[y]);
+				double const product = factor * row[j];
+				double const sum = R[i] + R[j];
+				double const q = product - sum;
+				if (have && q > best_q) continue;
+				std::uint32_t const lo(std::min(id[i], id[j])), hi(std::max(id[i], id[j]));
+				if (!have || q < best_q || lo < best_lo || (lo == best_lo && hi < best_hi)) {
+					have = true; best_q = q; best_lo = lo; best_hi = hi; best_x = x; best_y = y;
+				}
+			}
+		}
+		bool const a_first(id[live[best_x]] == best_lo);
+		u64 const pa(live[a_first ? best_x : best_y]), pb(live[a_first ? best_y : best_x]);
+		double const d_ab = D[pa * n + pb];
+		double const difference = R[pa] - R[pb];
+		double const delta = difference / factor;
+		double const with_delta = d_ab + delta;
+		double const len_a = 0.5 * with_delta;
+		double const len_b = d_ab - len_a;
+		nodes[t] = v2m_nj_node{best_lo, best_hi, V2M_NJ_NONE, 0, len_a, len_b, 0.0};
+		double const both = R[pa] + R[pb];
+		double const product = double(r) * d_ab;
+		double const remainder = both - product;
+		double const r_u = 0.5 * remainder;
+		for (u64 x(0); x < r; ++x) {
+			u64 const k(live[x]);
+			if (k == pa || k == pb) continue;
+			double const s = D[pa * n + k] + D[pb * n + k];
+			double const less = s - d_ab;
+			double const d_uk = 0.5 * less;
+			double const without = R[k] - s;
+			R[k] = without + d_uk;
+			D[pa * n + k] = d_uk;
+			D[k * n + pa] = d_uk;
+		}
+		R[pa] = r_u;
+		id[pa] = std::uint32_t(n + t);
+		live.erase(live.begin() + std::ptrdiff_t(a_first ? best_y : best_x));
+	}
+	u64 p[3] = {live[0], live[1], live[2]};
+	std::sort(p, p + 3, [&](u64 x, u64 y) { return id[x] < id[y]; });
+	double const d_ab = D[p[0] * n + p[1]], d_ac = D[p[0] * n + p[2]], d_bc = D[p[1] * n + p[2]];
+	double const ab_ac = d_ab + d_ac, ab_bc = d_ab + d_bc, ac_bc = d_ac + d_bc;
+	double const for_a = ab_ac - d_bc, for_b = ab_bc - d_ac, for_c = ac_bc - d_ab;
+	nodes[t] = v2m_nj_node{id[p[0]], id[p[1]], id[p[2]], 0, 0.5 * for_a, 0.5 * for_b, 0.5 * for_c};
+}
+
+
+std::string nj_newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels)
+{
+	u64 const n(n_leaves);
+	if (n < 3) throw std::invalid_argument("a tree has at least 3 leaves");
+	if (labels.size() != n) throw std::invalid_argument("the tree has " + std::to_string(n) + " leaves and " + std::to_string(labels.size()) + " labels");
+	u64 const root(n - 3);   // the last record's index
+	// the records are a tree over the leaves: every id but the root's is a child exactly once, and a node is made before it is joined
+	std::vector<char> used(2 * n - 3, 0);
+	for (u64 rec(0); rec <= root; ++rec) {
+		v2m_nj_node const &nd(nodes[rec]);
+		if ((rec < root) != (V2M_NJ_NONE == nd.c)) throw std::runtime_error("record " + std::to_string(rec) + " of the tree has " + (rec < root ? "three children" : "two children, and is the last"));
+		for (int k(0); k < (rec < root ? 2 : 3); ++k) {
+			u64 const child(0 == k ? nd.a : 1 == k ? nd.b : nd.c);
+			if (child >= n + rec) throw std::runtime_error("record " + std::to_string(rec) + " of the tree names node " + std::to_string(child) + ", which is not made before it");
+			if (used[child]) throw std::runtime_error("node " + std::to_string(child) + " of the tree is joined twice");
+			used[child] = 1;
+		}
+	}
+	auto const append_label([](std::string &text, std::string const &label) {
+		bool bare(!label.empty());
+		for (unsigned char const c : label) bare = bare && (std::isalnum(c) || '.' == c || '-' == c) && c < 0x80;
+		if (bare) { text += label; return; }
+		text += '\'';
+		for (char const c : label) { if ('\'' == c) text += '\''; text += c; }
+		text += '\'';
+	});
+	auto const append_length([](std::string &text, double len) {
+		char buf[48];
+		std::snprintf(buf, sizeof(buf), ":%.10g", len);
+		text += buf;
+	});
+	struct frame { u64 rec; int next; };
+	std::vector<frame> stack{{root, 0}};
+	std::string text("(");
+	while (!stack.empty()) {
+		frame const f(stack.back());
+		v2m_nj_node const &nd(nodes[f.rec]);
+		int const children(f.rec == root ? 3 : 2);
+		if (f.next > 0) append_length(text, 1 == f.next ? nd.len_a : 2 == f.next ? nd.len_b : nd.len_c);   // (of the child just closed)
+		if (f.next == children) {
+			text += ')';
+			stack.pop_back();
+			continue;
+		}
+		if (f.next > 0) text += ',';
+		u64 const child(0 == f.next ? nd.a : 1 == f.next ? nd.b : nd.c);
+		++stack.back().next;
+		if (child < n) append_label(text, labels[child]);
+		else {
+			stack.push_back({child - n, 0});
+			text += '(';
+		}
+	}
+	text += ";\n";
+	return text;
+}
+
+
+void output::output_tree(variant_graph const &graph, std::ostream &stream, bool acgt_only, bool verbose)
+{
+	if (!m_more_gpus.empty()) throw std::runtime_error("--output-tree needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-tree needs every chromosome copy on one GPU context");
+	row_set const rows(chain_rows(graph));   // (the rows of a2m_rows() under the names --output-distances writes)
+	v2m_row_batch batch{};
+	batch.n_rows = rows.copy_index.size();
+	batch.copy_index = rows.copy_index.data();
+	if (rows.any_cuts) {
+		batch.cut_offsets = rows.cut_offsets.data();
+		batch.cut_nodes = rows.cut_nodes.data();
+		batch.cut_copies = rows.cut_copies.data();
+	}
+	if (batch.n_rows < 3) throw std::runtime_error("--output-tree needs at least three sequences (got " + std::to_string(batch.n_rows) + ")");
+	std::vector<v2m_nj_node> nodes(batch.n_rows - 2);
+	v2m_nj_tree_info info{};
+	m_gpu.check(v2m_nj_tree(m_gpu.get(), &batch, acgt_only ? V2M_DIST_ACGT_ONLY : 0, nodes.data(), &info));
+	std::string const text(nj_newick_text(nodes.data(), batch.n_rows, rows.ids));
+	stream.write(text.data(), std::streamsize(text.size()));
+	if (verbose)
+		std::fprintf(stderr, "Tree: %llu rows, %llu columns, %llu sites, %llu joins.\n", (unsigned long long) batch.n_rows, (unsigned long long) info.n_columns,
+			(unsigned long long) info.n_sites, (unsigned long long) (info.n_nodes - 1));
+}
+
+
+void output::output_tree(variant_graph const &graph, char const *path, bool acgt_only, bool verbose)
+{
+	std::ofstream stream(path, std::ios::binary | std::ios::trunc);
+	if (!stream) throw std::runtime_error(std::string("unable to open ") + path + " for writing");
+	output_tree(graph, stream, acgt_only, verbose);
+	stream.flush();
+	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+}
+
+
 // --- haplotype_output (haplotype_output.cc:38-132) ------------------------------------------------------------
 output::row_set haplotype_output::rows_for(variant_graph const &graph, char sep, char const *suffix)
 {

@@ -88,6 +88,18 @@ std::string site_ld_text(u64 n_rows, u64 n_columns, v2m_ld_site const *sites, u6
 // --ld-min-r2's value from its digits, with no floating point: DIGITS[.DIGITS], at most 6 decimals, inside [0, 1]; in lowest terms.
 bool parse_decimal_fraction(char const *text, std::uint32_t &numerator, std::uint32_t &denominator);
 
+// The neighbour-joining tree (include/v2m_hip.h, "neighbour joining") of the n >= 3 taxa of dist (u32[n][pitch], of which only the
+// upper triangle is read), restated in plain loops: nodes receives the n - 2 records.  The second yardstick of the GPU's result and
+// the CPU baseline of its measurement.  O(n^3) time, n^2 doubles of memory.
+void nj_tree_cpu(std::uint32_t const *dist, u64 n, u64 pitch, v2m_nj_node *nodes);
+
+// --output-tree's text: the tree of the n - 2 records over the n leaves named `labels` in Newick form, a pure function of its
+// arguments.  Node n + t is written (<a>:<len_a>,<b>:<len_b>), the tree (<a>:...,<b>:...,<c>:...); and a line break; internal nodes
+// carry no label; lengths are printed %.10g.  A label of A-Z, a-z, 0-9, '.' and '-' only is written bare, any other (an empty one and
+// one with '_', which a Newick reader would take for a space, included) in single quotes with ' doubled.  Built without recursion.
+// Throws when the records are no tree over the leaves: an id out of range or used twice, or c set before the last record.
+std::string nj_newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -176,6 +188,12 @@ public:
 	// number.  verbose prints the rows, columns, sites, candidates and pairs to stderr.
 	void output_ld(variant_graph const &graph, char const *path, v2m_site_ld_params const &params, bool verbose = false);
 	void output_ld(variant_graph const &graph, std::ostream &stream, v2m_site_ld_params const &params, bool verbose = false);
+
+	// --output-tree: nj_newick_text above for the rows of the A2M output (REF first, unless omitted) under the names --output-distances
+	// writes, over the view in force (--region: the window's columns), from v2m_nj_tree on the first context, which must hold every
+	// copy.  acgt_only: V2M_DIST_ACGT_ONLY; verbose prints the rows, columns, sites and joins to stderr.
+	void output_tree(variant_graph const &graph, char const *path, bool acgt_only = false, bool verbose = false);
+	void output_tree(variant_graph const &graph, std::ostream &stream, bool acgt_only = false, bool verbose = false);
 
 protected:
 	struct row_set {

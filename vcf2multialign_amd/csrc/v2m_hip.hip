@@ -33,6 +33,7 @@
 #include "distance_kernels.hpp"
 #include "site_kernels.hpp"
 #include "ld_kernels.hpp"
+#include "nj_kernels.hpp"
 
 using v2m::u32;
 using v2m::u64;
@@ -267,6 +268,8 @@ struct v2m_ctx {
 	pinned_buf h_column_total;
 	// pair distances (v2m_pair_distances): the site list, a pass's bit planes, and the host form's matrix
 	scratch_buf d_dist_sites, d_dist_planes, d_dist_matrix;
+	// neighbour joining (v2m_nj_tree[_of_distances]): the working matrix, R, the ids, the row minima and the records
+	scratch_buf d_nj_matrix, d_nj_sums, d_nj_ids, d_nj_best, d_nj_nodes;
 	// variable sites (v2m_variable_sites): the site list, the host form's gathered slices (two, used in turn), the list's pinned staging
 	scratch_buf d_site_columns, d_site_bytes[2];
 	pinned_buf h_site_columns;
@@ -3999,6 +4002,113 @@ int v2m_site_ld(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_site_ld_param
 	if (0 == rows->n_rows) return V2M_OK;
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 	return site_ld_run(ctx, rows, *params, site_ld_dest{false, nullptr, 0, nullptr, 0, nullptr, nullptr, sites_sink, pairs_sink, user, info});
+}
+
+
+// ---- neighbour joining (nj_kernels.hpp) ------------------------------------------------------------
+
+namespace {
+
+static_assert(sizeof(v2m_nj_node) == 40 && sizeof(v2m_nj_tree_info) == 48, "the header's sizes");
+static_assert(V2M_NJ_NONE == v2m::kNjNone, "one value for no id");
+
+int check_nj_matrix(v2m_ctx *ctx, void const *d_dist, u64 n, u64 pitch, v2m_nj_node const *nodes, char const *name)
+{
+	if (!d_dist) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_dist is NULL");
+	if (!nodes) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "nodes is NULL");
+	if (reinterpret_cast<uintptr_t>(d_dist) & 15) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_dist must be 16-byte aligned");
+	if ((pitch & 3) || pitch < n)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "pitch %llu must be a multiple of 4 and at least n = %llu", (unsigned long long) pitch, (unsigned long long) n);
+	if (n > V2M_NJ_MAX_ROWS)
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes at most V2M_NJ_MAX_ROWS = %u taxa (got %llu)", name, V2M_NJ_MAX_ROWS, (unsigned long long) n);
+	return V2M_OK;
+}
+
+int nj_too_few(v2m_ctx *ctx, u64 n, char const *name)
+{
+	return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s needs at least 3 taxa: %llu %s no tree", name, (unsigned long long) n, 1 == n ? "has" : "have");
+}
+
+// Queues and completes the tree of the n >= 3 taxa of d_dist (u32[n][dist_pitch], device) into nodes (host, n - 2).  All launches go to
+// the context's stream in order, none waits for the host; tree_ms: the stream time from the first to the last while profiling is on.
+int nj_run(v2m_ctx *ctx, u32 const *d_dist, u64 n, u64 dist_pitch, v2m_nj_node *nodes, double *tree_ms)
+{
+	u64 const pitch((n + 1) & ~u64(1));
+	auto const ensure([&](scratch_buf &buf, u64 bytes, char const *what) -> int {
+		hipError_t const st(buf.ensure(bytes));
+		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "neighbour joining: %llu bytes of %s: %s", (unsigned long long) bytes, what, hipGetErrorString(st));
+		return V2M_OK;
+	});
+	if (int const rc = ensure(ctx->d_nj_matrix, n * pitch * sizeof(double), "working matrix")) return rc;
+	if (int const rc = ensure(ctx->d_nj_sums, pitch * sizeof(double), "row sums")) return rc;
+	if (int const rc = ensure(ctx->d_nj_ids, pitch * sizeof(u32), "ids")) return rc;
+	if (int const rc = ensure(ctx->d_nj_best, n * sizeof(v2m::nj_best), "row minima")) return rc;
+	if (int const rc = ensure(ctx->d_nj_nodes, (n - 2) * sizeof(v2m_nj_node), "records")) return rc;
+	double *const D(ctx->d_nj_matrix.as<double>()), *const R(ctx->d_nj_sums.as<double>());
+	u32 *const ids(ctx->d_nj_ids.as<u32>());
+	v2m::nj_best *const best(ctx->d_nj_best.as<v2m::nj_best>());
+	v2m_nj_node *const d_nodes(ctx->d_nj_nodes.as<v2m_nj_node>());
+
+	stage_times times(ctx);
+	times.begin(0);
+	hipLaunchKernelGGL(v2m::nj_init_kernel, dim3(unsigned(n)), dim3(v2m::kNjInitThreads), 0, ctx->stream, d_dist, dist_pitch, u32(n), D, pitch, R, ids);
+	for (u64 t(0); t + 3 < n; ++t) {
+		u32 const r(u32(n - t));
+		unsigned const groups((r - 1 + v2m::kNjRowsPerGroup - 1) / v2m::kNjRowsPerGroup);
+		hipLaunchKernelGGL(v2m::nj_rowmin_kernel, dim3(groups), dim3(v2m::kNjRowminThreads), 0, ctx->stream, D, pitch, R, ids, r, best);
+		hipLaunchKernelGGL(v2m::nj_join_kernel, dim3(1), dim3(v2m::kNjJoinThreads), 0, ctx->stream, D, pitch, R, ids, r, u32(n + t), best, d_nodes + t);
+	}
+	hipLaunchKernelGGL(v2m::nj_last_kernel, dim3(1), dim3(v2m::kWave), 0, ctx->stream, D, pitch, ids, d_nodes + (n - 3));
+	times.end();
+	hipError_t const launched(hipGetLastError());
+	hipError_t copied(hipMemcpyAsync(nodes, d_nodes, (n - 2) * sizeof(v2m_nj_node), hipMemcpyDeviceToHost, ctx->stream));
+	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
+	if (hipSuccess != launched) return fail(ctx, V2M_ERR_HIP, "neighbour joining: a kernel did not launch: %s", hipGetErrorString(launched));
+	V2M_HIP_TRY(ctx, copied);
+	V2M_HIP_TRY(ctx, st);
+	if (tree_ms) {
+		double ms[stage_times::n_stages] = {};
+		times.sum(ms);
+		*tree_ms = ms[0];
+	}
+	return V2M_OK;
+}
+
+} // namespace
+
+int v2m_nj_tree_of_distances(v2m_ctx *ctx, const void *d_dist, uint64_t n, uint64_t pitch, v2m_nj_node *nodes, v2m_nj_tree_info *info)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (int const rc = check_nj_matrix(ctx, d_dist, n, pitch, nodes, "v2m_nj_tree_of_distances")) return rc;
+	if (0 == n) return V2M_OK;
+	if (n < 3) return nj_too_few(ctx, n, "v2m_nj_tree_of_distances");
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	v2m_nj_tree_info out{};
+	out.n_nodes = n - 2;
+	if (int const rc = nj_run(ctx, static_cast<u32 const *>(d_dist), n, pitch, nodes, &out.tree_ms)) return rc;
+	if (info) *info = out;
+	return V2M_OK;
+}
+
+int v2m_nj_tree(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_nj_node *nodes, v2m_nj_tree_info *info)
+{
+	static_assert(V2M_NJ_MAX_ROWS == V2M_PAIR_DISTANCES_MAX_ROWS, "the pair distances' check bounds the taxa");
+	if (int const rc = check_pair_distances(ctx, rows, flags, "v2m_nj_tree")) return rc;
+	if (!nodes) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "nodes is NULL");
+	u64 const n(rows->n_rows), pitch((n + 3) & ~u64(3));
+	if (0 == n) return V2M_OK;
+	if (n < 3) return nj_too_few(ctx, n, "v2m_nj_tree");
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	V2M_HIP_TRY(ctx, ctx->d_dist_matrix.ensure(n * pitch * 4));
+	v2m_pair_distances_info distances{};
+	if (int const rc = pair_distances_run(ctx, rows, flags, ctx->d_dist_matrix.as<u32>(), pitch, &distances)) return rc;
+	v2m_nj_tree_info out{};
+	out.n_nodes = n - 2;
+	out.n_sites = distances.n_sites; out.n_columns = distances.n_columns; out.n_passes = distances.n_passes;
+	out.distances_ms = distances.counts_ms + distances.pack_ms + distances.pairs_ms;
+	if (int const rc = nj_run(ctx, ctx->d_dist_matrix.as<u32>(), n, pitch, nodes, &out.tree_ms)) return rc;
+	if (info) *info = out;
+	return V2M_OK;
 }
 
 

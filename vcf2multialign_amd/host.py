@@ -83,6 +83,10 @@ def _load():
 			C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_parse_decimal_fraction.restype = C.c_int
 		L.v2mh_parse_decimal_fraction.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+		L.v2mh_nj_tree_cpu.restype = C.c_int
+		L.v2mh_nj_tree_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+		L.v2mh_nj_newick_text.restype = C.c_int64
+		L.v2mh_nj_newick_text.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -226,6 +230,46 @@ def parse_decimal_fraction(text):
 	if not _load().v2mh_parse_decimal_fraction(str(text).encode(), C.byref(num), C.byref(den)):
 		raise ValueError("%r is no decimal number from 0 to 1 with at most 6 decimals" % (text,))
 	return int(num.value), int(den.value)
+
+
+def nj_tree_cpu(dist):
+	"""The host library's plain-loop neighbour joining (csrc/host/output.cc: nj_tree_cpu; no GPU): the n - 2 v2m_nj_node records, as a
+	structured array, of the tree of dist[n, n] (u32; only the upper triangle is read), n >= 3."""
+	from . import _native as N
+	dist = np.ascontiguousarray(dist, dtype=np.uint32)
+	if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+		raise ValueError("dist is no square matrix")
+	n = dist.shape[0]
+	if n < 3:
+		raise ValueError("a neighbour-joining tree needs at least 3 taxa (got %d)" % n)
+	nodes = np.zeros(n - 2, dtype=np.dtype(N.NJ_NODE_DTYPE))
+	if 0 != _load().v2mh_nj_tree_cpu(dist.ctypes.data, n, n, nodes.ctypes.data):
+		raise ValueError("v2mh_nj_tree_cpu failed")
+	return nodes
+
+
+def nj_newick_text(nodes, labels):
+	"""The host library's Newick writer (csrc/host/output.cc: nj_newick_text; no GPU): the text, as bytes, of the tree of the
+	v2m_nj_node records `nodes` (len(labels) - 2 of them) over the leaves named `labels`."""
+	from . import _native as N
+	names = [i if isinstance(i, bytes) else str(i).encode() for i in labels]
+	n = len(names)
+	nodes = np.ascontiguousarray(nodes, dtype=np.dtype(N.NJ_NODE_DTYPE))
+	if n < 3 or len(nodes) != n - 2:
+		raise ValueError("%d records and %d labels are no tree" % (len(nodes), n))
+	if any(b"\0" in i for i in names):
+		raise ValueError("a label holds a NUL byte")
+	array = (C.c_char_p * n)(*names)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (nodes.ctypes.data, n, array)
+	size = L.v2mh_nj_newick_text(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != L.v2mh_nj_newick_text(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
 
 
 def write_cut_positions(path, cut_positions, min_distance, score):

@@ -123,6 +123,22 @@ class Output:
 		stream.write(host.site_ld_text(len(rows), info["n_columns"], sites, pairs, graph.reference_positions, graph.aligned_positions, **params))
 		return info
 
+	def _write_tree(self, stream, ids, rows, graph, acgt_only):
+		"""--output-tree: the Newick text of host.nj_newick_text for `rows` named `ids` from Context.nj_tree, over the region's columns
+		when there is one.  Returns the info of the call."""
+		from . import host
+		if len(rows) < 3:
+			raise ValueError("--output-tree needs at least three sequences (got %d)" % len(rows))
+		if self.region is not None:
+			self.ctx.set_column_window(*columns_of_reference_range(graph.reference_positions, graph.aligned_positions, *self.region))
+		try:
+			nodes, info = self.ctx.nj_tree(RowBatch(rows), acgt_only=acgt_only, info=True)
+		finally:
+			if self.region is not None:
+				self.ctx.set_column_window(0, self.ctx.aligned_length)
+		stream.write(host.nj_newick_text(nodes, ids))
+		return info
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -171,14 +187,24 @@ class HaplotypeOutput(Output):
 				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
 		return self._write_column_counts(stream, rows, graph, all_columns)
 
-	def output_distances(self, graph, stream, acgt_only=False):
-		"""--output-distances for the rows of output_a2m (REF first, unless omitted), named as one file per sequence would be."""
+	def _distance_rows(self, graph):
+		"""(ids, rows): the rows of output_a2m (REF first, unless omitted), named as one file per sequence would be."""
 		ids, rows = ([self._chain_name("REF")], [PLOIDY_MAX]) if self.should_output_reference else ([], [])
 		for sample_idx in range(len(graph.sample_names)):
 			for chr_copy_idx in range(graph.sample_ploidy(sample_idx)):
 				ids.append(self._chain_name("%s.%d" % (graph.sample_names[sample_idx], 1 + chr_copy_idx)))
 				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
+		return ids, rows
+
+	def output_distances(self, graph, stream, acgt_only=False):
+		"""--output-distances for the rows of output_a2m (REF first, unless omitted), named as one file per sequence would be."""
+		ids, rows = self._distance_rows(graph)
 		return self._write_distances(stream, ids, rows, graph, acgt_only)
+
+	def output_tree(self, graph, stream, acgt_only=False):
+		"""--output-tree (acgt_only: --tree-acgt-only) for the rows of output_distances under its names."""
+		ids, rows = self._distance_rows(graph)
+		return self._write_tree(stream, ids, rows, graph, acgt_only)
 
 	def output_variable_sites(self, graph, stream, snp_only=False, positions=None):
 		"""--output-variable-sites (with --snp-sites and --output-site-positions) for the rows of output_a2m under its names."""
@@ -244,8 +270,8 @@ class FounderSequenceGreedyOutput(Output):
 			rows.append(list(zip(cut_positions[:-1], col)))
 		return self._write_column_counts(stream, rows, graph, all_columns)
 
-	def output_distances(self, graph, cut_positions, assigned_samples_column_major, stream, acgt_only=False):
-		"""--output-distances for the rows of output_a2m (REF first, unless omitted, then the founder rows)."""
+	def _distance_rows(self, cut_positions, assigned_samples_column_major):
+		"""(ids, rows): the rows of output_a2m (REF first, unless omitted, then the founder rows)."""
 		n_rows = len(cut_positions) - 1
 		n_founders = len(assigned_samples_column_major) // n_rows if n_rows else 0
 		ids, rows = ([self._chain_name("REF")], [PLOIDY_MAX]) if self.should_output_reference else ([], [])
@@ -253,7 +279,17 @@ class FounderSequenceGreedyOutput(Output):
 			col = assigned_samples_column_major[col_idx * n_rows:(col_idx + 1) * n_rows]
 			ids.append(self._chain_name(str(1 + col_idx)))
 			rows.append(list(zip(cut_positions[:-1], col)))
+		return ids, rows
+
+	def output_distances(self, graph, cut_positions, assigned_samples_column_major, stream, acgt_only=False):
+		"""--output-distances for the rows of output_a2m (REF first, unless omitted, then the founder rows)."""
+		ids, rows = self._distance_rows(cut_positions, assigned_samples_column_major)
 		return self._write_distances(stream, ids, rows, graph, acgt_only)
+
+	def output_tree(self, graph, cut_positions, assigned_samples_column_major, stream, acgt_only=False):
+		"""--output-tree (acgt_only: --tree-acgt-only) for the rows of output_distances under its names."""
+		ids, rows = self._distance_rows(cut_positions, assigned_samples_column_major)
+		return self._write_tree(stream, ids, rows, graph, acgt_only)
 
 	def output_variable_sites(self, graph, cut_positions, assigned_samples_column_major, stream, snp_only=False, positions=None):
 		"""--output-variable-sites for the rows of output_a2m (REF first, unless omitted, then the founder rows) under its names."""
