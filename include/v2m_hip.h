@@ -42,7 +42,9 @@
  * v2m_column_counts_sink_fn, the V2M_COUNTS_* flags and the V2M_KERNEL_COLUMN_* ids), and v2m_pair_distances / v2m_pair_distances_device
  * (with v2m_pair_distances_info, V2M_DIST_ACGT_ONLY and V2M_PAIR_DISTANCES_MAX_ROWS; no kernel ids: the info carries their times), and
  * v2m_variable_sites / v2m_variable_sites_device (with v2m_variable_sites_info, the two sink types and V2M_SITES_SNP; no kernel ids either),
- * and v2m_nj_tree / v2m_nj_tree_of_distances (with v2m_nj_node, v2m_nj_tree_info, V2M_NJ_NONE and V2M_NJ_MAX_ROWS; no kernel ids).
+ * and v2m_nj_tree / v2m_nj_tree_of_distances (with v2m_nj_node, v2m_nj_tree_info, V2M_NJ_NONE and V2M_NJ_MAX_ROWS; no kernel ids),
+ * and v2m_pair_distances_weighted / v2m_bootstrap_distances / v2m_nj_bootstrap (with v2m_nj_bootstrap_info and
+ * V2M_NJ_BOOTSTRAP_MAX_REPLICATES; no kernel ids).
  *
  * Conventions
  *   - Plain C: pointers + sizes, no exceptions, no C++/torch types.  Every function that can
@@ -729,6 +731,78 @@ int v2m_nj_tree_of_distances(v2m_ctx *ctx, const void *d_dist, uint64_t n, uint6
 
 int v2m_nj_tree(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_DIST_ACGT_ONLY */, v2m_nj_node *nodes /* host, n_rows - 2 */,
                 v2m_nj_tree_info *info /* may be NULL */);
+
+/* ---- bootstrap ----------------------------------------------------------------------------------
+ *
+ * Felsenstein's bootstrap of the neighbour-joining tree: the columns of the view are resampled with replacement, the tree is built
+ * again from every replicate's distances, and each join of the real tree is given the number of replicate trees that hold its split.
+ * The view, the seven classes, flags (0 or V2M_DIST_ACGT_ONLY), the row limits and the L < 2^32 limit are those of the pair
+ * distances.  differ(i, j, c) is what column c of the view adds to dist[i][j] there: 0 or 1.
+ *
+ * Weighted distances.  For weights w[c], one u32 per column of the view: dist_w[i][j] = sum over c of w[c] * differ(i, j, c).  The sum
+ * of w[c] over ALL columns of the view must be below 2^32 -- checked on the host before any device work, else
+ * V2M_ERR_INVALID_ARGUMENT --, so that no entry can overflow a u32.  All-ones weights give the pair distances, all-zero weights give
+ * zeros.  A column that is no site may carry any weight: it counts toward the sum rule and adds nothing else.
+ *
+ * The draws.  All arithmetic is mod 2^64.  G = 0x9E3779B97F4A7C15.  mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9, then
+ * z = (z ^ (z >> 27)) * 0x94D049BB133111EB, then z ^ (z >> 31) (splitmix64's finaliser).  key = mix(seed + G).  Draw k (0 <= k < L) of
+ * replicate r (a u32) is x = mix(key + ((r << 32 | k) + 1) * G) and selects column floor(x * L / 2^64): the high half of the 128-bit
+ * product.  Replicate r's weight of column c is the number of its L draws that selected c; the weights sum to L, so the sum rule
+ * always holds.  This is the bootstrap over the columns of the view, as seqboot does it, not a resampling of the variable sites only
+ * (that the implementation looks at the sites alone is its own business).
+ *
+ * Replicate tree r: the tree v2m_nj_tree_of_distances builds from replicate r's weighted matrix, with the same arithmetic and ties.
+ *
+ * Support.  Join record t (0 <= t <= n - 4) of the main tree creates node n + t; the leaves under that node and the remaining leaves
+ * are the split of the record.  The n - 3 splits of a tree are distinct and non-trivial.  Two splits are equal when they are the same
+ * partition of the leaves into two sets, whichever side the node lies on and in whatever order the joins came.  support[t] is the
+ * number of replicates 0 ... B - 1 whose tree holds the split of record t.  The trifurcation record has none; with n == 3 the array
+ * is empty.
+ *
+ * v2m_pair_distances_weighted: weights is host memory, one u32 per column of the view (it may be NULL when L == 0); dist and info as
+ * for v2m_pair_distances.  v2m_bootstrap_distances: replicate `replicate`'s weighted matrix, for any u32 replicate number.
+ * v2m_nj_bootstrap: nodes (n - 2) receives the main tree, equal to v2m_nj_tree's; support (n - 3; may be NULL only when n == 3) the
+ * counts; replicate_nodes, when not NULL, the n_replicates x (n - 2) records of the replicate trees.  1 <= n_replicates <=
+ * V2M_NJ_BOOTSTRAP_MAX_REPLICATES and n >= 3, else V2M_ERR_INVALID_ARGUMENT in v2m_nj_tree's words; n == 0 returns V2M_OK and touches
+ * nothing.  The other errors are those of the pair distances and of v2m_nj_tree, each before any device work.  With no site (V == 0
+ * or L == 0) every matrix is zero, the trees are those of the zero matrix and every support is n_replicates.
+ * All three calls are synchronous and leave the column window, the window set and what v2m_column_counts returns as they were.
+ *
+ * How (csrc/bootstrap_kernels.hpp, csrc/nj_support.hpp).  The counts, the site list and the bit planes are the pair distances'.  A
+ * replicate's weights are kept by site rank, u32 w[V]: bootstrap_weights_kernel makes the L draws, finds each column in the site
+ * list by bisection and adds the hits with integer atomicAdd (explicit weights: a gather).  weight_slices_kernel cuts w into 32 bit
+ * slices laid out as a plane is and ORs all weights into one word, from which the host -- one 4-byte copy and one synchronisation a
+ * replicate -- takes K, the bit length of the largest weight.  pair_distances_weighted_kernel<acgt_only> is pair_distances_kernel with
+ * acc += sum over b < K of popcount(m & slice[b][word]) << b; K == 0 writes zeros and launches nothing.  When the planes fit
+ * V2M_PAIR_DISTANCES_PLANE_BYTES they are packed ONCE and stay resident across the main matrix and every replicate
+ * (n_pack_passes = n_passes = 1); otherwise every replicate runs the passes over again, the main matrix sharing those of
+ * replicate 0 (n_pack_passes = n_replicates * n_passes for v2m_nj_bootstrap).  V2M_PAIR_DISTANCES_PARTS acts as on the plain path.  The splits are counted on the host, exactly. */
+#define V2M_NJ_BOOTSTRAP_MAX_REPLICATES 100000u
+
+typedef struct {
+	uint64_t n_rows;          /* n */
+	uint64_t n_sites;         /* of the pair distances */
+	uint64_t n_columns;       /* L */
+	uint64_t n_passes;        /* site ranges of one matrix (0 when there was no site) */
+	uint64_t n_pack_passes;   /* times a range of planes was packed over the whole call */
+	uint64_t n_replicates;    /* B */
+	uint64_t max_slices;      /* the largest K of any replicate */
+	double distances_ms;      /* the main matrix: counts, pack and pairs (stream time, see "pair distances") */
+	double weights_ms;        /* all replicates: draws (or gather) and slices */
+	double pairs_ms;          /* all replicates: pair_distances_weighted_kernel, with the zeroing and any repeated pack */
+	double trees_ms;          /* the main tree and all replicate trees */
+} v2m_nj_bootstrap_info;     /* 88 bytes */
+
+int v2m_pair_distances_weighted(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_DIST_ACGT_ONLY */,
+                                const uint32_t *weights /* host, one per column of the view */, uint32_t *dist /* n_rows x n_rows, host */,
+                                v2m_pair_distances_info *info /* may be NULL */);
+
+int v2m_bootstrap_distances(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_DIST_ACGT_ONLY */, uint64_t seed, uint32_t replicate,
+                            uint32_t *dist /* n_rows x n_rows, host */, v2m_pair_distances_info *info /* may be NULL */);
+
+int v2m_nj_bootstrap(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 0 or V2M_DIST_ACGT_ONLY */, uint32_t n_replicates, uint64_t seed,
+                     v2m_nj_node *nodes /* host, n_rows - 2 */, uint32_t *support /* host, n_rows - 3 */,
+                     v2m_nj_node *replicate_nodes /* NULL, or host, n_replicates x (n_rows - 2) */, v2m_nj_bootstrap_info *info /* may be NULL */);
 
 /* ---- founder search: the chunk walks ---------------------------------- */
 

@@ -67,6 +67,12 @@ NJ_NONE = 0xFFFFFFFF
 NJ_MAX_ROWS = 32768
 NJ_ROWS_PER_GROUP = 8
 NJ_JOIN_THREADS = 256
+# v2m_pair_distances_weighted, v2m_bootstrap_distances, v2m_nj_bootstrap: the limit, and csrc/bootstrap_kernels.hpp's kBootDrawThreads
+# (draws per workgroup of bootstrap_weights_kernel) and kBootSlices (bit slices of a weight); tests/test_nj_bootstrap_host.py holds them
+# to the sources
+NJ_BOOTSTRAP_MAX_REPLICATES = 100000
+BOOT_DRAW_THREADS = 256
+BOOT_SLICES = 32
 # csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
 # kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
 DISTINCT_CHUNK_BYTES = 8192
@@ -147,6 +153,12 @@ class NjTreeInfo(C.Structure):   # v2m_nj_tree_info
 	_fields_ = [("n_nodes", C.c_uint64), ("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("n_passes", C.c_uint64), ("distances_ms", C.c_double), ("tree_ms", C.c_double)]
 
 
+class NjBootstrapInfo(C.Structure):   # v2m_nj_bootstrap_info
+	_fields_ = [("n_rows", C.c_uint64), ("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("n_passes", C.c_uint64), ("n_pack_passes", C.c_uint64),
+		("n_replicates", C.c_uint64), ("max_slices", C.c_uint64), ("distances_ms", C.c_double), ("weights_ms", C.c_double), ("pairs_ms", C.c_double),
+		("trees_ms", C.c_double)]
+
+
 NJ_NODE_DTYPE = [("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("reserved", "<u4"), ("len_a", "<f8"), ("len_b", "<f8"), ("len_c", "<f8")]   # v2m_nj_node
 SITE_COLUMNS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_site_columns_sink_fn
 SITE_ROWS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_site_rows_sink_fn
@@ -195,6 +207,9 @@ SIGNATURES = {
 	"v2m_site_ld_device": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.POINTER(SiteLdParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p, _u64p]),
 	"v2m_nj_tree_of_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(NjTreeInfo)]),
 	"v2m_nj_tree": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.POINTER(NjTreeInfo)]),
+	"v2m_pair_distances_weighted": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(PairDistancesInfo)]),
+	"v2m_bootstrap_distances": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(PairDistancesInfo)]),
+	"v2m_nj_bootstrap": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NjBootstrapInfo)]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -456,6 +456,42 @@ class Context:
 			return dist, {name: getattr(record, name) for name, _ in N.PairDistancesInfo._fields_}
 		return dist
 
+	def _weighted_result(self, n, dist, record, info):
+		dist = dist[:n * n].reshape(n, n)
+		if n == 0:
+			record.n_columns = self.window_length   # (with no rows the call returns before it writes the info)
+		if info:
+			return dist, {name: getattr(record, name) for name, _ in N.PairDistancesInfo._fields_}
+		return dist
+
+	def pair_distances_weighted(self, rows, weights, acgt_only=False, info=False):
+		"""v2m_pair_distances_weighted: np.uint32[n, n], the pair distances with column c of the view in force counted weights[c] times
+		(one u32 per column of the view; their sum must be below 2^32).  With info=True: (matrix, dict of v2m_pair_distances_info's
+		fields)."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		weights = np.ascontiguousarray(weights, dtype=np.uint32)
+		if weights.ndim != 1 or weights.size != self.window_length:
+			raise ValueError("weights holds %d values and the view %d columns" % (weights.size, self.window_length))
+		n = int(rows.struct.n_rows)
+		dist = np.zeros(max(1, n * n), dtype=np.uint32)
+		record = N.PairDistancesInfo()
+		self._check(self._lib.v2m_pair_distances_weighted(self._h, C.byref(rows.struct), N.DIST_ACGT_ONLY if acgt_only else 0,
+			weights.ctypes.data if weights.size else None, dist.ctypes.data, C.byref(record)))
+		return self._weighted_result(n, dist, record, info)
+
+	def bootstrap_distances(self, rows, seed, replicate, acgt_only=False, info=False):
+		"""v2m_bootstrap_distances: np.uint32[n, n], the weighted pair distances of bootstrap replicate `replicate` (any u32) under
+		`seed` (any u64): the columns of the view in force drawn with replacement as include/v2m_hip.h, "bootstrap", defines the draws."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = int(rows.struct.n_rows)
+		dist = np.zeros(max(1, n * n), dtype=np.uint32)
+		record = N.PairDistancesInfo()
+		self._check(self._lib.v2m_bootstrap_distances(self._h, C.byref(rows.struct), N.DIST_ACGT_ONLY if acgt_only else 0, int(seed), int(replicate),
+			dist.ctypes.data, C.byref(record)))
+		return self._weighted_result(n, dist, record, info)
+
 	def pair_distances_device(self, rows, ptr, pitch, acgt_only=False):
 		"""v2m_pair_distances_device: the matrix into device memory at `ptr`, u32[n][pitch] (16-byte aligned, pitch a multiple of 4 and at
 		least n); elements [i][j < n] are overwritten, nothing else is touched."""
@@ -613,6 +649,30 @@ class Context:
 		if n == 0:
 			record.n_columns = self.window_length   # (with no rows the call returns before it writes the info)
 		return self._nj_result(n, nodes, record, info)
+
+	def nj_bootstrap(self, rows, n_replicates, seed=1, acgt_only=False, replicates=False, info=False):
+		"""v2m_nj_bootstrap: (nodes, support) -- nj_tree's records and, per join record, the number of the n_replicates bootstrap
+		replicates under `seed` whose tree holds the record's split (np.uint32[n - 3]).  replicates=True adds the replicate trees, a
+		structured array [n_replicates, n - 2]; info=True adds the dict of v2m_nj_bootstrap_info's fields."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = int(rows.struct.n_rows)
+		n_replicates = int(n_replicates)
+		if not 0 <= n_replicates < 1 << 32 or not 0 <= int(seed) < 1 << 64:
+			raise ValueError("n_replicates is a u32 and seed a u64 (got %d and %d)" % (n_replicates, int(seed)))
+		nodes = np.zeros(max(1, n - 2), dtype=np.dtype(N.NJ_NODE_DTYPE))   # (never a NULL pointer: no rows is no error)
+		support = np.zeros(max(1, n - 3), dtype=np.uint32)
+		keep = replicates and 1 <= n_replicates <= N.NJ_BOOTSTRAP_MAX_REPLICATES
+		trees = np.zeros((n_replicates if keep else 1, max(1, n - 2)), dtype=np.dtype(N.NJ_NODE_DTYPE))
+		record = N.NjBootstrapInfo()
+		self._check(self._lib.v2m_nj_bootstrap(self._h, C.byref(rows.struct), N.DIST_ACGT_ONLY if acgt_only else 0, n_replicates, int(seed),
+			nodes.ctypes.data, support.ctypes.data, trees.ctypes.data if keep else None, C.byref(record)))
+		result = [nodes[:max(0, n - 2)] if n >= 3 else nodes[:0], support[:max(0, n - 3)]]
+		if replicates:
+			result.append(trees[:, :n - 2] if n >= 3 else trees[:0, :0])
+		if info:
+			result.append({name: getattr(record, name) for name, _ in N.NjBootstrapInfo._fields_})
+		return tuple(result)
 
 	def nj_tree_of_distances(self, ptr, n, pitch, info=False):
 		"""v2m_nj_tree_of_distances: the tree of the n taxa whose distances lie in device memory at `ptr`, u32[n][pitch] (16-byte aligned,

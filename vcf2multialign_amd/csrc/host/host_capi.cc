@@ -546,4 +546,34 @@ int64_t v2mh_nj_newick_text(v2m_nj_node const *nodes, uint64_t n_leaves, char co
 	}
 }
 
+// nj_newick_support_text() of output.hh (no GPU), handed over as v2mh_nj_newick_text hands over its text; support holds n_leaves - 3
+// counts.
+int64_t v2mh_nj_newick_support_text(v2m_nj_node const *nodes, uint64_t n_leaves, char const *const *labels, uint32_t const *support, char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		if (!nodes || !labels) throw std::runtime_error("nodes or labels is NULL");
+		std::vector<std::string> names;
+		for (uint64_t i(0); i < n_leaves; ++i) names.emplace_back(labels[i]);
+		std::string const text(vh::nj_newick_support_text(nodes, n_leaves, names, support));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
+// nj_split_support() of csrc/nj_support.hpp (no GPU): support[t], t < n - 3, = the n_replicates trees of replicate_nodes (n - 2 records
+// each) that hold the split of join record t of main_nodes.  0, or -1 for a NULL pointer, n < 3, records that are no tree, or no memory.
+int v2mh_nj_split_support(uint64_t n, v2m_nj_node const *main_nodes, v2m_nj_node const *replicate_nodes, uint64_t n_replicates, uint32_t *support)
+{
+	try {
+		if (!main_nodes || (!replicate_nodes && n_replicates) || (!support && n > 3)) return -1;
+		vh::nj_split_support(n, main_nodes, replicate_nodes, n_replicates, support);
+		return 0;
+	} catch (std::exception const &) {
+		return -1;
+	}
+}
+
 } // extern "C"

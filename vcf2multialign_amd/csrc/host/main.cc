@@ -7,6 +7,7 @@
 #include <getopt.h>
 #include <sys/resource.h>
 
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -65,6 +66,10 @@ struct options {
 	v2m_site_ld_params ld_params{1000, 1, 1, 5, 0};
 	char const *output_tree{};            // --output-tree=FILE: the neighbour-joining tree of the output rows in Newick form, from v2m_nj_tree
 	bool tree_acgt_only{};                // --tree-acgt-only (with --output-tree): the tree of the distances --acgt-only counts
+	char const *tree_bootstrap{}, *tree_seed{};   // --tree-bootstrap=B (with --output-tree), --tree-seed=S (with --tree-bootstrap; default 1)
+	char const *output_tree_replicates{};         // --output-tree-replicates=FILE (with --tree-bootstrap): the replicate trees, a Newick line each
+	std::uint32_t tree_replicates{};              // B, or 0: no bootstrap
+	std::uint64_t tree_seed_value{1};
 	bool all_columns{};                   // --all-columns (with --output-column-counts): every column, not only the variable ones
 	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
 	std::vector<int> devices{0};
@@ -167,6 +172,12 @@ void usage()
 		"                                     several --device entries\n"
 		"      --tree-acgt-only               With --output-tree: the distances count only the columns where both sequences hold A, C, G\n"
 		"                                     or T (as --acgt-only does for --output-distances)\n"
+		"      --tree-bootstrap=B             With --output-tree: Felsenstein's bootstrap.  The columns are resampled with replacement B\n"
+		"                                     times (1 to 100000) on the GPU, the tree is built again from every replicate, and each\n"
+		"                                     join of the tree is labelled with the number of replicates that hold its split\n"
+		"      --tree-seed=S                  With --tree-bootstrap: the seed of the draws (0 to 2^64 - 1; default 1)\n"
+		"      --output-tree-replicates=FILE  With --tree-bootstrap: write the replicate trees, one Newick line each (the input of\n"
+		"                                     consense)\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -266,6 +277,16 @@ bool parse_count(char const *text, std::uint64_t &out)
 	return true;
 }
 
+// A seed: decimal, 0 to 2^64 - 1.
+bool parse_seed(char const *text, std::uint64_t &out)
+{
+	std::string const t(text);
+	if (t.empty() || t.size() > 20 || std::string::npos != t.find_first_not_of("0123456789")) return false;
+	errno = 0;
+	out = std::strtoull(t.c_str(), nullptr, 10);
+	return 0 == errno;
+}
+
 // --region's value: START-END, decimal, 1 <= START <= END (the reference length is checked once the reference is read).
 bool parse_region(char const *text, std::uint64_t &start, std::uint64_t &end)
 {
@@ -362,7 +383,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_output_tree, o_tree_acgt_only, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_output_tree, o_tree_acgt_only, o_tree_bootstrap, o_tree_seed, o_output_tree_replicates, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -378,6 +399,7 @@ int main(int argc, char **argv)
 		{"output-ld", required_argument, nullptr, o_output_ld}, {"ld-window", required_argument, nullptr, o_ld_window}, {"ld-window-columns", required_argument, nullptr, o_ld_window_columns},
 		{"ld-min-r2", required_argument, nullptr, o_ld_min_r2}, {"ld-min-count", required_argument, nullptr, o_ld_min_count},
 		{"output-tree", required_argument, nullptr, o_output_tree}, {"tree-acgt-only", no_argument, nullptr, o_tree_acgt_only},
+		{"tree-bootstrap", required_argument, nullptr, o_tree_bootstrap}, {"tree-seed", required_argument, nullptr, o_tree_seed}, {"output-tree-replicates", required_argument, nullptr, o_output_tree_replicates},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -441,6 +463,9 @@ int main(int argc, char **argv)
 			case o_ld_min_count: opt.ld_min_count = optarg; break;
 			case o_output_tree: opt.output_tree = optarg; break;
 			case o_tree_acgt_only: opt.tree_acgt_only = true; break;
+			case o_tree_bootstrap: opt.tree_bootstrap = optarg; break;
+			case o_tree_seed: opt.tree_seed = optarg; break;
+			case o_output_tree_replicates: opt.output_tree_replicates = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -495,6 +520,21 @@ int main(int argc, char **argv)
 		if (other) { std::cerr << "ERROR: --output-distances cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
 	}
 	if (opt.tree_acgt_only && !opt.output_tree) { std::cerr << "ERROR: --tree-acgt-only requires --output-tree.\n"; return EXIT_FAILURE; }
+	if (opt.tree_bootstrap && !opt.output_tree) { std::cerr << "ERROR: --tree-bootstrap requires --output-tree.\n"; return EXIT_FAILURE; }
+	if (opt.tree_seed && !opt.tree_bootstrap) { std::cerr << "ERROR: --tree-seed requires --tree-bootstrap.\n"; return EXIT_FAILURE; }
+	if (opt.output_tree_replicates && !opt.tree_bootstrap) { std::cerr << "ERROR: --output-tree-replicates requires --tree-bootstrap.\n"; return EXIT_FAILURE; }
+	if (opt.tree_bootstrap) {
+		std::uint64_t value(0);
+		if (!parse_count(opt.tree_bootstrap, value) || value < 1 || value > V2M_NJ_BOOTSTRAP_MAX_REPLICATES) {
+			std::cerr << "ERROR: --tree-bootstrap must be a number of replicates from 1 to " << V2M_NJ_BOOTSTRAP_MAX_REPLICATES << ", got \"" << opt.tree_bootstrap << "\".\n";
+			return EXIT_FAILURE;
+		}
+		opt.tree_replicates = std::uint32_t(value);
+		if (opt.tree_seed && !parse_seed(opt.tree_seed, opt.tree_seed_value)) {
+			std::cerr << "ERROR: --tree-seed must be a number from 0 to 18446744073709551615, got \"" << opt.tree_seed << "\".\n";
+			return EXIT_FAILURE;
+		}
+	}
 	if (opt.output_tree) {
 		// one matrix and one tree from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
 		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
@@ -794,7 +834,7 @@ int main(int argc, char **argv)
 			}
 			if (opt.output_tree) {
 				std::cerr << "Outputting the tree..." << std::flush;
-				output.output_tree(graph, opt.output_tree, opt.tree_acgt_only, opt.verbose);
+				output.output_tree(graph, opt.output_tree, opt.tree_acgt_only, opt.verbose, opt.tree_replicates, opt.tree_seed_value, opt.output_tree_replicates);
 				std::cerr << " Done.\n";
 			}
 		});

@@ -1,4 +1,5 @@
 #include "output.hh"
+#include "../nj_support.hpp"
 #include <cstdlib>
 #include <cstdio>
 #include <chrono>
@@ -1506,7 +1507,31 @@ void nj_tree_cpu(std::uint32_t const *dist, u64 n, u64 pitch, v2m_nj_node *nodes
 }
 
 
+namespace {
+std::string newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *support);
+}
+
 std::string nj_newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels)
+{
+	return newick_text(nodes, n_leaves, labels, nullptr);
+}
+
+std::string nj_newick_support_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *support)
+{
+	if (!support && n_leaves > 3) throw std::invalid_argument("support is NULL");
+	static std::uint32_t const none(0);
+	return newick_text(nodes, n_leaves, labels, support ? support : &none);
+}
+
+void nj_split_support(u64 n_leaves, v2m_nj_node const *main_nodes, v2m_nj_node const *replicate_nodes, u64 n_replicates, std::uint32_t *support)
+{
+	std::string const err(v2m::nj_split_support(n_leaves, main_nodes, replicate_nodes, n_replicates, support));
+	if (!err.empty()) throw std::runtime_error(err);
+}
+
+namespace {
+// support: NULL, or the labels of the join nodes
+std::string newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *support)
 {
 	u64 const n(n_leaves);
 	if (n < 3) throw std::invalid_argument("a tree has at least 3 leaves");
@@ -1547,6 +1572,7 @@ std::string nj_newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<s
 		if (f.next > 0) append_length(text, 1 == f.next ? nd.len_a : 2 == f.next ? nd.len_b : nd.len_c);   // (of the child just closed)
 		if (f.next == children) {
 			text += ')';
+			if (support && f.rec != root) text += std::to_string(support[f.rec]);
 			stack.pop_back();
 			continue;
 		}
@@ -1562,9 +1588,10 @@ std::string nj_newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<s
 	text += ";\n";
 	return text;
 }
+} // namespace
 
 
-void output::output_tree(variant_graph const &graph, std::ostream &stream, bool acgt_only, bool verbose)
+void output::output_tree(variant_graph const &graph, std::ostream &stream, bool acgt_only, bool verbose, std::uint32_t bootstrap, std::uint64_t seed, std::ostream *replicates)
 {
 	if (!m_more_gpus.empty()) throw std::runtime_error("--output-tree needs every chromosome copy on one GPU context");
 	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-tree needs every chromosome copy on one GPU context");
@@ -1579,23 +1606,52 @@ void output::output_tree(variant_graph const &graph, std::ostream &stream, bool 
 	}
 	if (batch.n_rows < 3) throw std::runtime_error("--output-tree needs at least three sequences (got " + std::to_string(batch.n_rows) + ")");
 	std::vector<v2m_nj_node> nodes(batch.n_rows - 2);
-	v2m_nj_tree_info info{};
-	m_gpu.check(v2m_nj_tree(m_gpu.get(), &batch, acgt_only ? V2M_DIST_ACGT_ONLY : 0, nodes.data(), &info));
-	std::string const text(nj_newick_text(nodes.data(), batch.n_rows, rows.ids));
+	if (0 == bootstrap) {
+		v2m_nj_tree_info info{};
+		m_gpu.check(v2m_nj_tree(m_gpu.get(), &batch, acgt_only ? V2M_DIST_ACGT_ONLY : 0, nodes.data(), &info));
+		std::string const text(nj_newick_text(nodes.data(), batch.n_rows, rows.ids));
+		stream.write(text.data(), std::streamsize(text.size()));
+		if (verbose)
+			std::fprintf(stderr, "Tree: %llu rows, %llu columns, %llu sites, %llu joins.\n", (unsigned long long) batch.n_rows, (unsigned long long) info.n_columns,
+				(unsigned long long) info.n_sites, (unsigned long long) (info.n_nodes - 1));
+		return;
+	}
+	std::vector<std::uint32_t> support(batch.n_rows - 3);
+	std::vector<v2m_nj_node> replicate_nodes(replicates ? std::size_t(bootstrap) * nodes.size() : 0);
+	v2m_nj_bootstrap_info info{};
+	m_gpu.check(v2m_nj_bootstrap(m_gpu.get(), &batch, acgt_only ? V2M_DIST_ACGT_ONLY : 0, bootstrap, seed, nodes.data(), support.data(),
+		replicates ? replicate_nodes.data() : nullptr, &info));
+	std::string const text(nj_newick_support_text(nodes.data(), batch.n_rows, rows.ids, support.data()));
 	stream.write(text.data(), std::streamsize(text.size()));
+	if (replicates) {
+		for (std::uint32_t r(0); r < bootstrap; ++r) {
+			std::string const line(nj_newick_text(replicate_nodes.data() + std::size_t(r) * nodes.size(), batch.n_rows, rows.ids));
+			replicates->write(line.data(), std::streamsize(line.size()));
+		}
+	}
 	if (verbose)
-		std::fprintf(stderr, "Tree: %llu rows, %llu columns, %llu sites, %llu joins.\n", (unsigned long long) batch.n_rows, (unsigned long long) info.n_columns,
-			(unsigned long long) info.n_sites, (unsigned long long) (info.n_nodes - 1));
+		std::fprintf(stderr, "Tree: %llu rows, %llu columns, %llu sites, %llu joins; %llu replicates, K = %llu, %llu pack passes.\n", (unsigned long long) batch.n_rows,
+			(unsigned long long) info.n_columns, (unsigned long long) info.n_sites, (unsigned long long) (batch.n_rows - 3), (unsigned long long) info.n_replicates,
+			(unsigned long long) info.max_slices, (unsigned long long) info.n_pack_passes);
 }
 
 
-void output::output_tree(variant_graph const &graph, char const *path, bool acgt_only, bool verbose)
+void output::output_tree(variant_graph const &graph, char const *path, bool acgt_only, bool verbose, std::uint32_t bootstrap, std::uint64_t seed, char const *replicates_path)
 {
 	std::ofstream stream(path, std::ios::binary | std::ios::trunc);
 	if (!stream) throw std::runtime_error(std::string("unable to open ") + path + " for writing");
-	output_tree(graph, stream, acgt_only, verbose);
+	std::ofstream replicates;
+	if (replicates_path) {
+		replicates.open(replicates_path, std::ios::binary | std::ios::trunc);
+		if (!replicates) throw std::runtime_error(std::string("unable to open ") + replicates_path + " for writing");
+	}
+	output_tree(graph, stream, acgt_only, verbose, bootstrap, seed, replicates_path ? &replicates : nullptr);
 	stream.flush();
 	if (!stream) throw std::runtime_error(std::string("error while writing ") + path);
+	if (replicates_path) {
+		replicates.flush();
+		if (!replicates) throw std::runtime_error(std::string("error while writing ") + replicates_path);
+	}
 }
 
 

@@ -100,6 +100,13 @@ void nj_tree_cpu(std::uint32_t const *dist, u64 n, u64 pitch, v2m_nj_node *nodes
 // Throws when the records are no tree over the leaves: an id out of range or used twice, or c set before the last record.
 std::string nj_newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels);
 
+// nj_newick_text with the support of every join node as its label: node n + t is written (<a>:<len_a>,<b>:<len_b>)<support[t]>, the
+// count in decimal.  support holds n - 3 counts (none is read with 3 leaves); the trifurcation carries no label.
+std::string nj_newick_support_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *support);
+
+// v2m::nj_split_support of csrc/nj_support.hpp, throwing what it reports.
+void nj_split_support(u64 n_leaves, v2m_nj_node const *main_nodes, v2m_nj_node const *replicate_nodes, u64 n_replicates, std::uint32_t *support);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -192,8 +199,13 @@ public:
 	// --output-tree: nj_newick_text above for the rows of the A2M output (REF first, unless omitted) under the names --output-distances
 	// writes, over the view in force (--region: the window's columns), from v2m_nj_tree on the first context, which must hold every
 	// copy.  acgt_only: V2M_DIST_ACGT_ONLY; verbose prints the rows, columns, sites and joins to stderr.
-	void output_tree(variant_graph const &graph, char const *path, bool acgt_only = false, bool verbose = false);
-	void output_tree(variant_graph const &graph, std::ostream &stream, bool acgt_only = false, bool verbose = false);
+	// bootstrap > 0 (--tree-bootstrap, with seed: --tree-seed): the tree and the support of its joins from v2m_nj_bootstrap, written by
+	// nj_newick_support_text; replicates (--output-tree-replicates), when given, receives the replicate trees, a line of
+	// nj_newick_text each.  verbose then prints the replicates, the largest K and the pack passes as well.
+	void output_tree(variant_graph const &graph, char const *path, bool acgt_only = false, bool verbose = false,
+		std::uint32_t bootstrap = 0, std::uint64_t seed = 1, char const *replicates_path = nullptr);
+	void output_tree(variant_graph const &graph, std::ostream &stream, bool acgt_only = false, bool verbose = false,
+		std::uint32_t bootstrap = 0, std::uint64_t seed = 1, std::ostream *replicates = nullptr);
 
 protected:
 	struct row_set {

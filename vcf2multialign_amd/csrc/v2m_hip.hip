@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -31,9 +32,11 @@
 #include "bgzf_kernels.hpp"
 #include "vcf_kernels.hpp"
 #include "distance_kernels.hpp"
+#include "bootstrap_kernels.hpp"
 #include "site_kernels.hpp"
 #include "ld_kernels.hpp"
 #include "nj_kernels.hpp"
+#include "nj_support.hpp"
 
 using v2m::u32;
 using v2m::u64;
@@ -268,6 +271,9 @@ struct v2m_ctx {
 	pinned_buf h_column_total;
 	// pair distances (v2m_pair_distances): the site list, a pass's bit planes, and the host form's matrix
 	scratch_buf d_dist_sites, d_dist_planes, d_dist_matrix;
+	// bootstrap (v2m_pair_distances_weighted, v2m_bootstrap_distances, v2m_nj_bootstrap): explicit weights by column, a replicate's
+	// weights by site rank, their 32 bit slices, the OR of the weights, and a replicate's matrix
+	scratch_buf d_boot_column_weights, d_boot_weights, d_boot_slices, d_boot_any, d_boot_matrix;
 	// neighbour joining (v2m_nj_tree[_of_distances]): the working matrix, R, the ids, the row minima and the records
 	scratch_buf d_nj_matrix, d_nj_sums, d_nj_ids, d_nj_best, d_nj_nodes;
 	// variable sites (v2m_variable_sites): the site list, the host form's gathered slices (two, used in turn), the list's pinned staging
@@ -3319,7 +3325,7 @@ namespace {
 // around everything the stage queues -- the counts and the pack segment span every slice -- so a figure is time elapsed on the stream,
 // with whatever gaps the host's queueing leaves between the launches, not summed kernel time.
 struct stage_times {
-	enum { counts, pack, pairs, n_stages };
+	enum { counts, pack, pairs, weights, weighted_pairs, n_stages };   // (the last two: the bootstrap's weighted path)
 	struct segment { int stage; hipEvent_t begin, end; };
 	v2m_ctx *ctx;
 	std::vector<segment> segments;
@@ -3369,29 +3375,64 @@ u64 pair_chunks_per_part(v2m_ctx const *ctx, u64 tile_pairs, u64 n_chunks, u64 f
 	return (n_chunks + want_parts - 1) / want_parts;
 }
 
-// Queues and completes the call: the matrix of the batch over the view in force into d_dist (u32[n_rows][pitch]).  n_rows >= 1.
-int pair_distances_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, u32 *d_dist, u64 pitch, v2m_pair_distances_info *info)
+// What a call of pair_matrices_run computes: the plain matrix, weighted matrices (include/v2m_hip.h, "bootstrap"), or both.  The
+// weighted matrices are made one after the other in d_weighted; after each is complete, with the stream idle, weighted_done(r) is
+// called, and plain_done() after the plain one.  A callback that returns non-zero ends the call with that status.
+struct pair_job {
+	u32 *d_plain{}; u64 plain_pitch{};              // the plain matrix (pair_distances_kernel), or NULL
+	u32 *d_weighted{}; u64 weighted_pitch{};        // one weighted matrix at a time
+	u64 n_weighted{};                               // weighted matrices: 1 with explicit weights
+	u32 const *weights{};                           // explicit weights, host, one per column of the view; or NULL: the draws of
+	u64 seed{}; u32 first_replicate{};              //   replicates first_replicate, first_replicate + 1, ... (mod 2^32) under seed
+	std::function<int()> plain_done;
+	std::function<int(u64)> weighted_done;
+	// what the call reports beside the info
+	u64 n_pack_passes{}, max_slices{};
+	double weights_ms{}, weighted_pairs_ms{};
+};
+
+// Queues and completes the call: the matrices of the batch over the view in force, u32[n_rows][pitch] each.  n_rows >= 1.
+// Stage (1), the counts and the site list, runs once.  Then rounds: a round is every pass (the pack, then the pair kernels) for the
+// plain matrix and the first weighted one together, or for one further weighted matrix.  Planes that fit the budget make one pass,
+// which is packed in the first round only and stays resident.  info's three times are the plain path's; the job's are the weighted
+// path's, the packs of later rounds among the weighted pairs.
+int pair_matrices_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, pair_job &job, v2m_pair_distances_info *info)
 {
 	u64 const L(ctx->view().length()), n(rows->n_rows);
 	stage_times times(ctx);
 	v2m_pair_distances_info out{};
 	out.n_columns = L;
-	auto const zeros([&]() -> int {
-		V2M_HIP_TRY(ctx, hipMemset2DAsync(d_dist, pitch * 4, 0, n * 4, n, ctx->stream));
+	auto const zero_matrix([&](u32 *d, u64 pitch) -> int {
+		V2M_HIP_TRY(ctx, hipMemset2DAsync(d, pitch * 4, 0, n * 4, n, ctx->stream));
 		return V2M_OK;
 	});
 	auto const finish([&](int rc) -> int {
 		hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
 		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
-		if (V2M_OK == rc && info) {
+		if (V2M_OK == rc) {
 			double ms[stage_times::n_stages] = {};
 			times.sum(ms);
 			out.counts_ms = ms[stage_times::counts]; out.pack_ms = ms[stage_times::pack]; out.pairs_ms = ms[stage_times::pairs];
-			*info = out;
+			job.weights_ms = ms[stage_times::weights]; job.weighted_pairs_ms = ms[stage_times::weighted_pairs];
+			if (info) *info = out;
 		}
 		return rc;
 	});
-	if (0 == L) return finish(zeros());
+	// no column, or no site: every matrix is zero
+	auto const all_zero([&]() -> int {
+		if (job.d_plain) {
+			if (int const rc = zero_matrix(job.d_plain, job.plain_pitch)) return rc;
+			V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			if (job.plain_done) if (int const rc = job.plain_done()) return rc;
+		}
+		for (u64 r(0); r < job.n_weighted; ++r) {
+			if (int const rc = zero_matrix(job.d_weighted, job.weighted_pitch)) return rc;
+			V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			if (job.weighted_done) if (int const rc = job.weighted_done(r)) return rc;
+		}
+		return V2M_OK;
+	});
+	if (0 == L) return finish(all_zero());
 
 	// (1) the counts and the site list
 	u64 const table_pitch((L + 3) & ~u64(3));
@@ -3417,11 +3458,13 @@ int pair_distances_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, u32 *
 	u64 const V(*ctx->h_column_total.as<u64>());
 	if (V > L) return finish(fail(ctx, V2M_ERR_HIP, "the site selection counted %llu of %llu columns", (unsigned long long) V, (unsigned long long) L));
 	out.n_sites = V;
-	if (0 == V) return finish(zeros());
-	{
-		hipError_t const st(ctx->d_dist_sites.ensure(V * sizeof(u32)));
-		if (hipSuccess != st) return finish(fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "pair distances: the site list: %s", hipGetErrorString(st)));
-	}
+	if (0 == V) return finish(all_zero());
+	auto const ensure([&](scratch_buf &buf, u64 bytes, char const *what) -> int {
+		hipError_t const st(buf.ensure(bytes));
+		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "pair distances: %llu bytes of %s: %s", (unsigned long long) bytes, what, hipGetErrorString(st));
+		return V2M_OK;
+	});
+	if (V2M_OK != (rc = ensure(ctx->d_dist_sites, V * sizeof(u32), "the site list"))) return finish(rc);
 	u32 *const sites(ctx->d_dist_sites.as<u32>());
 	times.begin(stage_times::counts);
 	hipLaunchKernelGGL(v2m::emit_site_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
@@ -3438,54 +3481,143 @@ int pair_distances_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, u32 *
 	out.n_passes = n_passes;
 	u64 const forced_parts(env_u64("V2M_PAIR_DISTANCES_PARTS", 0));
 	bool const atomics(n_passes > 1 || pair_chunks_per_part(ctx, tile_pairs, pass_chunks, forced_parts) < pass_chunks);
+	bool const resident(1 == n_passes);
 	slice_plan const p(plan_slices(ctx, n, false));
-	if (atomics) {
-		times.begin(stage_times::pairs);
-		rc = zeros();
-		times.end();
-		if (V2M_OK != rc) return finish(rc);
-	}
-	for (u64 pass(0); pass < n_passes; ++pass) {
-		u64 const c0(pass * pass_chunks), c1(std::min(n_chunks, c0 + pass_chunks)), chunks(c1 - c0);
-		u64 const site_begin(c0 * chunk_sites), site_end(std::min(V, c1 * chunk_sites));
-		{
-			hipError_t const st(ctx->d_dist_planes.ensure(pass_chunks * chunk_bytes));   // (refilled per pass in the checked build)
-			if (hipSuccess != st) return finish(fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "pair distances: %llu bytes of planes: %s", (unsigned long long) (pass_chunks * chunk_bytes), hipGetErrorString(st)));
+
+	// the weighted path's buffers, taken once a call
+	u64 const n_words(n_chunks * v2m::kPairChunkWords);   // site words of the whole call, padding included: a slice
+	u32 *w(nullptr), *any(nullptr), *h_any(nullptr);
+	u64 *slices(nullptr);
+	if (job.n_weighted) {
+		if (V2M_OK != (rc = ensure(ctx->d_boot_weights, V * sizeof(u32), "site weights"))) return finish(rc);
+		if (V2M_OK != (rc = ensure(ctx->d_boot_slices, u64(v2m::kBootSlices) * n_words * sizeof(u64), "weight slices"))) return finish(rc);
+		if (V2M_OK != (rc = ensure(ctx->d_boot_any, 16, "the weights' OR"))) return finish(rc);
+		w = ctx->d_boot_weights.as<u32>(); slices = ctx->d_boot_slices.as<u64>(); any = ctx->d_boot_any.as<u32>();
+		h_any = reinterpret_cast<u32 *>(ctx->h_column_total.as<u64>() + 1);
+		if (job.weights) {
+			if (V2M_OK != (rc = ensure(ctx->d_boot_column_weights, L * sizeof(u32), "column weights"))) return finish(rc);
+			if (hipSuccess != hipMemcpyAsync(ctx->d_boot_column_weights.p, job.weights, L * sizeof(u32), hipMemcpyHostToDevice, ctx->stream))
+				return finish(fail(ctx, V2M_ERR_HIP, "pair distances: the weights could not be uploaded"));
 		}
+	}
+	u64 const key(v2m::bootstrap_key(job.seed));
+
+	// (2) the planes of a pass: zeroed (padding sites and rows hold code 0), then packed slice by slice
+	auto const pack_pass([&](u64 chunks, u64 site_begin, u64 site_end) -> int {
+		if (int const e = ensure(ctx->d_dist_planes, pass_chunks * chunk_bytes, "planes")) return e;   // (refilled per pack in the checked build)
 		u64 *const planes(ctx->d_dist_planes.as<u64>());
-		// (2) the planes of the pass: zeroed (padding sites and rows hold code 0), then packed slice by slice
-		times.begin(stage_times::pack);
-		if (hipSuccess != hipMemsetAsync(planes, 0, chunks * chunk_bytes, ctx->stream)) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: the planes could not be zeroed"));
+		if (hipSuccess != hipMemsetAsync(planes, 0, chunks * chunk_bytes, ctx->stream)) return fail(ctx, V2M_ERR_HIP, "pair distances: the planes could not be zeroed");
 		u64 const pack_blocks((site_end - site_begin + v2m::kPackThreads - 1) / v2m::kPackThreads);
 		for (u64 s(0); s < p.n_slices; ++s) {
 			u64 const r0(s * p.rows_per_slice), r1(std::min(n, r0 + p.rows_per_slice)), nr(r1 - r0);
-			{
-				hipError_t const st(ctx->ring[0].ensure(p.slot_bytes));
-				if (hipSuccess != st) return finish(fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "pair distances: the row slot: %s", hipGetErrorString(st)));
-			}
+			if (int const e = ensure(ctx->ring[0], p.slot_bytes, "the row slot")) return e;
 			char *const d_rows(ctx->ring[0].as<char>());
-			if (V2M_OK != (rc = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch))) return finish(rc);
+			if (int const e = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch)) return e;
 			// row groups: with few site blocks, as many as bring the launch to about four workgroups per compute unit, of at least 16 rows
 			u64 const want_groups((4 * u64(ctx->n_cus) + pack_blocks - 1) / pack_blocks);
 			u64 const per_group(std::max<u64>({16, (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}));
 			u64 const groups((nr + per_group - 1) / per_group);
 			hipLaunchKernelGGL(v2m::pack_sites_kernel, dim3(unsigned(pack_blocks), unsigned(groups)), dim3(v2m::kPackThreads), 0, ctx->stream,
 				d_rows, p.pitch, u32(nr), u32(per_group), u32(r0), sites, site_begin, site_end, planes, n_pad);
-			if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pack_sites_kernel did not launch"));
+			if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "pair distances: pack_sites_kernel did not launch");
 		}
+		return V2M_OK;
+	});
+
+	// weighted matrix r's weights by site rank, their slices, and K: the one synchronisation that a matrix's weights cost
+	auto const make_weights([&](u64 r, u32 &n_slices) -> int {
+		times.begin(stage_times::weights);
+		if (hipSuccess != hipMemsetAsync(any, 0, sizeof(u32), ctx->stream)) { times.end(); return fail(ctx, V2M_ERR_HIP, "bootstrap: the weights could not be zeroed"); }
+		if (job.weights)
+			hipLaunchKernelGGL(v2m::gather_site_weights_kernel, dim3(unsigned((V + v2m::kBootGatherThreads - 1) / v2m::kBootGatherThreads)), dim3(v2m::kBootGatherThreads), 0, ctx->stream,
+				ctx->d_boot_column_weights.as<u32>(), sites, V, w);
+		else {
+			if (hipSuccess != hipMemsetAsync(w, 0, V * sizeof(u32), ctx->stream)) { times.end(); return fail(ctx, V2M_ERR_HIP, "bootstrap: the weights could not be zeroed"); }
+			hipLaunchKernelGGL(v2m::bootstrap_weights_kernel, dim3(unsigned((L + v2m::kBootDrawThreads - 1) / v2m::kBootDrawThreads)), dim3(v2m::kBootDrawThreads), 0, ctx->stream,
+				key, u32(job.first_replicate + u32(r)), L, sites, V, w);
+		}
+		hipLaunchKernelGGL(v2m::weight_slices_kernel, dim3(unsigned((n_words * 64 + v2m::kBootSliceThreads - 1) / v2m::kBootSliceThreads)), dim3(v2m::kBootSliceThreads), 0, ctx->stream,
+			w, V, n_words, slices, any);
 		times.end();
-		// (3) the pairs
-		u64 const per_part(pair_chunks_per_part(ctx, tile_pairs, chunks, forced_parts)), parts((chunks + per_part - 1) / per_part);
-		times.begin(stage_times::pairs);
-		hipLaunchKernelGGL((flags & V2M_DIST_ACGT_ONLY) ? v2m::pair_distances_kernel<true> : v2m::pair_distances_kernel<false>,
-			dim3(unsigned(tile_pairs), 1, unsigned(parts)), dim3(v2m::kPairThreads), 0, ctx->stream,
-			planes, n_pad, u32(chunks), u32(per_part), u32(n_tiles), u32(n), d_dist, pitch, atomics ? 1u : 0u);
-		times.end();
-		if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pair_distances_kernel did not launch"));
-		if (pass + 1 < n_passes && hipSuccess != hipStreamSynchronize(ctx->stream))   // (the planes are reused, and refilled in the checked build)
-			return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pass %llu failed", (unsigned long long) pass));
+		if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "bootstrap: the weight kernels did not launch");
+		if (hipSuccess != hipMemcpyAsync(h_any, any, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream) || hipSuccess != hipStreamSynchronize(ctx->stream))
+			return fail(ctx, V2M_ERR_HIP, "bootstrap: the largest weight did not arrive");
+		n_slices = 0;
+		for (u32 bits(*h_any); bits; bits >>= 1) ++n_slices;
+		job.max_slices = std::max<u64>(job.max_slices, n_slices);
+		return V2M_OK;
+	});
+
+	bool packed(false);
+	for (u64 round(0); 0 == round || round < job.n_weighted; ++round) {
+		bool const plain(0 == round && job.d_plain), weighted(round < job.n_weighted);
+		u32 n_slices(0);
+		if (weighted && V2M_OK != (rc = make_weights(round, n_slices))) return finish(rc);
+		if (plain && atomics) {
+			times.begin(stage_times::pairs);
+			rc = zero_matrix(job.d_plain, job.plain_pitch);
+			times.end();
+			if (V2M_OK != rc) return finish(rc);
+		}
+		if (weighted && (atomics || 0 == n_slices)) {
+			times.begin(stage_times::weighted_pairs);
+			rc = zero_matrix(job.d_weighted, job.weighted_pitch);
+			times.end();
+			if (V2M_OK != rc) return finish(rc);
+		}
+		bool const launches(plain || n_slices > 0);   // (K == 0: the zeros are the matrix, and nothing is launched)
+		for (u64 pass(0); launches && pass < n_passes; ++pass) {
+			u64 const c0(pass * pass_chunks), c1(std::min(n_chunks, c0 + pass_chunks)), chunks(c1 - c0);
+			u64 const site_begin(c0 * chunk_sites), site_end(std::min(V, c1 * chunk_sites));
+			if (!(resident && packed)) {
+				times.begin(0 == round ? int(stage_times::pack) : int(stage_times::weighted_pairs));
+				rc = pack_pass(chunks, site_begin, site_end);
+				times.end();
+				if (V2M_OK != rc) return finish(rc);
+				packed = true;
+				++job.n_pack_passes;
+			}
+			u64 const *const planes(ctx->d_dist_planes.as<u64>());
+			// (3) the pairs
+			u64 const per_part(pair_chunks_per_part(ctx, tile_pairs, chunks, forced_parts)), parts((chunks + per_part - 1) / per_part);
+			if (plain) {
+				times.begin(stage_times::pairs);
+				hipLaunchKernelGGL((flags & V2M_DIST_ACGT_ONLY) ? v2m::pair_distances_kernel<true> : v2m::pair_distances_kernel<false>,
+					dim3(unsigned(tile_pairs), 1, unsigned(parts)), dim3(v2m::kPairThreads), 0, ctx->stream,
+					planes, n_pad, u32(chunks), u32(per_part), u32(n_tiles), u32(n), job.d_plain, job.plain_pitch, atomics ? 1u : 0u);
+				times.end();
+				if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pair_distances_kernel did not launch"));
+			}
+			if (n_slices > 0) {
+				times.begin(stage_times::weighted_pairs);
+				hipLaunchKernelGGL((flags & V2M_DIST_ACGT_ONLY) ? v2m::pair_distances_weighted_kernel<true> : v2m::pair_distances_weighted_kernel<false>,
+					dim3(unsigned(tile_pairs), 1, unsigned(parts)), dim3(v2m::kPairThreads), 0, ctx->stream,
+					planes, n_pad, u32(chunks), u32(per_part), u32(n_tiles), u32(n), slices, n_words, c0 * v2m::kPairChunkWords, n_slices,
+					job.d_weighted, job.weighted_pitch, atomics ? 1u : 0u);
+				times.end();
+				if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pair_distances_weighted_kernel did not launch"));
+			}
+			if (pass + 1 < n_passes && hipSuccess != hipStreamSynchronize(ctx->stream))   // (the planes are reused, and refilled in the checked build)
+				return finish(fail(ctx, V2M_ERR_HIP, "pair distances: pass %llu failed", (unsigned long long) pass));
+		}
+		if (plain && job.plain_done) {
+			V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			if (V2M_OK != (rc = job.plain_done())) return finish(rc);
+		}
+		if (weighted && job.weighted_done) {
+			V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			if (V2M_OK != (rc = job.weighted_done(round))) return finish(rc);
+		}
 	}
 	return finish(V2M_OK);
+}
+
+// The plain matrix alone.
+int pair_distances_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, u32 *d_dist, u64 pitch, v2m_pair_distances_info *info)
+{
+	pair_job job;
+	job.d_plain = d_dist; job.plain_pitch = pitch;
+	return pair_matrices_run(ctx, rows, flags, job, info);
 }
 
 } // namespace
@@ -4107,6 +4239,105 @@ int v2m_nj_tree(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_nj_
 	out.n_sites = distances.n_sites; out.n_columns = distances.n_columns; out.n_passes = distances.n_passes;
 	out.distances_ms = distances.counts_ms + distances.pack_ms + distances.pairs_ms;
 	if (int const rc = nj_run(ctx, ctx->d_dist_matrix.as<u32>(), n, pitch, nodes, &out.tree_ms)) return rc;
+	if (info) *info = out;
+	return V2M_OK;
+}
+
+
+// ---- bootstrap (bootstrap_kernels.hpp, nj_support.hpp) ---------------------------------------------
+
+namespace {
+
+static_assert(sizeof(v2m_nj_bootstrap_info) == 88, "the header's size");
+
+// One weighted matrix through the context's matrix to the host: explicit weights, or replicate `replicate` under seed.
+int weighted_distances_to_host(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, u32 const *weights, u64 seed, u32 replicate, u32 *dist, v2m_pair_distances_info *info)
+{
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	u64 const n(rows->n_rows), pitch((n + 3) & ~u64(3));
+	V2M_HIP_TRY(ctx, ctx->d_boot_matrix.ensure(n * pitch * 4));
+	pair_job job;
+	job.d_weighted = ctx->d_boot_matrix.as<u32>(); job.weighted_pitch = pitch;
+	job.n_weighted = 1; job.weights = weights; job.seed = seed; job.first_replicate = replicate;
+	v2m_pair_distances_info out{};
+	if (int const rc = pair_matrices_run(ctx, rows, flags, job, &out)) return rc;
+	out.pairs_ms += job.weights_ms + job.weighted_pairs_ms;
+	V2M_HIP_TRY(ctx, hipMemcpy2D(dist, n * 4, ctx->d_boot_matrix.p, pitch * 4, n * 4, n, hipMemcpyDeviceToHost));
+	if (info) *info = out;
+	return V2M_OK;
+}
+
+} // namespace
+
+int v2m_pair_distances_weighted(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, const uint32_t *weights, uint32_t *dist, v2m_pair_distances_info *info)
+{
+	if (int const rc = check_pair_distances(ctx, rows, flags, "v2m_pair_distances_weighted")) return rc;
+	if (!dist) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "dist is NULL");
+	u64 const L(ctx->view().length());
+	if (!weights && L) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "weights is NULL");
+	u64 sum(0);
+	for (u64 c(0); c < L; ++c) sum += weights[c];   // (L < 2^32 values below 2^32: no overflow)
+	if (sum >> 32) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "v2m_pair_distances_weighted takes weights that sum to less than 2^32 (got %llu)", (unsigned long long) sum);
+	if (0 == rows->n_rows) return V2M_OK;
+	return weighted_distances_to_host(ctx, rows, flags, weights, 0, 0, dist, info);
+}
+
+int v2m_bootstrap_distances(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, uint64_t seed, uint32_t replicate, uint32_t *dist, v2m_pair_distances_info *info)
+{
+	if (int const rc = check_pair_distances(ctx, rows, flags, "v2m_bootstrap_distances")) return rc;
+	if (!dist) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "dist is NULL");
+	if (0 == rows->n_rows) return V2M_OK;
+	return weighted_distances_to_host(ctx, rows, flags, nullptr, seed, replicate, dist, info);
+}
+
+int v2m_nj_bootstrap(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, uint32_t n_replicates, uint64_t seed, v2m_nj_node *nodes, uint32_t *support,
+	v2m_nj_node *replicate_nodes, v2m_nj_bootstrap_info *info)
+{
+	if (int const rc = check_pair_distances(ctx, rows, flags, "v2m_nj_bootstrap")) return rc;
+	if (!nodes) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "nodes is NULL");
+	if (0 == n_replicates || n_replicates > V2M_NJ_BOOTSTRAP_MAX_REPLICATES)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "v2m_nj_bootstrap takes 1 to V2M_NJ_BOOTSTRAP_MAX_REPLICATES = %u replicates (got %u)", V2M_NJ_BOOTSTRAP_MAX_REPLICATES, n_replicates);
+	u64 const n(rows->n_rows), pitch((n + 3) & ~u64(3));
+	if (0 == n) return V2M_OK;
+	if (n < 3) return nj_too_few(ctx, n, "v2m_nj_bootstrap");
+	if (!support && n > 3) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "support is NULL");
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	V2M_HIP_TRY(ctx, ctx->d_dist_matrix.ensure(n * pitch * 4));
+	V2M_HIP_TRY(ctx, ctx->d_boot_matrix.ensure(n * pitch * 4));
+	v2m_nj_bootstrap_info out{};
+	out.n_rows = n; out.n_replicates = n_replicates;
+	try {
+		v2m::nj_split_counter counter;
+		std::vector<v2m_nj_node> tree(replicate_nodes ? 0 : n - 2);   // a replicate's records, where the caller keeps none
+		pair_job job;
+		job.d_plain = ctx->d_dist_matrix.as<u32>(); job.plain_pitch = pitch;
+		job.d_weighted = ctx->d_boot_matrix.as<u32>(); job.weighted_pitch = pitch;
+		job.n_weighted = n_replicates; job.seed = seed;
+		job.plain_done = [&]() -> int {
+			double ms(0);
+			if (int const rc = nj_run(ctx, job.d_plain, n, pitch, nodes, &ms)) return rc;
+			out.trees_ms += ms;
+			std::string const err(counter.begin(n, nodes, support));
+			return err.empty() ? V2M_OK : fail(ctx, V2M_ERR_HIP, "v2m_nj_bootstrap: the main tree: %s", err.c_str());
+		};
+		job.weighted_done = [&](u64 r) -> int {
+			v2m_nj_node *const dst(replicate_nodes ? replicate_nodes + r * (n - 2) : tree.data());
+			double ms(0);
+			if (int const rc = nj_run(ctx, job.d_weighted, n, pitch, dst, &ms)) return rc;
+			out.trees_ms += ms;
+			std::string const err(counter.add(dst));
+			return err.empty() ? V2M_OK : fail(ctx, V2M_ERR_HIP, "v2m_nj_bootstrap: replicate %llu: %s", (unsigned long long) r, err.c_str());
+		};
+		v2m_pair_distances_info distances{};
+		if (int const rc = pair_matrices_run(ctx, rows, flags, job, &distances)) return rc;
+		out.n_sites = distances.n_sites; out.n_columns = distances.n_columns; out.n_passes = distances.n_passes;
+		out.n_pack_passes = job.n_pack_passes; out.max_slices = job.max_slices;
+		out.distances_ms = distances.counts_ms + distances.pack_ms + distances.pairs_ms;
+		out.weights_ms = job.weights_ms; out.pairs_ms = job.weighted_pairs_ms;
+	} catch (std::bad_alloc const &) {
+		(void) hipStreamSynchronize(ctx->stream);
+		return fail(ctx, V2M_ERR_OUT_OF_MEMORY, "v2m_nj_bootstrap: no host memory for the splits");
+	}
 	if (info) *info = out;
 	return V2M_OK;
 }

@@ -87,6 +87,10 @@ def _load():
 		L.v2mh_nj_tree_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
 		L.v2mh_nj_newick_text.restype = C.c_int64
 		L.v2mh_nj_newick_text.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_nj_newick_support_text.restype = C.c_int64
+		L.v2mh_nj_newick_support_text.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_nj_split_support.restype = C.c_int
+		L.v2mh_nj_split_support.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -270,6 +274,48 @@ def nj_newick_text(nodes, labels):
 	if size != L.v2mh_nj_newick_text(*args, dst, size, err, len(err)):
 		raise ValueError(err.value.decode())
 	return dst.raw[:size]
+
+
+def nj_newick_support_text(nodes, labels, support):
+	"""The host library's Newick writer with bootstrap support (csrc/host/output.cc: nj_newick_support_text; no GPU): nj_newick_text
+	with support[t] written as the label of join node len(labels) + t."""
+	from . import _native as N
+	names = [i if isinstance(i, bytes) else str(i).encode() for i in labels]
+	n = len(names)
+	nodes = np.ascontiguousarray(nodes, dtype=np.dtype(N.NJ_NODE_DTYPE))
+	support = np.ascontiguousarray(support, dtype=np.uint32)
+	if n < 3 or len(nodes) != n - 2 or support.shape != (n - 3,):
+		raise ValueError("%d records, %d labels and %d counts are no tree with support" % (len(nodes), n, support.size))
+	if any(b"\0" in i for i in names):
+		raise ValueError("a label holds a NUL byte")
+	array = (C.c_char_p * n)(*names)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (nodes.ctypes.data, n, array, support.ctypes.data if n > 3 else None)
+	size = L.v2mh_nj_newick_support_text(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != L.v2mh_nj_newick_support_text(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
+
+
+def nj_split_support(main_nodes, replicate_nodes):
+	"""The host library's split counting (csrc/nj_support.hpp; no GPU): np.uint32[n - 3], per join record of the tree `main_nodes`
+	(n - 2 v2m_nj_node records) the number of the trees `replicate_nodes` ([B, n - 2]) that hold the record's split.  ValueError for
+	records that are no tree."""
+	from . import _native as N
+	main_nodes = np.ascontiguousarray(main_nodes, dtype=np.dtype(N.NJ_NODE_DTYPE))
+	n = len(main_nodes) + 2
+	replicate_nodes = np.ascontiguousarray(replicate_nodes, dtype=np.dtype(N.NJ_NODE_DTYPE)).reshape(-1, n - 2)
+	if main_nodes.ndim != 1 or n < 3:
+		raise ValueError("a tree has at least one record")
+	support = np.zeros(max(1, n - 3), dtype=np.uint32)
+	B = replicate_nodes.shape[0]
+	if 0 != _load().v2mh_nj_split_support(n, main_nodes.ctypes.data, replicate_nodes.ctypes.data if B else None, B, support.ctypes.data):
+		raise ValueError("v2mh_nj_split_support: the records are no trees over %d leaves" % n)
+	return support[:n - 3]
 
 
 def write_cut_positions(path, cut_positions, min_distance, score):

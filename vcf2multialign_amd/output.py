@@ -123,20 +123,33 @@ class Output:
 		stream.write(host.site_ld_text(len(rows), info["n_columns"], sites, pairs, graph.reference_positions, graph.aligned_positions, **params))
 		return info
 
-	def _write_tree(self, stream, ids, rows, graph, acgt_only):
+	def _write_tree(self, stream, ids, rows, graph, acgt_only, bootstrap=0, seed=1, replicates_path=None):
 		"""--output-tree: the Newick text of host.nj_newick_text for `rows` named `ids` from Context.nj_tree, over the region's columns
-		when there is one.  Returns the info of the call."""
+		when there is one.  bootstrap > 0 (--tree-bootstrap, --tree-seed): the text of host.nj_newick_support_text from
+		Context.nj_bootstrap, and with replicates_path (--output-tree-replicates) the replicate trees into that file, a line each.
+		Returns the info of the call."""
 		from . import host
 		if len(rows) < 3:
 			raise ValueError("--output-tree needs at least three sequences (got %d)" % len(rows))
 		if self.region is not None:
 			self.ctx.set_column_window(*columns_of_reference_range(graph.reference_positions, graph.aligned_positions, *self.region))
 		try:
-			nodes, info = self.ctx.nj_tree(RowBatch(rows), acgt_only=acgt_only, info=True)
+			if bootstrap:
+				keep = replicates_path is not None
+				nodes, support, *trees, info = self.ctx.nj_bootstrap(RowBatch(rows), bootstrap, seed=seed, acgt_only=acgt_only, replicates=keep, info=True)
+			else:
+				nodes, info = self.ctx.nj_tree(RowBatch(rows), acgt_only=acgt_only, info=True)
 		finally:
 			if self.region is not None:
 				self.ctx.set_column_window(0, self.ctx.aligned_length)
-		stream.write(host.nj_newick_text(nodes, ids))
+		if not bootstrap:
+			stream.write(host.nj_newick_text(nodes, ids))
+			return info
+		stream.write(host.nj_newick_support_text(nodes, ids, support))
+		if replicates_path is not None:
+			with open(replicates_path, "wb") as f:
+				for tree in trees[0]:
+					f.write(host.nj_newick_text(tree, ids))
 		return info
 
 	def _write_rows(self, stream, ids, rows, graph):
@@ -205,6 +218,12 @@ class HaplotypeOutput(Output):
 		"""--output-tree (acgt_only: --tree-acgt-only) for the rows of output_distances under its names."""
 		ids, rows = self._distance_rows(graph)
 		return self._write_tree(stream, ids, rows, graph, acgt_only)
+
+	def output_tree_bootstrap(self, graph, stream, bootstrap, seed=1, replicates_path=None, acgt_only=False):
+		"""--output-tree with --tree-bootstrap=bootstrap (seed: --tree-seed; replicates_path: --output-tree-replicates; acgt_only:
+		--tree-acgt-only) for the rows of output_tree."""
+		ids, rows = self._distance_rows(graph)
+		return self._write_tree(stream, ids, rows, graph, acgt_only, int(bootstrap), seed, replicates_path)
 
 	def output_variable_sites(self, graph, stream, snp_only=False, positions=None):
 		"""--output-variable-sites (with --snp-sites and --output-site-positions) for the rows of output_a2m under its names."""
@@ -290,6 +309,12 @@ class FounderSequenceGreedyOutput(Output):
 		"""--output-tree (acgt_only: --tree-acgt-only) for the rows of output_distances under its names."""
 		ids, rows = self._distance_rows(cut_positions, assigned_samples_column_major)
 		return self._write_tree(stream, ids, rows, graph, acgt_only)
+
+	def output_tree_bootstrap(self, graph, cut_positions, assigned_samples_column_major, stream, bootstrap, seed=1, replicates_path=None, acgt_only=False):
+		"""--output-tree with --tree-bootstrap=bootstrap (seed: --tree-seed; replicates_path: --output-tree-replicates; acgt_only:
+		--tree-acgt-only) for the rows of output_tree."""
+		ids, rows = self._distance_rows(cut_positions, assigned_samples_column_major)
+		return self._write_tree(stream, ids, rows, graph, acgt_only, int(bootstrap), seed, replicates_path)
 
 	def output_variable_sites(self, graph, cut_positions, assigned_samples_column_major, stream, snp_only=False, positions=None):
 		"""--output-variable-sites for the rows of output_a2m (REF first, unless omitted, then the founder rows) under its names."""
