@@ -27,12 +27,13 @@ NODE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("reserved", "<
 
 @functools.lru_cache(maxsize=None)
 def kernel_constants():
-	"""(W, B): kNjRowsPerGroup, the rows a workgroup of nj_rowmin_kernel takes, and kNjJoinThreads, the size of nj_join_kernel's one
-	workgroup, read from csrc/nj_kernels.hpp."""
+	"""(W, B, J): kNjRowsPerGroup, the rows a workgroup of nj_rowmin_kernel takes, kNjJoinThreads, the size of nj_join_kernel's one
+	workgroup, and kNjJoinBatch, the live slots a lane of it has in flight (a trip of its loop takes J B slots), read from
+	csrc/nj_kernels.hpp."""
 	with open(NJ_KERNELS_HPP) as f:
 		text = f.read()
 	out = []
-	for name in ("kNjRowsPerGroup", "kNjJoinThreads"):
+	for name in ("kNjRowsPerGroup", "kNjJoinThreads", "kNjJoinBatch"):
 		found = re.findall(r"^constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text, re.M)
 		assert len(found) == 1, "%s: %d definitions of the form `constexpr int %s = value;`" % (name, len(found), name)
 		out.append(int(found[0]))
@@ -341,14 +342,14 @@ class Item:
 
 
 def seam_counts():
-	W, B = kernel_constants()
+	W, B, _ = kernel_constants()
 	return sorted({3, 4, 5, W - 1, W, W + 1, B - 1, B, B + 1, 2 * B + 1})
 
 
 @functools.lru_cache(maxsize=None)
 def corpus():
 	"""The matrices every test of the tree runs."""
-	W, B = kernel_constants()
+	W, B, _ = kernel_constants()
 	items = []
 	for n in seam_counts():
 		items.append(Item("noise_%d" % n, path_noise(n, 1000 + n)))
@@ -376,10 +377,24 @@ def corpus():
 	return items
 
 
+def join_batch_counts():
+	"""Taxa around a full trip of nj_join_kernel's loop over the live slots, J B at a time, element e of a lane's batch the slot e B + lane:
+	(J - 1) B + 1 -- element J - 1 runs, in lane 0 only; J B -- the batch exactly full, no second trip; J B + 64 -- 64 joins with
+	r > J B, a wave of lanes in the second trip."""
+	_, B, J = kernel_constants()
+	return ((J - 1) * B + 1, J * B, J * B + 64)
+
+
+@functools.lru_cache(maxsize=None)
+def join_batch_items():
+	"""A list of its own: corpus() ends at 2 B + 1 taxa, which its tests assert, and nj_exact() must not run at these sizes."""
+	return [Item("path_noise_%d_1" % n, path_noise(n, 1)) for n in join_batch_counts()]
+
+
 @functools.lru_cache(maxsize=None)
 def expected(name):
-	"""The model's records of a corpus item: computed once, shared, read-only."""
-	item = next(i for i in corpus() if i.name == name)
+	"""The model's records of an item of corpus() or join_batch_items(): computed once, shared, read-only."""
+	item = next(i for i in corpus() + join_batch_items() if i.name == name)
 	nodes = nj(item.d)
 	nodes.setflags(write=False)
 	return nodes

@@ -246,3 +246,43 @@ def corpus():
 	items += [Item("sites_%d" % V, sites_graph_of(V), SITE_ROWS) for V in site_counts()]
 	items += [Item("window_%d_%d" % w, window_graph(), SITE_ROWS, w) for w in windows()]
 	return items
+
+
+# ---- rows that all differ --------------------------------------------------------------------------------------------------------------------
+#
+# row_count_rows(n) repeats with period 16, which divides the 16 rows of pack_sites_kernel's smallest row group, the 32 of pair_row()'s
+# second half and the 64 of a tile: a row group written one group off, two halves of a tile exchanged or a tile taken for its neighbour
+# give the same matrix (tests/test_pair_distances_host.py asserts that, and that the items below tell every one of them).
+
+def distinct_rows(g, n):
+	"""n rows over a sites_graph of n copies: the REF row, copy 0, copies 2 ... n - 4 (copy 1 takes no edge and equals REF) and the three
+	cut_rows(g), one near the front, one in the middle, one last."""
+	rows = [PLOIDY_MAX, 0] + list(range(2, n - 3))
+	for at, cut in zip((7, n // 2, n - 1), cut_rows(g)):
+		rows.insert(at, cut)
+	assert len(rows) == n
+	return rows
+
+
+def distinct_counts():
+	"""(rows, variable columns, seed): 3 T + 1 rows are four tiles, the last of one row, with a full tile pair (1, 2) off the diagonal that
+	does not touch tile 0, over two chunks of sites and five more; 8 T + 1 rows are 45 tile pairs over a chunk and 70 sites; J B + 64 rows
+	(J B: the slots nj_join_kernel takes in one trip) are 17 tiles, 153 tile pairs, over about 60 sites."""
+	import nj_tree_model
+	T, C = kernel_constants()
+	_, B, J = nj_tree_model.kernel_constants()
+	return ((3 * T + 1, 2 * 64 * C + 5, 11), (8 * T + 1, 64 * C + 70, 12), (J * B + 64, 60, 13))
+
+
+@functools.lru_cache(maxsize=None)
+def distinct_items():
+	"""Items whose rows all differ, in the class matrix and in the expected matrix under both definitions."""
+	items = []
+	for n, V, seed in distinct_counts():
+		g = sites_graph_of(V, n_copies=n, seed=seed)
+		items.append(Item("distinct_%d" % n, g, distinct_rows(g, n)))
+	return items
+
+
+def distinct_item(n):
+	return next(i for i in distinct_items() if len(i.rows) == n)

@@ -360,3 +360,14 @@ def corpus():
 	names = [i.name for i in items]
 	assert len(set(names)) == len(names)
 	return items
+
+
+@functools.lru_cache(maxsize=None)
+def row_words_item():
+	"""64 * 5 + 7 rows over the graph of the row counts: six 64-row words, the last one ragged, for ld_pack_kernel's groups of several
+	words (tests/test_gpu_site_ld.py: V2M_SITE_LD_WORDS_PER_GROUP).  The rows repeat with period 17, which no word is a multiple of."""
+	T, _ = kernel_constants()
+	g = random_graph(T + 1, seed=3)
+	rows = CM.repeated(all_rows(g), 64 * 5 + 7)
+	assert len(all_rows(g)) == 17 and (len(rows) + 63) // 64 == 6 and len(rows) % 64 == 7
+	return Item("row_words_%d" % len(rows), g, rows, Params(window_sites=T))

@@ -103,6 +103,24 @@ def test_explicit_weights(v2m, ctx, item):
 	check_explicit(ctx, v2m, item)
 
 
+def test_distinct_rows_weighted_and_resampled(v2m, ctx):
+	"""Four tiles of rows that all differ (tests/pair_distances_model.py: distinct_items(); the rows of ROW_ITEMS repeat with period 16,
+	which hides rows, halves of a tile and tiles taken for one another): the weighted kernel under all ones and under 2^b on site b, and
+	one replicate under each definition, every entry held to the model."""
+	T, _ = PM.kernel_constants()
+	item = PM.distinct_item(3 * T + 1)
+	upload(v2m, ctx, item)
+	patterns = {name: w for name, w, _ in BM.explicit_patterns(item)}
+	for name in ("ones", "powers"):
+		for acgt in (False, True):
+			got, info = weighted(ctx, v2m, item.rows, patterns[name], acgt)
+			same_matrix(got, BM.expected_weighted(item, patterns[name], acgt), "%s %s acgt=%s" % (item.name, name, acgt))
+			assert info.n_sites == PM.variable_columns(item.g)
+	for seed, r, acgt in ((1, 0, False), (BM.MASK, 1, True)):
+		got, _ = replicate(ctx, v2m, item.rows, seed, r, acgt)
+		same_matrix(got, BM.expected_replicate(item, seed, r, acgt), "%s seed %d replicate %d acgt=%s" % (item.name, seed, r, acgt))
+
+
 def test_a_sum_of_two_to_the_32_is_refused(v2m, ctx):
 	from vcf2multialign_amd import _native as N
 	item = SITE_ITEMS[3]
@@ -418,6 +436,7 @@ def test_cli_founders(v2m, ctx, tmp_path):
 
 CHECKED_CORPUS = [
 	"tests/test_gpu_nj_bootstrap.py::test_explicit_weights",
+	"tests/test_gpu_nj_bootstrap.py::test_distinct_rows_weighted_and_resampled",
 	"tests/test_gpu_nj_bootstrap.py::test_parts_and_passes_through_the_knobs",
 	"tests/test_gpu_nj_bootstrap.py::test_bootstrap_distances",
 	"tests/test_gpu_nj_bootstrap.py::test_draw_block_seams",

@@ -4,6 +4,7 @@ tests/pair_distances_model.py through v2m_nj_tree under both definitions, the er
 the checked build.  The largest matrix has 2 B + 1 taxa (B: nj_join_kernel's workgroup): a few thousand short launches."""
 
 import ctypes as C
+import functools
 import io
 import os
 
@@ -29,7 +30,7 @@ GUARD_ROWS = 2
 def v2m():
 	import vcf2multialign_amd as v
 	from vcf2multialign_amd import _native as N
-	assert (N.NJ_ROWS_PER_GROUP, N.NJ_JOIN_THREADS) == M.kernel_constants() and np.dtype(N.NJ_NODE_DTYPE) == M.NODE_DTYPE
+	assert (N.NJ_ROWS_PER_GROUP, N.NJ_JOIN_THREADS, N.NJ_JOIN_BATCH) == M.kernel_constants() and np.dtype(N.NJ_NODE_DTYPE) == M.NODE_DTYPE
 	return v
 
 
@@ -96,6 +97,44 @@ def test_the_six_leaf_tree_under_every_relabeling(v2m, ctx):
 	assert len(six) == 720
 	for item in six:
 		check_matrix(ctx, item)
+
+
+# ---- beyond one batch of the join kernel ------------------------------------------------------------------------------------------------------
+
+JOIN_BATCH_ITEMS = M.join_batch_items()
+
+
+@pytest.mark.parametrize("item", JOIN_BATCH_ITEMS, ids=[i.name for i in JOIN_BATCH_ITEMS])
+def test_join_batches(v2m, ctx, item):
+	"""(J - 1) B + 1, J B and J B + 64 taxa (J B: the live slots nj_join_kernel's loop takes in one trip): the last element of a lane's
+	batch, the batch exactly full, and 64 joins whose loop makes a second trip.  tests/test_nj_tree_host.py asserts that those joins move
+	slots of the first trip and of the second.  About two launches a taxon, and the model takes a few seconds at these sizes."""
+	check_matrix(ctx, item)
+
+
+@functools.lru_cache(maxsize=None)
+def distinct_rows_beyond_a_batch(acgt):
+	"""(the item, the model's matrix, the model's records of it): computed once, shared, read-only."""
+	_, B, J = M.kernel_constants()
+	item = PM.distinct_item(J * B + 64)
+	d, V, L = PM.expected(item.g, item.rows, acgt_only=acgt)
+	nodes = M.nj(d)
+	for a in (d, nodes):
+		a.setflags(write=False)
+	return item, d, V, L, nodes
+
+
+@pytest.mark.parametrize("acgt", [False, True], ids=["all", "acgt"])
+def test_distinct_rows_beyond_a_join_batch(v2m, ctx, acgt):
+	"""J B + 64 rows that all differ, from rows to records: 17 tiles of pack and pair kernels, then the tree of the matrix they left on
+	the device, held to the model's records of the model's matrix; ctx.pair_distances of the same rows is that matrix."""
+	item, d, V, L, want = distinct_rows_beyond_a_batch(acgt)
+	upload(v2m, ctx, item.g)
+	nodes, info = ctx.nj_tree(item.rows, acgt_only=acgt, info=True)
+	same_records(nodes, want, "%s acgt=%s" % (item.name, acgt))
+	assert (info["n_nodes"], info["n_sites"], info["n_columns"]) == (len(item.rows) - 2, V, L), info
+	got = ctx.pair_distances(item.rows, acgt_only=acgt)
+	assert got.dtype == np.uint32 and np.array_equal(got, d), "%s acgt=%s: pair_distances" % (item.name, acgt)
 
 
 def test_stage_times_while_profiling(v2m, ctx):
@@ -310,6 +349,7 @@ def test_cli_founders(v2m, ctx, tmp_path):
 CHECKED_CORPUS = [
 	"tests/test_gpu_nj_tree.py::test_corpus",
 	"tests/test_gpu_nj_tree.py::test_the_six_leaf_tree_under_every_relabeling",
+	"tests/test_gpu_nj_tree.py::test_join_batches[%s]" % M.join_batch_items()[-1].name,      # J B + 64 taxa: a slot nobody updated holds poison
 	"tests/test_gpu_nj_tree.py::test_graph_items",
 	"tests/test_gpu_nj_tree.py::test_the_views_are_left_as_they_were",
 ]

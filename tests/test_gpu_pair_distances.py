@@ -182,6 +182,77 @@ def test_passes(v2m, ctx, monkeypatch):
 	check_forms(ctx, g, CM.repeated(rows[:8], T + 1), what="T + 1 rows in passes", passes=3)
 
 
+# ---- rows that all differ ----------------------------------------------------------------------------------------------------------------------
+#
+# The rows of the corpus above repeat with period 16 or 8, which a row group, the halves of pair_row() and a tile are multiples of; in the
+# items of PM.distinct_items() no two rows are equal, and tests/test_pair_distances_host.py asserts that a row group written one group off,
+# two rows, halves or tiles exchanged each change their expected matrices.
+
+DISTINCT = PM.distinct_items()
+
+
+@pytest.mark.parametrize("item", DISTINCT, ids=[i.name for i in DISTINCT])
+def test_distinct_rows(v2m, ctx, item):
+	"""4, 9 and 17 tiles of rows that all differ: 10, 45 and 153 tile pairs decoded from blockIdx.x, every entry held to the model."""
+	upload(v2m, ctx, item.g)
+	check_forms(ctx, item.g, item.rows, what=item.name)
+
+
+def test_distinct_rows_in_parts_and_passes(v2m, ctx, monkeypatch):
+	"""The 3 T + 1 rows over three chunks of sites: one part (plain stores), two parts (atomics on the zeroed matrix), and a plane budget
+	of two chunks (two passes)."""
+	item = PM.distinct_item(3 * T + 1)
+	upload(v2m, ctx, item.g)
+	assert -(-PM.variable_columns(item.g) // CHUNK_SITES) == 3 and split_of(3, 2) == [2, 1]
+	for forced in ("1", "2"):
+		monkeypatch.setenv("V2M_PAIR_DISTANCES_PARTS", forced)
+		check_forms(ctx, item.g, item.rows, what="%s, %s parts" % (item.name, forced))
+	monkeypatch.delenv("V2M_PAIR_DISTANCES_PARTS")
+	chunk_bytes = CHUNK * 3 * 4 * T * 8            # the planes of one chunk of sites for four tiles of rows
+	monkeypatch.setenv("V2M_PAIR_DISTANCES_PLANE_BYTES", str(2 * chunk_bytes))
+	check_forms(ctx, item.g, item.rows, what=item.name + ", two passes", passes=2)
+
+
+# ---- row groups above the floor ----------------------------------------------------------------------------------------------------------------
+
+# V2M_SITE_ROWS_PER_GROUP over the 3 T + 1 distinct rows: a row a group; one unrolled trip of four and a tail row in every group, the groups
+# starting at every residue mod 4; a tail of two, the groups starting at the even residues; 67; exactly one group; one group of more rows than there are (what the rule gives when the
+# site blocks alone fill the device)
+SITE_ROWS_PER_GROUP = (1, 5, 18, 67, 3 * T + 1, 1000000)
+
+
+@pytest.mark.parametrize("per_group", SITE_ROWS_PER_GROUP)
+def test_row_groups_of_the_pack(v2m, ctx, monkeypatch, per_group):
+	"""pack_sites_kernel with groups of other sizes than the rule's floor of 16, over two chunks of sites and five more."""
+	item = PM.distinct_item(3 * T + 1)
+	assert PM.variable_columns(item.g) == 2 * CHUNK_SITES + 5 and {b % 4 for b in range(0, len(item.rows), 5)} == {0, 1, 2, 3}
+	upload(v2m, ctx, item.g)
+	monkeypatch.setenv("V2M_SITE_ROWS_PER_GROUP", str(per_group))
+	check_forms(ctx, item.g, item.rows, what="%s, %d rows a group" % (item.name, per_group))
+
+
+@pytest.mark.parametrize("per_group", (18, 1000000))
+def test_row_groups_of_the_pack_in_slices(v2m, ctx, monkeypatch, per_group):
+	"""The same under slices of 50 rows: a slice's first row is neither the batch's first nor a multiple of the group."""
+	item = PM.distinct_item(3 * T + 1)
+	upload(v2m, ctx, item.g)
+	pitch = int(ctx.min_row_pitch)
+	monkeypatch.setenv("V2M_RING_SLOT_BYTES", str(50 * pitch + pitch // 2))
+	monkeypatch.setenv("V2M_SITE_ROWS_PER_GROUP", str(per_group))
+	from vcf2multialign_amd import _native as N
+	ctx.profile_enable(True)
+	ctx.profile_reset()
+	try:
+		d = ctx.pair_distances(item.rows)
+		launches = ctx.profile_get(N.KERNEL_COLUMN_COUNTS)[0]
+	finally:
+		ctx.profile_reset()
+		ctx.profile_enable(False)
+	assert launches == 4, launches      # three slices of 50 rows and one of 43
+	same_matrix(d, PM.expected(item.g, item.rows)[0], "in slices, profiling on")
+	check_forms(ctx, item.g, item.rows, what="%s, %d rows a group, slices of 50 rows" % (item.name, per_group))
+
+
 def test_the_views_are_left_as_they_were(v2m, ctx):
 	g = PM.window_graph()
 	upload(v2m, ctx, g)
@@ -373,6 +444,10 @@ CHECKED_CORPUS = [
 	"tests/test_gpu_pair_distances.py::test_site_split_and_single_part",
 	"tests/test_gpu_pair_distances.py::test_row_slices",
 	"tests/test_gpu_pair_distances.py::test_passes",
+	"tests/test_gpu_pair_distances.py::test_distinct_rows",
+	"tests/test_gpu_pair_distances.py::test_distinct_rows_in_parts_and_passes",
+	"tests/test_gpu_pair_distances.py::test_row_groups_of_the_pack",
+	"tests/test_gpu_pair_distances.py::test_row_groups_of_the_pack_in_slices",
 	"tests/test_gpu_pair_distances.py::test_the_views_are_left_as_they_were",
 	"tests/test_gpu_pair_distances.py::test_reference_fixtures",
 ]

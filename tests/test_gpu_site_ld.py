@@ -204,6 +204,32 @@ def test_row_slices(v2m, ctx, monkeypatch):
 	assert check_item(ctx, item, "one slice again") == want
 
 
+# V2M_SITE_LD_WORDS_PER_GROUP over six row words, the last one ragged: groups of two, of three, of four (a full group and a ragged one of
+# two) and one group of more words than there are (what the rule gives when the site blocks alone fill the device)
+LD_WORDS_PER_GROUP = (2, 3, 4, 1000000)
+
+
+@pytest.mark.parametrize("per_group", LD_WORDS_PER_GROUP)
+def test_word_groups_of_the_pack(v2m, ctx, monkeypatch, per_group):
+	"""ld_pack_kernel with more than one word a group: its loop over a group's words makes a second trip and more."""
+	item = LM.row_words_item()
+	upload(v2m, ctx, item.g)
+	monkeypatch.setenv("V2M_SITE_LD_WORDS_PER_GROUP", str(per_group))
+	check_item(ctx, item, "%s, %d words a group" % (item.name, per_group))
+
+
+@pytest.mark.parametrize("per_group", LD_WORDS_PER_GROUP)
+def test_word_groups_of_the_pack_in_slices(v2m, ctx, monkeypatch, per_group):
+	"""The same under slices of 50 rows: a slice's first word is the previous slice's last, which both launches OR into, and a slice
+	of 50 rows spans two words, so a group of two or more holds them both."""
+	item = LM.row_words_item()
+	upload(v2m, ctx, item.g)
+	pitch = int(ctx.min_row_pitch)
+	monkeypatch.setenv("V2M_RING_SLOT_BYTES", str(50 * pitch + pitch // 2))
+	monkeypatch.setenv("V2M_SITE_LD_WORDS_PER_GROUP", str(per_group))
+	check_item(ctx, item, "%s, %d words a group, slices of 50 rows" % (item.name, per_group))
+
+
 def test_emit_ranges(v2m, ctx, monkeypatch):
 	"""The smallest V2M_SITE_LD_BLOCK_BYTES: one strip of T sites per emit range, the blocks in order and together all pairs; and a
 	block size that takes two strips."""
@@ -459,6 +485,8 @@ CHECKED_CORPUS = [
 	"tests/test_gpu_site_ld.py::test_corpus",
 	"tests/test_gpu_site_ld.py::test_capacities",
 	"tests/test_gpu_site_ld.py::test_row_slices",
+	"tests/test_gpu_site_ld.py::test_word_groups_of_the_pack",
+	"tests/test_gpu_site_ld.py::test_word_groups_of_the_pack_in_slices",
 	"tests/test_gpu_site_ld.py::test_emit_ranges",
 	"tests/test_gpu_site_ld.py::test_plane_budget",
 	"tests/test_gpu_site_ld.py::test_sinks",

@@ -207,6 +207,42 @@ def test_row_slices(v2m, ctx, monkeypatch):
 	assert check_forms(ctx, g, rows, what="one slice again") == want
 
 
+# ---- row groups above the floor ----------------------------------------------------------------------------------------------------------------
+
+# V2M_SITE_ROWS_PER_GROUP over the 3 T + 1 distinct rows of tests/pair_distances_model.py: a row a group; one unrolled trip of four and a
+# tail row in every group, the groups starting at every residue mod 4; a tail of two, the groups starting at the even residues; 67; exactly one group; one group of more rows than
+# there are (what the rule gives when the site blocks alone fill the device)
+GROUP_ITEM_ROWS = 3 * PM.kernel_constants()[0] + 1
+SITE_ROWS_PER_GROUP = (1, 5, 18, 67, GROUP_ITEM_ROWS, 1000000)
+
+
+@pytest.mark.parametrize("per_group", SITE_ROWS_PER_GROUP)
+def test_row_groups_of_the_gather(v2m, ctx, monkeypatch, per_group):
+	"""gather_sites_kernel with groups of other sizes than the rule's floor, over rows that all differ: a group written one group off
+	shows in every byte."""
+	item = PM.distinct_item(GROUP_ITEM_ROWS)
+	assert GROUP not in SITE_ROWS_PER_GROUP and len(VM.expected(item.g, item.rows)[0]) == PM.variable_columns(item.g) == 2 * 64 * PM.kernel_constants()[1] + 5
+	upload(v2m, ctx, item.g)
+	monkeypatch.setenv("V2M_SITE_ROWS_PER_GROUP", str(per_group))
+	check_forms(ctx, item.g, item.rows, what="%s, %d rows a group" % (item.name, per_group))
+
+
+@pytest.mark.parametrize("per_group", (18, 1000000))
+def test_row_groups_of_the_gather_in_slices(v2m, ctx, monkeypatch, per_group):
+	"""The same under slices of 50 rows: a slice's first row is neither the batch's first nor a multiple of the group."""
+	item = PM.distinct_item(GROUP_ITEM_ROWS)
+	upload(v2m, ctx, item.g)
+	pitch = int(ctx.min_row_pitch)
+	monkeypatch.setenv("V2M_RING_SLOT_BYTES", str(50 * pitch + pitch // 2))
+	monkeypatch.setenv("V2M_SITE_ROWS_PER_GROUP", str(per_group))
+	for snp_only in (False, True):
+		want_columns, want_bytes, _ = VM.expected(item.g, item.rows, snp_only=snp_only)
+		columns, data = ctx.variable_sites(item.rows, snp_only=snp_only)
+		assert ctx.variable_sites_blocks == [(0, 50), (50, 50), (100, 50), (150, GROUP_ITEM_ROWS - 150)]
+		assert np.array_equal(columns, want_columns) and np.array_equal(data, want_bytes)
+		check_device(ctx, item.rows, want_columns, want_bytes, 0, snp_only, "device form in slices, %d rows a group" % per_group)
+
+
 def test_sinks(v2m, ctx):
 	"""A sink that returns non-zero gives V2M_ERR_SINK (and the other sink is not called afterwards); NULL sinks are accepted."""
 	from vcf2multialign_amd import _native as N
@@ -475,6 +511,8 @@ CHECKED_CORPUS = [
 	"tests/test_gpu_variable_sites.py::test_exact_pitch_and_no_columns",
 	"tests/test_gpu_variable_sites.py::test_too_small_a_pitch",
 	"tests/test_gpu_variable_sites.py::test_row_slices",
+	"tests/test_gpu_variable_sites.py::test_row_groups_of_the_gather",
+	"tests/test_gpu_variable_sites.py::test_row_groups_of_the_gather_in_slices",
 	"tests/test_gpu_variable_sites.py::test_sinks",
 	"tests/test_gpu_variable_sites.py::test_the_views_are_left_as_they_were",
 	"tests/test_gpu_variable_sites.py::test_reference_fixtures",

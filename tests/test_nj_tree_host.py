@@ -91,9 +91,9 @@ def test_the_six_leaf_tree_puts_the_joined_slots_everywhere():
 # ---- reach: what the corpus holds --------------------------------------------------------------------------------------------------------------
 
 def test_the_corpus_reaches_the_counts_it_names():
-	W, B = M.kernel_constants()
+	W, B, J = M.kernel_constants()
 	from vcf2multialign_amd import _native as N
-	assert (W, B) == (N.NJ_ROWS_PER_GROUP, N.NJ_JOIN_THREADS)
+	assert (W, B, J) == (N.NJ_ROWS_PER_GROUP, N.NJ_JOIN_THREADS, N.NJ_JOIN_BATCH)
 	by_n = {item.n for item in M.corpus()}
 	assert {3, 4, 5, W - 1, W, W + 1, B - 1, B, B + 1, 2 * B + 1} <= by_n and max(by_n) == 2 * B + 1
 	names = [item.name for item in M.corpus()]
@@ -115,6 +115,54 @@ def graph_items_hold_what_the_issue_names():
 	assert any(PM.PLOIDY_MAX in [r for r in item.rows if not isinstance(r, list)] for item in items)
 	assert any(len({repr(r) for r in item.rows}) < len(item.rows) for item in items)      # repeated rows
 	return True
+
+
+# ---- beyond one batch of the join kernel ---------------------------------------------------------------------------------------------------------
+
+def replay_slots(nodes, n):
+	"""Per join of the records, in order: (r, p, q) -- the live slots before it and the two joined slots, p < q -- by the library's rule
+	for the slots: the new node takes the lower slot, the taxon of the last live slot moves into the other."""
+	slot_of = {k: k for k in range(n)}
+	taxon_in = list(range(n))
+	out = []
+	for t in range(n - 3):
+		r = n - t
+		sa, sb = slot_of.pop(int(nodes["a"][t])), slot_of.pop(int(nodes["b"][t]))
+		p, q, last = min(sa, sb), max(sa, sb), r - 1
+		assert q <= last
+		out.append((r, p, q))
+		taxon_in[p] = n + t
+		slot_of[n + t] = p
+		if q != last:
+			taxon_in[q] = taxon_in[last]
+			slot_of[taxon_in[q]] = q
+	assert sorted(slot_of.values()) == [0, 1, 2]
+	return out
+
+
+def test_the_join_batch_items_fill_a_batch_and_pass_it():
+	"""nj_join_kernel takes the live slots J B at a time, slot e B + lane element e of a lane's batch.  The three sizes, the
+	restatement against the model at each, and on the largest the joins the GPU test is there for: in the second trip slots of the
+	first trip are updated and moved into, and a slot of the second trip is joined."""
+	from vcf2multialign_amd import host
+	_, B, J = M.kernel_constants()
+	items = M.join_batch_items()
+	assert [item.n for item in items] == [(J - 1) * B + 1, J * B, J * B + 64] == [769, 1024, 1088]
+	assert not {item.name for item in items} & {item.name for item in M.corpus()}
+	for item in items:
+		assert item.d.dtype == np.uint32 and np.array_equal(item.d, item.d.T) and not np.diag(item.d).any(), item.name
+		assert host.nj_tree_cpu(item.d).tobytes() == M.expected(item.name).tobytes(), item.name
+	large = items[-1]
+	joins = replay_slots(M.expected(large.name), large.n)
+	second_trip = [(r, p, q) for r, p, q in joins if r > J * B]
+	assert len(second_trip) == 64
+	both_below = sum(1 for r, p, q in second_trip if q < J * B and q != r - 1)          # every lane of the second trip updates column p and moves into column q
+	one_above = sum(1 for r, p, q in second_trip if q >= J * B)
+	last_element = [(r, p, q) for r, p, q in joins if J * B >= r > (J - 1) * B]
+	last_above = sum(1 for r, p, q in last_element if q >= (J - 1) * B)
+	print("joins with r > J B: %d with both slots below J B and q not the last, %d with a slot at or above J B; with J B >= r > (J - 1) B: %d with a slot at or above (J - 1) B"
+		% (both_below, one_above, last_above))
+	assert both_below >= 1 and one_above >= 1 and len(last_element) == B and last_above >= 1
 
 
 def test_every_step_of_the_equal_matrix_is_a_full_tie():

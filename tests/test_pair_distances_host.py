@@ -130,6 +130,82 @@ def test_the_corpus_reaches_the_counts_it_names():
 	assert any(not site[b:e].any() for b, e in ws) and any(site[b:e].any() and not site[b] and not site[e - 1] for b, e in ws)
 
 
+# ---- reach: the rows that all differ ---------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def distinct():
+	"""Per distinct item: (item, the class matrix, both distance matrices)."""
+	out = []
+	for item in PM.distinct_items():
+		cls = PM.classes(CM.matrix(item.g, item.rows))
+		out.append((item, cls, PM.distances(cls), PM.distances(cls, acgt_only=True)))
+	return out
+
+
+def conjugated(d, perm):
+	"""d with rows and columns taken through perm: what a kernel gives that takes row perm[i] for row i throughout."""
+	return d[np.ix_(perm, perm)]
+
+
+def near_miss_permutations(n):
+	"""(name, perm) over n rows, each the identity beyond the full tiles: the row mix-ups a kernel can make that a corpus of period 16
+	cannot see, and two of a shorter reach."""
+	T, _ = PM.kernel_constants()
+	full = n // T * T
+	i = np.arange(n)
+	out = []
+	for bit in (1, 2, 16, 32):                                       # neighbouring rows, a lane's pair for its other pair, a row group for the next, the halves pair_row() splits a tile into
+		out.append(("i ^ %d" % bit, np.where(i < full, i ^ bit, i)))
+	for a, b in ((0, 1), (1, 2)):                                    # tile a taken for tile b and back
+		p = i.copy()
+		p[a * T:(a + 1) * T], p[b * T:(b + 1) * T] = i[b * T:(b + 1) * T], i[a * T:(a + 1) * T]
+		out.append(("tiles %d and %d exchanged" % (a, b), p))
+	out.append(("shifted by a row group of 16", np.where(i < full, (i + 16) % full, i)))
+	for name, p in out:
+		assert sorted(p.tolist()) == list(range(n)) and (p != i).any(), name
+	return out
+
+
+def test_the_distinct_rows_all_differ(distinct):
+	T, C_ = PM.kernel_constants()
+	import nj_tree_model
+	_, B, J = nj_tree_model.kernel_constants()
+	assert [len(item.rows) for item, *_ in distinct] == [3 * T + 1, 8 * T + 1, J * B + 64] == [193, 513, 1088]
+	assert [(len(item.rows) + T - 1) // T for item, *_ in distinct] == [4, 9, 17]            # tiles: 10, 45 and 153 tile pairs
+	for item, cls, d_all, d_acgt in distinct:
+		n = len(item.rows)
+		assert len(np.unique(cls, axis=0)) == n, item.name
+		for d in (d_all, d_acgt):
+			assert len(np.unique(d, axis=0)) == n, item.name
+			assert np.array_equal(d, d.T) and (np.diag(d) == 0).all(), item.name
+		assert d_all[~np.eye(n, dtype=bool)].all() and not np.array_equal(d_all, d_acgt), item.name
+		assert item.rows[0] == PM.PLOIDY_MAX and 1 not in item.rows and sum(isinstance(r, list) for r in item.rows) == 3, item.name
+	# the 3 T + 1 item lies over two chunks of sites and five more (the sites of the row-group tests)
+	item = PM.distinct_item(3 * T + 1)
+	assert PM.expected(item.g, item.rows)[1] == 2 * 64 * C_ + 5 == PM.variable_columns(item.g)
+	assert 50 <= PM.expected(distinct[2][0].g, distinct[2][0].rows)[1] <= 70
+
+
+def test_the_distinct_rows_tell_the_row_mix_ups_apart(distinct):
+	"""Conjugating the expected matrix by each near-miss permutation changes it, under both definitions -- while the matrix of
+	row_count_rows(3 T + 1), whose rows repeat with period 16, is the same bit for bit under i ^ 16 and i ^ 32: why these items exist."""
+	T, _ = PM.kernel_constants()
+	for item, cls, d_all, d_acgt in distinct[:2]:
+		n = len(item.rows)
+		for name, perm in near_miss_permutations(n):
+			for d in (d_all, d_acgt):
+				assert not np.array_equal(conjugated(d, perm), d), (item.name, name)
+	n = 3 * T + 1
+	rows = PM.row_count_rows(n)
+	cls = PM.classes(CM.matrix(PM.row_count_graph(), rows))
+	blind = dict(near_miss_permutations(n))
+	for acgt in (False, True):
+		d = PM.distances(cls, acgt)
+		for name in ("i ^ 16", "i ^ 32", "tiles 1 and 2 exchanged"):
+			assert np.array_equal(conjugated(d, blind[name]), d), name
+		assert not np.array_equal(conjugated(d, blind["i ^ 1"]), d)
+
+
 # ---- the text ------------------------------------------------------------------------------------------------------------------------------
 
 def test_text():
@@ -228,6 +304,10 @@ def test_the_site_split_rule_the_gpu_test_assumes():
 	assert "parts((chunks + per_part - 1) / per_part)" in library
 	assert library.count('env_u64("V2M_PAIR_DISTANCES_PARTS"') == 1          # read once per call
 	assert "V2M_PAIR_DISTANCES_PARTS" in _header()
+	# the rows of a row group of pack_sites_kernel: the rule, and the knob that replaces it, read once per call
+	assert "forced_site_group(forced_site_rows, std::max<u64>({16, (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}), nr)" in library
+	assert library.count('u64 const forced_site_rows(env_u64("V2M_SITE_ROWS_PER_GROUP", 0));') == 1
+	assert "return forced ? std::max<u64>(forced, (n + 65534) / 65535) : rule;" in library
 	with open(PM.DISTANCE_KERNELS_HPP) as f:
 		kernel = f.read()
 	assert "n_chunks - chunk_begin < chunks_per_part ? n_chunks : chunk_begin + chunks_per_part" in kernel

@@ -291,6 +291,12 @@ def test_the_kernels_are_in_the_library_source():
 	assert library.index('#include "site_kernels.hpp"') < library.index('#include "ld_kernels.hpp"')
 	# the band's tiles per strip, which the corpus' window sizes are chosen for
 	assert "(u64(prm.window_sites) + v2m::kLdTile - 1) / v2m::kLdTile + 1" in library
+	# the words of a row group: the rule, and the knob tests/test_gpu_site_ld.py sets, read once per call
+	assert "forced_site_group(forced_words, std::max<u64>(1, (words + want_groups - 1) / want_groups), words)" in library
+	assert library.count('env_u64("V2M_SITE_LD_WORDS_PER_GROUP"') == 1
+	# the six-word item of the groups holds what its name says
+	item = LM.row_words_item()
+	assert len(item.rows) == 64 * 5 + 7 and len(LM.expected(item)[0]) == T + 1 and len(LM.expected(item)[1]) > 0
 	from vcf2multialign_amd import build
 	assert LM.LD_KERNELS_HPP in build.deps("HIP_DEPS")
 

@@ -214,6 +214,9 @@ def test_the_kernels_are_in_the_library_source():
 	assert library.index('#include "distance_kernels.hpp"') < library.index('#include "site_kernels.hpp"')
 	# the row-group rule the corpus' row counts are chosen for
 	assert "std::max<u64>({u64(v2m::kGatherMinGroupRows), (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535})" in library
+	# and the knob that replaces it in tests/test_gpu_variable_sites.py, read once per call in either form
+	assert "forced_site_group(forced_rows, std::max<u64>({u64(v2m::kGatherMinGroupRows)," in library
+	assert library.count('u64 const forced_rows(env_u64("V2M_SITE_ROWS_PER_GROUP", 0));') == 2
 	from vcf2multialign_amd import build
 	assert VM.SITE_KERNELS_HPP in build.deps("HIP_DEPS")
 

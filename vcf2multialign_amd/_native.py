@@ -62,11 +62,13 @@ SITE_LD_MAX_ROWS = 32768
 LD_TILE = 64
 LD_CHUNK_WORDS = 8
 # v2m_nj_tree[_of_distances]: the id that is none, the limit, and csrc/nj_kernels.hpp's kNjRowsPerGroup (rows per workgroup of
-# nj_rowmin_kernel) and kNjJoinThreads (nj_join_kernel's one workgroup); tests/test_nj_tree_host.py holds them to the sources
+# nj_rowmin_kernel), kNjJoinThreads (nj_join_kernel's one workgroup) and kNjJoinBatch (the live slots a lane of it has in flight);
+# tests/test_nj_tree_host.py holds them to the sources
 NJ_NONE = 0xFFFFFFFF
 NJ_MAX_ROWS = 32768
 NJ_ROWS_PER_GROUP = 8
 NJ_JOIN_THREADS = 256
+NJ_JOIN_BATCH = 4
 # v2m_pair_distances_weighted, v2m_bootstrap_distances, v2m_nj_bootstrap: the limit, and csrc/bootstrap_kernels.hpp's kBootDrawThreads
 # (draws per workgroup of bootstrap_weights_kernel) and kBootSlices (bit slices of a weight); tests/test_nj_bootstrap_host.py holds them
 # to the sources

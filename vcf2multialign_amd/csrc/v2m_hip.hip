@@ -3166,6 +3166,15 @@ u64 column_counts_rows_per_group(v2m_ctx const *ctx, u64 n_rows, u64 column_bloc
 	return std::max<u64>({1, forced ? forced : spread, (n_rows + 65534) / 65535});   // (the grid's y)
 }
 
+// The kernels that walk a slice at its sites split its rows by the same rule (pack_sites_kernel and gather_sites_kernel: groups of at
+// least 16 rows; ld_pack_kernel: of at least one 64-row word).  V2M_SITE_ROWS_PER_GROUP and V2M_SITE_LD_WORDS_PER_GROUP override it as
+// V2M_COLUMN_COUNTS_ROWS_PER_GROUP does above, the floor included (test knobs, read once per call: the kernels take any value >= 1);
+// the bound of the grid's y still holds.
+u64 forced_site_group(u64 forced, u64 rule, u64 n)
+{
+	return forced ? std::max<u64>(forced, (n + 65534) / 65535) : rule;
+}
+
 // Adds the counts of the batch's rows over the view in force to the table: the batch in row slices through one device slot, per slice
 // the aligned splice and column_counts_kernel.  Queues only; the caller synchronises.
 // Staged form: when the call takes several slices and a full slice is one row group of at most kCountRun rows -- whole rows of a hundred
@@ -3480,6 +3489,7 @@ int pair_matrices_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, pair_j
 	u64 const n_passes((n_chunks + pass_chunks - 1) / pass_chunks);
 	out.n_passes = n_passes;
 	u64 const forced_parts(env_u64("V2M_PAIR_DISTANCES_PARTS", 0));
+	u64 const forced_site_rows(env_u64("V2M_SITE_ROWS_PER_GROUP", 0));
 	bool const atomics(n_passes > 1 || pair_chunks_per_part(ctx, tile_pairs, pass_chunks, forced_parts) < pass_chunks);
 	bool const resident(1 == n_passes);
 	slice_plan const p(plan_slices(ctx, n, false));
@@ -3515,7 +3525,7 @@ int pair_matrices_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, pair_j
 			if (int const e = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch)) return e;
 			// row groups: with few site blocks, as many as bring the launch to about four workgroups per compute unit, of at least 16 rows
 			u64 const want_groups((4 * u64(ctx->n_cus) + pack_blocks - 1) / pack_blocks);
-			u64 const per_group(std::max<u64>({16, (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}));
+			u64 const per_group(forced_site_group(forced_site_rows, std::max<u64>({16, (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}), nr));
 			u64 const groups((nr + per_group - 1) / per_group);
 			hipLaunchKernelGGL(v2m::pack_sites_kernel, dim3(unsigned(pack_blocks), unsigned(groups)), dim3(v2m::kPackThreads), 0, ctx->stream,
 				d_rows, p.pitch, u32(nr), u32(per_group), u32(r0), sites, site_begin, site_end, planes, n_pad);
@@ -3714,8 +3724,8 @@ int variable_sites_select(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, st
 }
 
 // Stage (2) for rows [r0, r1) of the batch: the aligned splice into ring slot 0, then gather_sites_kernel into out, where batch row r
-// lands at out + (r - out_first_row) * out_pitch.  Queues only.
-int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_plan const &p, u64 r0, u64 r1, u64 V, char *out, u64 out_first_row, u64 out_pitch, stage_times &times)
+// lands at out + (r - out_first_row) * out_pitch.  forced_rows: V2M_SITE_ROWS_PER_GROUP as the call read it (0: the rule).  Queues only.
+int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_plan const &p, u64 r0, u64 r1, u64 V, char *out, u64 out_first_row, u64 out_pitch, u64 forced_rows, stage_times &times)
 {
 	u64 const nr(r1 - r0);
 	{
@@ -3730,7 +3740,7 @@ int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_p
 	u64 const block_sites(u64(v2m::kGatherThreads) * v2m::kGatherSites);
 	u64 const site_blocks((V + block_sites - 1) / block_sites);
 	u64 const want_groups((4 * u64(ctx->n_cus) + site_blocks - 1) / site_blocks);
-	u64 const per_group(std::max<u64>({u64(v2m::kGatherMinGroupRows), (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}));
+	u64 const per_group(forced_site_group(forced_rows, std::max<u64>({u64(v2m::kGatherMinGroupRows), (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}), nr));
 	u64 const groups((nr + per_group - 1) / per_group);
 	hipLaunchKernelGGL(v2m::gather_sites_kernel, dim3(unsigned(site_blocks), unsigned(groups)), dim3(v2m::kGatherThreads), 0, ctx->stream,
 		d_rows, p.pitch, u32(nr), u32(per_group), r0 - out_first_row, ctx->d_site_columns.as<u32>(), V, out, out_pitch);
@@ -3773,8 +3783,9 @@ int v2m_variable_sites_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t 
 		if (d_columns && hipSuccess != hipMemcpyAsync(d_columns, ctx->d_site_columns.p, V * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream))
 			rc = fail(ctx, V2M_ERR_HIP, "variable sites: the site list could not be copied");
 		slice_plan const p(plan_slices(ctx, n, false));
+		u64 const forced_rows(env_u64("V2M_SITE_ROWS_PER_GROUP", 0));
 		for (u64 s(0); s < p.n_slices && V2M_OK == rc; ++s)
-			rc = variable_sites_gather_slice(ctx, rows, p, s * p.rows_per_slice, std::min(n, (s + 1) * p.rows_per_slice), V, static_cast<char *>(d_bytes), 0, pitch, times);
+			rc = variable_sites_gather_slice(ctx, rows, p, s * p.rows_per_slice, std::min(n, (s + 1) * p.rows_per_slice), V, static_cast<char *>(d_bytes), 0, pitch, forced_rows, times);
 	}
 	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
 	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
@@ -3820,6 +3831,7 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 	// while slice k + 1 is spliced and gathered.  Both buffers of slice k are free again when slice k - 2 has been handed over,
 	// which waits for its copy on the host before slice k - 1 is queued.
 	slice_plan const p(plan_slices(ctx, n, false));
+	u64 const forced_rows(env_u64("V2M_SITE_ROWS_PER_GROUP", 0));
 	u64 const out_pitch((V + 15) & ~u64(15)), slice_bytes(p.rows_per_slice * out_pitch);
 	if (int const rc = ensure_host_slots(ctx, std::min<u64>(2, p.n_slices), slice_bytes)) return finish(rc);
 	auto const first_row([&](u64 s) { return s * p.rows_per_slice; });
@@ -3833,7 +3845,7 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 			if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "variable sites: %llu bytes of sites: %s", (unsigned long long) slice_bytes, hipGetErrorString(st));
 		}
 		V2M_POISON_HOST(slot.host.p, slice_bytes);
-		if (int const rc = variable_sites_gather_slice(ctx, rows, p, r0, r1, V, ctx->d_site_bytes[b].as<char>(), r0, out_pitch, times)) return rc;
+		if (int const rc = variable_sites_gather_slice(ctx, rows, p, r0, r1, V, ctx->d_site_bytes[b].as<char>(), r0, out_pitch, forced_rows, times)) return rc;
 		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
 		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
 		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, ctx->d_site_bytes[b].p, (r1 - r0) * out_pitch, hipMemcpyDeviceToHost, ctx->copy_stream));
@@ -3993,6 +4005,7 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 
 	// (2) the planes: zeroed, then ORed into slice by slice
 	slice_plan const p(plan_slices(ctx, n, false));
+	u64 const forced_words(env_u64("V2M_SITE_LD_WORDS_PER_GROUP", 0));
 	times.begin(stage_times::pack);
 	if (hipSuccess != hipMemsetAsync(planes, 0, plane_bytes, ctx->stream)) return finish(fail(ctx, V2M_ERR_HIP, "site LD: the planes could not be zeroed"));
 	u64 const pack_blocks((V + v2m::kLdPackThreads - 1) / v2m::kLdPackThreads);
@@ -4004,7 +4017,7 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 		// word-aligned row groups: with few site blocks, as many as bring the launch to about four workgroups per compute unit
 		u64 const words((r1 - 1) / 64 - r0 / 64 + 1);
 		u64 const want_groups((4 * u64(ctx->n_cus) + pack_blocks - 1) / pack_blocks);
-		u64 const per_group(std::max<u64>(1, (words + want_groups - 1) / want_groups));
+		u64 const per_group(forced_site_group(forced_words, std::max<u64>(1, (words + want_groups - 1) / want_groups), words));
 		u64 const groups((words + per_group - 1) / per_group);
 		hipLaunchKernelGGL(v2m::ld_pack_kernel, dim3(unsigned(pack_blocks), unsigned(groups)), dim3(v2m::kLdPackThreads), 0, ctx->stream,
 			d_rows, p.pitch, u32(nr), u32(per_group), u32(r0), sites, records, V, planes, v_pad);
