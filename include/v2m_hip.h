@@ -804,6 +804,83 @@ int v2m_nj_bootstrap(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags /* 
                      v2m_nj_node *nodes /* host, n_rows - 2 */, uint32_t *support /* host, n_rows - 3 */,
                      v2m_nj_node *replicate_nodes /* NULL, or host, n_replicates x (n_rows - 2) */, v2m_nj_bootstrap_info *info /* may be NULL */);
 
+/* ---- parsimony ----------------------------------------------------------------------------------
+ *
+ * What changed where on a tree of the batch's rows: Fitch's parsimony (Fitch 1971) of every SNP site on the join records of a tree,
+ * in integers throughout, so that every result has exactly one value.
+ *
+ * Tree.  n >= 3 leaves 0 ... n - 1 and n - 2 records of v2m_nj_node, as v2m_nj_tree writes them; any records that form a tree are
+ * taken, they need not come from neighbour joining.  Record t makes node n + t from children with smaller ids, a < b (< c); only the
+ * last record has a c; every id 0 ... 2 n - 4 is a child exactly once.  Anything else is V2M_ERR_INVALID_ARGUMENT, decided on the host
+ * before any device work.  The lengths are ignored.  The root is the last node, 2 n - 3; every other node x has one branch, to its
+ * parent.
+ *
+ * States.  A leaf's set at a site is a 4-bit mask: 1 << class for the column counts' classes 0-3 (A, C, G, T, either case), and 0xF
+ * -- missing, compatible with anything -- for every other byte (N, gap, other, and the 0 padding of the gather).
+ *
+ * Up, per site, the records in order: X = S(a) & S(b); when that is empty, X = S(a) | S(b) and steps += 1.  The last record only:
+ * Y = X & S(c); when Y is empty, steps += 1 and X stays, else X = Y.  S(n + t) = X.  present = the OR of the masks of the leaves
+ * that are not missing.
+ * Down, per site: state(root) = the lowest set bit of S(root).  Then the records from the last to the first, within a record the
+ * children in the order a, b, c: state(x) = state(parent) when that bit is in S(x), else the lowest set bit of S(x).  Where state(x)
+ * differs from the parent's, that is one mutation (site, x, from, to), from and to as classes 0-3.  A missing leaf never carries one.
+ *
+ * Results.  Per site, steps and present.  Per node x < 2 n - 3, branch_changes[x]: the mutations on its branch, summed over the
+ * sites.  The mutations, ascending by site and within a site in the order of the down pass.  The mutations of a site number exactly
+ * its steps, which is the least number of changes any assignment of states needs; the sum of branch_changes is the sum of steps.
+ * steps does not depend on which node is the root; the mutations' branches and directions do: they are those of the root 2 n - 3.
+ *
+ * v2m_parsimony_of_sites (device form): d_bytes is u8[n][pitch] in device memory as v2m_variable_sites_device writes it, 16-byte
+ * aligned with pitch % 16 == 0 and pitch >= V; only the first V bytes of a row count, and nothing is modified.  No graph is needed.
+ * nodes is host memory.  d_sites (v2m_parsimony_site[V]), d_branch_changes (u32[2 n - 3]) and d_mutations (v2m_tree_mutation[capacity];
+ * may be NULL with capacity 0, to ask for everything but the list) are device memory, 16-byte aligned.  *n_mutations is always set
+ * when the passes ran.  When the mutations exceed a capacity that is not 0 the call fails with V2M_ERR_INVALID_ARGUMENT and a message
+ * that names their number; d_sites is written, the list and d_branch_changes are not.  The sets are context-owned: (n - 2) * pitch bytes.
+ * v2m_tree_parsimony (host form): the sites are those of v2m_variable_sites with V2M_SITES_SNP over the view in force -- no other
+ * column can have steps > 0 -- for the rows of the batch as the leaves, row r leaf r.  flags is 0.  The sites are cut into ranges
+ * that start at multiples of 256 sites and whose leaf bytes and sets, 2 n - 2 bytes a site, fit V2M_PARSIMONY_BYTES (environment,
+ * read per call; default 16 GiB, at least 256 sites); per range the second pass of the variable sites over the row slices, the two
+ * passes above, and the range's records and mutations on their way to the host on the copy stream while the next range runs.
+ * branch_changes (host, 2 n - 3; may be NULL) accumulates over the ranges.  sites_sink is called once with all V records (column
+ * absolute), after the last range; mutations_sink receives blocks of mutations in order, site indices into those V records.  Both
+ * get memory valid during the call only, neither is ever called with n = 0, either may be NULL; a non-zero return is V2M_ERR_SINK.
+ * info, which may be NULL, receives V, L, the mutations (the tree's length), the ranges and -- while v2m_profile_enable is on, else
+ * 0 -- the stream time of the three stages.  With V == 0 every branch count is 0 and no sink is called.
+ * Limits and errors, worded and ordered as for v2m_variable_sites and v2m_nj_tree: n == 0 returns V2M_OK and touches nothing; n == 1
+ * and n == 2 are V2M_ERR_INVALID_ARGUMENT; n > V2M_NJ_MAX_ROWS, V >= 2^32 and a call whose mutations reach 2^32 (the number is in the
+ * message) are V2M_ERR_UNSUPPORTED.  Both calls are synchronous; the column window, the window set and what v2m_column_counts
+ * returns afterwards are left as they were.
+ * How (csrc/parsimony_kernels.hpp).  A lane owns four adjacent sites for the whole tree, a mask per byte of one u32, and the rule
+ * above is a few byte-parallel operations on it.  fitch_up_kernel walks the records, classifies leaf bytes in flight, writes the
+ * sets, the site records and its workgroup's steps; scan_tile_counts_kernel turns those into offsets; fitch_down_kernel<false> walks
+ * the records backwards, writes states over the sets and adds every branch's changes with one integer atomicAdd per wave;
+ * fitch_down_kernel<true> also writes each mutation at its site's offset plus its rank: the order above with no sort.  No
+ * V2M_KERNEL_* ids: V2M_KERNEL_LIMIT keeps its value. */
+typedef struct { uint32_t steps, present; } v2m_parsimony_site;               /* 8 bytes: device form */
+typedef struct { uint64_t column; uint32_t steps, present; } v2m_tree_site;   /* 16 bytes: host form, column absolute */
+typedef struct { uint32_t site, node, from, to; } v2m_tree_mutation;          /* 16 bytes */
+
+typedef struct {
+	uint64_t n_sites;      /* V: the SNP columns of the view for this batch */
+	uint64_t n_columns;    /* L */
+	uint64_t n_mutations;  /* the tree's length: the sum of steps */
+	uint64_t n_ranges;     /* site ranges (0 when there was no site) */
+	double counts_ms;      /* column counts + site selection: stream time elapsed over the stage */
+	double gather_ms;      /* splices of the second pass + gather_sites_kernel, summed over the ranges */
+	double parsimony_ms;   /* fitch_up_kernel, the scan, fitch_down_kernel: likewise */
+} v2m_tree_parsimony_info;    /* 56 bytes */
+
+typedef int (*v2m_tree_sites_sink_fn)(void *user, const v2m_tree_site *sites, uint64_t n);
+typedef int (*v2m_tree_mutations_sink_fn)(void *user, const v2m_tree_mutation *mutations, uint64_t n);
+
+int v2m_parsimony_of_sites(v2m_ctx *ctx, const void *d_bytes, uint64_t n, uint64_t n_sites, uint64_t pitch, const v2m_nj_node *nodes /* host, n - 2 */,
+                           void *d_sites, void *d_branch_changes /* u32[2 n - 3] */, void *d_mutations /* may be NULL with capacity 0 */, uint64_t capacity,
+                           uint64_t *n_mutations);
+
+int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_node *nodes /* host, n_rows - 2 */, uint32_t flags /* 0 */,
+                       uint32_t *branch_changes /* host, 2 n_rows - 3, or NULL */, v2m_tree_sites_sink_fn sites_sink /* may be NULL */,
+                       v2m_tree_mutations_sink_fn mutations_sink /* may be NULL */, void *user, v2m_tree_parsimony_info *info /* may be NULL */);
+
 /* ---- founder search: the chunk walks ---------------------------------- */
 
 /* The edge-by-edge part of find_initial_cut_positions_lambda_min (libvcf2multialign/find_cut_positions.cc:126-176): the pBWT

@@ -75,6 +75,11 @@ NJ_JOIN_BATCH = 4
 NJ_BOOTSTRAP_MAX_REPLICATES = 100000
 BOOT_DRAW_THREADS = 256
 BOOT_SLICES = 32
+# v2m_parsimony_of_sites, v2m_tree_parsimony: csrc/parsimony_kernels.hpp's kFitchSites (sites a lane owns), kFitchThreads (lanes of a
+# workgroup) and kFitchBatch (records whose leaf rows a lane reads ahead); tests/test_tree_parsimony_host.py holds them to the sources
+FITCH_SITES = 4
+FITCH_THREADS = 256
+FITCH_BATCH = 4
 # csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
 # kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
 DISTINCT_CHUNK_BYTES = 8192
@@ -161,6 +166,15 @@ class NjBootstrapInfo(C.Structure):   # v2m_nj_bootstrap_info
 		("trees_ms", C.c_double)]
 
 
+class TreeParsimonyInfo(C.Structure):   # v2m_tree_parsimony_info
+	_fields_ = [("n_sites", C.c_uint64), ("n_columns", C.c_uint64), ("n_mutations", C.c_uint64), ("n_ranges", C.c_uint64),
+		("counts_ms", C.c_double), ("gather_ms", C.c_double), ("parsimony_ms", C.c_double)]
+
+
+PARSIMONY_SITE_DTYPE = [("steps", "<u4"), ("present", "<u4")]   # v2m_parsimony_site
+TREE_SITE_DTYPE = [("column", "<u8"), ("steps", "<u4"), ("present", "<u4")]   # v2m_tree_site
+TREE_MUTATION_DTYPE = [("site", "<u4"), ("node", "<u4"), ("from", "<u4"), ("to", "<u4")]   # v2m_tree_mutation
+TREE_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_tree_sites_sink_fn, v2m_tree_mutations_sink_fn
 NJ_NODE_DTYPE = [("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("reserved", "<u4"), ("len_a", "<f8"), ("len_b", "<f8"), ("len_c", "<f8")]   # v2m_nj_node
 SITE_COLUMNS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)   # v2m_site_columns_sink_fn
 SITE_ROWS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64)   # v2m_site_rows_sink_fn
@@ -212,6 +226,8 @@ SIGNATURES = {
 	"v2m_pair_distances_weighted": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(PairDistancesInfo)]),
 	"v2m_bootstrap_distances": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(PairDistancesInfo)]),
 	"v2m_nj_bootstrap": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NjBootstrapInfo)]),
+	"v2m_parsimony_of_sites": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+	"v2m_tree_parsimony": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_void_p, C.c_uint32, C.c_void_p, TREE_SINK_FN, TREE_SINK_FN, C.c_void_p, C.POINTER(TreeParsimonyInfo)]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

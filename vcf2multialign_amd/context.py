@@ -683,6 +683,82 @@ class Context:
 		self._check(self._lib.v2m_nj_tree_of_distances(self._h, ptr, n, int(pitch), nodes.ctypes.data, C.byref(record)))
 		return self._nj_result(n, nodes, record, info)
 
+	def tree_parsimony(self, rows, nodes, info=False, want_sites=True, want_mutations=True, want_branch_changes=True):
+		"""v2m_tree_parsimony: Fitch's parsimony of the SNP sites of the view in force on the tree of `nodes` (n - 2 v2m_nj_node records
+		over the batch's rows as leaves, as nj_tree returns them): (sites, branch_changes, mutations) -- structured arrays of
+		v2m_tree_site (column, steps, present) and v2m_tree_mutation (site, node, from, to) records and np.uint32[2 n - 3].  With
+		info=True: (..., dict of v2m_tree_parsimony_info's fields).  want_* = False pass a NULL sink or pointer (an empty array comes
+		back).  self.tree_parsimony_blocks: the sizes of the blocks the mutations arrived in."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		n = int(rows.struct.n_rows)
+		nodes = np.ascontiguousarray(nodes, dtype=np.dtype(N.NJ_NODE_DTYPE))
+		sites, blocks, error = [], [], []
+
+		def _sites(_user, records, count):
+			try:
+				if count == 0:
+					raise AssertionError("a call with no site")
+				sites.append(_records(records, count, N.TREE_SITE_DTYPE))
+				return 0
+			except BaseException as e:  # propagate through the C frame as V2M_ERR_SINK
+				error.append(e)
+				return 1
+
+		def _mutations(_user, records, count):
+			try:
+				if count == 0:
+					raise AssertionError("a block of no mutations")
+				if sites:
+					raise AssertionError("a mutation after the sites")
+				blocks.append(_records(records, count, N.TREE_MUTATION_DTYPE))
+				return 0
+			except BaseException as e:
+				error.append(e)
+				return 1
+
+		def _records(ptr, count, dtype):
+			out = np.empty(count, dtype=np.dtype(dtype))                     # (a block of mutations may hold more than 2^31 bytes)
+			C.memmove(out.ctypes.data, ptr, out.nbytes)
+			return out
+
+		branch_changes = np.zeros(max(1, 2 * n - 3), dtype=np.uint32)
+		record = N.TreeParsimonyInfo()
+		no_sink = C.cast(None, N.TREE_SINK_FN)
+		rc = self._lib.v2m_tree_parsimony(self._h, C.byref(rows.struct), nodes.ctypes.data if len(nodes) else None, 0,
+			branch_changes.ctypes.data if want_branch_changes else None, N.TREE_SINK_FN(_sites) if want_sites else no_sink,
+			N.TREE_SINK_FN(_mutations) if want_mutations else no_sink, None, C.byref(record))
+		if error:
+			raise error[0]
+		self._check(rc)
+		if len(sites) > 1:
+			raise AssertionError("the sites arrived %d times" % len(sites))
+		self.tree_parsimony_blocks = [len(b) for b in blocks]
+		result = [sites[0] if sites else np.zeros(0, dtype=np.dtype(N.TREE_SITE_DTYPE)),
+			branch_changes[:2 * n - 3] if n >= 3 and want_branch_changes else branch_changes[:0],
+			np.concatenate(blocks) if blocks else np.zeros(0, dtype=np.dtype(N.TREE_MUTATION_DTYPE))]
+		if n == 0:
+			record.n_columns = self.window_length   # (with no rows the call returns before it writes the info)
+		if info:
+			result.append({name: getattr(record, name) for name, _ in N.TreeParsimonyInfo._fields_})
+		return tuple(result)
+
+	def parsimony_of_sites(self, bytes_ptr, n, n_sites, pitch, nodes, sites_ptr, branch_changes_ptr, mutations_ptr=None, capacity=0):
+		"""v2m_parsimony_of_sites: the parsimony of the n_sites sites of the n rows in device memory at `bytes_ptr`, u8[n][pitch] (16-byte
+		aligned, pitch a multiple of 16 and at least n_sites; nothing is written there), on the tree of `nodes` (host, n - 2 records):
+		v2m_parsimony_site[n_sites] to `sites_ptr`, u32[2 n - 3] to `branch_changes_ptr` and the mutations to `mutations_ptr`
+		(v2m_tree_mutation[capacity]; None with capacity 0 asks for everything but the list), all device memory.  Returns the number of
+		mutations; when they exceed a non-zero capacity the call raises (self.parsimony_mutations then holds their number) and has
+		written neither the list nor the branch counts."""
+		nodes = np.ascontiguousarray(nodes, dtype=np.dtype(N.NJ_NODE_DTYPE))
+		n_mutations = C.c_uint64(0)
+		self.parsimony_mutations = None
+		rc = self._lib.v2m_parsimony_of_sites(self._h, bytes_ptr, int(n), int(n_sites), int(pitch), nodes.ctypes.data if len(nodes) else None, sites_ptr, branch_changes_ptr,
+			mutations_ptr, int(capacity), C.byref(n_mutations))
+		self.parsimony_mutations = int(n_mutations.value)
+		self._check(rc)
+		return self.parsimony_mutations
+
 	def bgzf_compress(self, data):
 		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
 		src = bytes(data)

@@ -563,6 +563,70 @@ int64_t v2mh_nj_newick_support_text(v2m_nj_node const *nodes, uint64_t n_leaves,
 	}
 }
 
+// tree_parsimony_cpu() of output.hh (no GPU): the parsimony of the n_sites sites of bytes (u8[n][pitch]) on the tree of the n - 2 records;
+// sites (n_sites), branch_changes (2 n - 3) and, when it fits capacity, mutations (may be NULL with capacity 0) are written.  The number
+// of mutations, or -1 with a message in err for a NULL pointer or records that are no tree.
+int64_t v2mh_tree_parsimony_cpu(unsigned char const *bytes, uint64_t n, uint64_t n_sites, uint64_t pitch, v2m_nj_node const *nodes, v2m_parsimony_site *sites,
+	uint32_t *branch_changes, v2m_tree_mutation *mutations, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		if (!nodes || !branch_changes || ((!bytes || !sites) && n_sites) || (!mutations && capacity)) throw std::invalid_argument("a pointer is NULL");
+		return int64_t(vh::tree_parsimony_cpu(bytes, n, n_sites, pitch, nodes, sites, branch_changes, mutations, capacity));
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
+// nj_newick_parsimony_text() of output.hh (no GPU), handed over as v2mh_nj_newick_text hands over its text; branch_changes holds
+// 2 n_leaves - 3 counts.
+int64_t v2mh_nj_newick_parsimony_text(v2m_nj_node const *nodes, uint64_t n_leaves, char const *const *labels, uint32_t const *branch_changes, char *dst, uint64_t capacity,
+	char *err, size_t errlen)
+{
+	try {
+		if (!nodes || !labels) throw std::runtime_error("nodes or labels is NULL");
+		std::vector<std::string> names;
+		for (uint64_t i(0); i < n_leaves; ++i) names.emplace_back(labels[i]);
+		std::string const text(vh::nj_newick_parsimony_text(nodes, n_leaves, names, branch_changes));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
+// tree_mutations_text() of output.hh (no GPU), handed over likewise; labels are n_leaves NUL-terminated strings.
+int64_t v2mh_tree_mutations_text(v2m_tree_mutation const *mutations, uint64_t n_mutations, v2m_tree_site const *sites, uint64_t n_sites, char const *const *labels, uint64_t n_leaves,
+	uint64_t const *reference_positions, uint64_t const *aligned_positions, uint64_t node_count, char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		if (!labels) throw std::runtime_error("labels is NULL");
+		std::vector<std::string> names;
+		for (uint64_t i(0); i < n_leaves; ++i) names.emplace_back(labels[i]);
+		std::string const text(vh::tree_mutations_text(mutations, n_mutations, sites, n_sites, names, reference_positions, aligned_positions, node_count));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
+// tree_sites_text() of output.hh (no GPU), handed over likewise.
+int64_t v2mh_tree_sites_text(v2m_tree_site const *sites, uint64_t n_sites, uint64_t const *reference_positions, uint64_t const *aligned_positions, uint64_t node_count,
+	char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		std::string const text(vh::tree_sites_text(sites, n_sites, reference_positions, aligned_positions, node_count));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
 // nj_split_support() of csrc/nj_support.hpp (no GPU): support[t], t < n - 3, = the n_replicates trees of replicate_nodes (n - 2 records
 // each) that hold the split of join record t of main_nodes.  0, or -1 for a NULL pointer, n < 3, records that are no tree, or no memory.
 int v2mh_nj_split_support(uint64_t n, v2m_nj_node const *main_nodes, v2m_nj_node const *replicate_nodes, uint64_t n_replicates, uint32_t *support)

@@ -69,6 +69,9 @@ struct options {
 	char const *tree_bootstrap{}, *tree_seed{};   // --tree-bootstrap=B (with --output-tree), --tree-seed=S (with --tree-bootstrap; default 1)
 	char const *output_tree_replicates{};         // --output-tree-replicates=FILE (with --tree-bootstrap): the replicate trees, a Newick line each
 	std::uint32_t tree_replicates{};              // B, or 0: no bootstrap
+	// --output-tree-parsimony=FILE, --output-tree-mutations=FILE, --output-tree-sites=FILE (with --output-tree): Fitch's parsimony of the SNP
+	// sites on that tree, from v2m_tree_parsimony
+	char const *output_tree_parsimony{}, *output_tree_mutations{}, *output_tree_sites{};
 	std::uint64_t tree_seed_value{1};
 	bool all_columns{};                   // --all-columns (with --output-column-counts): every column, not only the variable ones
 	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
@@ -178,6 +181,14 @@ void usage()
 		"      --tree-seed=S                  With --tree-bootstrap: the seed of the draws (0 to 2^64 - 1; default 1)\n"
 		"      --output-tree-replicates=FILE  With --tree-bootstrap: write the replicate trees, one Newick line each (the input of\n"
 		"                                     consense)\n"
+		"      --output-tree-parsimony=FILE   With --output-tree: write the same tree in Newick form with every branch length the number\n"
+		"                                     of changes Fitch's parsimony puts on the branch, over the SNP columns of the alignment\n"
+		"                                     (A, C, G, T; anything else counts as missing), rooted at the trifurcation, and every\n"
+		"                                     internal node labelled node<t> by its join.  Computed on the GPU, in integers\n"
+		"      --output-tree-mutations=FILE   With --output-tree: write those changes, one line each: node (the sequence, or node<t>),\n"
+		"                                     column, reference position (as --output-site-positions writes them), from, to\n"
+		"      --output-tree-sites=FILE       With --output-tree: write one line per SNP column: column, reference position, the letters\n"
+		"                                     present, the steps on the tree, and the homoplasy steps - (letters - 1)\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -383,7 +394,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_output_tree, o_tree_acgt_only, o_tree_bootstrap, o_tree_seed, o_output_tree_replicates, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_output_tree, o_tree_acgt_only, o_tree_bootstrap, o_tree_seed, o_output_tree_replicates, o_output_tree_parsimony, o_output_tree_mutations, o_output_tree_sites, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -400,6 +411,8 @@ int main(int argc, char **argv)
 		{"ld-min-r2", required_argument, nullptr, o_ld_min_r2}, {"ld-min-count", required_argument, nullptr, o_ld_min_count},
 		{"output-tree", required_argument, nullptr, o_output_tree}, {"tree-acgt-only", no_argument, nullptr, o_tree_acgt_only},
 		{"tree-bootstrap", required_argument, nullptr, o_tree_bootstrap}, {"tree-seed", required_argument, nullptr, o_tree_seed}, {"output-tree-replicates", required_argument, nullptr, o_output_tree_replicates},
+		{"output-tree-parsimony", required_argument, nullptr, o_output_tree_parsimony}, {"output-tree-mutations", required_argument, nullptr, o_output_tree_mutations},
+		{"output-tree-sites", required_argument, nullptr, o_output_tree_sites},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -466,6 +479,9 @@ int main(int argc, char **argv)
 			case o_tree_bootstrap: opt.tree_bootstrap = optarg; break;
 			case o_tree_seed: opt.tree_seed = optarg; break;
 			case o_output_tree_replicates: opt.output_tree_replicates = optarg; break;
+			case o_output_tree_parsimony: opt.output_tree_parsimony = optarg; break;
+			case o_output_tree_mutations: opt.output_tree_mutations = optarg; break;
+			case o_output_tree_sites: opt.output_tree_sites = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -523,6 +539,10 @@ int main(int argc, char **argv)
 	if (opt.tree_bootstrap && !opt.output_tree) { std::cerr << "ERROR: --tree-bootstrap requires --output-tree.\n"; return EXIT_FAILURE; }
 	if (opt.tree_seed && !opt.tree_bootstrap) { std::cerr << "ERROR: --tree-seed requires --tree-bootstrap.\n"; return EXIT_FAILURE; }
 	if (opt.output_tree_replicates && !opt.tree_bootstrap) { std::cerr << "ERROR: --output-tree-replicates requires --tree-bootstrap.\n"; return EXIT_FAILURE; }
+	for (auto const &[name, value] : {std::pair<char const *, char const *>{"--output-tree-parsimony", opt.output_tree_parsimony}, {"--output-tree-mutations", opt.output_tree_mutations},
+		{"--output-tree-sites", opt.output_tree_sites}}) {
+		if (value && !opt.output_tree) { std::cerr << "ERROR: " << name << " requires --output-tree.\n"; return EXIT_FAILURE; }
+	}
 	if (opt.tree_bootstrap) {
 		std::uint64_t value(0);
 		if (!parse_count(opt.tree_bootstrap, value) || value < 1 || value > V2M_NJ_BOOTSTRAP_MAX_REPLICATES) {
@@ -836,6 +856,11 @@ int main(int argc, char **argv)
 				std::cerr << "Outputting the tree..." << std::flush;
 				output.output_tree(graph, opt.output_tree, opt.tree_acgt_only, opt.verbose, opt.tree_replicates, opt.tree_seed_value, opt.output_tree_replicates);
 				std::cerr << " Done.\n";
+				if (opt.output_tree_parsimony || opt.output_tree_mutations || opt.output_tree_sites) {
+					std::cerr << "Outputting the parsimony on the tree..." << std::flush;
+					output.output_tree_parsimony(graph, opt.output_tree_parsimony, opt.output_tree_mutations, opt.output_tree_sites, opt.verbose);
+					std::cerr << " Done.\n";
+				}
 			}
 		});
 

@@ -1508,7 +1508,7 @@ void nj_tree_cpu(std::uint32_t const *dist, u64 n, u64 pitch, v2m_nj_node *nodes
 
 
 namespace {
-std::string newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *support);
+std::string newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *support, std::uint32_t const *branch_changes = nullptr);
 }
 
 std::string nj_newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels)
@@ -1530,8 +1530,8 @@ void nj_split_support(u64 n_leaves, v2m_nj_node const *main_nodes, v2m_nj_node c
 }
 
 namespace {
-// support: NULL, or the labels of the join nodes
-std::string newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *support)
+// support: NULL, or the labels of the join nodes; branch_changes: NULL, or the integer lengths by lower node, with every internal node labelled node<t>
+std::string newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *support, std::uint32_t const *branch_changes)
 {
 	u64 const n(n_leaves);
 	if (n < 3) throw std::invalid_argument("a tree has at least 3 leaves");
@@ -1569,10 +1569,14 @@ std::string newick_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std:
 		frame const f(stack.back());
 		v2m_nj_node const &nd(nodes[f.rec]);
 		int const children(f.rec == root ? 3 : 2);
-		if (f.next > 0) append_length(text, 1 == f.next ? nd.len_a : 2 == f.next ? nd.len_b : nd.len_c);   // (of the child just closed)
+		if (f.next > 0) {   // (of the child just closed)
+			if (branch_changes) text += ':' + std::to_string(branch_changes[1 == f.next ? nd.a : 2 == f.next ? nd.b : nd.c]);
+			else append_length(text, 1 == f.next ? nd.len_a : 2 == f.next ? nd.len_b : nd.len_c);
+		}
 		if (f.next == children) {
 			text += ')';
 			if (support && f.rec != root) text += std::to_string(support[f.rec]);
+			if (branch_changes) text += "node" + std::to_string(f.rec);
 			stack.pop_back();
 			continue;
 		}
@@ -1611,6 +1615,7 @@ void output::output_tree(variant_graph const &graph, std::ostream &stream, bool 
 		m_gpu.check(v2m_nj_tree(m_gpu.get(), &batch, acgt_only ? V2M_DIST_ACGT_ONLY : 0, nodes.data(), &info));
 		std::string const text(nj_newick_text(nodes.data(), batch.n_rows, rows.ids));
 		stream.write(text.data(), std::streamsize(text.size()));
+		m_tree_nodes = nodes;
 		if (verbose)
 			std::fprintf(stderr, "Tree: %llu rows, %llu columns, %llu sites, %llu joins.\n", (unsigned long long) batch.n_rows, (unsigned long long) info.n_columns,
 				(unsigned long long) info.n_sites, (unsigned long long) (info.n_nodes - 1));
@@ -1623,6 +1628,7 @@ void output::output_tree(variant_graph const &graph, std::ostream &stream, bool 
 		replicates ? replicate_nodes.data() : nullptr, &info));
 	std::string const text(nj_newick_support_text(nodes.data(), batch.n_rows, rows.ids, support.data()));
 	stream.write(text.data(), std::streamsize(text.size()));
+	m_tree_nodes = nodes;
 	if (replicates) {
 		for (std::uint32_t r(0); r < bootstrap; ++r) {
 			std::string const line(nj_newick_text(replicate_nodes.data() + std::size_t(r) * nodes.size(), batch.n_rows, rows.ids));
@@ -1651,6 +1657,219 @@ void output::output_tree(variant_graph const &graph, char const *path, bool acgt
 	if (replicates_path) {
 		replicates.flush();
 		if (!replicates) throw std::runtime_error(std::string("error while writing ") + replicates_path);
+	}
+}
+
+
+// --- parsimony on the tree ------------------------------------------------------------------------------------
+
+u64 tree_parsimony_cpu(unsigned char const *bytes, u64 n, u64 n_sites, u64 pitch, v2m_nj_node const *nodes, v2m_parsimony_site *sites, std::uint32_t *branch_changes,
+	v2m_tree_mutation *mutations, u64 capacity)
+{
+	{
+		std::string err(n > V2M_NJ_MAX_ROWS ? std::string("more than V2M_NJ_MAX_ROWS taxa") : v2m::nj_records_error(nodes, n));
+		for (u64 t(0); err.empty() && t < n - 2; ++t) {
+			if (nodes[t].a >= nodes[t].b || (t == n - 3 && nodes[t].b >= nodes[t].c))
+				err = "record " + std::to_string(t) + " of the tree does not name its children in ascending order";
+		}
+		if (!err.empty()) throw std::invalid_argument(err);
+	}
+	if (pitch < n_sites) throw std::invalid_argument("the pitch is smaller than the sites");
+	auto const leaf_set([](unsigned char byte) -> unsigned {
+		switch (byte | 0x20) {
+			case 'a': return 1;
+			case 'c': return 2;
+			case 'g': return 4;
+			case 't': return 8;
+			default: return 0xF;
+		}
+	});
+	auto const lowest([](unsigned set) -> unsigned { return set & (0u - set); });
+	auto const class_of([](unsigned one_hot) -> std::uint32_t { return 1 == one_hot ? 0 : 2 == one_hot ? 1 : 4 == one_hot ? 2 : 3; });
+	u64 const root(2 * n - 3);
+	std::fill(branch_changes, branch_changes + root, 0u);
+	std::vector<unsigned char> set(root + 1), state(root + 1);
+	u64 total(0);
+	for (u64 site(0); site < n_sites; ++site) {
+		unsigned present(0);
+		for (u64 leaf(0); leaf < n; ++leaf) {
+			set[leaf] = (unsigned char) leaf_set(bytes[leaf * pitch + site]);
+			if (0xF != set[leaf]) present |= set[leaf];
+		}
+		std::uint32_t steps(0);
+		for (u64 t(0); t < n - 2; ++t) {
+			unsigned x(set[nodes[t].a] & set[nodes[t].b]);
+			if (!x) { x = set[nodes[t].a] | set[nodes[t].b]; ++steps; }
+			if (t == n - 3) {
+				unsigned const y(x & set[nodes[t].c]);
+				if (y) x = y; else ++steps;
+			}
+			set[n + t] = (unsigned char) x;
+		}
+		sites[site] = v2m_parsimony_site{steps, present};
+		state[root] = (unsigned char) lowest(set[root]);
+		for (u64 t(n - 2); t-- > 0;) {
+			unsigned const parent(state[n + t]);
+			for (int k(0); k < (t == n - 3 ? 3 : 2); ++k) {
+				u64 const x(0 == k ? nodes[t].a : 1 == k ? nodes[t].b : nodes[t].c);
+				state[x] = (unsigned char) ((set[x] & parent) ? parent : lowest(set[x]));
+				if (state[x] == parent) continue;
+				if (mutations && total < capacity) mutations[total] = v2m_tree_mutation{std::uint32_t(site), std::uint32_t(x), class_of(parent), class_of(state[x])};
+				++total;
+				++branch_changes[x];
+			}
+		}
+	}
+	return total;
+}
+
+
+std::string nj_newick_parsimony_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *branch_changes)
+{
+	if (!branch_changes) throw std::invalid_argument("branch_changes is NULL");
+	return newick_text(nodes, n_leaves, labels, nullptr, branch_changes);
+}
+
+
+std::string tree_mutations_text(v2m_tree_mutation const *mutations, u64 n_mutations, v2m_tree_site const *sites, u64 n_sites, std::vector<std::string> const &labels,
+	u64 const *reference_positions, u64 const *aligned_positions, u64 node_count)
+{
+	static char const letters[] = "ACGT";
+	u64 const n(labels.size());
+	std::string text;
+	u64 node(0);
+	for (u64 i(0); i < n_mutations; ++i) {
+		v2m_tree_mutation const &m(mutations[i]);
+		if (m.site >= n_sites) throw std::runtime_error("mutation " + std::to_string(i) + " names site " + std::to_string(m.site) + " of " + std::to_string(n_sites));
+		if (n < 3 || m.node >= 2 * n - 3 || m.from > 3 || m.to > 3) throw std::runtime_error("mutation " + std::to_string(i) + " names no branch or no class");
+		if (m.node < n) {
+			for (char const c : labels[m.node]) if ('\t' == c || '\n' == c || '\r' == c) throw std::runtime_error("a label holds a tab or a line break");
+			text += labels[m.node];
+		}
+		else text += "node" + std::to_string(m.node - n);
+		text += '\t';
+		append_column_and_position(text, sites[m.site].column, reference_positions, aligned_positions, node_count, node);
+		text += '\t';
+		text += letters[m.from];
+		text += '\t';
+		text += letters[m.to];
+		text += '\n';
+	}
+	return text;
+}
+
+
+std::string tree_sites_text(v2m_tree_site const *sites, u64 n_sites, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count)
+{
+	static char const letters[] = "ACGT";
+	std::string text;
+	u64 node(0);
+	for (u64 i(0); i < n_sites; ++i) {
+		v2m_tree_site const &site(sites[i]);
+		append_column_and_position(text, site.column, reference_positions, aligned_positions, node_count, node);
+		text += '\t';
+		int present(0);
+		for (int k(0); k < 4; ++k) if (site.present >> k & 1) { text += letters[k]; ++present; }
+		text += '\t';
+		text += std::to_string(site.steps);
+		text += '\t';
+		text += std::to_string(std::int64_t(site.steps) - (present - 1));
+		text += '\n';
+	}
+	return text;
+}
+
+
+namespace {
+	struct tree_parsimony_state {
+		std::vector<v2m_tree_site> sites;
+		std::vector<v2m_tree_mutation> mutations;
+		bool keep_mutations;
+		std::exception_ptr error;
+	};
+
+	int tree_parsimony_sites_sink(void *user, v2m_tree_site const *sites, uint64_t n)
+	{
+		auto &st(*static_cast<tree_parsimony_state *>(user));
+		try {
+			st.sites.assign(sites, sites + n);
+			return 0;
+		} catch (...) {   // nothing may cross the C boundary
+			st.error = std::current_exception();
+			return 1;
+		}
+	}
+
+	int tree_parsimony_mutations_sink(void *user, v2m_tree_mutation const *mutations, uint64_t n)
+	{
+		auto &st(*static_cast<tree_parsimony_state *>(user));
+		try {
+			st.mutations.insert(st.mutations.end(), mutations, mutations + n);
+			return 0;
+		} catch (...) {
+			st.error = std::current_exception();
+			return 1;
+		}
+	}
+}
+
+
+void output::output_tree_parsimony(variant_graph const &graph, std::ostream *newick, std::ostream *mutations, std::ostream *sites, bool verbose)
+{
+	if (!m_more_gpus.empty()) throw std::runtime_error("--output-tree-parsimony needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-tree-parsimony needs every chromosome copy on one GPU context");
+	row_set const rows(chain_rows(graph));   // (the rows and names of output_tree())
+	v2m_row_batch batch{};
+	batch.n_rows = rows.copy_index.size();
+	batch.copy_index = rows.copy_index.data();
+	if (rows.any_cuts) {
+		batch.cut_offsets = rows.cut_offsets.data();
+		batch.cut_nodes = rows.cut_nodes.data();
+		batch.cut_copies = rows.cut_copies.data();
+	}
+	if (batch.n_rows < 3 || m_tree_nodes.size() != batch.n_rows - 2) throw std::runtime_error("the parsimony outputs need the tree of output_tree() for the same rows");
+	std::vector<std::uint32_t> branch_changes(2 * batch.n_rows - 3);
+	tree_parsimony_state st{};
+	v2m_tree_parsimony_info info{};
+	// the mutations name their sites by index: the site records are needed for either text
+	int const rc(v2m_tree_parsimony(m_gpu.get(), &batch, m_tree_nodes.data(), 0, branch_changes.data(), (mutations || sites) ? tree_parsimony_sites_sink : nullptr,
+		mutations ? tree_parsimony_mutations_sink : nullptr, &st, &info));
+	if (st.error) std::rethrow_exception(st.error);
+	m_gpu.check(rc);
+	auto const *const ref_pos(graph.reference_positions.data());
+	auto const *const aln_pos(graph.aligned_positions.data());
+	if (newick) {
+		std::string const text(nj_newick_parsimony_text(m_tree_nodes.data(), batch.n_rows, rows.ids, branch_changes.data()));
+		newick->write(text.data(), std::streamsize(text.size()));
+	}
+	if (mutations) {
+		std::string const text(tree_mutations_text(st.mutations.data(), st.mutations.size(), st.sites.data(), st.sites.size(), rows.ids, ref_pos, aln_pos, graph.node_count()));
+		mutations->write(text.data(), std::streamsize(text.size()));
+	}
+	if (sites) {
+		std::string const text(tree_sites_text(st.sites.data(), st.sites.size(), ref_pos, aln_pos, graph.node_count()));
+		sites->write(text.data(), std::streamsize(text.size()));
+	}
+	if (verbose)
+		std::fprintf(stderr, "Parsimony: %llu rows, %llu columns, %llu sites, %llu mutations, %llu ranges.\n", (unsigned long long) batch.n_rows, (unsigned long long) info.n_columns,
+			(unsigned long long) info.n_sites, (unsigned long long) info.n_mutations, (unsigned long long) info.n_ranges);
+}
+
+
+void output::output_tree_parsimony(variant_graph const &graph, char const *newick_path, char const *mutations_path, char const *sites_path, bool verbose)
+{
+	std::ofstream streams[3];
+	char const *const paths[3] = {newick_path, mutations_path, sites_path};
+	for (int k(0); k < 3; ++k) {
+		if (!paths[k]) continue;
+		streams[k].open(paths[k], std::ios::binary | std::ios::trunc);
+		if (!streams[k]) throw std::runtime_error(std::string("unable to open ") + paths[k] + " for writing");
+	}
+	output_tree_parsimony(graph, newick_path ? &streams[0] : nullptr, mutations_path ? &streams[1] : nullptr, sites_path ? &streams[2] : nullptr, verbose);
+	for (int k(0); k < 3; ++k) {
+		if (!paths[k]) continue;
+		streams[k].flush();
+		if (!streams[k]) throw std::runtime_error(std::string("error while writing ") + paths[k]);
 	}
 }
 

@@ -107,6 +107,28 @@ std::string nj_newick_support_text(v2m_nj_node const *nodes, u64 n_leaves, std::
 // v2m::nj_split_support of csrc/nj_support.hpp, throwing what it reports.
 void nj_split_support(u64 n_leaves, v2m_nj_node const *main_nodes, v2m_nj_node const *replicate_nodes, u64 n_replicates, std::uint32_t *support);
 
+// Parsimony on a tree (include/v2m_hip.h, "parsimony") restated in plain loops over bytes (u8[n][pitch], of which the first n_sites
+// bytes of a row count) and the n - 2 records: sites receives n_sites records, branch_changes 2 n - 3 counts, and mutations -- which
+// may be NULL with capacity 0 -- the list when it fits capacity.  Returns the number of mutations.  The yardstick of the GPU's result
+// and the CPU baseline of its measurement.  Throws std::invalid_argument when the records are no tree in the header's sense.
+u64 tree_parsimony_cpu(unsigned char const *bytes, u64 n, u64 n_sites, u64 pitch, v2m_nj_node const *nodes, v2m_parsimony_site *sites, std::uint32_t *branch_changes,
+	v2m_tree_mutation *mutations, u64 capacity);
+
+// --output-tree-parsimony's text: the topology nj_newick_text writes, every branch length the integer branch_changes[x] of the
+// branch's lower node x, every internal node labelled node<t> by its record, the root included: (...)node7:3 and (...)node<n - 3>;
+std::string nj_newick_parsimony_text(v2m_nj_node const *nodes, u64 n_leaves, std::vector<std::string> const &labels, std::uint32_t const *branch_changes);
+
+// --output-tree-mutations' text: one line per mutation, in the list's order,
+//   <node><TAB><column><TAB><reference position | .><TAB><from><TAB><to>
+// node the leaf's label or node<t>, column and position as site_positions_text writes them for the mutation's site, from and to of ACGT.
+std::string tree_mutations_text(v2m_tree_mutation const *mutations, u64 n_mutations, v2m_tree_site const *sites, u64 n_sites, std::vector<std::string> const &labels,
+	u64 const *reference_positions, u64 const *aligned_positions, u64 node_count);
+
+// --output-tree-sites' text: one line per site,
+//   <column><TAB><reference position | .><TAB><states><TAB><steps><TAB><homoplasy>
+// states the letters of ACGT present, homoplasy = steps - (popcount(present) - 1) as a signed number.
+std::string tree_sites_text(v2m_tree_site const *sites, u64 n_sites, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -207,6 +229,13 @@ public:
 	void output_tree(variant_graph const &graph, std::ostream &stream, bool acgt_only = false, bool verbose = false,
 		std::uint32_t bootstrap = 0, std::uint64_t seed = 1, std::ostream *replicates = nullptr);
 
+	// --output-tree-parsimony, --output-tree-mutations, --output-tree-sites: nj_newick_parsimony_text, tree_mutations_text and
+	// tree_sites_text above (each where its stream or path is given) from v2m_tree_parsimony on the tree the last output_tree() call of
+	// this object wrote -- with a bootstrap, the main tree --, for the same rows under the same names and over the view in force.  The
+	// mutations are kept (16 bytes each) until the last has arrived.  verbose prints the rows, columns, sites, mutations and ranges.
+	void output_tree_parsimony(variant_graph const &graph, char const *newick_path, char const *mutations_path, char const *sites_path, bool verbose = false);
+	void output_tree_parsimony(variant_graph const &graph, std::ostream *newick, std::ostream *mutations, std::ostream *sites, bool verbose = false);
+
 protected:
 	struct row_set {
 		std::vector<std::string> ids;           // FASTA identifiers (a2m) or file names (separate)
@@ -241,6 +270,7 @@ protected:
 	bool m_should_output_reference{};
 	bool m_should_output_unaligned{};
 	bool m_bgzf{};
+	std::vector<v2m_nj_node> m_tree_nodes;   // the main tree of the last output_tree()
 };
 
 class haplotype_output final : public output {

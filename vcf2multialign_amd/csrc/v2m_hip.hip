@@ -33,6 +33,7 @@
 #include "vcf_kernels.hpp"
 #include "distance_kernels.hpp"
 #include "bootstrap_kernels.hpp"
+#include "parsimony_kernels.hpp"
 #include "site_kernels.hpp"
 #include "ld_kernels.hpp"
 #include "nj_kernels.hpp"
@@ -276,6 +277,10 @@ struct v2m_ctx {
 	scratch_buf d_boot_column_weights, d_boot_weights, d_boot_slices, d_boot_any, d_boot_matrix;
 	// neighbour joining (v2m_nj_tree[_of_distances]): the working matrix, R, the ids, the row minima and the records
 	scratch_buf d_nj_matrix, d_nj_sums, d_nj_ids, d_nj_best, d_nj_nodes;
+	// parsimony (v2m_parsimony_of_sites, v2m_tree_parsimony): the sets, the join table, the workgroups' steps and the call's total with
+	// its pinned staging, and for the host form a range's leaf bytes, the branch counters and a range's records and mutations (two, in turn)
+	scratch_buf d_fitch_sets, d_fitch_joins, d_fitch_blocks, d_fitch_total, d_fitch_bytes, d_fitch_branches, d_fitch_sites[2], d_fitch_mutations[2];
+	pinned_buf h_fitch_total;
 	// variable sites (v2m_variable_sites): the site list, the host form's gathered slices (two, used in turn), the list's pinned staging
 	scratch_buf d_site_columns, d_site_bytes[2];
 	pinned_buf h_site_columns;
@@ -3723,9 +3728,10 @@ int variable_sites_select(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, st
 	return V2M_OK;
 }
 
-// Stage (2) for rows [r0, r1) of the batch: the aligned splice into ring slot 0, then gather_sites_kernel into out, where batch row r
+// Stage (2) for rows [r0, r1) of the batch: the aligned splice into ring slot 0, then gather_sites_kernel at the V sites of site_list
+// (the context's list, or a 16-byte aligned range of it that ends with the list or at a multiple of four) into out, where batch row r
 // lands at out + (r - out_first_row) * out_pitch.  forced_rows: V2M_SITE_ROWS_PER_GROUP as the call read it (0: the rule).  Queues only.
-int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_plan const &p, u64 r0, u64 r1, u64 V, char *out, u64 out_first_row, u64 out_pitch, u64 forced_rows, stage_times &times)
+int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_plan const &p, u64 r0, u64 r1, u32 const *site_list, u64 V, char *out, u64 out_first_row, u64 out_pitch, u64 forced_rows, stage_times &times)
 {
 	u64 const nr(r1 - r0);
 	{
@@ -3743,7 +3749,7 @@ int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_p
 	u64 const per_group(forced_site_group(forced_rows, std::max<u64>({u64(v2m::kGatherMinGroupRows), (nr + want_groups - 1) / want_groups, (nr + 65534) / 65535}), nr));
 	u64 const groups((nr + per_group - 1) / per_group);
 	hipLaunchKernelGGL(v2m::gather_sites_kernel, dim3(unsigned(site_blocks), unsigned(groups)), dim3(v2m::kGatherThreads), 0, ctx->stream,
-		d_rows, p.pitch, u32(nr), u32(per_group), r0 - out_first_row, ctx->d_site_columns.as<u32>(), V, out, out_pitch);
+		d_rows, p.pitch, u32(nr), u32(per_group), r0 - out_first_row, site_list, V, out, out_pitch);
 	times.end();
 	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "variable sites: gather_sites_kernel did not launch");
 	return V2M_OK;
@@ -3785,7 +3791,7 @@ int v2m_variable_sites_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t 
 		slice_plan const p(plan_slices(ctx, n, false));
 		u64 const forced_rows(env_u64("V2M_SITE_ROWS_PER_GROUP", 0));
 		for (u64 s(0); s < p.n_slices && V2M_OK == rc; ++s)
-			rc = variable_sites_gather_slice(ctx, rows, p, s * p.rows_per_slice, std::min(n, (s + 1) * p.rows_per_slice), V, static_cast<char *>(d_bytes), 0, pitch, forced_rows, times);
+			rc = variable_sites_gather_slice(ctx, rows, p, s * p.rows_per_slice, std::min(n, (s + 1) * p.rows_per_slice), ctx->d_site_columns.as<u32>(), V, static_cast<char *>(d_bytes), 0, pitch, forced_rows, times);
 	}
 	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
 	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
@@ -3845,7 +3851,7 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 			if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "variable sites: %llu bytes of sites: %s", (unsigned long long) slice_bytes, hipGetErrorString(st));
 		}
 		V2M_POISON_HOST(slot.host.p, slice_bytes);
-		if (int const rc = variable_sites_gather_slice(ctx, rows, p, r0, r1, V, ctx->d_site_bytes[b].as<char>(), r0, out_pitch, forced_rows, times)) return rc;
+		if (int const rc = variable_sites_gather_slice(ctx, rows, p, r0, r1, ctx->d_site_columns.as<u32>(), V, ctx->d_site_bytes[b].as<char>(), r0, out_pitch, forced_rows, times)) return rc;
 		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
 		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
 		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, ctx->d_site_bytes[b].p, (r1 - r0) * out_pitch, hipMemcpyDeviceToHost, ctx->copy_stream));
@@ -4353,6 +4359,294 @@ int v2m_nj_bootstrap(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, ui
 	}
 	if (info) *info = out;
 	return V2M_OK;
+}
+
+
+// ---- parsimony (parsimony_kernels.hpp) -------------------------------------------------------------
+
+namespace {
+
+static_assert(sizeof(v2m_parsimony_site) == 8 && sizeof(v2m_tree_site) == 16 && sizeof(v2m_tree_mutation) == 16 && sizeof(v2m_tree_parsimony_info) == 56, "the header's sizes");
+static_assert(sizeof(v2m_parsimony_site) == sizeof(v2m::parsimony_site_record) && sizeof(v2m_tree_mutation) == sizeof(v2m::tree_mutation_record), "the kernels' records");
+
+// What both forms refuse about the tree before any device work; 0 == n is the caller's.
+int check_parsimony_tree(v2m_ctx *ctx, u64 n, v2m_nj_node const *nodes, char const *name)
+{
+	if (!nodes) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "nodes is NULL");
+	if (n < 3) return nj_too_few(ctx, n, name);
+	if (n > V2M_NJ_MAX_ROWS)
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes at most V2M_NJ_MAX_ROWS = %u taxa (got %llu)", name, V2M_NJ_MAX_ROWS, (unsigned long long) n);
+	try {
+		std::string err(v2m::nj_records_error(nodes, n));
+		for (u64 t(0); err.empty() && t < n - 2; ++t) {
+			if (nodes[t].a >= nodes[t].b || (t == n - 3 && nodes[t].b >= nodes[t].c))
+				err = "record " + std::to_string(t) + " of the tree does not name its children in ascending order";
+		}
+		if (!err.empty()) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s: %s", name, err.c_str());
+	} catch (std::bad_alloc const &) {
+		return fail(ctx, V2M_ERR_OUT_OF_MEMORY, "%s: no host memory for the tree's check", name);
+	}
+	return V2M_OK;
+}
+
+// The join table of a checked tree into ctx->d_fitch_joins (synchronous); the third child of the last record to last_c.
+int parsimony_upload_tree(v2m_ctx *ctx, u64 n, v2m_nj_node const *nodes, u32 &last_c)
+{
+	try {
+		std::vector<v2m::fitch_join> joins(n - 2);
+		for (u64 t(0); t < n - 2; ++t) joins[t] = v2m::fitch_join{nodes[t].a, nodes[t].b};
+		last_c = nodes[n - 3].c;
+		V2M_HIP_TRY(ctx, ctx->d_fitch_joins.ensure(joins.size() * sizeof(v2m::fitch_join)));
+		V2M_HIP_TRY(ctx, hipMemcpy(ctx->d_fitch_joins.p, joins.data(), joins.size() * sizeof(v2m::fitch_join), hipMemcpyHostToDevice));
+	} catch (std::bad_alloc const &) {
+		return fail(ctx, V2M_ERR_OUT_OF_MEMORY, "parsimony: no host memory for the join table");
+	}
+	return V2M_OK;
+}
+
+u64 fitch_blocks(u64 V) { return (V + u64(v2m::kFitchThreads) * v2m::kFitchSites - 1) / (u64(v2m::kFitchThreads) * v2m::kFitchSites); }
+
+// The scratch of one range of V >= 1 sites at `pitch`: the sets, the workgroups' steps, the total and its staging.
+int parsimony_ensure(v2m_ctx *ctx, u64 n, u64 V, u64 pitch)
+{
+	auto const ensure([&](scratch_buf &buf, u64 bytes, char const *what) -> int {
+		hipError_t const st(buf.ensure(bytes));
+		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "parsimony: %llu bytes of %s: %s", (unsigned long long) bytes, what, hipGetErrorString(st));
+		return V2M_OK;
+	});
+	if (int const rc = ensure(ctx->d_fitch_sets, (n - 2) * pitch, "sets")) return rc;
+	if (int const rc = ensure(ctx->d_fitch_blocks, std::max<u64>(fitch_blocks(V) * sizeof(u32), 16), "workgroup steps")) return rc;
+	if (int const rc = ensure(ctx->d_fitch_total, 2 * sizeof(u64), "totals")) return rc;
+	V2M_HIP_TRY(ctx, ctx->h_fitch_total.ensure(sizeof(u64)));
+	return V2M_OK;
+}
+
+// The up pass and the scan of one range, completed: the sets, d_sites[V], the workgroups' offsets, and the range's mutations to total.
+int parsimony_up(v2m_ctx *ctx, unsigned char const *d_bytes, u64 n, u64 V, u64 pitch, u32 last_c, v2m::parsimony_site_record *d_sites, stage_times &times, u64 &total)
+{
+	unsigned const blocks(unsigned(fitch_blocks(V)));
+	unsigned long long *const d_total(ctx->d_fitch_total.as<unsigned long long>());
+	V2M_POISON_HOST(ctx->h_fitch_total.p, sizeof(u64));
+	times.begin(stage_times::pairs);
+	hipError_t st(hipMemsetAsync(d_total, 0, 2 * sizeof(u64), ctx->stream));
+	hipLaunchKernelGGL(v2m::fitch_up_kernel, dim3(blocks), dim3(v2m::kFitchThreads), 0, ctx->stream,
+		d_bytes, ctx->d_fitch_sets.as<unsigned char>(), pitch, u32(n), V, ctx->d_fitch_joins.as<v2m::fitch_join>(), last_c, d_sites, ctx->d_fitch_blocks.as<u32>(), d_total);
+	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->d_fitch_blocks.as<u32>(), blocks, ctx->d_fitch_total.as<u64>() + 1);
+	times.end();
+	if (hipSuccess != st || hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "parsimony: the up pass did not launch");
+	if (hipSuccess != hipMemcpyAsync(ctx->h_fitch_total.p, d_total, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
+		|| hipSuccess != hipStreamSynchronize(ctx->stream))
+		return fail(ctx, V2M_ERR_HIP, "parsimony: the number of mutations did not arrive");
+	total = *ctx->h_fitch_total.as<u64>();
+	return V2M_OK;
+}
+
+// Queues the down pass of the range the up pass left in the sets; d_mutations NULL: the branch counts only.
+int parsimony_down(v2m_ctx *ctx, unsigned char const *d_bytes, u64 n, u64 V, u64 pitch, u32 last_c, v2m::parsimony_site_record const *d_sites, u32 *d_branches,
+	u64 site_base, v2m::tree_mutation_record *d_mutations, stage_times &times)
+{
+	unsigned const blocks(unsigned(fitch_blocks(V)));
+	times.begin(stage_times::pairs);
+	hipLaunchKernelGGL(d_mutations ? v2m::fitch_down_kernel<true> : v2m::fitch_down_kernel<false>, dim3(blocks), dim3(v2m::kFitchThreads), 0, ctx->stream,
+		d_bytes, ctx->d_fitch_sets.as<unsigned char>(), pitch, u32(n), V, ctx->d_fitch_joins.as<v2m::fitch_join>(), last_c, d_branches,
+		d_sites, ctx->d_fitch_blocks.as<u32>(), u32(site_base), d_mutations);
+	times.end();
+	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "parsimony: the down pass did not launch");
+	return V2M_OK;
+}
+
+int parsimony_too_long(v2m_ctx *ctx, char const *name, u64 total)
+{
+	return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes a tree of fewer than 2^32 mutations (got %llu)", name, (unsigned long long) total);
+}
+
+} // namespace
+
+int v2m_parsimony_of_sites(v2m_ctx *ctx, const void *d_bytes, uint64_t n, uint64_t n_sites, uint64_t pitch, const v2m_nj_node *nodes, void *d_sites, void *d_branch_changes,
+	void *d_mutations, uint64_t capacity, uint64_t *n_mutations)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!n_mutations) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "n_mutations is NULL");
+	if (0 == n) return V2M_OK;
+	if (int const rc = check_parsimony_tree(ctx, n, nodes, "v2m_parsimony_of_sites")) return rc;
+	u64 const V(n_sites);
+	if (!d_bytes && V) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_bytes is NULL");
+	if (!d_sites && V) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_sites is NULL");
+	if (!d_branch_changes) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_branch_changes is NULL");
+	if (!d_mutations && capacity) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_mutations is NULL with a capacity of %llu", (unsigned long long) capacity);
+	if ((reinterpret_cast<uintptr_t>(d_bytes) | reinterpret_cast<uintptr_t>(d_sites) | reinterpret_cast<uintptr_t>(d_branch_changes) | reinterpret_cast<uintptr_t>(d_mutations)) & 15)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_bytes, d_sites, d_branch_changes and d_mutations must be 16-byte aligned");
+	if ((pitch & 15) || pitch < V)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "pitch %llu must be a multiple of 16 and at least n_sites = %llu", (unsigned long long) pitch, (unsigned long long) V);
+	if (V >= (u64(1) << 32)) return fail(ctx, V2M_ERR_UNSUPPORTED, "v2m_parsimony_of_sites takes fewer than 2^32 sites (got %llu)", (unsigned long long) V);
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (0 == V) {
+		*n_mutations = 0;
+		V2M_HIP_TRY(ctx, hipMemsetAsync(d_branch_changes, 0, (2 * n - 3) * sizeof(u32), ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		return V2M_OK;
+	}
+	u32 last_c(0);
+	if (int const rc = parsimony_upload_tree(ctx, n, nodes, last_c)) return rc;
+	if (int const rc = parsimony_ensure(ctx, n, V, pitch)) return rc;
+	stage_times times(ctx);
+	u64 total(0);
+	auto *const sites(static_cast<v2m::parsimony_site_record *>(d_sites));
+	int rc(parsimony_up(ctx, static_cast<unsigned char const *>(d_bytes), n, V, pitch, last_c, sites, times, total));
+	if (V2M_OK == rc) {
+		*n_mutations = total;
+		if (total >> 32) rc = parsimony_too_long(ctx, "v2m_parsimony_of_sites", total);
+		else if (capacity && total > capacity)
+			rc = fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%llu mutations do not fit a capacity of %llu: size d_mutations for n_mutations = %llu and call again",
+				(unsigned long long) total, (unsigned long long) capacity, (unsigned long long) total);
+	}
+	if (V2M_OK == rc && hipSuccess != hipMemsetAsync(d_branch_changes, 0, (2 * n - 3) * sizeof(u32), ctx->stream)) rc = fail(ctx, V2M_ERR_HIP, "parsimony: the branch counts could not be zeroed");
+	if (V2M_OK == rc)
+		rc = parsimony_down(ctx, static_cast<unsigned char const *>(d_bytes), n, V, pitch, last_c, sites, static_cast<u32 *>(d_branch_changes), 0,
+			capacity ? static_cast<v2m::tree_mutation_record *>(d_mutations) : nullptr, times);
+	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
+	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
+	return rc;
+}
+
+int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_node *nodes, uint32_t flags, uint32_t *branch_changes, v2m_tree_sites_sink_fn sites_sink,
+	v2m_tree_mutations_sink_fn mutations_sink, void *user, v2m_tree_parsimony_info *info)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!rows) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "rows is NULL");
+	if (flags) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "v2m_tree_parsimony takes 0 as flags (got 0x%x)", flags);
+	if (int const rc = check_variable_sites(ctx, rows, V2M_SITES_SNP, "v2m_tree_parsimony")) return rc;
+	u64 const n(rows->n_rows);
+	if (0 == n) return V2M_OK;
+	if (int const rc = check_parsimony_tree(ctx, n, nodes, "v2m_tree_parsimony")) return rc;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	u64 const L(ctx->view().length()), view_begin(ctx->view().begin), n_branches(2 * n - 3);
+	stage_times times(ctx);
+	u64 V(0), n_mutations(0), n_ranges(0);
+	auto const finish([&](int rc) -> int {
+		// leave both streams idle whatever happened
+		hipError_t const st(hipStreamSynchronize(ctx->stream));
+		(void) hipStreamSynchronize(ctx->copy_stream);
+		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
+		if (V2M_OK == rc && info) {
+			double ms[stage_times::n_stages] = {};
+			times.sum(ms);
+			*info = v2m_tree_parsimony_info{V, L, n_mutations, n_ranges, ms[stage_times::counts], ms[stage_times::pack], ms[stage_times::pairs]};
+		}
+		return rc;
+	});
+	if (L) if (int const rc = variable_sites_select(ctx, rows, V2M_SITES_SNP, times, V)) return finish(rc);
+	if (0 == V) {
+		if (branch_changes) std::fill(branch_changes, branch_changes + n_branches, 0u);
+		return finish(V2M_OK);
+	}
+
+	// Ranges of whole waves of sites whose leaf bytes and sets fit the budget.  Range k's records and mutations go to device buffers and
+	// pinned slot k & 1 and cross the link on the copy stream while range k + 1 is gathered and walked; the mutations reach their sink
+	// then, the records are kept for the one call of theirs after the last range.
+	u64 const unit(u64(v2m::kFitchSites) * 64);
+	u64 const budget_sites(env_u64("V2M_PARSIMONY_BYTES", u64(16) << 30) / (2 * n - 2));
+	u64 const range_sites(std::min<u64>((V + unit - 1) / unit * unit, std::max<u64>(unit, budget_sites / unit * unit)));
+	u64 const pitch((std::min(range_sites, V) + 15) & ~u64(15));
+	n_ranges = (V + range_sites - 1) / range_sites;
+	std::vector<v2m_tree_site> site_records;
+	u32 last_c(0);
+	try {
+		if (sites_sink) site_records.resize(V);
+	} catch (std::bad_alloc const &) {
+		return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "v2m_tree_parsimony: no host memory for %llu site records", (unsigned long long) V));
+	}
+	if (sites_sink) {
+		// the site list: over the link as it is, widened to absolute columns on the host
+		if (hipSuccess != ctx->h_site_columns.ensure(V * sizeof(u32))) return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "v2m_tree_parsimony: %llu bytes of pinned site list", (unsigned long long) (V * sizeof(u32))));
+		V2M_POISON_HOST(ctx->h_site_columns.p, V * sizeof(u32));
+		if (hipSuccess != hipMemcpyAsync(ctx->h_site_columns.p, ctx->d_site_columns.p, V * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream)
+			|| hipSuccess != hipStreamSynchronize(ctx->stream))
+			return finish(fail(ctx, V2M_ERR_HIP, "v2m_tree_parsimony: the site list did not arrive"));
+		u32 const *const relative(ctx->h_site_columns.as<u32>());
+		for (u64 i(0); i < V; ++i) site_records[i].column = view_begin + relative[i];
+	}
+	if (int const rc = parsimony_upload_tree(ctx, n, nodes, last_c)) return finish(rc);
+	if (int const rc = parsimony_ensure(ctx, n, std::min(range_sites, V), pitch)) return finish(rc);
+	if (int const rc = ensure_host_slots(ctx, std::min<u64>(2, n_ranges), 0)) return finish(rc);
+	{
+		hipError_t st(ctx->d_fitch_bytes.ensure(n * pitch));
+		if (hipSuccess == st) st = ctx->d_fitch_branches.ensure(n_branches * sizeof(u32));
+		if (hipSuccess == st) st = hipMemsetAsync(ctx->d_fitch_branches.p, 0, n_branches * sizeof(u32), ctx->stream);
+		if (hipSuccess != st) return finish(fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "v2m_tree_parsimony: %llu bytes of leaf rows: %s", (unsigned long long) (n * pitch), hipGetErrorString(st)));
+	}
+	unsigned char *const d_bytes(ctx->d_fitch_bytes.as<unsigned char>());
+	slice_plan const p(plan_slices(ctx, n, false));
+	u64 const gather_group_rows(env_u64("V2M_SITE_ROWS_PER_GROUP", 0));   // (the gather's test knob, read once per call)
+	struct delivery { u64 first_site{}, n_sites{}, n_mutations{}, mutations_at{}; bool pending{}; } deliveries[2];
+	auto const issue([&](u64 k) -> int {
+		int const b(int(k & 1));
+		u64 const s0(k * range_sites), Vr(std::min(V, s0 + range_sites) - s0);
+		for (u64 s(0); s < p.n_slices; ++s)
+			if (int const rc = variable_sites_gather_slice(ctx, rows, p, s * p.rows_per_slice, std::min(n, (s + 1) * p.rows_per_slice), ctx->d_site_columns.as<u32>() + s0, Vr,
+				reinterpret_cast<char *>(d_bytes), 0, pitch, gather_group_rows, times)) return rc;
+		{
+			hipError_t const st(ctx->d_fitch_sites[b].ensure(Vr * sizeof(v2m_parsimony_site)));
+			if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "v2m_tree_parsimony: the site records: %s", hipGetErrorString(st));
+		}
+		auto *const d_sites(ctx->d_fitch_sites[b].as<v2m::parsimony_site_record>());
+		u64 total(0);
+		if (int const rc = parsimony_up(ctx, d_bytes, n, Vr, pitch, last_c, d_sites, times, total)) return rc;
+		n_mutations += total;
+		if (n_mutations >> 32) return parsimony_too_long(ctx, "v2m_tree_parsimony", n_mutations);
+		bool const emit(mutations_sink && total);
+		if (emit) {
+			hipError_t const st(ctx->d_fitch_mutations[b].ensure(total * sizeof(v2m_tree_mutation)));
+			if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "v2m_tree_parsimony: %llu mutations: %s", (unsigned long long) total, hipGetErrorString(st));
+		}
+		if (int const rc = parsimony_down(ctx, d_bytes, n, Vr, pitch, last_c, d_sites, ctx->d_fitch_branches.as<u32>(), s0,
+			emit ? ctx->d_fitch_mutations[b].as<v2m::tree_mutation_record>() : nullptr, times)) return rc;
+		delivery &d(deliveries[b]);
+		d = delivery{s0, sites_sink ? Vr : 0, emit ? total : 0, (Vr * sizeof(v2m_parsimony_site) + 15) & ~u64(15), false};
+		if (0 == d.n_sites && 0 == d.n_mutations) return V2M_OK;
+		v2m_row_hold &slot(*ctx->host_slots[b]);
+		u64 const slot_bytes(d.mutations_at + d.n_mutations * sizeof(v2m_tree_mutation));
+		V2M_HIP_TRY(ctx, slot.host.ensure(slot_bytes));
+		V2M_POISON_HOST(slot.host.p, slot_bytes);
+		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
+		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
+		if (d.n_sites) V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, d_sites, Vr * sizeof(v2m_parsimony_site), hipMemcpyDeviceToHost, ctx->copy_stream));
+		if (d.n_mutations)
+			V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.as<char>() + d.mutations_at, ctx->d_fitch_mutations[b].p, d.n_mutations * sizeof(v2m_tree_mutation), hipMemcpyDeviceToHost, ctx->copy_stream));
+		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
+		d.pending = true;
+		return V2M_OK;
+	});
+	auto const hand_over([&](u64 k) -> int {
+		delivery &d(deliveries[k & 1]);
+		if (!d.pending) return V2M_OK;
+		d.pending = false;
+		v2m_row_hold &slot(*ctx->host_slots[k & 1]);
+		V2M_HIP_TRY(ctx, hipEventSynchronize(slot.copied));
+		auto const *const records(slot.host.as<v2m_parsimony_site>());
+		for (u64 i(0); i < d.n_sites; ++i) {
+			site_records[d.first_site + i].steps = records[i].steps;
+			site_records[d.first_site + i].present = records[i].present;
+		}
+		if (d.n_mutations && mutations_sink(user, reinterpret_cast<v2m_tree_mutation const *>(slot.host.as<char>() + d.mutations_at), d.n_mutations))
+			return fail(ctx, V2M_ERR_SINK, "sink aborted");
+		return V2M_OK;
+	});
+	int rc(V2M_OK);
+	u64 launched(0);
+	for (u64 k(0); k < n_ranges && V2M_OK == rc; ++k) {
+		if (V2M_OK != (rc = issue(k))) break;
+		launched = k + 1;
+		if (k >= 1) rc = hand_over(k - 1);   // its copies ran under this range's kernels
+	}
+	if (V2M_OK == rc && launched) rc = hand_over(launched - 1);
+	if (V2M_OK == rc && branch_changes) {
+		if (hipSuccess != hipMemcpyAsync(branch_changes, ctx->d_fitch_branches.p, n_branches * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream)
+			|| hipSuccess != hipStreamSynchronize(ctx->stream))
+			rc = fail(ctx, V2M_ERR_HIP, "v2m_tree_parsimony: the branch counts did not arrive");
+	}
+	if (V2M_OK == rc && sites_sink && sites_sink(user, site_records.data(), V)) rc = fail(ctx, V2M_ERR_SINK, "sink aborted");
+	return finish(rc);
 }
 
 

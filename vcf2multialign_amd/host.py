@@ -91,6 +91,15 @@ def _load():
 		L.v2mh_nj_newick_support_text.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_nj_split_support.restype = C.c_int
 		L.v2mh_nj_split_support.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+		L.v2mh_tree_parsimony_cpu.restype = C.c_int64
+		L.v2mh_tree_parsimony_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_nj_newick_parsimony_text.restype = C.c_int64
+		L.v2mh_nj_newick_parsimony_text.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_tree_mutations_text.restype = C.c_int64
+		L.v2mh_tree_mutations_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+			C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_tree_sites_text.restype = C.c_int64
+		L.v2mh_tree_sites_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -316,6 +325,105 @@ def nj_split_support(main_nodes, replicate_nodes):
 	if 0 != _load().v2mh_nj_split_support(n, main_nodes.ctypes.data, replicate_nodes.ctypes.data if B else None, B, support.ctypes.data):
 		raise ValueError("v2mh_nj_split_support: the records are no trees over %d leaves" % n)
 	return support[:n - 3]
+
+
+def tree_parsimony_cpu(rows, nodes, n_sites=None, want_mutations=True):
+	"""The host library's plain-loop parsimony (csrc/host/output.cc: tree_parsimony_cpu; no GPU) of the sites of rows[n, pitch] (u8; the
+	first n_sites bytes of a row count, all of them by default) on the tree of the n - 2 v2m_nj_node records `nodes`: (sites,
+	branch_changes, mutations) -- v2m_parsimony_site[n_sites], np.uint32[2 n - 3] and the v2m_tree_mutation records (none with
+	want_mutations=False).  ValueError for records that are no tree."""
+	from . import _native as N
+	rows = np.ascontiguousarray(rows, dtype=np.uint8)
+	if rows.ndim != 2:
+		raise ValueError("rows is no matrix of bytes")
+	n, pitch = rows.shape
+	V = pitch if n_sites is None else int(n_sites)
+	nodes = np.ascontiguousarray(nodes, dtype=np.dtype(N.NJ_NODE_DTYPE))
+	if n < 3 or len(nodes) != n - 2 or not 0 <= V <= pitch:
+		raise ValueError("%d records, %d rows and %d sites of %d bytes are no tree with sites" % (len(nodes), n, V, pitch))
+	sites = np.zeros(V, dtype=np.dtype(N.PARSIMONY_SITE_DTYPE))
+	branch_changes = np.zeros(2 * n - 3, dtype=np.uint32)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (rows.ctypes.data if rows.size else None, n, V, pitch, nodes.ctypes.data, sites.ctypes.data if V else None, branch_changes.ctypes.data)
+	total = L.v2mh_tree_parsimony_cpu(*args, None, 0, err, len(err))
+	if total < 0:
+		raise ValueError(err.value.decode())
+	mutations = np.zeros(total if want_mutations else 0, dtype=np.dtype(N.TREE_MUTATION_DTYPE))
+	if want_mutations and total and total != L.v2mh_tree_parsimony_cpu(*args, mutations.ctypes.data, total, err, len(err)):
+		raise ValueError(err.value.decode())
+	return sites, branch_changes, mutations
+
+
+def nj_newick_parsimony_text(nodes, labels, branch_changes):
+	"""The host library's Newick writer of --output-tree-parsimony (csrc/host/output.cc: nj_newick_parsimony_text; no GPU):
+	nj_newick_text's topology with branch_changes[x] as the length of node x's branch and node<t> as the label of internal node
+	len(labels) + t."""
+	from . import _native as N
+	names = [i if isinstance(i, bytes) else str(i).encode() for i in labels]
+	n = len(names)
+	nodes = np.ascontiguousarray(nodes, dtype=np.dtype(N.NJ_NODE_DTYPE))
+	branch_changes = np.ascontiguousarray(branch_changes, dtype=np.uint32)
+	if n < 3 or len(nodes) != n - 2 or branch_changes.shape != (2 * n - 3,):
+		raise ValueError("%d records, %d labels and %d counts are no tree with branch changes" % (len(nodes), n, branch_changes.size))
+	if any(b"\0" in i for i in names):
+		raise ValueError("a label holds a NUL byte")
+	array = (C.c_char_p * n)(*names)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (nodes.ctypes.data, n, array, branch_changes.ctypes.data)
+	size = L.v2mh_nj_newick_parsimony_text(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != L.v2mh_nj_newick_parsimony_text(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
+
+
+def tree_mutations_text(mutations, sites, labels, reference_positions, aligned_positions):
+	"""The host library's formatter of --output-tree-mutations (csrc/host/output.cc: tree_mutations_text; no GPU): one line per
+	v2m_tree_mutation record, `node<TAB>column<TAB>reference position<TAB>from<TAB>to`, as bytes; sites are the v2m_tree_site records the
+	mutations index, labels the leaves' names."""
+	from . import _native as N
+	mutations = np.ascontiguousarray(mutations, dtype=np.dtype(N.TREE_MUTATION_DTYPE))
+	sites = np.ascontiguousarray(sites, dtype=np.dtype(N.TREE_SITE_DTYPE))
+	names = [i if isinstance(i, bytes) else str(i).encode() for i in labels]
+	if any(b"\0" in i for i in names):
+		raise ValueError("a label holds a NUL byte")
+	array = (C.c_char_p * max(1, len(names)))(*names)
+	ref = np.ascontiguousarray(reference_positions, dtype=np.uint64)
+	aln = np.ascontiguousarray(aligned_positions, dtype=np.uint64)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (mutations.ctypes.data if len(mutations) else None, len(mutations), sites.ctypes.data if len(sites) else None, len(sites), array, len(names),
+		ref.ctypes.data, aln.ctypes.data, len(aln))
+	size = L.v2mh_tree_mutations_text(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != L.v2mh_tree_mutations_text(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
+
+
+def tree_sites_text(sites, reference_positions, aligned_positions):
+	"""The host library's formatter of --output-tree-sites (csrc/host/output.cc: tree_sites_text; no GPU): one line per v2m_tree_site
+	record, `column<TAB>reference position<TAB>states<TAB>steps<TAB>homoplasy`, as bytes."""
+	from . import _native as N
+	sites = np.ascontiguousarray(sites, dtype=np.dtype(N.TREE_SITE_DTYPE))
+	ref = np.ascontiguousarray(reference_positions, dtype=np.uint64)
+	aln = np.ascontiguousarray(aligned_positions, dtype=np.uint64)
+	L = _load()
+	err = C.create_string_buffer(512)
+	args = (sites.ctypes.data if len(sites) else None, len(sites), ref.ctypes.data, aln.ctypes.data, len(aln))
+	size = L.v2mh_tree_sites_text(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != L.v2mh_tree_sites_text(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
 
 
 def write_cut_positions(path, cut_positions, min_distance, score):

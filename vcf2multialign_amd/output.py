@@ -152,6 +152,34 @@ class Output:
 					f.write(host.nj_newick_text(tree, ids))
 		return info
 
+	def _write_tree_parsimony(self, ids, rows, graph, acgt_only, parsimony, mutations, sites, bootstrap=0, seed=1):
+		"""--output-tree-parsimony, --output-tree-mutations, --output-tree-sites: the texts of host.nj_newick_parsimony_text,
+		host.tree_mutations_text and host.tree_sites_text (each into its stream, where one is given) from Context.tree_parsimony on the
+		tree --output-tree writes for `rows` named `ids` (with bootstrap > 0 the main tree of Context.nj_bootstrap, which is the same),
+		over the region's columns when there is one.  Returns the info of the parsimony call."""
+		from . import host
+		if len(rows) < 3:
+			raise ValueError("--output-tree needs at least three sequences (got %d)" % len(rows))
+		if self.region is not None:
+			self.ctx.set_column_window(*columns_of_reference_range(graph.reference_positions, graph.aligned_positions, *self.region))
+		try:
+			if bootstrap:
+				nodes = self.ctx.nj_bootstrap(RowBatch(rows), bootstrap, seed=seed, acgt_only=acgt_only)[0]
+			else:
+				nodes = self.ctx.nj_tree(RowBatch(rows), acgt_only=acgt_only)
+			site_records, branch_changes, mutation_records, info = self.ctx.tree_parsimony(RowBatch(rows), nodes, info=True,
+				want_sites=mutations is not None or sites is not None, want_mutations=mutations is not None)
+		finally:
+			if self.region is not None:
+				self.ctx.set_column_window(0, self.ctx.aligned_length)
+		if parsimony is not None:
+			parsimony.write(host.nj_newick_parsimony_text(nodes, ids, branch_changes))
+		if mutations is not None:
+			mutations.write(host.tree_mutations_text(mutation_records, site_records, ids, graph.reference_positions, graph.aligned_positions))
+		if sites is not None:
+			sites.write(host.tree_sites_text(site_records, graph.reference_positions, graph.aligned_positions))
+		return info
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -224,6 +252,12 @@ class HaplotypeOutput(Output):
 		--tree-acgt-only) for the rows of output_tree."""
 		ids, rows = self._distance_rows(graph)
 		return self._write_tree(stream, ids, rows, graph, acgt_only, int(bootstrap), seed, replicates_path)
+
+	def output_tree_parsimony(self, graph, parsimony=None, mutations=None, sites=None, acgt_only=False, bootstrap=0, seed=1):
+		"""--output-tree-parsimony, --output-tree-mutations and --output-tree-sites (each a stream, or None) on the tree output_tree
+		(bootstrap > 0: output_tree_bootstrap) writes for the same rows."""
+		ids, rows = self._distance_rows(graph)
+		return self._write_tree_parsimony(ids, rows, graph, acgt_only, parsimony, mutations, sites, int(bootstrap), seed)
 
 	def output_variable_sites(self, graph, stream, snp_only=False, positions=None):
 		"""--output-variable-sites (with --snp-sites and --output-site-positions) for the rows of output_a2m under its names."""
@@ -315,6 +349,12 @@ class FounderSequenceGreedyOutput(Output):
 		--tree-acgt-only) for the rows of output_tree."""
 		ids, rows = self._distance_rows(cut_positions, assigned_samples_column_major)
 		return self._write_tree(stream, ids, rows, graph, acgt_only, int(bootstrap), seed, replicates_path)
+
+	def output_tree_parsimony(self, graph, cut_positions, assigned_samples_column_major, parsimony=None, mutations=None, sites=None, acgt_only=False, bootstrap=0, seed=1):
+		"""--output-tree-parsimony, --output-tree-mutations and --output-tree-sites (each a stream, or None) on the tree output_tree
+		(bootstrap > 0: output_tree_bootstrap) writes for the same rows."""
+		ids, rows = self._distance_rows(cut_positions, assigned_samples_column_major)
+		return self._write_tree_parsimony(ids, rows, graph, acgt_only, parsimony, mutations, sites, int(bootstrap), seed)
 
 	def output_variable_sites(self, graph, cut_positions, assigned_samples_column_major, stream, snp_only=False, positions=None):
 		"""--output-variable-sites for the rows of output_a2m (REF first, unless omitted, then the founder rows) under its names."""
