@@ -8,7 +8,8 @@ records, the reported pairs in the order (s, t) and the number of candidates, as
 graph_from_choice() makes graphs of biallelic sites from a matrix of what every copy holds at every site (the reference base, the
 other base, or a byte that is missing data), ld_graph() a small one with the pairs a random graph rarely holds, random_graph() graphs of
 a chosen number of sites with founders behind them, so that r^2 takes many values.  corpus() is what tests/test_gpu_site_ld.py runs,
-kept here so that tests/test_site_ld_host.py can assert what it holds."""
+kept here so that tests/test_site_ld_host.py can assert what it holds; wide_items() are batches of 4 160 and 32 768 rows, where the two
+sides of the threshold pass 2^64, and band_items() 581 sites under windows of 4 to 10 tiles a strip."""
 
 import functools
 import math
@@ -116,10 +117,34 @@ def evaluate(cls, params, first_column=0):
 	return records, pairs, keep
 
 
+def evaluate_arrays(cls, params, first_column=0):
+	"""evaluate() without its loops over the pairs, for the bands of many tiles (band_items(): 170 000 candidates): the candidates from
+	the index pairs above the diagonal, which numpy lists in the order (s, t), and the rule on arrays of Python's integers (dtype
+	object), which round no more than is_reported() does.  tests/test_site_ld_host.py holds it equal to evaluate() on every item of
+	corpus() and wide_items()."""
+	records = sites(cls, params.min_allele_count, first_column)
+	called, carries = planes(cls, records, first_column)
+	counts = pair_counts(called, carries)
+	cols = records["column"].astype(np.int64)
+	s, t = np.triu_indices(len(records), k=1)
+	ok = t - s <= params.window_sites
+	if params.window_columns:
+		ok &= cols[t] - cols[s] <= params.window_columns
+	s, t = s[ok], t[ok]
+	pairs = np.zeros(len(s), dtype=PAIR_DTYPE)
+	pairs["site_a"], pairs["site_b"] = s, t
+	for name, c in zip(("n", "n_a", "n_b", "n_ab"), counts):
+		pairs[name] = c[s, t]
+	n, n_a, n_b, n_ab = (c[s, t].astype(object) for c in counts)
+	d, den = n * n_ab - n_a * n_b, n_a * (n - n_a) * n_b * (n - n_b)
+	keep = (den != 0).astype(bool) & (d * d * int(params.min_r2[1]) >= int(params.min_r2[0]) * den).astype(bool)
+	return records, pairs, keep
+
+
 @functools.lru_cache(maxsize=None)
 def _expected(item):
 	m = CM.matrix(item.g, item.rows, item.window)
-	records, pairs, keep = evaluate(PM.classes(m), item.params, item.window[0] if item.window else 0)
+	records, pairs, keep = (evaluate_arrays if item.arrays else evaluate)(PM.classes(m), item.params, item.window[0] if item.window else 0)
 	return records, pairs[keep], len(pairs), m.shape[1]
 
 
@@ -263,8 +288,8 @@ def all_rows(g):
 # ---- the corpus of the GPU tests -----------------------------------------------------------------------------------------------------------
 
 class Item:
-	def __init__(self, name, g, rows, params=None, window=None):
-		self.name, self.g, self.rows, self.params, self.window = name, g, rows, params or Params(), window
+	def __init__(self, name, g, rows, params=None, window=None, arrays=False):
+		self.name, self.g, self.rows, self.params, self.window, self.arrays = name, g, rows, params or Params(), window, arrays   # arrays: expected() goes through evaluate_arrays()
 
 	def __repr__(self):
 		return self.name
@@ -371,3 +396,92 @@ def row_words_item():
 	rows = CM.repeated(all_rows(g), 64 * 5 + 7)
 	assert len(all_rows(g)) == 17 and (len(rows) + 63) // 64 == 6 and len(rows) % 64 == 7
 	return Item("row_words_%d" % len(rows), g, rows, Params(window_sites=T))
+
+
+# ---- batches of 4 160 to 32 768 rows: the threshold's two products beyond 64 bits -----------------------------------------------------------
+
+WIDE_CHOICE = np.array([
+	# copy: 0  1  2  3  4  5
+	[0, 1, 0, 1, 2, 0],      # site 0
+	[0, 0, 1, 1, 1, 2],      # site 1: copies 0-3 hold (0,0), (1,0), (0,1), (1,1) at sites (0, 1); copy 4 is missing at site 0, copy 5 at site 1
+	[1, 0, 1, 0, 1, 1],      # site 2: site 0 with its two bases exchanged: against site 1 the same den and D of the other sign
+	[0, 1, 1, 0, 0, 1],      # site 3: differs where exactly one of sites 0 and 1 holds its other base
+	[0, 0, 1, 1, 0, 1],      # site 4: site 1 with every copy called
+]).T
+
+
+@functools.lru_cache(maxsize=None)
+def wide_graph():
+	return graph_from_choice(WIDE_CHOICE, name="wide_graph")
+
+
+# (name, (c00, c10, c01, c11): how often copies 0-3 occur, (copies 4, 5), min_r2 as Context.site_ld gets it, NOT in lowest terms).
+# At sites (0, 1): n = c00 + c10 + c01 + c11, n_a = c10 + c11, n_b = c01 + c11, n_ab = c11 and D = c00 c11 - c10 c01.
+WIDE_TABLES = (
+	("r1", (138, 22801, 7297, 2532), (0, 0), (333333, 1000000)),
+	("r2", (16716, 1931, 8117, 6004), (0, 0), (999999, 1000000)),
+	("r3a", (31921, 78, 413, 356), (0, 0), (333333, 1000000)),
+	("r3b", (32326, 240, 39, 163), (0, 0), (333333, 1000000)),
+	("tie_quarter", (12288, 4096, 4096, 12288), (0, 0), (250000, 1000000)),            # D = 2^27, den = 2^56: r^2 = 1/4
+	("tie_quarter_above", (12289, 4095, 4096, 12288), (0, 0), (250000, 1000000)),      # one row from copy 1 to copy 0
+	("tie_quarter_below", (12287, 4097, 4096, 12288), (0, 0), (250000, 1000000)),      # one row from copy 0 to copy 1
+	("tie_one", (16384, 0, 0, 16384), (0, 0), (1000000, 1000000)),                     # r^2 = 1: nothing lies above it
+	("tie_one_below", (16383, 1, 0, 16384), (0, 0), (1000000, 1000000)),
+	("missing", (1900, 14727, 13182, 2448), (300, 211), (333333, 1000000)),            # 32 768 rows, n = 32 257 at sites (0, 1)
+	("rows_4160_r1", (2080, 1, 0, 2079), (0, 0), (500000, 1000000)),                   # 65 row words: the ninth LDS chunk holds one word
+	("rows_4160_r3b", (2070, 0, 1, 2089), (0, 0), (999999, 1000000)),
+)
+WIDE_MAX_ROWS = 32768
+
+
+@functools.lru_cache(maxsize=None)
+def wide_items():
+	"""Batches over wide_graph() whose rows are its six copies, each as often as WIDE_TABLES says, in a fixed random order: D^2 min_r2_den
+	and min_r2_num den pass 2^64 (from about 4 145 rows on with a denominator of 10^6), which no batch of corpus() reaches."""
+	items = []
+	for k, (name, table, missing, min_r2) in enumerate(WIDE_TABLES):
+		rows = np.repeat(np.arange(6), list(table) + list(missing))
+		rows = [int(r) for r in np.random.default_rng(100 + k).permutation(rows)]
+		item = Item("wide_%s" % name, wide_graph(), rows, Params(min_r2=min_r2))
+		item.table, item.missing = table, missing
+		items.append(item)
+	return items
+
+
+# ---- bands of 4 to 10 tiles over 10 strips -------------------------------------------------------------------------------------------------
+
+DEFAULT_WINDOW = 1000      # Context.site_ld's and --ld-window's
+
+
+def band_sites():
+	T, _ = kernel_constants()
+	return 9 * T + 5
+
+
+def band_windows():
+	T, _ = kernel_constants()
+	return (3 * T, 3 * T + 1, 4 * T + 1, 8 * T, 8 * T + 1, DEFAULT_WINDOW, MAX_WINDOW)
+
+
+BAND_THRESHOLDS = ((0, 1), (1, 5))      # every candidate with den != 0; few enough that whole tiles of a band hold no pair
+
+
+@functools.lru_cache(maxsize=None)
+def band_items():
+	"""band_sites() sites (10 strips) under windows that reach 4, 5, 6, 9 and all 10 tiles of a strip, and one graph with a site every
+	three bases whose window_columns ends inside the farthest tile of window_sites."""
+	T, _ = kernel_constants()
+	g = random_graph(band_sites(), seed=6)
+	items = [Item("band_w%d_r2_%d_%d" % (w, r2[0], r2[1]), g, all_rows(g), Params(window_sites=w, min_r2=r2), arrays=True) for w in band_windows() for r2 in BAND_THRESHOLDS]
+	g = random_graph(band_sites(), seed=7, spacing=3)
+	reach = int(g.site_columns[4 * T + 30] - g.site_columns[0])      # window_sites 5 T: the sixth tile holds the distances 4 T + 1 to 5 T
+	items.append(Item("band_columns_%d" % reach, g, all_rows(g), Params(window_sites=5 * T, window_columns=reach, min_r2=(0, 1)), arrays=True))
+	return items
+
+
+def strips_and_blocks(n_sites, window_sites):
+	"""(n_strips, n_blocks) as include/v2m_hip.h and csrc/ld_kernels.hpp say them: strips of T sites, and per strip the tiles its band
+	reaches, the strip's own and ceil(window_sites / T) more, at most all strips."""
+	T, _ = kernel_constants()
+	n_strips = -(-n_sites // T)
+	return n_strips, min(n_strips, -(-window_sites // T) + 1)

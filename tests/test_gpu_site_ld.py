@@ -4,7 +4,8 @@ through the device form, with guard bytes around its buffers, and the site and p
 record and in order.
 
 tests/test_site_ld_host.py asserts, without a GPU, that the corpus holds the site counts, bands, row counts, thresholds, windows and
-bytes it is here for."""
+bytes it is here for, that wide_items() (4 160 and 32 768 rows) reach every way the threshold's two 128-bit products can compare, and
+that band_items() (581 sites) reach bands of 4 to 10 tiles a strip."""
 
 import ctypes as C
 import io
@@ -256,6 +257,101 @@ def test_emit_ranges(v2m, ctx, monkeypatch):
 	check_item(ctx, item, "one range again")
 
 
+# ---- the threshold beyond 64 bits: batches of 4 160 and 32 768 rows --------------------------------------------------------------------------
+
+def wide_named(name):
+	return next(i for i in LM.wide_items() if i.name == name)
+
+
+@pytest.mark.parametrize("item", LM.wide_items(), ids=[i.name for i in LM.wide_items()])
+def test_wide_rows(v2m, ctx, item):
+	"""ld_reported() where D^2 min_r2_den and min_r2_num den pass 2^64: the high words decide against the low ones (R1, R2), are equal
+	and not 0 (R3, the ties and their neighbours); tests/test_site_ld_host.py names the regime of every item."""
+	upload(v2m, ctx, item.g)
+	check_item(ctx, item)
+
+
+def test_wide_rows_in_slices(v2m, ctx, monkeypatch):
+	"""V2M_SITE_LD_MAX_ROWS rows in slices of 1 000: 33 launches of ld_pack_kernel into 512 row words, no slice but the first beginning
+	on a word."""
+	from vcf2multialign_amd import _native as N
+	item = wide_named("wide_r1")
+	assert len(item.rows) == N.SITE_LD_MAX_ROWS
+	upload(v2m, ctx, item.g)
+	pitch = int(ctx.min_row_pitch)
+	monkeypatch.setenv("V2M_RING_SLOT_BYTES", str(1000 * pitch + pitch // 2))
+	ctx.profile_enable(True)
+	ctx.profile_reset()
+	try:
+		sites, pairs = ctx.site_ld(item.rows, **item.params.kwargs())
+		launches = ctx.profile_get(N.KERNEL_COLUMN_COUNTS)[0]
+		assert launches == (len(item.rows) + 999) // 1000 == 33, launches
+	finally:
+		ctx.profile_reset()
+		ctx.profile_enable(False)
+	want_sites, want_pairs, _, _ = LM.expected(item)
+	same_records(sites, want_sites, "in slices: the sites")
+	same_records(pairs, want_pairs, "in slices: the pairs")
+	check_item(ctx, item, "%s in slices of 1000 rows" % item.name)
+
+
+def test_wide_rows_in_word_groups(v2m, ctx, monkeypatch):
+	"""The 512 row words in groups of three: 170 whole groups and one of two words."""
+	item = wide_named("wide_r1")
+	upload(v2m, ctx, item.g)
+	monkeypatch.setenv("V2M_SITE_LD_WORDS_PER_GROUP", "3")
+	check_item(ctx, item, "%s, 3 words a group" % item.name)
+
+
+# ---- bands of 4 to 10 tiles over 10 strips ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("item", LM.band_items(), ids=[i.name for i in LM.band_items()])
+def test_bands(v2m, ctx, item):
+	"""A strip's cells in one, two and three trips of scan_tile_counts_kernel, ld_pairs_kernel<true>'s cells[cell + 1] across up to ten
+	tiles, interior strips whose whole band is live and strips whose band leaves the strips."""
+	upload(v2m, ctx, item.g)
+	check_item(ctx, item)
+
+
+def ranges_of(per_strip, block_pairs):
+	"""The pairs of the emit ranges as include/v2m_hip.h says them: whole strips while their records fit the block, at least one strip;
+	a range without a pair is passed over.  [(first strip, strips, pairs)]."""
+	out, i = [], 0
+	while i < len(per_strip):
+		j, count = i + 1, per_strip[i]
+		while j < len(per_strip) and count + per_strip[j] <= block_pairs:
+			count += per_strip[j]
+			j += 1
+		if count:
+			out.append((i, j - i, count))
+		i = j
+	return out
+
+
+def test_band_emit_ranges(v2m, ctx, monkeypatch):
+	"""Emit ranges over ten strips of a band of five tiles: a strip a range, and three strips a range, so that ranges begin at strips
+	3 and 6 and ld_pairs_kernel<true> takes strip_bases[ti] - out_base for a strip_first beyond 2."""
+	item = next(i for i in LM.band_items() if i.name == "band_w%d_r2_0_1" % (3 * T + 1))
+	upload(v2m, ctx, item.g)
+	want_sites, want_pairs, _, _ = LM.expected(item)
+	per_strip = np.bincount(want_pairs["site_a"] // T, minlength=10).tolist()
+	assert len(per_strip) == 10 and all(per_strip) and sum(per_strip) == len(want_pairs)
+	three = max(sum(per_strip[i:i + 3]) for i in range(8))
+	for block_bytes, strips in ((1, 1), (RECORD * three, 3)):
+		ranges = ranges_of(per_strip, max(1, block_bytes // RECORD))
+		assert ranges[0][1] == strips and len(ranges) >= 3 and ranges[1][0] == strips and (strips == 1 or ranges[1][1] == 3 and ranges[2][0] == 6), ranges
+		monkeypatch.setenv("V2M_SITE_LD_BLOCK_BYTES", str(block_bytes))
+		sites, pairs = ctx.site_ld(item.rows, **item.params.kwargs())
+		assert ctx.site_ld_blocks == [count for _, _, count in ranges], (ctx.site_ld_blocks, ranges)
+		same_records(sites, want_sites, "%d strips a range: the sites" % strips)
+		order = pairs["site_a"].astype(np.int64) * len(want_sites) + pairs["site_b"]
+		assert (np.diff(order) > 0).all(), "%d strips a range: the pairs are not in the order (s, t)" % strips
+		same_records(pairs, want_pairs, "%d strips a range: the pairs" % strips)
+		check_device(ctx, item.rows, item.params, want_sites, want_pairs, "device form, %d strips a range" % strips)
+	monkeypatch.delenv("V2M_SITE_LD_BLOCK_BYTES")
+	check_item(ctx, item, "one range again")
+
+
 def test_plane_budget(v2m, ctx, monkeypatch):
 	"""A plane budget one byte too small is V2M_ERR_UNSUPPORTED with the bytes needed in the message; the exact budget passes."""
 	from vcf2multialign_amd import _native as N
@@ -491,6 +587,12 @@ CHECKED_CORPUS = [
 	"tests/test_gpu_site_ld.py::test_plane_budget",
 	"tests/test_gpu_site_ld.py::test_sinks",
 	"tests/test_gpu_site_ld.py::test_the_views_are_left_as_they_were",
+	# batches of 4 160 and 32 768 rows (512 row words of planes), strips of up to 640 cells
+	"tests/test_gpu_site_ld.py::test_wide_rows",
+	"tests/test_gpu_site_ld.py::test_wide_rows_in_slices",
+	"tests/test_gpu_site_ld.py::test_wide_rows_in_word_groups",
+	"tests/test_gpu_site_ld.py::test_bands",
+	"tests/test_gpu_site_ld.py::test_band_emit_ranges",
 ]
 
 

@@ -192,6 +192,191 @@ def test_the_windows(modelled):
 			assert records["column"].astype(np.int64).tolist() == [c for c in whole if b <= c < e]      # absolute columns
 
 
+# ---- the threshold beyond 64 bits (wide_items()) ---------------------------------------------------------------------------------------------
+
+WORD = 1 << 64
+
+
+def products(p, min_r2):
+	"""(D, A, B): the sides of the rule, A = D^2 min_r2_den and B = min_r2_num den, as Python's integers."""
+	d, den = LM.d_and_den(p["n"], p["n_a"], p["n_b"], p["n_ab"])
+	return d, d * d * int(min_r2[1]), int(min_r2[0]) * den
+
+
+def regime(a, b):
+	"""Where a comparison of A and B by 64-bit words is decided."""
+	a_hi, a_lo, b_hi, b_lo = a // WORD, a % WORD, b // WORD, b % WORD
+	if a_hi == 0 and b_hi == 0:
+		return "low words only"
+	if a == b:
+		return "tie"
+	if a_hi == b_hi:
+		return "R3a" if a_lo >= b_lo else "R3b"
+	if a_hi > b_hi:
+		return "R1" if a_lo < b_lo else "high and low agree: reported"
+	return "R2" if a_lo >= b_lo else "high and low agree: not reported"
+
+
+@pytest.fixture(scope="module")
+def wide():
+	"""{name: (item, site records, pairs of every candidate, reported)} of wide_items()."""
+	out = {}
+	for item in LM.wide_items():
+		records, pairs, keep = LM.evaluate(PM.classes(CM.matrix(item.g, item.rows)), item.params)
+		out[item.name] = (item, records, pairs, keep)
+	return out
+
+
+def pair_01(entry):
+	"""The pair of sites 0 and 1 of wide_graph() (its first two columns)."""
+	item, records, pairs, keep = entry
+	cols = [int(c) for c in item.g.site_columns[:2]]
+	assert [int(c) for c in records["column"][:2]] == cols
+	k = next(i for i, p in enumerate(pairs) if (p["site_a"], p["site_b"]) == (0, 1))
+	return pairs[k], bool(keep[k])
+
+
+def test_no_old_item_leaves_64_bits(modelled):
+	"""The gap wide_items() is there for: in every pair corpus() and row_words_item() evaluate both products are below 2^64 (below 2^58)."""
+	most = 0
+	item = LM.row_words_item()
+	extra = LM.evaluate(PM.classes(CM.matrix(item.g, item.rows)), item.params)
+	for item, pairs in [(i, p) for i, _, _, p, _ in modelled] + [(item, extra[1])]:
+		for p in pairs:
+			_, a, b = products(p, item.params.min_r2)
+			most = max(most, a, b)
+			assert regime(a, b) == "low words only", (item.name, p)
+	assert max(len(item.rows) for item, *_ in modelled) == 128 * CHUNK + 1 and 0 < most < 1 << 58
+
+
+def test_wide_items_reach_every_regime(wide):
+	assert [n for n in wide] == ["wide_" + t[0] for t in LM.WIDE_TABLES]
+	from vcf2multialign_amd import _native as N
+	assert LM.WIDE_MAX_ROWS == N.SITE_LD_MAX_ROWS
+	# the tables are what sites 0 and 1 count, and their pair lands in the regime it is named for
+	named = {"wide_r1": ("R1", True), "wide_r2": ("R2", False), "wide_r3a": ("R3a", True), "wide_r3b": ("R3b", False), "wide_tie_quarter": ("tie", True),
+		"wide_tie_one": ("tie", True), "wide_missing": ("R1", True), "wide_rows_4160_r1": ("R1", True), "wide_rows_4160_r3b": ("R3b", False)}
+	for name, entry in wide.items():
+		item = entry[0]
+		c00, c10, c01, c11 = item.table
+		p, kept = pair_01(entry)
+		assert tuple(int(p[k]) for k in ("n", "n_a", "n_b", "n_ab")) == (c00 + c10 + c01 + c11, c10 + c11, c01 + c11, c11), name
+		d, a, b = products(p, item.params.min_r2)
+		assert d == c00 * c11 - c10 * c01 and kept == (a >= b) and a // WORD, name
+		assert len(item.rows) == sum(item.table) + sum(item.missing) and item.params.min_r2[1] == 1000000      # the largest denominator, also where the fraction has a smaller one
+		if name in named:
+			assert (regime(a, b), kept) == named[name], (name, regime(a, b), kept)
+	assert {math.gcd(*wide[n][0].params.min_r2) for n in ("wide_tie_quarter", "wide_tie_one", "wide_rows_4160_r1")} == {250000, 1000000, 500000}      # passed on as they are
+	# a tie's neighbours, one row moved between two copies: A - B on either side of 0, within one part in a thousand of A, and the outcome flips
+	for tie, near in (("wide_tie_quarter", (("wide_tie_quarter_above", True), ("wide_tie_quarter_below", False))), ("wide_tie_one", (("wide_tie_one_below", False),))):
+		_, a0, b0 = products(pair_01(wide[tie])[0], wide[tie][0].params.min_r2)
+		assert a0 == b0
+		for name, above in near:
+			item = wide[name][0]
+			assert sum(abs(x - y) for x, y in zip(item.table, wide[tie][0].table)) == 2 and item.params.min_r2 == wide[tie][0].params.min_r2
+			p, kept = pair_01(wide[name])
+			_, a, b = products(p, item.params.min_r2)
+			assert kept == above == (a > b) and a != b and a // WORD and abs(a - b) * 1000 < a, name
+	assert (regime(*products(pair_01(wide["wide_tie_quarter_above"])[0], (250000, 1000000))[1:]), regime(*products(pair_01(wide["wide_tie_quarter_below"])[0], (250000, 1000000))[1:])) == ("R3a", "R3b")
+	# every regime, D of either sign beyond 64 bits, missing rows, and the row counts
+	seen, signs, short = set(), set(), 0
+	for name, (item, records, pairs, keep) in wide.items():
+		assert len(pairs) >= 3, name                       # several pairs a call
+		for p, k in zip(pairs, keep):
+			d, a, b = products(p, item.params.min_r2)
+			r = regime(a, b)
+			seen.add(r)
+			if r != "low words only":
+				signs.add(d > 0)
+				short += int(p["n"] < len(item.rows))
+				assert d * d < 1 << 60 and LM.d_and_den(p["n"], p["n_a"], p["n_b"], p["n_ab"])[1] <= 1 << 56      # the header's bounds
+	assert {"R1", "R2", "R3a", "R3b", "tie", "high and low agree: reported", "high and low agree: not reported"} <= seen, seen
+	assert signs == {True, False} and short >= 3
+	rows = sorted({len(item.rows) for item, *_ in wide.values()})
+	assert rows == [65 * 64, LM.WIDE_MAX_ROWS] and sum(1 for item, *_ in wide.values() if len(item.rows) == LM.WIDE_MAX_ROWS) >= 10
+	assert (65 * 64 + 63) // 64 == 8 * CHUNK + 1           # 65 row words: a ninth chunk of one word
+	p, _ = pair_01(wide["wide_missing"])
+	assert p["n"] == LM.WIDE_MAX_ROWS - 511
+	# the rows are mixed: no 64-row word of the largest batch holds one copy only
+	item = wide["wide_r1"][0]
+	assert all(len(set(item.rows[w:w + 64])) > 1 for w in range(0, len(item.rows), 64))
+	# the smallest row count at which a product can pass 2^64: |D| <= n^2 / 4
+	least = next(n for n in range(1, 5000) if (n * n // 4) ** 2 * 1000000 >= WORD)
+	assert 64 * 64 < least <= 65 * 64 and least == 4145
+
+
+def test_evaluate_arrays_is_evaluate(modelled, wide):
+	"""The model's path without loops against the one with, on every item of the old corpus and of wide_items(), and on a band."""
+	def same(item, records, pairs, keep):
+		r, p, k = LM.evaluate_arrays(PM.classes(CM.matrix(item.g, item.rows, item.window)), item.params, item.window[0] if item.window else 0)
+		assert r.dtype == records.dtype and p.dtype == pairs.dtype == LM.PAIR_DTYPE and k.dtype == keep.dtype == bool, item.name
+		assert np.array_equal(r, records) and np.array_equal(p, pairs) and np.array_equal(k, keep), item.name
+	for item, _, records, pairs, keep in modelled:
+		same(item, records, pairs, keep)
+	for item, records, pairs, keep in wide.values():
+		same(item, records, pairs, keep)
+	for name in ("band_w%d_r2_1_5" % (3 * T + 1), next(i.name for i in LM.band_items() if i.name.startswith("band_columns"))):
+		item = next(i for i in LM.band_items() if i.name == name)
+		same(item, *LM.evaluate(PM.classes(CM.matrix(item.g, item.rows)), item.params))
+
+
+# ---- bands of more than three tiles (band_items()) -------------------------------------------------------------------------------------------
+
+def test_band_items_reach_every_band_shape():
+	items = {i.name: i for i in LM.band_items()}
+	V = LM.band_sites()
+	assert V == 9 * T + 5 and LM.DEFAULT_WINDOW == 1000
+	import inspect
+	import vcf2multialign_amd as v
+	assert inspect.signature(v.Context.site_ld).parameters["window_sites"].default == LM.DEFAULT_WINDOW
+	# n_strips = ceil(V / T), n_blocks = min(n_strips, ceil(window_sites / T) + 1), restated here
+	want = {3 * T: 4, 3 * T + 1: 5, 4 * T + 1: 6, 8 * T: 9, 8 * T + 1: 10, LM.DEFAULT_WINDOW: 10, LM.MAX_WINDOW: 10}
+	assert tuple(want) == LM.band_windows()
+	cells = set()
+	for w, n_blocks in want.items():
+		n_strips = (V + T - 1) // T
+		assert n_strips == 10 and min(n_strips, (w + T - 1) // T + 1) == n_blocks == LM.strips_and_blocks(V, w)[1]
+		cells.add(T * n_blocks)
+		for r2 in LM.BAND_THRESHOLDS:
+			item = items["band_w%d_r2_%d_%d" % (w, r2[0], r2[1])]
+			records, pairs, n_candidates, _ = LM.expected(item)
+			assert len(records) == V and len(item.rows) == 17 and item.params.window_sites == w and item.params.window_columns == 0
+			assert n_candidates == sum(min(V - 1 - s, w) for s in range(V))
+			if r2 == (0, 1):
+				assert n_candidates - 200 < len(pairs) <= n_candidates      # all but those with den = 0: every rank of every cell is written
+			else:
+				assert 0 < 4 * len(pairs) < n_candidates
+	# scan_tile_counts_kernel over a strip's cells: exactly one trip of 256, two trips, three
+	assert {256, 320, 576} <= cells and max(cells) == 640
+	assert items["band_w%d_r2_0_1" % (LM.DEFAULT_WINDOW)].params.window_sites == 1000 > V
+	# an interior strip whose whole band lies inside the strips; a strip before the last two with a tile beyond them
+	for w in (3 * T, 3 * T + 1, 4 * T + 1):
+		n_strips, n_blocks = LM.strips_and_blocks(V, w)
+		assert any(0 < ti < n_strips - 1 and ti + n_blocks <= n_strips for ti in range(n_strips))
+		assert any(ti < n_strips - 2 and ti + n_blocks - 1 >= n_strips for ti in range(n_strips))
+	# ... and the pairs are there: the farthest tile of an interior strip reports pairs, ranges begin beyond strip 2, and under
+	# r^2 >= 1/5 some tile inside the strips holds no reported pair while its strip holds some (tile_live)
+	for w, n_blocks in want.items():
+		dense = LM.expected(items["band_w%d_r2_0_1" % w])[1]
+		tiles = set(zip((dense["site_a"] // T).tolist(), (dense["site_b"] // T).tolist()))
+		assert (1, n_blocks) in tiles or n_blocks == 10, w
+		assert (0, n_blocks - 1) in tiles and all(tj - ti < n_blocks for ti, tj in tiles)
+		assert {ti for ti, _ in tiles} == set(range(10))
+	sparse = LM.expected(items["band_w%d_r2_1_5" % (3 * T + 1)])[1]
+	tiles = set(zip((sparse["site_a"] // T).tolist(), (sparse["site_b"] // T).tolist()))
+	dead = [(ti, ti + b) for ti in range(10) for b in range(5) if ti + b < 10 and (ti, ti + b) not in tiles]
+	assert sum(1 for ti, _ in dead if any(x == ti for x, _ in tiles)) >= 3, dead
+	# the graph with a site every three bases: window_columns ends inside the sixth tile, the farthest of window_sites = 5 T
+	item = next(i for i in LM.band_items() if i.name.startswith("band_columns"))
+	records, pairs, n_candidates, _ = LM.expected(item)
+	assert len(records) == V and (np.diff(records["column"].astype(np.int64)) == 3).all() and item.params.window_columns == 3 * (4 * T + 30)
+	assert LM.strips_and_blocks(V, item.params.window_sites) == (10, 6)
+	far = pairs[pairs["site_b"] // T - pairs["site_a"] // T == 5]
+	gap = (pairs["site_b"].astype(np.int64) - pairs["site_a"]).max()
+	assert len(far) and gap == 4 * T + 30 and 4 * T + 1 < gap < item.params.window_sites
+	assert n_candidates == sum(min(V - 1 - s, 4 * T + 30) for s in range(V))
+
+
 # ---- the text --------------------------------------------------------------------------------------------------------------------------------
 
 def test_site_ld_text():
@@ -224,6 +409,25 @@ def test_site_ld_text():
 		host.site_ld_text(8, L, records, bad, g.reference_positions, g.aligned_positions)
 	with pytest.raises(ValueError):
 		host.site_ld_text(8, L, records[:1], pairs[:1], g.reference_positions, g.aligned_positions)
+
+
+def test_site_ld_text_beyond_2_53(wide):
+	"""r2 of pairs whose D^2 (and den) no double holds exactly: both integers are rounded to doubles once, then divided."""
+	from vcf2multialign_amd import host
+	beyond = 0
+	for name, (item, records, pairs, keep) in wide.items():
+		L = item.g.aligned_length
+		for chosen in (pairs[keep], pairs[[den_of(p) != 0 for p in pairs]]):      # as reported; and every pair the text takes
+			got = host.site_ld_text(len(item.rows), L, records, chosen, item.g.reference_positions, item.g.aligned_positions, **item.params.kwargs())
+			assert got == LM.text(item.g, len(item.rows), L, records, chosen, item.params), name
+			for p in chosen:
+				d, den = LM.d_and_den(p["n"], p["n_a"], p["n_b"], p["n_ab"])
+				beyond += int(d * d > 1 << 53 and float(d * d) != d * d)
+	assert beyond > 20, beyond
+	# the two ties, spelt out
+	for name, r2 in (("wide_tie_quarter", "0.250000"), ("wide_tie_one", "1.000000")):
+		p = pair_01(wide[name])[0]
+		assert LM.d_and_den(p["n"], p["n_a"], p["n_b"], p["n_ab"])[0] ** 2 > 1 << 53 and LM.r2_text(p) == r2
 
 
 def test_parse_decimal_fraction():
