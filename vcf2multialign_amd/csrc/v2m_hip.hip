@@ -267,10 +267,12 @@ struct v2m_ctx {
 	pinned_buf h_ops_stage, h_ops_out;
 	std::vector<v2m_aln_op> ops_row;
 	// column counts (v2m_column_counts): the sink form's table, the staged byte lanes of a call whose slices hold few rows, a column
-	// range's block counts and total, its records (two, used in turn) and the total's pinned staging (two likewise)
+	// range's block counts and total, its records (two, used in turn) and the total's pinned staging (two likewise).  The table, the
+	// block counts, the total and its staging are also what select_sites_count takes for every analysis that selects sites (pair
+	// distances, variable sites, site LD, parsimony); the staging's second word is the weighted pair distances' OR of the weights
 	scratch_buf d_column_table, d_column_stage, d_column_blocks, d_column_total, d_column_records[2];
 	pinned_buf h_column_total;
-	// pair distances (v2m_pair_distances): the site list, a pass's bit planes, and the host form's matrix
+	// pair distances (v2m_pair_distances): the site list (select_rule_sites_emit), a pass's bit planes, and the host form's matrix
 	scratch_buf d_dist_sites, d_dist_planes, d_dist_matrix;
 	// bootstrap (v2m_pair_distances_weighted, v2m_bootstrap_distances, v2m_nj_bootstrap): explicit weights by column, a replicate's
 	// weights by site rank, their 32 bit slices, the OR of the weights, and a replicate's matrix
@@ -281,7 +283,8 @@ struct v2m_ctx {
 	// its pinned staging, and for the host form a range's leaf bytes, the branch counters and a range's records and mutations (two, in turn)
 	scratch_buf d_fitch_sets, d_fitch_joins, d_fitch_blocks, d_fitch_total, d_fitch_bytes, d_fitch_branches, d_fitch_sites[2], d_fitch_mutations[2];
 	pinned_buf h_fitch_total;
-	// variable sites (v2m_variable_sites): the site list, the host form's gathered slices (two, used in turn), the list's pinned staging
+	// variable sites (v2m_variable_sites) and parsimony: the site list (select_rule_sites_emit), the host form's gathered slices (two,
+	// used in turn), the list's pinned staging (fetch_site_columns)
 	scratch_buf d_site_columns, d_site_bytes[2];
 	pinned_buf h_site_columns;
 	// site LD (v2m_site_ld): the site list and the records, the bit planes, the (site, tile) cells, the strips' totals and bases, the
@@ -3145,6 +3148,179 @@ int v2m_row_ops(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_ops
 }
 
 
+// ---- what the analyses share -----------------------------------------------------------------------
+// The host-side steps that every analysis below (column counts to parsimony) takes the same way.  A new analysis starts from these.
+
+extern "C++" {   // (templates and overloads, within the C ABI's block)
+namespace {
+
+// The stages of an analysis call, timed with events of their own while profiling is on (they have no V2M_KERNEL_* ids): a stage's
+// segments are bracketed as they are queued and summed after the call's last synchronisation.  A segment is one event pair around
+// everything the stage queues -- the counts and the pack segment span every slice -- so a figure is time elapsed on the stream, with
+// whatever gaps the host's queueing leaves between the launches, not summed kernel time.
+struct stage_times {
+	enum { counts, pack, pairs, weights, weighted_pairs, n_stages };   // (the last two: the bootstrap's weighted path)
+	struct segment { int stage; hipEvent_t begin, end; };
+	v2m_ctx *ctx;
+	std::vector<segment> segments;
+	explicit stage_times(v2m_ctx *c) : ctx(c) {}
+	stage_times(stage_times const &) = delete;
+	~stage_times() { for (auto &s : segments) { (void) hipEventDestroy(s.begin); (void) hipEventDestroy(s.end); } }
+	void begin(int stage)
+	{
+		if (!ctx->profiling) return;
+		segment s{stage, nullptr, nullptr};
+		if (hipSuccess != hipEventCreate(&s.begin)) return;
+		if (hipSuccess != hipEventCreate(&s.end)) { (void) hipEventDestroy(s.begin); return; }
+		(void) hipEventRecord(s.begin, ctx->stream);
+		segments.push_back(s);
+	}
+	void end() { if (ctx->profiling && !segments.empty()) (void) hipEventRecord(segments.back().end, ctx->stream); }
+	// a stage's sum, after the stream is idle
+	double ms(int stage) const
+	{
+		double sum(0);
+		for (auto const &s : segments) {
+			float t(0);
+			if (s.stage == stage && hipSuccess == hipEventElapsedTime(&t, s.begin, s.end)) sum += double(t);
+		}
+		return sum;
+	}
+};
+
+// Takes `bytes` of a call's scratch; a refusal names the call (`prefix`), the size and the buffer (`what`).
+int ensure_named(v2m_ctx *ctx, scratch_buf &buf, u64 bytes, char const *prefix, char const *what)
+{
+	hipError_t const st(buf.ensure(bytes));
+	if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "%s: %llu bytes of %s: %s", prefix, (unsigned long long) bytes, what, hipGetErrorString(st));
+	return V2M_OK;
+}
+
+// The same for pinned staging, which is host memory whatever the runtime calls its refusal.
+int ensure_named(v2m_ctx *ctx, pinned_buf &buf, u64 bytes, char const *prefix, char const *what)
+{
+	if (hipSuccess != buf.ensure(bytes)) return fail(ctx, V2M_ERR_OUT_OF_MEMORY, "%s: %llu bytes of pinned %s", prefix, (unsigned long long) bytes, what);
+	return V2M_OK;
+}
+
+// The end of a call: leaves the compute stream, and the copy stream where the call used it, idle whatever happened.  Returns rc; the
+// synchronisation's own error only when rc was V2M_OK.
+int drain(v2m_ctx *ctx, int rc, bool both_streams)
+{
+	hipError_t const st(hipStreamSynchronize(ctx->stream));
+	if (both_streams) (void) hipStreamSynchronize(ctx->copy_stream);
+	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
+	return rc;
+}
+
+// Two buffers in turn: unit k is issued into device buffer and pinned slot k & 1 and crosses the link on the copy stream while unit
+// k + 1 is issued; hand_over(k) waits for unit k's copy on the host, so both buffers of unit k are free again when unit k - 2 has been
+// handed over, before unit k - 1 is queued.  Ends at the first status that is not V2M_OK and returns it.
+template <typename t_issue, typename t_hand_over>
+int in_turn(u64 n, t_issue const &issue, t_hand_over const &hand_over)
+{
+	for (u64 k(0); k < n; ++k) {
+		if (int const rc = issue(k)) return rc;
+		if (k >= 1) if (int const rc = hand_over(k - 1)) return rc;   // its copy ran under unit k's kernels
+	}
+	return n ? hand_over(n - 1) : V2M_OK;
+}
+
+// The tail of an issue: what the compute stream has queued so far into d_src crosses the link into pinned slot b, at host_offset.
+// The caller records the slot's `copied` after the last copy of the unit.
+int copy_to_slot(v2m_ctx *ctx, int b, void const *d_src, u64 bytes, u64 host_offset = 0)
+{
+	V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
+	V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
+	V2M_HIP_TRY(ctx, hipMemcpyAsync(ctx->host_slots[b]->host.as<char>() + host_offset, d_src, bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
+	return V2M_OK;
+}
+
+int column_counts_zero(v2m_ctx *ctx, u32 *d_table, u64 plane_pitch, u64 L);
+int column_counts_accumulate(v2m_ctx *ctx, v2m_row_batch const *rows, u32 *d_table, u64 plane_pitch);
+
+// What the first half of a site selection leaves: the counts' table, the selection's blocks with their offsets, and the sites' number.
+struct site_selection { u32 *table{}; u64 table_pitch{}; u32 *blocks{}; u64 select_blocks{}; u64 V{}; };
+
+// The first half of a site selection, completed on the stream: the counts of the batch over the view in force into
+// ctx->d_column_table, the rule's count kernel -- launch_count(table, table_pitch, blocks, select_blocks) -- over them, the scan of its
+// blocks, and the total (d_column_total through h_column_total, whose second word is the caller's).  One segment of the counts stage;
+// the caller's emit is the second.  n_rows >= 1, L >= 1.
+template <typename t_launch>
+int select_sites_count(v2m_ctx *ctx, v2m_row_batch const *rows, stage_times &times, char const *prefix, t_launch const &launch_count, site_selection &sel)
+{
+	u64 const L(ctx->view().length());
+	sel.table_pitch = (L + 3) & ~u64(3);
+	sel.select_blocks = (L + v2m::kSelectColumns - 1) / v2m::kSelectColumns;
+	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(V2M_COUNT_CLASSES * sel.table_pitch * 4));
+	V2M_HIP_TRY(ctx, ctx->d_column_blocks.ensure(std::max<u64>(sel.select_blocks * sizeof(u32), 16)));
+	V2M_HIP_TRY(ctx, ctx->d_column_total.ensure(sizeof(u64)));
+	V2M_HIP_TRY(ctx, ctx->h_column_total.ensure(2 * sizeof(u64)));
+	V2M_POISON_HOST(ctx->h_column_total.p, 2 * sizeof(u64));
+	sel.table = ctx->d_column_table.as<u32>();
+	sel.blocks = ctx->d_column_blocks.as<u32>();
+	times.begin(stage_times::counts);
+	int rc(column_counts_zero(ctx, sel.table, sel.table_pitch, L));
+	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, sel.table, sel.table_pitch);
+	if (V2M_OK != rc) return rc;
+	launch_count(sel.table, sel.table_pitch, sel.blocks, sel.select_blocks);
+	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, sel.blocks, u32(sel.select_blocks), ctx->d_column_total.as<u64>());
+	times.end();
+	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "%s: the site selection did not launch", prefix);
+	if (hipSuccess != hipMemcpyAsync(ctx->h_column_total.p, ctx->d_column_total.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
+		|| hipSuccess != hipStreamSynchronize(ctx->stream))
+		return fail(ctx, V2M_ERR_HIP, "%s: the site count did not arrive", prefix);
+	sel.V = *ctx->h_column_total.as<u64>();
+	if (sel.V > L) return fail(ctx, V2M_ERR_HIP, "the site selection counted %llu of %llu columns", (unsigned long long) sel.V, (unsigned long long) L);
+	return V2M_OK;
+}
+
+// Both halves for the variable-site rule (snp: the SNP rule, site_kernels.hpp) over a batch of n rows.  The emit half takes `entries`
+// >= sel.V >= 1 entries of `list` and leaves the sites' columns, relative to the view, in it; `emit_name` is what a refused launch is
+// called.
+int select_rule_sites_count(v2m_ctx *ctx, v2m_row_batch const *rows, bool snp, stage_times &times, char const *prefix, site_selection &sel)
+{
+	return select_sites_count(ctx, rows, times, prefix, [&](u32 *table, u64 table_pitch, u32 *blocks, u64 select_blocks) {
+		if (snp)
+			hipLaunchKernelGGL(v2m::count_snp_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream, table, table_pitch, ctx->view().length(), blocks);
+		else
+			hipLaunchKernelGGL(v2m::count_variable_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+				table, table_pitch, u64(0), ctx->view().length(), u32(rows->n_rows), 1u, blocks);
+	}, sel);
+}
+
+int select_rule_sites_emit(v2m_ctx *ctx, u64 n, bool snp, stage_times &times, char const *prefix, site_selection const &sel, scratch_buf &list, u64 entries, char const *emit_name)
+{
+	u64 const L(ctx->view().length());
+	if (int const rc = ensure_named(ctx, list, entries * sizeof(u32), prefix, "the site list")) return rc;
+	u32 *const sites(list.as<u32>());
+	times.begin(stage_times::counts);
+	if (snp)
+		hipLaunchKernelGGL(v2m::emit_snp_columns_kernel, dim3(unsigned(sel.select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream, sel.table, sel.table_pitch, L, sel.blocks, sites, sel.V);
+	else
+		hipLaunchKernelGGL(v2m::emit_site_columns_kernel, dim3(unsigned(sel.select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+			sel.table, sel.table_pitch, L, u32(n), sel.blocks, sites, sel.V);
+	times.end();
+	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "%s: %s did not launch", prefix, emit_name);
+	return V2M_OK;
+}
+
+// The V sites of ctx->d_site_columns through pinned staging to the host, completed: relative to the view, as the kernels leave them.
+int fetch_site_columns(v2m_ctx *ctx, u64 V, char const *prefix, u32 const *&relative)
+{
+	if (int const rc = ensure_named(ctx, ctx->h_site_columns, V * sizeof(u32), prefix, "site list")) return rc;
+	V2M_POISON_HOST(ctx->h_site_columns.p, V * sizeof(u32));
+	if (hipSuccess != hipMemcpyAsync(ctx->h_site_columns.p, ctx->d_site_columns.p, V * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream)
+		|| hipSuccess != hipStreamSynchronize(ctx->stream))
+		return fail(ctx, V2M_ERR_HIP, "%s: the site list did not arrive", prefix);
+	relative = ctx->h_site_columns.as<u32>();
+	return V2M_OK;
+}
+
+} // namespace
+} // extern "C++"
+
+
 // ---- column counts ---------------------------------------------------------------------------------
 
 namespace {
@@ -3249,9 +3425,7 @@ int v2m_column_counts_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t f
 	int rc(V2M_OK);
 	if (!(flags & V2M_COUNTS_ACCUMULATE)) rc = column_counts_zero(ctx, table, plane_pitch, L);
 	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, table, plane_pitch);
-	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
-	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
-	return rc;
+	return drain(ctx, rc, false);
 }
 
 int v2m_column_counts(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_column_counts_sink_fn sink, void *user)
@@ -3334,38 +3508,6 @@ int v2m_column_counts(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v
 
 namespace {
 
-// The three stages of a pair-distance call, timed with events of their own while profiling is on (they have no V2M_KERNEL_* ids):
-// a stage's segments are bracketed as they are queued and summed after the call's last synchronisation.  A segment is one event pair
-// around everything the stage queues -- the counts and the pack segment span every slice -- so a figure is time elapsed on the stream,
-// with whatever gaps the host's queueing leaves between the launches, not summed kernel time.
-struct stage_times {
-	enum { counts, pack, pairs, weights, weighted_pairs, n_stages };   // (the last two: the bootstrap's weighted path)
-	struct segment { int stage; hipEvent_t begin, end; };
-	v2m_ctx *ctx;
-	std::vector<segment> segments;
-	explicit stage_times(v2m_ctx *c) : ctx(c) {}
-	stage_times(stage_times const &) = delete;
-	~stage_times() { for (auto &s : segments) { (void) hipEventDestroy(s.begin); (void) hipEventDestroy(s.end); } }
-	void begin(int stage)
-	{
-		if (!ctx->profiling) return;
-		segment s{stage, nullptr, nullptr};
-		if (hipSuccess != hipEventCreate(&s.begin)) return;
-		if (hipSuccess != hipEventCreate(&s.end)) { (void) hipEventDestroy(s.begin); return; }
-		(void) hipEventRecord(s.begin, ctx->stream);
-		segments.push_back(s);
-	}
-	void end() { if (ctx->profiling && !segments.empty()) (void) hipEventRecord(segments.back().end, ctx->stream); }
-	// after the stream is idle
-	void sum(double (&ms)[n_stages]) const
-	{
-		for (auto const &s : segments) {
-			float t(0);
-			if (hipSuccess == hipEventElapsedTime(&t, s.begin, s.end)) ms[s.stage] += double(t);
-		}
-	}
-};
-
 int check_pair_distances(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, char const *name)
 {
 	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
@@ -3421,13 +3563,9 @@ int pair_matrices_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, pair_j
 		return V2M_OK;
 	});
 	auto const finish([&](int rc) -> int {
-		hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
-		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
-		if (V2M_OK == rc) {
-			double ms[stage_times::n_stages] = {};
-			times.sum(ms);
-			out.counts_ms = ms[stage_times::counts]; out.pack_ms = ms[stage_times::pack]; out.pairs_ms = ms[stage_times::pairs];
-			job.weights_ms = ms[stage_times::weights]; job.weighted_pairs_ms = ms[stage_times::weighted_pairs];
+		if (V2M_OK == (rc = drain(ctx, rc, false))) {
+			out.counts_ms = times.ms(stage_times::counts); out.pack_ms = times.ms(stage_times::pack); out.pairs_ms = times.ms(stage_times::pairs);
+			job.weights_ms = times.ms(stage_times::weights); job.weighted_pairs_ms = times.ms(stage_times::weighted_pairs);
 			if (info) *info = out;
 		}
 		return rc;
@@ -3449,42 +3587,15 @@ int pair_matrices_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, pair_j
 	if (0 == L) return finish(all_zero());
 
 	// (1) the counts and the site list
-	u64 const table_pitch((L + 3) & ~u64(3));
-	u64 const select_blocks((L + v2m::kSelectColumns - 1) / v2m::kSelectColumns);
-	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(V2M_COUNT_CLASSES * table_pitch * 4));
-	V2M_HIP_TRY(ctx, ctx->d_column_blocks.ensure(std::max<u64>(select_blocks * sizeof(u32), 16)));
-	V2M_HIP_TRY(ctx, ctx->d_column_total.ensure(sizeof(u64)));
-	V2M_HIP_TRY(ctx, ctx->h_column_total.ensure(2 * sizeof(u64)));
-	V2M_POISON_HOST(ctx->h_column_total.p, 2 * sizeof(u64));
-	u32 *const table(ctx->d_column_table.as<u32>());
-	times.begin(stage_times::counts);
-	int rc(column_counts_zero(ctx, table, table_pitch, L));
-	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, table, table_pitch);
+	char const *const who("pair distances");
+	site_selection sel;
+	int rc(select_rule_sites_count(ctx, rows, false, times, who, sel));
 	if (V2M_OK != rc) return finish(rc);
-	hipLaunchKernelGGL(v2m::count_variable_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
-		table, table_pitch, u64(0), L, u32(n), 1u, ctx->d_column_blocks.as<u32>());
-	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->d_column_blocks.as<u32>(), u32(select_blocks), ctx->d_column_total.as<u64>());
-	times.end();
-	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: the site selection did not launch"));
-	if (hipSuccess != hipMemcpyAsync(ctx->h_column_total.p, ctx->d_column_total.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
-		|| hipSuccess != hipStreamSynchronize(ctx->stream))
-		return finish(fail(ctx, V2M_ERR_HIP, "pair distances: the site count did not arrive"));
-	u64 const V(*ctx->h_column_total.as<u64>());
-	if (V > L) return finish(fail(ctx, V2M_ERR_HIP, "the site selection counted %llu of %llu columns", (unsigned long long) V, (unsigned long long) L));
+	u64 const V(sel.V);
 	out.n_sites = V;
 	if (0 == V) return finish(all_zero());
-	auto const ensure([&](scratch_buf &buf, u64 bytes, char const *what) -> int {
-		hipError_t const st(buf.ensure(bytes));
-		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "pair distances: %llu bytes of %s: %s", (unsigned long long) bytes, what, hipGetErrorString(st));
-		return V2M_OK;
-	});
-	if (V2M_OK != (rc = ensure(ctx->d_dist_sites, V * sizeof(u32), "the site list"))) return finish(rc);
+	if (V2M_OK != (rc = select_rule_sites_emit(ctx, n, false, times, who, sel, ctx->d_dist_sites, V, "emit_site_columns_kernel"))) return finish(rc);
 	u32 *const sites(ctx->d_dist_sites.as<u32>());
-	times.begin(stage_times::counts);
-	hipLaunchKernelGGL(v2m::emit_site_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
-		table, table_pitch, L, u32(n), ctx->d_column_blocks.as<u32>(), sites, V);
-	times.end();
-	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "pair distances: emit_site_columns_kernel did not launch"));
 
 	// the passes: ranges of whole chunks whose planes fit the budget
 	u64 const n_tiles((n + v2m::kPairTile - 1) / v2m::kPairTile), n_pad(n_tiles * v2m::kPairTile), tile_pairs(n_tiles * (n_tiles + 1) / 2);
@@ -3504,13 +3615,13 @@ int pair_matrices_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, pair_j
 	u32 *w(nullptr), *any(nullptr), *h_any(nullptr);
 	u64 *slices(nullptr);
 	if (job.n_weighted) {
-		if (V2M_OK != (rc = ensure(ctx->d_boot_weights, V * sizeof(u32), "site weights"))) return finish(rc);
-		if (V2M_OK != (rc = ensure(ctx->d_boot_slices, u64(v2m::kBootSlices) * n_words * sizeof(u64), "weight slices"))) return finish(rc);
-		if (V2M_OK != (rc = ensure(ctx->d_boot_any, 16, "the weights' OR"))) return finish(rc);
+		if (V2M_OK != (rc = ensure_named(ctx, ctx->d_boot_weights, V * sizeof(u32), who, "site weights"))) return finish(rc);
+		if (V2M_OK != (rc = ensure_named(ctx, ctx->d_boot_slices, u64(v2m::kBootSlices) * n_words * sizeof(u64), who, "weight slices"))) return finish(rc);
+		if (V2M_OK != (rc = ensure_named(ctx, ctx->d_boot_any, 16, who, "the weights' OR"))) return finish(rc);
 		w = ctx->d_boot_weights.as<u32>(); slices = ctx->d_boot_slices.as<u64>(); any = ctx->d_boot_any.as<u32>();
 		h_any = reinterpret_cast<u32 *>(ctx->h_column_total.as<u64>() + 1);
 		if (job.weights) {
-			if (V2M_OK != (rc = ensure(ctx->d_boot_column_weights, L * sizeof(u32), "column weights"))) return finish(rc);
+			if (V2M_OK != (rc = ensure_named(ctx, ctx->d_boot_column_weights, L * sizeof(u32), who, "column weights"))) return finish(rc);
 			if (hipSuccess != hipMemcpyAsync(ctx->d_boot_column_weights.p, job.weights, L * sizeof(u32), hipMemcpyHostToDevice, ctx->stream))
 				return finish(fail(ctx, V2M_ERR_HIP, "pair distances: the weights could not be uploaded"));
 		}
@@ -3519,13 +3630,13 @@ int pair_matrices_run(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, pair_j
 
 	// (2) the planes of a pass: zeroed (padding sites and rows hold code 0), then packed slice by slice
 	auto const pack_pass([&](u64 chunks, u64 site_begin, u64 site_end) -> int {
-		if (int const e = ensure(ctx->d_dist_planes, pass_chunks * chunk_bytes, "planes")) return e;   // (refilled per pack in the checked build)
+		if (int const e = ensure_named(ctx, ctx->d_dist_planes, pass_chunks * chunk_bytes, who, "planes")) return e;   // (refilled per pack in the checked build)
 		u64 *const planes(ctx->d_dist_planes.as<u64>());
 		if (hipSuccess != hipMemsetAsync(planes, 0, chunks * chunk_bytes, ctx->stream)) return fail(ctx, V2M_ERR_HIP, "pair distances: the planes could not be zeroed");
 		u64 const pack_blocks((site_end - site_begin + v2m::kPackThreads - 1) / v2m::kPackThreads);
 		for (u64 s(0); s < p.n_slices; ++s) {
 			u64 const r0(s * p.rows_per_slice), r1(std::min(n, r0 + p.rows_per_slice)), nr(r1 - r0);
-			if (int const e = ensure(ctx->ring[0], p.slot_bytes, "the row slot")) return e;
+			if (int const e = ensure_named(ctx, ctx->ring[0], p.slot_bytes, who, "the row slot")) return e;
 			char *const d_rows(ctx->ring[0].as<char>());
 			if (int const e = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch)) return e;
 			// row groups: with few site blocks, as many as bring the launch to about four workgroups per compute unit, of at least 16 rows
@@ -3682,50 +3793,12 @@ int check_variable_sites(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, cha
 // (V + 3) & ~3 entries).  Completes on the stream; V to n_sites.  n_rows >= 1, L >= 1.
 int variable_sites_select(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, stage_times &times, u64 &n_sites)
 {
-	u64 const L(ctx->view().length()), n(rows->n_rows);
 	bool const snp(flags & V2M_SITES_SNP);
-	u64 const table_pitch((L + 3) & ~u64(3));
-	u64 const select_blocks((L + v2m::kSelectColumns - 1) / v2m::kSelectColumns);
-	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(V2M_COUNT_CLASSES * table_pitch * 4));
-	V2M_HIP_TRY(ctx, ctx->d_column_blocks.ensure(std::max<u64>(select_blocks * sizeof(u32), 16)));
-	V2M_HIP_TRY(ctx, ctx->d_column_total.ensure(sizeof(u64)));
-	V2M_HIP_TRY(ctx, ctx->h_column_total.ensure(2 * sizeof(u64)));
-	V2M_POISON_HOST(ctx->h_column_total.p, 2 * sizeof(u64));
-	u32 *const table(ctx->d_column_table.as<u32>());
-	u32 *const blocks(ctx->d_column_blocks.as<u32>());
-	times.begin(stage_times::counts);
-	int rc(column_counts_zero(ctx, table, table_pitch, L));
-	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, table, table_pitch);
-	if (V2M_OK != rc) return rc;
-	if (snp)
-		hipLaunchKernelGGL(v2m::count_snp_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream, table, table_pitch, L, blocks);
-	else
-		hipLaunchKernelGGL(v2m::count_variable_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
-			table, table_pitch, u64(0), L, u32(n), 1u, blocks);
-	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, blocks, u32(select_blocks), ctx->d_column_total.as<u64>());
-	times.end();
-	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "variable sites: the site selection did not launch");
-	if (hipSuccess != hipMemcpyAsync(ctx->h_column_total.p, ctx->d_column_total.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
-		|| hipSuccess != hipStreamSynchronize(ctx->stream))
-		return fail(ctx, V2M_ERR_HIP, "variable sites: the site count did not arrive");
-	u64 const V(*ctx->h_column_total.as<u64>());
-	if (V > L) return fail(ctx, V2M_ERR_HIP, "the site selection counted %llu of %llu columns", (unsigned long long) V, (unsigned long long) L);
-	n_sites = V;
-	if (0 == V) return V2M_OK;
-	{
-		hipError_t const st(ctx->d_site_columns.ensure(((V + 3) & ~u64(3)) * sizeof(u32)));
-		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "variable sites: the site list: %s", hipGetErrorString(st));
-	}
-	u32 *const sites(ctx->d_site_columns.as<u32>());
-	times.begin(stage_times::counts);
-	if (snp)
-		hipLaunchKernelGGL(v2m::emit_snp_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream, table, table_pitch, L, blocks, sites, V);
-	else
-		hipLaunchKernelGGL(v2m::emit_site_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
-			table, table_pitch, L, u32(n), blocks, sites, V);
-	times.end();
-	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "variable sites: the site list did not launch");
-	return V2M_OK;
+	site_selection sel;
+	if (int const rc = select_rule_sites_count(ctx, rows, snp, times, "variable sites", sel)) return rc;
+	n_sites = sel.V;
+	if (0 == sel.V) return V2M_OK;
+	return select_rule_sites_emit(ctx, rows->n_rows, snp, times, "variable sites", sel, ctx->d_site_columns, (sel.V + 3) & ~u64(3), "the site list");
 }
 
 // Stage (2) for rows [r0, r1) of the batch: the aligned splice into ring slot 0, then gather_sites_kernel at the V sites of site_list
@@ -3734,10 +3807,7 @@ int variable_sites_select(v2m_ctx *ctx, v2m_row_batch const *rows, u32 flags, st
 int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_plan const &p, u64 r0, u64 r1, u32 const *site_list, u64 V, char *out, u64 out_first_row, u64 out_pitch, u64 forced_rows, stage_times &times)
 {
 	u64 const nr(r1 - r0);
-	{
-		hipError_t const st(ctx->ring[0].ensure(p.slot_bytes));   // (the slice takes its device slot: refilled in the checked build)
-		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "variable sites: the row slot: %s", hipGetErrorString(st));
-	}
+	if (int const rc = ensure_named(ctx, ctx->ring[0], p.slot_bytes, "variable sites", "the row slot")) return rc;   // (the slice takes its device slot: refilled in the checked build)
 	char *const d_rows(ctx->ring[0].as<char>());
 	times.begin(stage_times::pack);   // (the second pass's stage, as the pair distances number it)
 	if (int const rc = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch)) return rc;
@@ -3753,14 +3823,6 @@ int variable_sites_gather_slice(v2m_ctx *ctx, v2m_row_batch const *rows, slice_p
 	times.end();
 	if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "variable sites: gather_sites_kernel did not launch");
 	return V2M_OK;
-}
-
-void variable_sites_report(stage_times const &times, u64 V, u64 L, v2m_variable_sites_info *info)
-{
-	if (!info) return;
-	double ms[stage_times::n_stages] = {};
-	times.sum(ms);
-	*info = v2m_variable_sites_info{V, L, ms[stage_times::counts], ms[stage_times::pack]};
 }
 
 } // namespace
@@ -3793,9 +3855,7 @@ int v2m_variable_sites_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t 
 		for (u64 s(0); s < p.n_slices && V2M_OK == rc; ++s)
 			rc = variable_sites_gather_slice(ctx, rows, p, s * p.rows_per_slice, std::min(n, (s + 1) * p.rows_per_slice), ctx->d_site_columns.as<u32>(), V, static_cast<char *>(d_bytes), 0, pitch, forced_rows, times);
 	}
-	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
-	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
-	return rc;
+	return drain(ctx, rc, false);
 }
 
 int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, v2m_site_columns_sink_fn columns_sink, v2m_site_rows_sink_fn rows_sink, void *user,
@@ -3808,11 +3868,7 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 	stage_times times(ctx);
 	u64 V(0);
 	auto const finish([&](int rc) -> int {
-		// leave both streams idle whatever happened
-		hipError_t const st(hipStreamSynchronize(ctx->stream));
-		(void) hipStreamSynchronize(ctx->copy_stream);
-		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
-		if (V2M_OK == rc) variable_sites_report(times, V, L, info);
+		if (V2M_OK == (rc = drain(ctx, rc, true)) && info) *info = v2m_variable_sites_info{V, L, times.ms(stage_times::counts), times.ms(stage_times::pack)};
 		return rc;
 	});
 	if (0 == L) return finish(V2M_OK);
@@ -3821,13 +3877,9 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 
 	// the site list: over the link as it is, widened to absolute columns on the host
 	if (columns_sink) {
-		if (hipSuccess != ctx->h_site_columns.ensure(V * sizeof(u32))) return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "variable sites: %llu bytes of pinned site list", (unsigned long long) (V * sizeof(u32))));
-		V2M_POISON_HOST(ctx->h_site_columns.p, V * sizeof(u32));
-		if (hipSuccess != hipMemcpyAsync(ctx->h_site_columns.p, ctx->d_site_columns.p, V * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream)
-			|| hipSuccess != hipStreamSynchronize(ctx->stream))
-			return finish(fail(ctx, V2M_ERR_HIP, "variable sites: the site list did not arrive"));
+		u32 const *relative(nullptr);
+		if (int const rc = fetch_site_columns(ctx, V, "variable sites", relative)) return finish(rc);
 		std::vector<u64> absolute(V);
-		u32 const *const relative(ctx->h_site_columns.as<u32>());
 		for (u64 i(0); i < V; ++i) absolute[i] = view_begin + relative[i];
 		if (columns_sink(user, absolute.data(), V)) return finish(fail(ctx, V2M_ERR_SINK, "sink aborted"));
 	}
@@ -3846,15 +3898,10 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 		int const b(int(s & 1));
 		v2m_row_hold &slot(*ctx->host_slots[b]);
 		u64 const r0(first_row(s)), r1(end_row(s));
-		{
-			hipError_t const st(ctx->d_site_bytes[b].ensure(slice_bytes));   // (refilled per slice in the checked build)
-			if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "variable sites: %llu bytes of sites: %s", (unsigned long long) slice_bytes, hipGetErrorString(st));
-		}
+		if (int const rc = ensure_named(ctx, ctx->d_site_bytes[b], slice_bytes, "variable sites", "sites")) return rc;   // (refilled per slice in the checked build)
 		V2M_POISON_HOST(slot.host.p, slice_bytes);
 		if (int const rc = variable_sites_gather_slice(ctx, rows, p, r0, r1, ctx->d_site_columns.as<u32>(), V, ctx->d_site_bytes[b].as<char>(), r0, out_pitch, forced_rows, times)) return rc;
-		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
-		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
-		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, ctx->d_site_bytes[b].p, (r1 - r0) * out_pitch, hipMemcpyDeviceToHost, ctx->copy_stream));
+		if (int const rc = copy_to_slot(ctx, b, ctx->d_site_bytes[b].p, (r1 - r0) * out_pitch)) return rc;
 		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
 		return V2M_OK;
 	});
@@ -3864,15 +3911,7 @@ int v2m_variable_sites(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t flags, 
 		if (rows_sink(user, first_row(s), end_row(s) - first_row(s), slot.host.as<char>(), out_pitch, V)) return fail(ctx, V2M_ERR_SINK, "sink aborted");
 		return V2M_OK;
 	});
-	int rc(V2M_OK);
-	u64 launched(0);
-	for (u64 s(0); s < p.n_slices && V2M_OK == rc; ++s) {
-		if (V2M_OK != (rc = issue(s))) break;
-		launched = s + 1;
-		if (s >= 1) rc = hand_over(s - 1);   // its copy ran under this slice's kernels
-	}
-	if (V2M_OK == rc && launched) rc = hand_over(launched - 1);
-	return finish(rc);
+	return finish(in_turn(p.n_slices, issue, hand_over));
 }
 
 
@@ -3932,14 +3971,8 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 	v2m_site_ld_info out{};
 	out.n_columns = L;
 	auto const finish([&](int rc) -> int {
-		// leave both streams idle whatever happened
-		hipError_t const st(hipStreamSynchronize(ctx->stream));
-		(void) hipStreamSynchronize(ctx->copy_stream);
-		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
-		if (V2M_OK == rc && dest.info) {
-			double ms[stage_times::n_stages] = {};
-			times.sum(ms);
-			out.counts_ms = ms[stage_times::counts]; out.pack_ms = ms[stage_times::pack]; out.pairs_ms = ms[stage_times::pairs];
+		if (V2M_OK == (rc = drain(ctx, rc, true)) && dest.info) {
+			out.counts_ms = times.ms(stage_times::counts); out.pack_ms = times.ms(stage_times::pack); out.pairs_ms = times.ms(stage_times::pairs);
 			*dest.info = out;
 		}
 		return rc;
@@ -3951,29 +3984,14 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 	if (0 == L) return nothing();
 
 	// (1) the counts and the number of sites
-	u64 const table_pitch((L + 3) & ~u64(3));
-	u64 const select_blocks((L + v2m::kSelectColumns - 1) / v2m::kSelectColumns);
-	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(V2M_COUNT_CLASSES * table_pitch * 4));
-	V2M_HIP_TRY(ctx, ctx->d_column_blocks.ensure(std::max<u64>(select_blocks * sizeof(u32), 16)));
-	V2M_HIP_TRY(ctx, ctx->d_column_total.ensure(sizeof(u64)));
-	V2M_HIP_TRY(ctx, ctx->h_column_total.ensure(2 * sizeof(u64)));
-	V2M_POISON_HOST(ctx->h_column_total.p, 2 * sizeof(u64));
-	u32 *const table(ctx->d_column_table.as<u32>());
-	u32 *const blocks(ctx->d_column_blocks.as<u32>());
-	times.begin(stage_times::counts);
-	int rc(column_counts_zero(ctx, table, table_pitch, L));
-	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows, table, table_pitch);
+	char const *const who("site LD");
+	site_selection sel;
+	int rc(select_sites_count(ctx, rows, times, who, [&](u32 *table, u64 table_pitch, u32 *blocks, u64 select_blocks) {
+		hipLaunchKernelGGL(v2m::count_ld_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+			table, table_pitch, L, prm.min_allele_count, blocks);
+	}, sel));
 	if (V2M_OK != rc) return finish(rc);
-	hipLaunchKernelGGL(v2m::count_ld_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
-		table, table_pitch, L, prm.min_allele_count, blocks);
-	hipLaunchKernelGGL(v2m::scan_tile_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, blocks, u32(select_blocks), ctx->d_column_total.as<u64>());
-	times.end();
-	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "site LD: the site selection did not launch"));
-	if (hipSuccess != hipMemcpyAsync(ctx->h_column_total.p, ctx->d_column_total.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
-		|| hipSuccess != hipStreamSynchronize(ctx->stream))
-		return finish(fail(ctx, V2M_ERR_HIP, "site LD: the site count did not arrive"));
-	u64 const V(*ctx->h_column_total.as<u64>());
-	if (V > L) return finish(fail(ctx, V2M_ERR_HIP, "the site selection counted %llu of %llu columns", (unsigned long long) V, (unsigned long long) L));
+	u64 const V(sel.V);
 	out.n_sites = V;
 	if (0 == V) return nothing();
 
@@ -3984,18 +4002,13 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 			(unsigned long long) V, (unsigned long long) n, (unsigned long long) plane_bytes, (unsigned long long) plane_budget));
 	u64 const n_blocks(std::min<u64>(n_strips, (u64(prm.window_sites) + v2m::kLdTile - 1) / v2m::kLdTile + 1));
 	u64 const strip_cells(u64(v2m::kLdTile) * n_blocks);
-	auto const ensure([&](scratch_buf &b, u64 bytes, char const *what) -> int {
-		hipError_t const st(b.ensure(bytes));
-		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "site LD: %llu bytes of %s: %s", (unsigned long long) bytes, what, hipGetErrorString(st));
-		return V2M_OK;
-	});
-	if (V2M_OK != (rc = ensure(ctx->d_ld_sites, v_pad * sizeof(u32), "site list"))) return finish(rc);
-	if (V2M_OK != (rc = ensure(ctx->d_ld_records, V * sizeof(v2m_ld_site), "site records"))) return finish(rc);
-	if (V2M_OK != (rc = ensure(ctx->d_ld_planes, plane_bytes, "planes"))) return finish(rc);
-	if (V2M_OK != (rc = ensure(ctx->d_ld_cells, n_strips * strip_cells * sizeof(u32), "cells"))) return finish(rc);
-	if (V2M_OK != (rc = ensure(ctx->d_ld_totals, n_strips * sizeof(u64), "strip totals"))) return finish(rc);
-	if (V2M_OK != (rc = ensure(ctx->d_ld_bases, n_strips * sizeof(u64), "strip bases"))) return finish(rc);
-	if (hipSuccess != ctx->h_ld_strips.ensure(2 * n_strips * sizeof(u64))) return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "site LD: %llu bytes of pinned strip totals", (unsigned long long) (2 * n_strips * sizeof(u64))));
+	if (V2M_OK != (rc = ensure_named(ctx, ctx->d_ld_sites, v_pad * sizeof(u32), who, "site list"))) return finish(rc);
+	if (V2M_OK != (rc = ensure_named(ctx, ctx->d_ld_records, V * sizeof(v2m_ld_site), who, "site records"))) return finish(rc);
+	if (V2M_OK != (rc = ensure_named(ctx, ctx->d_ld_planes, plane_bytes, who, "planes"))) return finish(rc);
+	if (V2M_OK != (rc = ensure_named(ctx, ctx->d_ld_cells, n_strips * strip_cells * sizeof(u32), who, "cells"))) return finish(rc);
+	if (V2M_OK != (rc = ensure_named(ctx, ctx->d_ld_totals, n_strips * sizeof(u64), who, "strip totals"))) return finish(rc);
+	if (V2M_OK != (rc = ensure_named(ctx, ctx->d_ld_bases, n_strips * sizeof(u64), who, "strip bases"))) return finish(rc);
+	if (V2M_OK != (rc = ensure_named(ctx, ctx->h_ld_strips, 2 * n_strips * sizeof(u64), who, "strip totals"))) return finish(rc);
 	V2M_POISON_HOST(ctx->h_ld_strips.p, 2 * n_strips * sizeof(u64));
 	u32 *const sites(ctx->d_ld_sites.as<u32>());
 	v2m::ld_site_record *const records(ctx->d_ld_records.as<v2m::ld_site_record>());
@@ -4004,8 +4017,8 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 	u64 *const totals(ctx->d_ld_totals.as<u64>());
 	u64 *const bases(ctx->d_ld_bases.as<u64>());
 	times.begin(stage_times::counts);
-	hipLaunchKernelGGL(v2m::emit_ld_columns_kernel, dim3(unsigned(select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
-		table, table_pitch, L, prm.min_allele_count, view_begin, blocks, sites, records, V);
+	hipLaunchKernelGGL(v2m::emit_ld_columns_kernel, dim3(unsigned(sel.select_blocks)), dim3(v2m::kSelectColumns), 0, ctx->stream,
+		sel.table, sel.table_pitch, L, prm.min_allele_count, view_begin, sel.blocks, sites, records, V);
 	times.end();
 	if (hipSuccess != hipGetLastError()) return finish(fail(ctx, V2M_ERR_HIP, "site LD: emit_ld_columns_kernel did not launch"));
 
@@ -4017,7 +4030,7 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 	u64 const pack_blocks((V + v2m::kLdPackThreads - 1) / v2m::kLdPackThreads);
 	for (u64 s(0); s < p.n_slices; ++s) {
 		u64 const r0(s * p.rows_per_slice), r1(std::min(n, r0 + p.rows_per_slice)), nr(r1 - r0);
-		if (V2M_OK != (rc = ensure(ctx->ring[0], p.slot_bytes, "row slot"))) return finish(rc);
+		if (V2M_OK != (rc = ensure_named(ctx, ctx->ring[0], p.slot_bytes, who, "row slot"))) return finish(rc);
 		char *const d_rows(ctx->ring[0].as<char>());
 		if (V2M_OK != (rc = splice_aligned_slice(ctx, rows, r0, r1, d_rows, p.pitch))) return finish(rc);
 		// word-aligned row groups: with few site blocks, as many as bring the launch to about four workgroups per compute unit
@@ -4071,7 +4084,7 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 
 	// the site records: over the link as they are
 	if (dest.sites_sink || dest.info) {
-		if (hipSuccess != ctx->h_ld_records.ensure(V * sizeof(v2m_ld_site))) return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "site LD: %llu bytes of pinned site records", (unsigned long long) (V * sizeof(v2m_ld_site))));
+		if (V2M_OK != (rc = ensure_named(ctx, ctx->h_ld_records, V * sizeof(v2m_ld_site), who, "site records"))) return finish(rc);
 		V2M_POISON_HOST(ctx->h_ld_records.p, V * sizeof(v2m_ld_site));
 		if (hipSuccess != hipMemcpyAsync(ctx->h_ld_records.p, records, V * sizeof(v2m_ld_site), hipMemcpyDeviceToHost, ctx->stream)
 			|| hipSuccess != hipStreamSynchronize(ctx->stream))
@@ -4101,15 +4114,13 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 		int const b(int(k & 1));
 		range const &g(ranges[k]);
 		v2m_row_hold &slot(*ctx->host_slots[b]);
-		if (int const rc2 = ensure(ctx->d_ld_pairs[b], most * sizeof(v2m_ld_pair), "pairs")) return rc2;   // (refilled per range in the checked build)
+		if (int const rc2 = ensure_named(ctx, ctx->d_ld_pairs[b], most * sizeof(v2m_ld_pair), who, "pairs")) return rc2;   // (refilled per range in the checked build)
 		V2M_POISON_HOST(slot.host.p, g.pairs * sizeof(v2m_ld_pair));
 		times.begin(stage_times::pairs);
 		pairs_launch(true, g.strip_begin, g.strip_end - g.strip_begin, g.base, ctx->d_ld_pairs[b].p);
 		times.end();
 		if (hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "site LD: ld_pairs_kernel did not launch");
-		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
-		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
-		V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, ctx->d_ld_pairs[b].p, g.pairs * sizeof(v2m_ld_pair), hipMemcpyDeviceToHost, ctx->copy_stream));
+		if (int const rc2 = copy_to_slot(ctx, b, ctx->d_ld_pairs[b].p, g.pairs * sizeof(v2m_ld_pair))) return rc2;
 		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
 		return V2M_OK;
 	});
@@ -4119,14 +4130,7 @@ int site_ld_run(v2m_ctx *ctx, v2m_row_batch const *rows, v2m_site_ld_params cons
 		if (dest.pairs_sink(dest.user, slot.host.as<v2m_ld_pair>(), ranges[k].pairs)) return fail(ctx, V2M_ERR_SINK, "sink aborted");
 		return V2M_OK;
 	});
-	u64 launched(0);
-	for (u64 k(0); k < ranges.size() && V2M_OK == rc; ++k) {
-		if (V2M_OK != (rc = issue(k))) break;
-		launched = k + 1;
-		if (k >= 1) rc = hand_over(k - 1);   // its copy ran under this range's kernel
-	}
-	if (V2M_OK == rc && launched) rc = hand_over(launched - 1);
-	return finish(rc);
+	return finish(in_turn(ranges.size(), issue, hand_over));
 }
 
 } // namespace
@@ -4185,16 +4189,12 @@ int nj_too_few(v2m_ctx *ctx, u64 n, char const *name)
 int nj_run(v2m_ctx *ctx, u32 const *d_dist, u64 n, u64 dist_pitch, v2m_nj_node *nodes, double *tree_ms)
 {
 	u64 const pitch((n + 1) & ~u64(1));
-	auto const ensure([&](scratch_buf &buf, u64 bytes, char const *what) -> int {
-		hipError_t const st(buf.ensure(bytes));
-		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "neighbour joining: %llu bytes of %s: %s", (unsigned long long) bytes, what, hipGetErrorString(st));
-		return V2M_OK;
-	});
-	if (int const rc = ensure(ctx->d_nj_matrix, n * pitch * sizeof(double), "working matrix")) return rc;
-	if (int const rc = ensure(ctx->d_nj_sums, pitch * sizeof(double), "row sums")) return rc;
-	if (int const rc = ensure(ctx->d_nj_ids, pitch * sizeof(u32), "ids")) return rc;
-	if (int const rc = ensure(ctx->d_nj_best, n * sizeof(v2m::nj_best), "row minima")) return rc;
-	if (int const rc = ensure(ctx->d_nj_nodes, (n - 2) * sizeof(v2m_nj_node), "records")) return rc;
+	char const *const who("neighbour joining");
+	if (int const rc = ensure_named(ctx, ctx->d_nj_matrix, n * pitch * sizeof(double), who, "working matrix")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_nj_sums, pitch * sizeof(double), who, "row sums")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_nj_ids, pitch * sizeof(u32), who, "ids")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_nj_best, n * sizeof(v2m::nj_best), who, "row minima")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_nj_nodes, (n - 2) * sizeof(v2m_nj_node), who, "records")) return rc;
 	double *const D(ctx->d_nj_matrix.as<double>()), *const R(ctx->d_nj_sums.as<double>());
 	u32 *const ids(ctx->d_nj_ids.as<u32>());
 	v2m::nj_best *const best(ctx->d_nj_best.as<v2m::nj_best>());
@@ -4217,11 +4217,7 @@ int nj_run(v2m_ctx *ctx, u32 const *d_dist, u64 n, u64 dist_pitch, v2m_nj_node *
 	if (hipSuccess != launched) return fail(ctx, V2M_ERR_HIP, "neighbour joining: a kernel did not launch: %s", hipGetErrorString(launched));
 	V2M_HIP_TRY(ctx, copied);
 	V2M_HIP_TRY(ctx, st);
-	if (tree_ms) {
-		double ms[stage_times::n_stages] = {};
-		times.sum(ms);
-		*tree_ms = ms[0];
-	}
+	if (tree_ms) *tree_ms = times.ms(0);
 	return V2M_OK;
 }
 
@@ -4409,14 +4405,9 @@ u64 fitch_blocks(u64 V) { return (V + u64(v2m::kFitchThreads) * v2m::kFitchSites
 // The scratch of one range of V >= 1 sites at `pitch`: the sets, the workgroups' steps, the total and its staging.
 int parsimony_ensure(v2m_ctx *ctx, u64 n, u64 V, u64 pitch)
 {
-	auto const ensure([&](scratch_buf &buf, u64 bytes, char const *what) -> int {
-		hipError_t const st(buf.ensure(bytes));
-		if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "parsimony: %llu bytes of %s: %s", (unsigned long long) bytes, what, hipGetErrorString(st));
-		return V2M_OK;
-	});
-	if (int const rc = ensure(ctx->d_fitch_sets, (n - 2) * pitch, "sets")) return rc;
-	if (int const rc = ensure(ctx->d_fitch_blocks, std::max<u64>(fitch_blocks(V) * sizeof(u32), 16), "workgroup steps")) return rc;
-	if (int const rc = ensure(ctx->d_fitch_total, 2 * sizeof(u64), "totals")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_fitch_sets, (n - 2) * pitch, "parsimony", "sets")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_fitch_blocks, std::max<u64>(fitch_blocks(V) * sizeof(u32), 16), "parsimony", "workgroup steps")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_fitch_total, 2 * sizeof(u64), "parsimony", "totals")) return rc;
 	V2M_HIP_TRY(ctx, ctx->h_fitch_total.ensure(sizeof(u64)));
 	return V2M_OK;
 }
@@ -4504,9 +4495,7 @@ int v2m_parsimony_of_sites(v2m_ctx *ctx, const void *d_bytes, uint64_t n, uint64
 	if (V2M_OK == rc)
 		rc = parsimony_down(ctx, static_cast<unsigned char const *>(d_bytes), n, V, pitch, last_c, sites, static_cast<u32 *>(d_branch_changes), 0,
 			capacity ? static_cast<v2m::tree_mutation_record *>(d_mutations) : nullptr, times);
-	hipError_t const st(hipStreamSynchronize(ctx->stream));   // (leave the stream idle whatever happened)
-	if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
-	return rc;
+	return drain(ctx, rc, false);
 }
 
 int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_node *nodes, uint32_t flags, uint32_t *branch_changes, v2m_tree_sites_sink_fn sites_sink,
@@ -4523,16 +4512,10 @@ int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_nod
 	u64 const L(ctx->view().length()), view_begin(ctx->view().begin), n_branches(2 * n - 3);
 	stage_times times(ctx);
 	u64 V(0), n_mutations(0), n_ranges(0);
+	char const *const who("v2m_tree_parsimony");
 	auto const finish([&](int rc) -> int {
-		// leave both streams idle whatever happened
-		hipError_t const st(hipStreamSynchronize(ctx->stream));
-		(void) hipStreamSynchronize(ctx->copy_stream);
-		if (V2M_OK == rc) V2M_HIP_TRY(ctx, st);
-		if (V2M_OK == rc && info) {
-			double ms[stage_times::n_stages] = {};
-			times.sum(ms);
-			*info = v2m_tree_parsimony_info{V, L, n_mutations, n_ranges, ms[stage_times::counts], ms[stage_times::pack], ms[stage_times::pairs]};
-		}
+		if (V2M_OK == (rc = drain(ctx, rc, true)) && info)
+			*info = v2m_tree_parsimony_info{V, L, n_mutations, n_ranges, times.ms(stage_times::counts), times.ms(stage_times::pack), times.ms(stage_times::pairs)};
 		return rc;
 	});
 	if (L) if (int const rc = variable_sites_select(ctx, rows, V2M_SITES_SNP, times, V)) return finish(rc);
@@ -4558,12 +4541,8 @@ int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_nod
 	}
 	if (sites_sink) {
 		// the site list: over the link as it is, widened to absolute columns on the host
-		if (hipSuccess != ctx->h_site_columns.ensure(V * sizeof(u32))) return finish(fail(ctx, V2M_ERR_OUT_OF_MEMORY, "v2m_tree_parsimony: %llu bytes of pinned site list", (unsigned long long) (V * sizeof(u32))));
-		V2M_POISON_HOST(ctx->h_site_columns.p, V * sizeof(u32));
-		if (hipSuccess != hipMemcpyAsync(ctx->h_site_columns.p, ctx->d_site_columns.p, V * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream)
-			|| hipSuccess != hipStreamSynchronize(ctx->stream))
-			return finish(fail(ctx, V2M_ERR_HIP, "v2m_tree_parsimony: the site list did not arrive"));
-		u32 const *const relative(ctx->h_site_columns.as<u32>());
+		u32 const *relative(nullptr);
+		if (int const rc = fetch_site_columns(ctx, V, who, relative)) return finish(rc);
 		for (u64 i(0); i < V; ++i) site_records[i].column = view_begin + relative[i];
 	}
 	if (int const rc = parsimony_upload_tree(ctx, n, nodes, last_c)) return finish(rc);
@@ -4585,20 +4564,14 @@ int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_nod
 		for (u64 s(0); s < p.n_slices; ++s)
 			if (int const rc = variable_sites_gather_slice(ctx, rows, p, s * p.rows_per_slice, std::min(n, (s + 1) * p.rows_per_slice), ctx->d_site_columns.as<u32>() + s0, Vr,
 				reinterpret_cast<char *>(d_bytes), 0, pitch, gather_group_rows, times)) return rc;
-		{
-			hipError_t const st(ctx->d_fitch_sites[b].ensure(Vr * sizeof(v2m_parsimony_site)));
-			if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "v2m_tree_parsimony: the site records: %s", hipGetErrorString(st));
-		}
+		if (int const rc = ensure_named(ctx, ctx->d_fitch_sites[b], Vr * sizeof(v2m_parsimony_site), who, "the site records")) return rc;
 		auto *const d_sites(ctx->d_fitch_sites[b].as<v2m::parsimony_site_record>());
 		u64 total(0);
 		if (int const rc = parsimony_up(ctx, d_bytes, n, Vr, pitch, last_c, d_sites, times, total)) return rc;
 		n_mutations += total;
 		if (n_mutations >> 32) return parsimony_too_long(ctx, "v2m_tree_parsimony", n_mutations);
 		bool const emit(mutations_sink && total);
-		if (emit) {
-			hipError_t const st(ctx->d_fitch_mutations[b].ensure(total * sizeof(v2m_tree_mutation)));
-			if (hipSuccess != st) return fail(ctx, hipErrorOutOfMemory == st ? V2M_ERR_OUT_OF_MEMORY : V2M_ERR_HIP, "v2m_tree_parsimony: %llu mutations: %s", (unsigned long long) total, hipGetErrorString(st));
-		}
+		if (emit) if (int const rc = ensure_named(ctx, ctx->d_fitch_mutations[b], total * sizeof(v2m_tree_mutation), who, "mutations")) return rc;
 		if (int const rc = parsimony_down(ctx, d_bytes, n, Vr, pitch, last_c, d_sites, ctx->d_fitch_branches.as<u32>(), s0,
 			emit ? ctx->d_fitch_mutations[b].as<v2m::tree_mutation_record>() : nullptr, times)) return rc;
 		delivery &d(deliveries[b]);
@@ -4608,11 +4581,8 @@ int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_nod
 		u64 const slot_bytes(d.mutations_at + d.n_mutations * sizeof(v2m_tree_mutation));
 		V2M_HIP_TRY(ctx, slot.host.ensure(slot_bytes));
 		V2M_POISON_HOST(slot.host.p, slot_bytes);
-		V2M_HIP_TRY(ctx, hipEventRecord(ctx->ev_compute[b], ctx->stream));
-		V2M_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute[b], 0));
-		if (d.n_sites) V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.p, d_sites, Vr * sizeof(v2m_parsimony_site), hipMemcpyDeviceToHost, ctx->copy_stream));
-		if (d.n_mutations)
-			V2M_HIP_TRY(ctx, hipMemcpyAsync(slot.host.as<char>() + d.mutations_at, ctx->d_fitch_mutations[b].p, d.n_mutations * sizeof(v2m_tree_mutation), hipMemcpyDeviceToHost, ctx->copy_stream));
+		if (d.n_sites) if (int const rc = copy_to_slot(ctx, b, d_sites, Vr * sizeof(v2m_parsimony_site))) return rc;
+		if (d.n_mutations) if (int const rc = copy_to_slot(ctx, b, ctx->d_fitch_mutations[b].p, d.n_mutations * sizeof(v2m_tree_mutation), d.mutations_at)) return rc;
 		V2M_HIP_TRY(ctx, hipEventRecord(slot.copied, ctx->copy_stream));
 		d.pending = true;
 		return V2M_OK;
@@ -4632,14 +4602,7 @@ int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_nod
 			return fail(ctx, V2M_ERR_SINK, "sink aborted");
 		return V2M_OK;
 	});
-	int rc(V2M_OK);
-	u64 launched(0);
-	for (u64 k(0); k < n_ranges && V2M_OK == rc; ++k) {
-		if (V2M_OK != (rc = issue(k))) break;
-		launched = k + 1;
-		if (k >= 1) rc = hand_over(k - 1);   // its copies ran under this range's kernels
-	}
-	if (V2M_OK == rc && launched) rc = hand_over(launched - 1);
+	int rc(in_turn(n_ranges, issue, hand_over));
 	if (V2M_OK == rc && branch_changes) {
 		if (hipSuccess != hipMemcpyAsync(branch_changes, ctx->d_fitch_branches.p, n_branches * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream)
 			|| hipSuccess != hipStreamSynchronize(ctx->stream))
