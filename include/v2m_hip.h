@@ -274,6 +274,10 @@ int v2m_splice_rows_device(v2m_ctx *ctx, const v2m_row_batch *rows, uint32_t fla
  * cares about those first seconds asks for one candidate. */
 int v2m_alloc_output(v2m_ctx *ctx, uint64_t bytes, int candidates, void **d_out);
 int v2m_free_output(v2m_ctx *ctx, void *d_ptr);
+/* `bytes` bytes of device memory at d_src (a buffer of v2m_alloc_output, or any device memory of the context's device) to host memory
+ * at dst, after everything queued on the context's stream: how a caller without a HIP runtime of its own reads what a device form
+ * (v2m_diversity_of_counts, for one) left on the device.  bytes == 0 returns V2M_OK.  Synchronous. */
+int v2m_read_output(v2m_ctx *ctx, const void *d_src, uint64_t bytes, void *dst);
 
 /* Upper bound of any unaligned row's length for the uploaded graph (with a column window: the window's length). */
 uint64_t v2m_max_unaligned_length(const v2m_ctx *ctx);
@@ -880,6 +884,108 @@ int v2m_parsimony_of_sites(v2m_ctx *ctx, const void *d_bytes, uint64_t n, uint64
 int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_node *nodes /* host, n_rows - 2 */, uint32_t flags /* 0 */,
                        uint32_t *branch_changes /* host, 2 n_rows - 3, or NULL */, v2m_tree_sites_sink_fn sites_sink /* may be NULL */,
                        v2m_tree_mutations_sink_fn mutations_sink /* may be NULL */, void *user, v2m_tree_parsimony_info *info /* may be NULL */);
+
+/* ---- window diversity ---------------------------------------------------------------------------
+ *
+ * The alignment summarised along the reference: per bin of columns the sums that nucleotide diversity, Watterson's theta, Tajima's D,
+ * d_xy and F_ST are made of, and the folded site frequency spectrum -- all of them sums over columns of small integer functions of
+ * the column counts (above), so every result is an integer with exactly one value, and the doubles are derived from them on the host.
+ *
+ * Per column.  A counts table is what v2m_column_counts_device writes, u32[V2M_COUNT_CLASSES][plane_pitch], counted over n rows; the
+ * classes are the column counts'.  For column i let a, c, g, t be planes 0-3 and m = a + c + g + t; planes 4 and 5 (N, gap) are never
+ * read.  All arithmetic is in u64.
+ *   diffs(i)        = a c + a g + a t + c g + c t + g t: the pairs of batch rows that both hold A, C, G or T and differ.  Rows that
+ *                     repeat count as the rows they are, as in the pair distances: summed over a view, diffs is the sum of the upper
+ *                     triangle of v2m_pair_distances(..., V2M_DIST_ACGT_ONLY) over the same view.
+ *   pairs(i)        = m (m - 1) / 2
+ *   called(i)       : m >= 2
+ *   segregating(i)  : at least two of a, c, g, t are non-zero
+ *   complete(i)     : m == n and n >= 2
+ * Between two tables over n_a and n_b rows (the same L and pitch), with m_A, m_B the two m:
+ *   diffs(i)        = m_A m_B - (a_A a_B + c_A c_B + g_A g_B + t_A t_B)
+ *   pairs(i)        = m_A m_B
+ *   called(i)       : m_A >= 1 and m_B >= 1
+ *
+ * Bins.  bounds is u64[n_bins + 1], ascending but not strictly so; bin k is the columns [bounds[k], bounds[k + 1]), an empty bin is
+ * legal, and columns before bounds[0] or from bounds[n_bins] on belong to no bin.  Bin k's record is v2m_diversity_bin (within) or
+ * v2m_diversity_between_bin (between): `columns` = bounds[k + 1] - bounds[k], the counts of the columns that are called, segregating,
+ * complete, complete and segregating, and the sums of diffs and pairs over the bin's columns and of diffs over its complete columns.
+ *
+ * Folded spectrum (within form only): sfs is u64[n / 2 + 1] over the columns of [bounds[0], bounds[n_bins]).  A complete column with
+ * exactly one non-zero letter adds 1 to sfs[0]; with exactly two, 1 to sfs[the smaller of the two counts]; with three or four, 1 to
+ * info->multiallelic.  Without a spectrum (sfs NULL) multiallelic is 0.
+ *
+ * Limits.  n, n_b <= V2M_DIVERSITY_MAX_ROWS (32 768, the limit of the pair distances) and L < 2^32: then no sum passes 2^62.  More rows, a
+ * longer view, or 2^32 - 1 bins and more is V2M_ERR_UNSUPPORTED with a message that names the limit, before any device work.
+ *
+ * The doubles.  IEEE double, only + - * / and sqrt, each operation rounded on its own (no fused multiply-add, no libm call), integers
+ * converted to double exactly (all are below 2^62, but only values below 2^53 convert without rounding: a conversion is one rounding
+ * like any operation), in exactly this order.  d(x) is the conversion of the integer x.  A value whose denominator is zero does not
+ * exist; the text writers print NA.  From a window's record (bins summed field by field as integers) and n:
+ *   pi       = d(diffs) / d(pairs)                                    exists when pairs > 0
+ *   a1       = 0; for i = 1 .. n - 1 ascending: a1 = a1 + 1 / d(i)
+ *   a2       = 0; for i = 1 .. n - 1 ascending: a2 = a2 + 1 / (d(i) * d(i))
+ *   S        = d(complete_segregating)
+ *   theta_w  = S / a1                                                 exists when n >= 2
+ *   b1       = (d(n) + 1) / (3 * (d(n) - 1))
+ *   b2       = (2 * (d(n) * d(n) + d(n) + 3)) / (9 * d(n) * (d(n) - 1))            [9 * d(n) first, then * (d(n) - 1)]
+ *   c1       = b1 - 1 / a1
+ *   c2       = (b2 - (d(n) + 2) / (a1 * d(n))) + a2 / (a1 * a1)
+ *   e1       = c1 / a1
+ *   e2       = c2 / (a1 * a1 + a2)
+ *   k        = d(complete_diffs) / (d(n) * (d(n) - 1) / 2)             [d(n) * (d(n) - 1) first, then / 2]
+ *   v        = e1 * S + (e2 * S) * (S - 1)
+ *   tajima_d = (k - S / a1) / sqrt(v)                                 exists when n >= 2 and v > 0
+ *   dxy      = d(diffs) / d(pairs) of a between record                exists when pairs > 0
+ *   fst      = 1 - (pi_A + pi_B) / (2 * dxy)                           Hudson's; exists when pi_A, pi_B and dxy exist and dxy > 0
+ * Sums and products of more than two terms are evaluated left to right.  (n = 10, S = 16, k = 3.888889: a1 = 2.8289682539682537,
+ * a2 = 1.5397677311665408, tajima_d = -1.4461719856148525.)
+ *
+ * v2m_diversity_of_counts (device form).  d_counts_a, and for the between form d_counts_b, are tables in device memory, 16-byte
+ * aligned, plane_pitch % 4 == 0 and plane_pitch >= (L + 3) & ~3; they are read below element (L + 3) & ~3 of planes 0-3 only and left as
+ * they were.  bounds is host memory, relative to the tables, bounds[n_bins] <= L.  d_bins (n_bins records) and d_sfs (u64[n_a / 2 + 1];
+ * may be NULL, and must be in the between form) are device memory, 16-byte aligned; they are overwritten and nothing else is touched.
+ * No graph is needed.  v2m_window_diversity (host form).  The tables are counted from rows_a and, for the between form, rows_b over
+ * the view in force (the whole row or the column window; a window set is ignored), as v2m_column_counts counts them; bounds is
+ * absolute and must lie inside the view; bins (n_bins records) and sfs (NULL, or u64[rows_a->n_rows / 2 + 1]) are host memory.  info,
+ * which may be NULL, receives L, n_bins, multiallelic and -- while v2m_profile_enable is on, else 0 -- the stream time of the counts
+ * and of the reduction, measured as for the pair distances (counts_ms is 0 in the device form).  Both are synchronous.
+ * Errors, as for the other analyses: V2M_ERR_INVALID_ARGUMENT for NULL pointers, descending bounds, bounds outside the table or the
+ * view, a misaligned pointer or a bad pitch, n_b != 0 without a second table, a spectrum in the between form; V2M_ERR_STATE without a
+ * graph and V2M_ERR_PRECONDITION for bad cuts (host form).  n_bins == 0, or a group of 0 rows, returns V2M_OK and touches nothing (info
+ * included).  The column window, the window set and what v2m_column_counts returns afterwards are left as they were.
+ * The driver (--output-diversity, --diversity-sfs, --output-divergence) cuts the reference range into steps of --diversity-step
+ * positions; the bin of a step begins at the column of its first position (columns_of_reference_range), so the columns of an insertion
+ * fall to the bin of the reference position before them.  A window is --diversity-window / --diversity-step consecutive bins summed
+ * field by field as integers; the doubles come after.
+ * How (csrc/diversity_kernels.hpp).  diversity_init_kernel writes every record's `columns` and zeroes its sums; diversity_bins_kernel:
+ * a lane takes four adjacent columns (one 16-byte load per plane), a workgroup a tile of 1 024; a tile inside one bin is a plain
+ * workgroup reduction; otherwise the lanes find their bins by binary search of the bounds (a device copy) and sums that share a bin
+ * meet in the wave by shuffles before one integer atomicAdd per wave, bin and field.  The spectrum goes through 4 096 u32 counters in
+ * LDS when n / 2 + 1 fits, else straight to global atomics.  No V2M_KERNEL_* ids: V2M_KERNEL_LIMIT keeps its value. */
+#define V2M_DIVERSITY_MAX_ROWS 32768u
+
+typedef struct {
+	uint64_t columns, called, diffs, pairs, segregating, complete, complete_segregating, complete_diffs;
+} v2m_diversity_bin;             /* 64 bytes */
+
+typedef struct { uint64_t columns, called, diffs, pairs; } v2m_diversity_between_bin;   /* 32 bytes */
+
+typedef struct {
+	uint64_t n_columns;      /* L */
+	uint64_t n_bins;
+	uint64_t multiallelic;   /* complete columns of three or four letters in [bounds[0], bounds[n_bins]); 0 without a spectrum */
+	double counts_ms;        /* the column counts of the group or groups: stream time elapsed over the stage */
+	double bins_ms;          /* diversity_init_kernel, diversity_bins_kernel and the zeroing of the spectrum: likewise */
+} v2m_window_diversity_info;     /* 40 bytes */
+
+int v2m_diversity_of_counts(v2m_ctx *ctx, const void *d_counts_a, const void *d_counts_b /* NULL: within */, uint64_t plane_pitch, uint64_t L,
+                            uint64_t n_a, uint64_t n_b, const uint64_t *bounds /* host, relative */, uint64_t n_bins, void *d_bins,
+                            void *d_sfs /* NULL, and NULL in the between form */, v2m_window_diversity_info *info /* may be NULL */);
+
+int v2m_window_diversity(v2m_ctx *ctx, const v2m_row_batch *rows_a, const v2m_row_batch *rows_b /* NULL: within */,
+                         const uint64_t *bounds /* host, absolute columns inside the view in force */, uint64_t n_bins, void *bins /* host */,
+                         uint64_t *sfs /* host or NULL */, v2m_window_diversity_info *info /* may be NULL */);
 
 /* ---- founder search: the chunk walks ---------------------------------- */
 

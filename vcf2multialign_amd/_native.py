@@ -80,6 +80,11 @@ BOOT_SLICES = 32
 FITCH_SITES = 4
 FITCH_THREADS = 256
 FITCH_BATCH = 4
+# v2m_diversity_of_counts, v2m_window_diversity: the limit, and csrc/diversity_kernels.hpp's kDiversityColumns (columns of a workgroup's
+# tile) and kDiversitySfsLdsBins (entries of the spectrum's on-chip histogram); tests/test_window_diversity_host.py holds them to the sources
+DIVERSITY_MAX_ROWS = 32768
+DIVERSITY_COLUMNS = 1024
+DIVERSITY_SFS_LDS_BINS = 4096
 # csrc/kernels.hpp: kDistinctChunkBytes (a long piece is hashed, gathered and verified in chunks of this many bytes) and
 # kDistinctLongBytes (windows longer than this are hashed in chunks); tests/test_distinct_model_host.py holds them to the source
 DISTINCT_CHUNK_BYTES = 8192
@@ -171,6 +176,13 @@ class TreeParsimonyInfo(C.Structure):   # v2m_tree_parsimony_info
 		("counts_ms", C.c_double), ("gather_ms", C.c_double), ("parsimony_ms", C.c_double)]
 
 
+class WindowDiversityInfo(C.Structure):   # v2m_window_diversity_info
+	_fields_ = [("n_columns", C.c_uint64), ("n_bins", C.c_uint64), ("multiallelic", C.c_uint64), ("counts_ms", C.c_double), ("bins_ms", C.c_double)]
+
+
+DIVERSITY_BIN_DTYPE = [("columns", "<u8"), ("called", "<u8"), ("diffs", "<u8"), ("pairs", "<u8"), ("segregating", "<u8"), ("complete", "<u8"),
+	("complete_segregating", "<u8"), ("complete_diffs", "<u8")]   # v2m_diversity_bin
+DIVERSITY_BETWEEN_BIN_DTYPE = [("columns", "<u8"), ("called", "<u8"), ("diffs", "<u8"), ("pairs", "<u8")]   # v2m_diversity_between_bin
 PARSIMONY_SITE_DTYPE = [("steps", "<u4"), ("present", "<u4")]   # v2m_parsimony_site
 TREE_SITE_DTYPE = [("column", "<u8"), ("steps", "<u4"), ("present", "<u4")]   # v2m_tree_site
 TREE_MUTATION_DTYPE = [("site", "<u4"), ("node", "<u4"), ("from", "<u4"), ("to", "<u4")]   # v2m_tree_mutation
@@ -228,6 +240,10 @@ SIGNATURES = {
 	"v2m_nj_bootstrap": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NjBootstrapInfo)]),
 	"v2m_parsimony_of_sites": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
 	"v2m_tree_parsimony": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.c_void_p, C.c_uint32, C.c_void_p, TREE_SINK_FN, TREE_SINK_FN, C.c_void_p, C.POINTER(TreeParsimonyInfo)]),
+	"v2m_diversity_of_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+		C.POINTER(WindowDiversityInfo)]),
+	"v2m_window_diversity": (C.c_int, [C.c_void_p, C.POINTER(RowBatchStruct), C.POINTER(RowBatchStruct), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+		C.POINTER(WindowDiversityInfo)]),
 	"v2m_pbwt_cut_trials": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_pbwt_cut_trials_streamed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -236,6 +252,7 @@ SIGNATURES = {
 		C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 	"v2m_alloc_output": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
 	"v2m_free_output": (C.c_int, [C.c_void_p, C.c_void_p]),
+	"v2m_read_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
 	"v2m_bgzf_bound": (C.c_uint64, [C.c_uint64]),
 	"v2m_bgzf_frame_stored": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
 	"v2m_bgzf_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),

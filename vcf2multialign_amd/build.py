@@ -73,7 +73,7 @@ HOST_DIR = os.path.join(CSRC, "host")
 HOST_SOURCES = [os.path.join(HOST_DIR, f) for f in ("graph_builder.cc", "readers.cc", "gpu_path.cc", "output.cc", "founder.cc", "graph_file.cc", "host_capi.cc")]
 CLI_PATH = os.path.join(PKG_DIR, "bin", "vcf2multialign")
 CLI_SOURCES = [os.path.join(HOST_DIR, "main.cc")]
-CXX_FLAGS = ["-O2", "-g", "-std=c++20", "-Wall", "-Wextra"]
+CXX_FLAGS = ["-O2", "-g", "-std=c++20", "-ffp-contract=off", "-Wall", "-Wextra"]   # (no fused multiply-add: the doubles of include/v2m_hip.h are defined operation by operation)
 
 # HIP_DEPS, SYNTH_DEPS, HOST_DEPS, CLI_DEPS: the include closures, computed on first use (module __getattr__ below) -- importing this
 # module reads no source file, and a broken include in one target does not stop the others from building.

@@ -759,6 +759,39 @@ class Context:
 		self._check(rc)
 		return self.parsimony_mutations
 
+	def window_diversity(self, rows, bounds, rows_b=None, want_sfs=True, info=False):
+		"""v2m_window_diversity: the bin records of include/v2m_hip.h's "window diversity" for the rows of the batch over the bins
+		[bounds[k], bounds[k + 1]) -- absolute columns inside the view in force, ascending.  Within form (rows_b None): (bins, sfs), a
+		structured array of v2m_diversity_bin and np.uint64[n / 2 + 1] (None with want_sfs=False).  Between form: (bins, None), bins of
+		v2m_diversity_between_bin.  info=True: (..., dict of v2m_window_diversity_info's fields)."""
+		if not isinstance(rows, RowBatch):
+			rows = RowBatch(rows)
+		if rows_b is not None and not isinstance(rows_b, RowBatch):
+			rows_b = RowBatch(rows_b)
+		bounds = np.ascontiguousarray(bounds, dtype=np.uint64)
+		n_bins = max(0, len(bounds) - 1)
+		n = int(rows.struct.n_rows)
+		bins = np.zeros(max(1, n_bins), dtype=np.dtype(N.DIVERSITY_BIN_DTYPE if rows_b is None else N.DIVERSITY_BETWEEN_BIN_DTYPE))
+		sfs = np.zeros(n // 2 + 1, dtype=np.uint64) if (want_sfs and rows_b is None) else None
+		record = N.WindowDiversityInfo()
+		self._check(self._lib.v2m_window_diversity(self._h, C.byref(rows.struct), C.byref(rows_b.struct) if rows_b is not None else None,
+			bounds.ctypes.data if len(bounds) else None, n_bins, bins.ctypes.data, sfs.ctypes.data if sfs is not None else None, C.byref(record)))
+		result = (bins[:n_bins], sfs)
+		if info:
+			result += ({name: getattr(record, name) for name, _ in N.WindowDiversityInfo._fields_},)
+		return result
+
+	def diversity_of_counts(self, counts_ptr, plane_pitch, length, n, bounds, bins_ptr, sfs_ptr=None, counts_b_ptr=None, n_b=0):
+		"""v2m_diversity_of_counts: the bin records, and with `sfs_ptr` the folded spectrum, of the counts table in device memory at
+		`counts_ptr` (u32[6][plane_pitch] over `length` columns, counted over n rows) -- with `counts_b_ptr`, a second table over n_b
+		rows, the between form -- over the bins of `bounds` (host, relative to the tables), into device memory at `bins_ptr` and
+		`sfs_ptr`.  Returns the dict of v2m_window_diversity_info's fields."""
+		bounds = np.ascontiguousarray(bounds, dtype=np.uint64)
+		record = N.WindowDiversityInfo()
+		self._check(self._lib.v2m_diversity_of_counts(self._h, counts_ptr, counts_b_ptr, int(plane_pitch), int(length), int(n), int(n_b),
+			bounds.ctypes.data if len(bounds) else None, max(0, len(bounds) - 1), bins_ptr, sfs_ptr, C.byref(record)))
+		return {name: getattr(record, name) for name, _ in N.WindowDiversityInfo._fields_}
+
 	def bgzf_compress(self, data):
 		"""v2m_bgzf_compress: `data` as BGZF members, compressed on the GPU by the kernels of splice_rows(bgzf=True) (no EOF member)."""
 		src = bytes(data)
@@ -785,6 +818,12 @@ class Context:
 
 	def free_output(self, ptr):
 		self._check(self._lib.v2m_free_output(self._h, ptr))
+
+	def read_output(self, ptr, count, dtype=np.uint8):
+		"""v2m_read_output: `count` elements of `dtype` from device memory at `ptr`, after everything queued on the context's stream."""
+		out = np.zeros(max(1, int(count)), dtype=np.dtype(dtype))
+		self._check(self._lib.v2m_read_output(self._h, ptr, int(count) * out.dtype.itemsize, out.ctypes.data))
+		return out[:int(count)]
 
 	def checksum_rows_device(self, d_rows, row_pitch, n_rows, length=0, lengths=None):
 		out = np.zeros(n_rows, dtype=np.uint64)

@@ -627,6 +627,86 @@ int64_t v2mh_tree_sites_text(v2m_tree_site const *sites, uint64_t n_sites, uint6
 	}
 }
 
+// window_diversity_cpu() of output.hh (no GPU).  0, or -1 with a message in err.
+int v2mh_window_diversity_cpu(unsigned char const *rows_a, uint64_t n_a, unsigned char const *rows_b, uint64_t n_b, uint64_t L, uint64_t pitch, uint64_t const *bounds,
+	uint64_t n_bins, void *bins, uint64_t *sfs, uint64_t *multiallelic, char *err, size_t errlen)
+{
+	try {
+		if (!bounds || (!bins && n_bins) || (!rows_a && n_a && L) || (!rows_b && n_b)) throw std::invalid_argument("a pointer is NULL");
+		vh::window_diversity_cpu(rows_a, n_a, rows_b, n_b, L, pitch, bounds, n_bins, bins, sfs, multiallelic);
+		return 0;
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
+// diversity_values_of() of output.hh per record: out is double[n_windows][3] -- pi, theta_w, tajima_d; a quiet NaN where none exists.
+int v2mh_window_diversity_values(v2m_diversity_bin const *windows, uint64_t n_windows, uint64_t n, double *out)
+{
+	if ((!windows || !out) && n_windows) return -1;
+	for (uint64_t i(0); i < n_windows; ++i) {
+		vh::diversity_values const v(vh::diversity_values_of(windows[i], n));
+		out[3 * i] = v.pi; out[3 * i + 1] = v.theta_w; out[3 * i + 2] = v.tajima_d;
+	}
+	return 0;
+}
+
+// divergence_values_of() of output.hh per record: out is double[n_windows][2] -- dxy, fst.
+int v2mh_window_divergence_values(v2m_diversity_between_bin const *between, v2m_diversity_bin const *windows_a, v2m_diversity_bin const *windows_b, uint64_t n_windows, double *out)
+{
+	if ((!between || !windows_a || !windows_b || !out) && n_windows) return -1;
+	for (uint64_t i(0); i < n_windows; ++i) {
+		vh::divergence_values const v(vh::divergence_values_of(between[i], windows_a[i], windows_b[i]));
+		out[2 * i] = v.dxy; out[2 * i + 1] = v.fst;
+	}
+	return 0;
+}
+
+// window_diversity_text() of output.hh (no GPU), handed over as v2mh_nj_newick_text hands over its text.
+int64_t v2mh_window_diversity_text(char const *group, uint64_t n, v2m_diversity_bin const *windows, uint64_t const *starts, uint64_t const *ends, uint64_t n_windows, int header,
+	char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		if (!group || ((!windows || !starts || !ends) && n_windows)) throw std::runtime_error("a pointer is NULL");
+		std::string const text(vh::window_diversity_text(group, n, windows, starts, ends, n_windows, 0 != header));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
+// window_divergence_text() of output.hh (no GPU), handed over likewise.
+int64_t v2mh_window_divergence_text(char const *group_a, char const *group_b, v2m_diversity_between_bin const *between, v2m_diversity_bin const *windows_a,
+	v2m_diversity_bin const *windows_b, uint64_t const *starts, uint64_t const *ends, uint64_t n_windows, int header, char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		if (!group_a || !group_b || ((!between || !windows_a || !windows_b || !starts || !ends) && n_windows)) throw std::runtime_error("a pointer is NULL");
+		std::string const text(vh::window_divergence_text(group_a, group_b, between, windows_a, windows_b, starts, ends, n_windows, 0 != header));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
+// diversity_sfs_text() of output.hh (no GPU), handed over likewise; sfs holds n / 2 + 1 entries.
+int64_t v2mh_diversity_sfs_text(char const *group, uint64_t n, uint64_t const *sfs, uint64_t multiallelic, int header, char *dst, uint64_t capacity, char *err, size_t errlen)
+{
+	try {
+		if (!group || !sfs) throw std::runtime_error("a pointer is NULL");
+		std::string const text(vh::diversity_sfs_text(group, n, sfs, multiallelic, 0 != header));
+		if (dst && text.size() <= capacity) std::memcpy(dst, text.data(), text.size());
+		return int64_t(text.size());
+	} catch (std::exception const &e) {
+		if (err && errlen) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+		return -1;
+	}
+}
+
 // nj_split_support() of csrc/nj_support.hpp (no GPU): support[t], t < n - 3, = the n_replicates trees of replicate_nodes (n - 2 records
 // each) that hold the split of join record t of main_nodes.  0, or -1 for a NULL pointer, n < 3, records that are no tree, or no memory.
 int v2mh_nj_split_support(uint64_t n, v2m_nj_node const *main_nodes, v2m_nj_node const *replicate_nodes, uint64_t n_replicates, uint32_t *support)

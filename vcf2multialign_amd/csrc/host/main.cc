@@ -74,9 +74,72 @@ struct options {
 	char const *output_tree_parsimony{}, *output_tree_mutations{}, *output_tree_sites{};
 	std::uint64_t tree_seed_value{1};
 	bool all_columns{};                   // --all-columns (with --output-column-counts): every column, not only the variable ones
+	// --output-diversity=FILE, --diversity-sfs=FILE, --output-divergence=FILE: windowed diversity, the folded spectrum and the divergence
+	// between groups, from v2m_window_diversity / v2m_diversity_of_counts; --diversity-window=BP, --diversity-step=BP, --diversity-groups=FILE
+	char const *output_diversity{}, *diversity_sfs{}, *output_divergence{}, *diversity_window{}, *diversity_step{}, *diversity_groups{};
+	std::uint64_t diversity_window_bp{10000}, diversity_step_bp{10000};
+	std::vector<std::pair<std::string, std::string>> diversity_group_of;
 	bool distinct{};                      // --distinct (with --regions-file): every distinct sequence of a region once, and <name>.classes.tsv
 	std::vector<int> devices{0};
 };
+
+// Reads --diversity-groups: a TSV of sequence id and group name a line; empty lines and lines that begin with '#' are skipped.  Returns
+// an error text, or the empty string.  More than 16 groups, a line without two fields and an id named twice are errors here; an id that
+// names no output sequence is one once the sequences are known.
+std::string read_groups_file(char const *path, std::vector<std::pair<std::string, std::string>> &group_of)
+{
+	std::ifstream in(path);
+	if (!in) return std::string("unable to open ") + path;
+	std::set<std::string> ids, groups;
+	std::string line;
+	std::size_t number(0);
+	while (std::getline(in, line)) {
+		++number;
+		if (!line.empty() && '\r' == line.back()) line.pop_back();
+		if (line.empty() || '#' == line[0]) continue;
+		auto const tab(line.find('\t'));
+		if (std::string::npos == tab || 0 == tab || tab + 1 == line.size() || std::string::npos != line.find('\t', tab + 1))
+			return std::string(path) + ", line " + std::to_string(number) + ": a line holds a sequence id, a tab and a group name";
+		std::string const id(line.substr(0, tab)), group(line.substr(tab + 1));
+		if (!ids.insert(id).second) return std::string(path) + ", line " + std::to_string(number) + ": \"" + id + "\" is named twice";
+		groups.insert(group);
+		if (groups.size() > 16) return std::string(path) + ", line " + std::to_string(number) + ": more than 16 groups";
+		group_of.emplace_back(id, group);
+	}
+	if (group_of.empty()) return std::string(path) + " names no sequence";
+	return std::string();
+}
+
+// The first id of group_of that is neither [prefix.]REF nor [prefix.]<sample>.<number> for a sample of the #CHROM line of the plain-text
+// VCF at `path`; the empty string when there is none, or when the file is compressed, cannot be read or has no such line.
+std::string unknown_group_id(char const *path, char const *chromosome_prefix, std::vector<std::pair<std::string, std::string>> const &group_of)
+{
+	std::ifstream in(path, std::ios::binary);
+	if (!in || 0x1f == in.peek()) return std::string();
+	std::set<std::string> samples;
+	std::string line;
+	bool found(false);
+	while (std::getline(in, line)) {
+		if (line.empty() || '#' != line[0]) break;
+		if (0 != line.compare(0, 6, "#CHROM")) continue;
+		if ('\r' == line.back()) line.pop_back();
+		std::istringstream fields(line);
+		std::string field;
+		for (int k(0); std::getline(fields, field, '\t'); ++k) if (k >= 9) samples.insert(field);
+		found = true;
+		break;
+	}
+	if (!found) return std::string();
+	std::string const prefix(chromosome_prefix ? std::string(chromosome_prefix) + '.' : std::string());
+	for (auto const &[id, group] : group_of) {
+		if (0 != id.compare(0, prefix.size(), prefix)) return id;
+		std::string const name(id.substr(prefix.size()));
+		if ("REF" == name) continue;
+		auto const dot(name.rfind('.'));
+		if (std::string::npos == dot || dot + 1 == name.size() || std::string::npos != name.find_first_not_of("0123456789", dot + 1) || !samples.count(name.substr(0, dot))) return id;
+	}
+	return std::string();
+}
 
 void usage()
 {
@@ -189,6 +252,20 @@ void usage()
 		"                                     column, reference position (as --output-site-positions writes them), from, to\n"
 		"      --output-tree-sites=FILE       With --output-tree: write one line per SNP column: column, reference position, the letters\n"
 		"                                     present, the steps on the tree, and the homoplasy steps - (letters - 1)\n"
+		"      --output-diversity=FILE        Write a TSV with one line per window of the reference and group of output sequences: group,\n"
+		"                                     start, end (reference positions, 1-based inclusive), columns, called, diffs, pairs, pi,\n"
+		"                                     segregating, complete, theta_w, tajima_d (nucleotide diversity, Watterson's theta and\n"
+		"                                     Tajima's D; NA where a value does not exist).  Computed on the GPU from the column counts,\n"
+		"                                     in integers; always of the aligned form; --region restricts the columns.  The columns of\n"
+		"                                     an insertion fall to the window of the reference position before them.  Not with\n"
+		"                                     --regions-file or several --device entries\n"
+		"      --diversity-window=BP          The window, in reference positions (default 10000)\n"
+		"      --diversity-step=BP            The step between window starts (default: the window); it must divide the window\n"
+		"      --diversity-sfs=FILE           Write the folded site frequency spectrum of every group: group, n, minor count, columns\n"
+		"      --diversity-groups=FILE        A TSV of sequence id (as --output-distances names them) and group name; a sequence it does\n"
+		"                                     not name belongs to no group; at most 16 groups.  Without it there is one group, all\n"
+		"      --output-divergence=FILE       With --diversity-groups: write per pair of groups and window group_a, group_b, start, end,\n"
+		"                                     columns, called, diffs, pairs, dxy, fst (Hudson's)\n"
 		"      --gpu-parse                    Parse the genotype columns of --input-variants on the first GPU, under the BGZF\n"
 		"                                     inflate for compressed input: the VCF text never reaches the host (not with -g).\n"
 		"                                     Input the scan does not support (more than 32 768 chromosome copies, a line longer\n"
@@ -394,7 +471,7 @@ int main(int argc, char **argv)
 	::setenv("V2M_NT_STORES", "1", 0);
 	::setenv("V2M_UNALIGNED_STORE", "plain", 0);
 	options opt;
-	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_output_tree, o_tree_acgt_only, o_tree_bootstrap, o_tree_seed, o_output_tree_replicates, o_output_tree_parsimony, o_output_tree_mutations, o_output_tree_sites, o_unsupported };
+	enum { o_keep_ref = 900, o_separate = 1000, o_sep_format, o_omit_ref, o_unaligned, o_overlaps, o_stats, o_mismatch, o_include, o_device, o_verbose, o_pipe, o_bgzf, o_region, o_gpu_parse, o_regions_file, o_output_chain, o_distinct, o_output_paf, o_output_column_counts, o_all_columns, o_output_distances, o_acgt_only, o_output_variable_sites, o_snp_sites, o_output_site_positions, o_output_ld, o_ld_window, o_ld_window_columns, o_ld_min_r2, o_ld_min_count, o_output_tree, o_tree_acgt_only, o_tree_bootstrap, o_tree_seed, o_output_tree_replicates, o_output_tree_parsimony, o_output_tree_mutations, o_output_tree_sites, o_output_diversity, o_diversity_window, o_diversity_step, o_diversity_sfs, o_diversity_groups, o_output_divergence, o_unsupported };
 	static option const longopts[] = {
 		{"haplotypes", no_argument, nullptr, 'H'}, {"founder-sequences", required_argument, nullptr, 'F'},
 		{"input-reference", required_argument, nullptr, 'r'}, {"reference-sequence", required_argument, nullptr, 'e'},
@@ -413,6 +490,9 @@ int main(int argc, char **argv)
 		{"tree-bootstrap", required_argument, nullptr, o_tree_bootstrap}, {"tree-seed", required_argument, nullptr, o_tree_seed}, {"output-tree-replicates", required_argument, nullptr, o_output_tree_replicates},
 		{"output-tree-parsimony", required_argument, nullptr, o_output_tree_parsimony}, {"output-tree-mutations", required_argument, nullptr, o_output_tree_mutations},
 		{"output-tree-sites", required_argument, nullptr, o_output_tree_sites},
+		{"output-diversity", required_argument, nullptr, o_output_diversity}, {"diversity-window", required_argument, nullptr, o_diversity_window},
+		{"diversity-step", required_argument, nullptr, o_diversity_step}, {"diversity-sfs", required_argument, nullptr, o_diversity_sfs},
+		{"diversity-groups", required_argument, nullptr, o_diversity_groups}, {"output-divergence", required_argument, nullptr, o_output_divergence},
 		{"minimum-distance", required_argument, nullptr, 'd'}, {"input-cut-positions", required_argument, nullptr, 'p'},
 		{"output-cut-positions", required_argument, nullptr, 't'}, {"keep-ref-edges", no_argument, nullptr, o_keep_ref},
 		{"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
@@ -482,6 +562,12 @@ int main(int argc, char **argv)
 			case o_output_tree_parsimony: opt.output_tree_parsimony = optarg; break;
 			case o_output_tree_mutations: opt.output_tree_mutations = optarg; break;
 			case o_output_tree_sites: opt.output_tree_sites = optarg; break;
+			case o_output_diversity: opt.output_diversity = optarg; break;
+			case o_diversity_window: opt.diversity_window = optarg; break;
+			case o_diversity_step: opt.diversity_step = optarg; break;
+			case o_diversity_sfs: opt.diversity_sfs = optarg; break;
+			case o_diversity_groups: opt.diversity_groups = optarg; break;
+			case o_output_divergence: opt.output_divergence = optarg; break;
 			case 'p': opt.input_cut_positions = optarg; break;
 			case 't': opt.output_cut_positions = optarg; break;
 			case 'h': usage(); return EXIT_SUCCESS;
@@ -534,6 +620,40 @@ int main(int argc, char **argv)
 		// one matrix from one context that holds every chromosome copy; a column window is fine, a window set is not a view of its own
 		char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
 		if (other) { std::cerr << "ERROR: --output-distances cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+	}
+	{
+		bool const any(opt.output_diversity || opt.diversity_sfs || opt.output_divergence);
+		for (auto const &[value, name] : {std::pair<char const *, char const *>{opt.diversity_window, "--diversity-window"}, {opt.diversity_step, "--diversity-step"},
+			{opt.diversity_groups, "--diversity-groups"}})
+			if (value && !any) { std::cerr << "ERROR: " << name << " requires --output-diversity, --diversity-sfs or --output-divergence.\n"; return EXIT_FAILURE; }
+		if (opt.output_divergence && !opt.diversity_groups) { std::cerr << "ERROR: --output-divergence requires --diversity-groups.\n"; return EXIT_FAILURE; }
+		if (any) {
+			char const *const other(opt.regions_file ? "--regions-file" : opt.devices.size() > 1 ? "more than one --device entry" : nullptr);
+			if (other) { std::cerr << "ERROR: the diversity outputs cannot be combined with " << other << ".\n"; return EXIT_FAILURE; }
+			if (opt.diversity_window && (!parse_count(opt.diversity_window, opt.diversity_window_bp) || 0 == opt.diversity_window_bp)) {
+				std::cerr << "ERROR: --diversity-window must be a positive number of reference positions, got \"" << opt.diversity_window << "\".\n";
+				return EXIT_FAILURE;
+			}
+			opt.diversity_step_bp = opt.diversity_window_bp;
+			if (opt.diversity_step && (!parse_count(opt.diversity_step, opt.diversity_step_bp) || 0 == opt.diversity_step_bp)) {
+				std::cerr << "ERROR: --diversity-step must be a positive number of reference positions, got \"" << opt.diversity_step << "\".\n";
+				return EXIT_FAILURE;
+			}
+			if (opt.diversity_window_bp % opt.diversity_step_bp) {
+				std::cerr << "ERROR: --diversity-step must divide --diversity-window (" << opt.diversity_window_bp << " is no multiple of " << opt.diversity_step_bp << ").\n";
+				return EXIT_FAILURE;
+			}
+			if (opt.diversity_groups) {
+				std::string const err(read_groups_file(opt.diversity_groups, opt.diversity_group_of));
+				if (!err.empty()) { std::cerr << "ERROR: " << err << ".\n"; return EXIT_FAILURE; }
+				// An id that can name no output sequence is refused before a device is opened, where the sample names can be read without one:
+				// from the #CHROM line of a plain-text VCF.  The copy numbers, and compressed or graph input, are checked once the graph is built.
+				if (opt.haplotypes && opt.input_variants) {
+					std::string const bad(unknown_group_id(opt.input_variants, opt.dst_chromosome, opt.diversity_group_of));
+					if (!bad.empty()) { std::cerr << "ERROR: " << opt.diversity_groups << ": \"" << bad << "\" names no output sequence.\n"; return EXIT_FAILURE; }
+				}
+			}
+		}
 	}
 	if (opt.tree_acgt_only && !opt.output_tree) { std::cerr << "ERROR: --tree-acgt-only requires --output-tree.\n"; return EXIT_FAILURE; }
 	if (opt.tree_bootstrap && !opt.output_tree) { std::cerr << "ERROR: --tree-bootstrap requires --output-tree.\n"; return EXIT_FAILURE; }
@@ -725,6 +845,17 @@ int main(int argc, char **argv)
 			return EXIT_FAILURE;
 		}
 
+		if (opt.haplotypes && !opt.diversity_group_of.empty()) {
+			// the names --output-distances gives the rows (output.cc: haplotype_output::rows_for), known before a device is opened
+			std::set<std::string> known;
+			std::string const prefix(opt.dst_chromosome ? std::string(opt.dst_chromosome) + '.' : std::string());
+			if (!opt.omit_reference) known.insert(prefix + "REF");
+			for (std::size_t s(0); s < graph.sample_names.size(); ++s)
+				for (vh::u32 c(0); c < graph.sample_ploidy(s); ++c) known.insert(prefix + graph.sample_names[s] + '.' + std::to_string(1 + c));
+			for (auto const &[id, group] : opt.diversity_group_of)
+				if (!known.count(id)) { std::cerr << "ERROR: " << opt.diversity_groups << ": \"" << id << "\" names no output sequence.\n"; return EXIT_FAILURE; }
+		}
+
 		if (opt.output_graph) {                                 // main.cc:418-426
 			std::cerr << "Outputting the variant graph..." << std::flush;
 			vh::write_graph(graph, opt.output_graph);
@@ -850,6 +981,18 @@ int main(int argc, char **argv)
 			if (opt.output_ld) {
 				std::cerr << "Outputting site LD..." << std::flush;
 				output.output_ld(graph, opt.output_ld, opt.ld_params, opt.verbose);
+				std::cerr << " Done.\n";
+			}
+			if (opt.output_diversity || opt.diversity_sfs || opt.output_divergence) {
+				std::cerr << "Outputting the window diversity..." << std::flush;
+				vh::output::diversity_params params;
+				params.window = opt.diversity_window_bp;
+				params.step = opt.diversity_step_bp;
+				params.ref_len = ref_seq.size();
+				params.ref_begin = opt.region ? opt.region_start - 1 : 0;
+				params.ref_end = opt.region ? opt.region_end : ref_seq.size();
+				params.groups = opt.diversity_group_of;
+				output.output_diversity(graph, params, opt.output_diversity, opt.diversity_sfs, opt.output_divergence, opt.verbose);
 				std::cerr << " Done.\n";
 			}
 			if (opt.output_tree) {

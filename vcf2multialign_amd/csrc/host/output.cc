@@ -12,6 +12,10 @@
 #include <atomic>
 #include <algorithm>
 #include <cctype>
+#include <cmath>
+#include <limits>
+#include <map>
+#include <set>
 #include <cerrno>
 #include <condition_variable>
 #include <cstring>
@@ -1866,6 +1870,425 @@ void output::output_tree_parsimony(variant_graph const &graph, char const *newic
 		if (!streams[k]) throw std::runtime_error(std::string("unable to open ") + paths[k] + " for writing");
 	}
 	output_tree_parsimony(graph, newick_path ? &streams[0] : nullptr, mutations_path ? &streams[1] : nullptr, sites_path ? &streams[2] : nullptr, verbose);
+	for (int k(0); k < 3; ++k) {
+		if (!paths[k]) continue;
+		streams[k].flush();
+		if (!streams[k]) throw std::runtime_error(std::string("error while writing ") + paths[k]);
+	}
+}
+
+
+// --- window diversity ---------------------------------------------------------------------------------------
+
+void window_diversity_cpu(unsigned char const *rows_a, u64 n_a, unsigned char const *rows_b, u64 n_b, u64 L, u64 pitch, u64 const *bounds, u64 n_bins, void *bins, u64 *sfs,
+	u64 *multiallelic)
+{
+	if (rows_b && sfs) throw std::invalid_argument("the between form has no spectrum");
+	if (pitch < L) throw std::invalid_argument("the pitch is smaller than the columns");
+	for (u64 k(0); k < n_bins; ++k) if (bounds[k] > bounds[k + 1]) throw std::invalid_argument("the bounds descend");
+	if (n_bins && bounds[n_bins] > L) throw std::invalid_argument("the bounds leave the columns");
+	auto const tally([pitch](unsigned char const *rows, u64 n, u64 column, u64 (&count)[4]) {
+		count[0] = count[1] = count[2] = count[3] = 0;
+		for (u64 r(0); r < n; ++r) {
+			switch (rows[r * pitch + column] | 0x20) {
+				case 'a': ++count[0]; break;
+				case 'c': ++count[1]; break;
+				case 'g': ++count[2]; break;
+				case 't': ++count[3]; break;
+				default: break;
+			}
+		}
+	});
+	if (sfs) std::fill(sfs, sfs + (n_a / 2 + 1), u64(0));
+	u64 many(0);
+	for (u64 k(0); k < n_bins; ++k) {
+		v2m_diversity_bin within{};
+		v2m_diversity_between_bin between{};
+		within.columns = between.columns = bounds[k + 1] - bounds[k];
+		for (u64 column(bounds[k]); column < bounds[k + 1]; ++column) {
+			u64 a[4], b[4];
+			tally(rows_a, n_a, column, a);
+			u64 const m(a[0] + a[1] + a[2] + a[3]);
+			if (rows_b) {
+				tally(rows_b, n_b, column, b);
+				u64 const m_b(b[0] + b[1] + b[2] + b[3]);
+				if (m >= 1 && m_b >= 1) ++between.called;
+				between.pairs += m * m_b;
+				for (int x(0); x < 4; ++x) for (int y(0); y < 4; ++y) if (x != y) between.diffs += a[x] * b[y];
+				continue;
+			}
+			u64 squares(0);
+			int letters(0);
+			for (int x(0); x < 4; ++x) { squares += a[x] * a[x]; if (a[x]) ++letters; }
+			u64 const diffs((m * m - squares) / 2);
+			bool const complete(m == n_a && n_a >= 2);
+			if (m >= 2) { ++within.called; within.pairs += m * (m - 1) / 2; }
+			within.diffs += diffs;
+			if (letters >= 2) ++within.segregating;
+			if (complete) {
+				++within.complete;
+				within.complete_diffs += diffs;
+				if (letters >= 2) ++within.complete_segregating;
+				if (letters >= 3) ++many;
+				else if (sfs) {
+					std::sort(a, a + 4);   // ascending: a[3] the major count, a[2] the minor one or 0
+					++sfs[a[2]];
+				}
+			}
+		}
+		if (rows_b) static_cast<v2m_diversity_between_bin *>(bins)[k] = between;
+		else static_cast<v2m_diversity_bin *>(bins)[k] = within;
+	}
+	if (multiallelic) *multiallelic = sfs ? many : 0;
+}
+
+
+// The header's order, one operation per statement.  The host library is compiled with -ffp-contract=off (build.py: CXX_FLAGS): without
+// it the compiler may fuse a product into the sum of a later statement where the target has a fused multiply-add.
+diversity_values diversity_values_of(v2m_diversity_bin const &w, u64 n_rows)
+{
+	double const none(std::numeric_limits<double>::quiet_NaN());
+	diversity_values out{none, none, none};
+	if (w.pairs) out.pi = double(w.diffs) / double(w.pairs);
+	if (n_rows < 2) return out;
+	double a1(0), a2(0);
+	for (u64 i(1); i < n_rows; ++i) {
+		double const di = double(i);
+		double const inverse = 1.0 / di;
+		a1 = a1 + inverse;
+		double const square = di * di;
+		double const inverse_square = 1.0 / square;
+		a2 = a2 + inverse_square;
+	}
+	double const n = double(n_rows);
+	double const S = double(w.complete_segregating);
+	double const theta = S / a1;
+	out.theta_w = theta;
+	double const n_plus = n + 1.0, n_minus = n - 1.0;
+	double const three = 3.0 * n_minus;
+	double const b1 = n_plus / three;
+	double const nn = n * n;
+	double const nn_n = nn + n;
+	double const nn_n_3 = nn_n + 3.0;
+	double const twice = 2.0 * nn_n_3;
+	double const nine_n = 9.0 * n;
+	double const nine_n_n1 = nine_n * n_minus;
+	double const b2 = twice / nine_n_n1;
+	double const inv_a1 = 1.0 / a1;
+	double const c1 = b1 - inv_a1;
+	double const n_plus_2 = n + 2.0;
+	double const a1_n = a1 * n;
+	double const middle = n_plus_2 / a1_n;
+	double const a1_a1 = a1 * a1;
+	double const tail = a2 / a1_a1;
+	double const c2_head = b2 - middle;
+	double const c2 = c2_head + tail;
+	double const e1 = c1 / a1;
+	double const e2_den = a1_a1 + a2;
+	double const e2 = c2 / e2_den;
+	double const n_n1 = n * n_minus;
+	double const half = n_n1 / 2.0;
+	double const k = double(w.complete_diffs) / half;
+	double const e1_S = e1 * S;
+	double const e2_S = e2 * S;
+	double const S_minus = S - 1.0;
+	double const e2_term = e2_S * S_minus;
+	double const v = e1_S + e2_term;
+	if (v > 0) {
+		double const numerator = k - theta;
+		double const root = std::sqrt(v);
+		out.tajima_d = numerator / root;
+	}
+	return out;
+}
+
+
+divergence_values divergence_values_of(v2m_diversity_between_bin const &between, v2m_diversity_bin const &window_a, v2m_diversity_bin const &window_b)
+{
+	double const none(std::numeric_limits<double>::quiet_NaN());
+	divergence_values out{none, none};
+	if (!between.pairs) return out;
+	out.dxy = double(between.diffs) / double(between.pairs);
+	if (!window_a.pairs || !window_b.pairs || !(out.dxy > 0)) return out;
+	double const pi_a = double(window_a.diffs) / double(window_a.pairs);
+	double const pi_b = double(window_b.diffs) / double(window_b.pairs);
+	double const sum = pi_a + pi_b;
+	double const twice = 2.0 * out.dxy;
+	double const ratio = sum / twice;
+	out.fst = 1.0 - ratio;
+	return out;
+}
+
+
+namespace {
+	void append_diversity_double(std::string &text, double value)
+	{
+		if (value != value) { text += "\tNA"; return; }
+		char buf[48];
+		std::snprintf(buf, sizeof(buf), "\t%.10g", value);
+		text += buf;
+	}
+
+	void check_group_name(std::string const &group)
+	{
+		for (char const c : group) if ('\t' == c || '\n' == c || '\r' == c) throw std::runtime_error("a group name holds a tab or a line break");
+	}
+}
+
+
+std::string window_diversity_text(std::string const &group, u64 n, v2m_diversity_bin const *windows, u64 const *starts, u64 const *ends, u64 n_windows, bool header)
+{
+	check_group_name(group);
+	std::string text;
+	if (header) text += "#group\tstart\tend\tcolumns\tcalled\tdiffs\tpairs\tpi\tsegregating\tcomplete\ttheta_w\ttajima_d\n";
+	for (u64 i(0); i < n_windows; ++i) {
+		v2m_diversity_bin const &w(windows[i]);
+		diversity_values const values(diversity_values_of(w, n));
+		text += group;
+		for (u64 const x : {starts[i], ends[i], w.columns, w.called, w.diffs, w.pairs}) { text += '\t'; text += std::to_string(x); }
+		append_diversity_double(text, values.pi);
+		for (u64 const x : {w.segregating, w.complete}) { text += '\t'; text += std::to_string(x); }
+		append_diversity_double(text, values.theta_w);
+		append_diversity_double(text, values.tajima_d);
+		text += '\n';
+	}
+	return text;
+}
+
+
+std::string window_divergence_text(std::string const &group_a, std::string const &group_b, v2m_diversity_between_bin const *between, v2m_diversity_bin const *windows_a,
+	v2m_diversity_bin const *windows_b, u64 const *starts, u64 const *ends, u64 n_windows, bool header)
+{
+	check_group_name(group_a);
+	check_group_name(group_b);
+	std::string text;
+	if (header) text += "#group_a\tgroup_b\tstart\tend\tcolumns\tcalled\tdiffs\tpairs\tdxy\tfst\n";
+	for (u64 i(0); i < n_windows; ++i) {
+		v2m_diversity_between_bin const &w(between[i]);
+		divergence_values const values(divergence_values_of(w, windows_a[i], windows_b[i]));
+		text += group_a;
+		text += '\t';
+		text += group_b;
+		for (u64 const x : {starts[i], ends[i], w.columns, w.called, w.diffs, w.pairs}) { text += '\t'; text += std::to_string(x); }
+		append_diversity_double(text, values.dxy);
+		append_diversity_double(text, values.fst);
+		text += '\n';
+	}
+	return text;
+}
+
+
+std::string diversity_sfs_text(std::string const &group, u64 n, u64 const *sfs, u64 multiallelic, bool header)
+{
+	check_group_name(group);
+	std::string text;
+	if (header) text += "#group\tn\tminor_count\tcolumns\n";
+	std::string const head(group + '\t' + std::to_string(n) + '\t');
+	for (u64 k(0); k < n / 2 + 1; ++k) text += head + std::to_string(k) + '\t' + std::to_string(sfs[k]) + '\n';
+	text += head + "multiallelic\t" + std::to_string(multiallelic) + '\n';
+	return text;
+}
+
+
+namespace {
+	// The rows of a row_set picked by index, as a batch of their own.
+	struct picked_rows {
+		std::vector<std::uint32_t> copy_index;
+		std::vector<std::uint64_t> cut_offsets{0}, cut_nodes;
+		std::vector<std::uint32_t> cut_copies;
+		bool any_cuts{};
+		v2m_row_batch batch() const
+		{
+			v2m_row_batch b{};
+			b.n_rows = copy_index.size();
+			b.copy_index = copy_index.data();
+			if (any_cuts) { b.cut_offsets = cut_offsets.data(); b.cut_nodes = cut_nodes.data(); b.cut_copies = cut_copies.data(); }
+			return b;
+		}
+	};
+
+	// Device memory of v2m_alloc_output, freed with the scope.
+	struct output_buffers {
+		gpu_context &gpu;
+		std::vector<void *> held;
+		explicit output_buffers(gpu_context &g) : gpu(g) {}
+		output_buffers(output_buffers const &) = delete;
+		~output_buffers() { for (void *p : held) (void) v2m_free_output(gpu.get(), p); }
+		void *take(u64 bytes)
+		{
+			void *p(nullptr);
+			gpu.check(v2m_alloc_output(gpu.get(), std::max<u64>(bytes, 16), 1, &p));
+			held.push_back(p);
+			return p;
+		}
+	};
+
+	template <typename t_record>
+	std::vector<t_record> summed_windows(std::vector<t_record> const &bins, u64 width, u64 n_windows)
+	{
+		static_assert(0 == sizeof(t_record) % sizeof(u64));
+		constexpr std::size_t fields(sizeof(t_record) / sizeof(u64));
+		std::vector<t_record> out(n_windows);
+		for (u64 j(0); j < n_windows; ++j) {
+			u64 sums[fields] = {};
+			for (u64 k(j); k < std::min<u64>(bins.size(), j + width); ++k) {
+				u64 one[fields];
+				std::memcpy(one, &bins[k], sizeof(t_record));
+				for (std::size_t f(0); f < fields; ++f) sums[f] += one[f];
+			}
+			std::memcpy(&out[j], sums, sizeof(t_record));
+		}
+		return out;
+	}
+}
+
+
+void output::output_diversity(variant_graph const &graph, diversity_params const &params, std::ostream *diversity, std::ostream *sfs_stream, std::ostream *divergence, bool verbose)
+{
+	if (!m_more_gpus.empty()) throw std::runtime_error("--output-diversity needs every chromosome copy on one GPU context");
+	if (!m_copy_shards.empty() && 0 != m_copy_shards.front().first) throw std::runtime_error("--output-diversity needs every chromosome copy on one GPU context");
+	if (0 == params.step || 0 == params.window || params.window % params.step) throw std::invalid_argument("--diversity-step must divide --diversity-window");
+	if (params.ref_begin >= params.ref_end || params.ref_end > params.ref_len) throw std::invalid_argument("the reference range of the diversity outputs is empty or outside the reference");
+	row_set const rows(chain_rows(graph));
+
+	// the groups, in the order their names first appear
+	std::vector<std::string> names;
+	std::vector<std::vector<std::size_t>> members;
+	if (params.groups.empty()) {
+		names.push_back("all");
+		members.emplace_back(rows.ids.size());
+		for (std::size_t r(0); r < rows.ids.size(); ++r) members[0][r] = r;
+	} else {
+		std::map<std::string, std::size_t> row_of;
+		for (std::size_t r(0); r < rows.ids.size(); ++r) row_of.emplace(rows.ids[r], r);
+		std::set<std::string> seen;
+		for (auto const &[id, group] : params.groups) {
+			auto const it(row_of.find(id));
+			if (row_of.end() == it) throw std::runtime_error("--diversity-groups: \"" + id + "\" names no output sequence");
+			if (!seen.insert(id).second) throw std::runtime_error("--diversity-groups: \"" + id + "\" is named twice");
+			auto at(std::find(names.begin(), names.end(), group));
+			if (names.end() == at) {
+				if (16 == names.size()) throw std::runtime_error("--diversity-groups: more than 16 groups");
+				names.push_back(group);
+				members.emplace_back();
+				at = names.end() - 1;
+			}
+			members[std::size_t(at - names.begin())].push_back(it->second);
+		}
+		for (auto &m : members) std::sort(m.begin(), m.end());   // (the rows in output order)
+	}
+	std::size_t const G(names.size());
+	if (divergence && G < 2) throw std::runtime_error("--output-divergence needs at least two groups");
+	std::vector<picked_rows> picked(G);
+	for (std::size_t g(0); g < G; ++g) {
+		picked[g].any_cuts = rows.any_cuts;
+		for (std::size_t const r : members[g]) {
+			picked[g].copy_index.push_back(rows.copy_index[r]);
+			if (rows.any_cuts) {
+				for (u64 k(rows.cut_offsets[r]); k < rows.cut_offsets[r + 1]; ++k) { picked[g].cut_nodes.push_back(rows.cut_nodes[k]); picked[g].cut_copies.push_back(rows.cut_copies[k]); }
+				picked[g].cut_offsets.push_back(picked[g].cut_nodes.size());
+			}
+		}
+	}
+
+	// the bins: one per step of reference positions, bounded by the columns of their first positions
+	u64 const span(params.ref_end - params.ref_begin), n_bins((span + params.step - 1) / params.step), width(params.window / params.step);
+	std::vector<u64> bounds(n_bins + 1);
+	for (u64 k(0); k < n_bins; ++k) bounds[k] = columns_of_reference_range(graph, params.ref_len, params.ref_begin + k * params.step, params.ref_end).begin;
+	bounds[n_bins] = columns_of_reference_range(graph, params.ref_len, params.ref_begin, params.ref_end).end;
+	u64 const L(v2m_window_length(m_gpu.get()));
+	if (bounds[n_bins] - bounds[0] != L) throw std::runtime_error("the view in force is not the columns of the diversity outputs' reference range");
+	u64 const n_windows(n_bins >= width ? n_bins - width + 1 : 1);
+	std::vector<u64> starts(n_windows), ends(n_windows);
+	for (u64 j(0); j < n_windows; ++j) {
+		starts[j] = params.ref_begin + j * params.step + 1;
+		ends[j] = std::min(params.ref_end, params.ref_begin + j * params.step + params.window);
+	}
+
+	std::vector<std::vector<v2m_diversity_bin>> within(G, std::vector<v2m_diversity_bin>(n_bins));
+	std::vector<std::vector<u64>> spectra(G);
+	std::vector<u64> multiallelic(G);
+	std::vector<std::vector<v2m_diversity_between_bin>> between;   // pairs (a, b), a < b, in order
+	for (std::size_t g(0); g < G; ++g) spectra[g].resize(members[g].size() / 2 + 1);
+	if (params.groups.empty()) {
+		v2m_row_batch const batch(picked[0].batch());
+		v2m_window_diversity_info info{};
+		m_gpu.check(v2m_window_diversity(m_gpu.get(), &batch, nullptr, bounds.data(), n_bins, within[0].data(), spectra[0].data(), &info));
+		multiallelic[0] = info.multiallelic;
+	} else {
+		u64 const pitch((L + 3) & ~u64(3)), table_bytes(u64(V2M_COUNT_CLASSES) * pitch * 4);
+		u64 limit(u64(16) << 30);
+		if (char const *const text = std::getenv("V2M_DIVERSITY_TABLE_BYTES")) limit = std::strtoull(text, nullptr, 10);
+		if (G * table_bytes > limit)
+			throw std::runtime_error("the counts tables of " + std::to_string(G) + " groups over " + std::to_string(L) + " columns take " + std::to_string(G * table_bytes)
+				+ " bytes, more than V2M_DIVERSITY_TABLE_BYTES = " + std::to_string(limit) + ": use --region or fewer groups");
+		std::vector<u64> relative(bounds);
+		for (auto &b : relative) b -= bounds[0];
+		output_buffers buffers(m_gpu);
+		std::vector<void *> tables(G);
+		u64 most(0);
+		for (std::size_t g(0); g < G; ++g) {
+			tables[g] = buffers.take(table_bytes);
+			v2m_row_batch const batch(picked[g].batch());
+			m_gpu.check(v2m_column_counts_device(m_gpu.get(), &batch, 0, tables[g], pitch));
+			most = std::max<u64>(most, members[g].size());
+		}
+		void *const d_bins(buffers.take(n_bins * sizeof(v2m_diversity_bin)));
+		void *const d_sfs(buffers.take((most / 2 + 1) * sizeof(u64)));
+		for (std::size_t g(0); g < G; ++g) {
+			v2m_window_diversity_info info{};
+			m_gpu.check(v2m_diversity_of_counts(m_gpu.get(), tables[g], nullptr, pitch, L, members[g].size(), 0, relative.data(), n_bins, d_bins, d_sfs, &info));
+			m_gpu.check(v2m_read_output(m_gpu.get(), d_bins, n_bins * sizeof(v2m_diversity_bin), within[g].data()));
+			m_gpu.check(v2m_read_output(m_gpu.get(), d_sfs, spectra[g].size() * sizeof(u64), spectra[g].data()));
+			multiallelic[g] = info.multiallelic;
+		}
+		if (divergence) {
+			for (std::size_t a(0); a < G; ++a) for (std::size_t b(a + 1); b < G; ++b) {
+				between.emplace_back(n_bins);
+				m_gpu.check(v2m_diversity_of_counts(m_gpu.get(), tables[a], tables[b], pitch, L, members[a].size(), members[b].size(), relative.data(), n_bins, d_bins, nullptr, nullptr));
+				m_gpu.check(v2m_read_output(m_gpu.get(), d_bins, n_bins * sizeof(v2m_diversity_between_bin), between.back().data()));
+			}
+		}
+	}
+
+	std::vector<std::vector<v2m_diversity_bin>> windows(G);
+	for (std::size_t g(0); g < G; ++g) windows[g] = summed_windows(within[g], width, n_windows);
+	if (diversity) {
+		for (std::size_t g(0); g < G; ++g) {
+			std::string const text(window_diversity_text(names[g], members[g].size(), windows[g].data(), starts.data(), ends.data(), n_windows, 0 == g));
+			diversity->write(text.data(), std::streamsize(text.size()));
+		}
+	}
+	if (sfs_stream) {
+		for (std::size_t g(0); g < G; ++g) {
+			std::string const text(diversity_sfs_text(names[g], members[g].size(), spectra[g].data(), multiallelic[g], 0 == g));
+			sfs_stream->write(text.data(), std::streamsize(text.size()));
+		}
+	}
+	if (divergence) {
+		std::size_t pair(0);
+		for (std::size_t a(0); a < G; ++a) for (std::size_t b(a + 1); b < G; ++b, ++pair) {
+			auto const sums(summed_windows(between[pair], width, n_windows));
+			std::string const text(window_divergence_text(names[a], names[b], sums.data(), windows[a].data(), windows[b].data(), starts.data(), ends.data(), n_windows, 0 == pair));
+			divergence->write(text.data(), std::streamsize(text.size()));
+		}
+	}
+	if (verbose)
+		std::fprintf(stderr, "Diversity: %llu rows, %llu columns, %llu groups, %llu bins, %llu windows.\n", (unsigned long long) rows.ids.size(), (unsigned long long) L,
+			(unsigned long long) G, (unsigned long long) n_bins, (unsigned long long) n_windows);
+}
+
+
+void output::output_diversity(variant_graph const &graph, diversity_params const &params, char const *diversity_path, char const *sfs_path, char const *divergence_path, bool verbose)
+{
+	std::ofstream streams[3];
+	char const *const paths[3] = {diversity_path, sfs_path, divergence_path};
+	for (int k(0); k < 3; ++k) {
+		if (!paths[k]) continue;
+		streams[k].open(paths[k], std::ios::binary | std::ios::trunc);
+		if (!streams[k]) throw std::runtime_error(std::string("unable to open ") + paths[k] + " for writing");
+	}
+	output_diversity(graph, params, diversity_path ? &streams[0] : nullptr, sfs_path ? &streams[1] : nullptr, divergence_path ? &streams[2] : nullptr, verbose);
 	for (int k(0); k < 3; ++k) {
 		if (!paths[k]) continue;
 		streams[k].flush();

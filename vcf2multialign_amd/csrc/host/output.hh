@@ -11,6 +11,7 @@
 #include <functional>
 #include <ostream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gpu_path.hh"
@@ -129,6 +130,38 @@ std::string tree_mutations_text(v2m_tree_mutation const *mutations, u64 n_mutati
 // states the letters of ACGT present, homoplasy = steps - (popcount(present) - 1) as a signed number.
 std::string tree_sites_text(v2m_tree_site const *sites, u64 n_sites, u64 const *reference_positions, u64 const *aligned_positions, u64 node_count);
 
+// Window diversity (include/v2m_hip.h, "window diversity") restated in plain loops from spliced rows, not from a counts table: rows_a is
+// u8[n_a][pitch] and, for the between form, rows_b u8[n_b][pitch] (else NULL), of which the first L bytes of a row count; bounds are
+// relative to the rows, bounds[n_bins] <= L.  Per column the letters of every row are tallied; diffs is (m^2 - the sum of the squared
+// tallies) / 2 within and the sum over unlike letters of the two groups' tallies between -- neither is the expression the kernel uses.
+// bins receives n_bins records of v2m_diversity_bin (within) or v2m_diversity_between_bin (between); sfs (within only, may be NULL)
+// n_a / 2 + 1 entries; *multiallelic (may be NULL) the count the spectrum defines.  Throws std::invalid_argument for descending bounds,
+// bounds beyond L or the pitch, or a spectrum in the between form.
+void window_diversity_cpu(unsigned char const *rows_a, u64 n_a, unsigned char const *rows_b, u64 n_b, u64 L, u64 pitch, u64 const *bounds, u64 n_bins, void *bins, u64 *sfs,
+	u64 *multiallelic);
+
+// The doubles of the header, operation by operation; a value that does not exist is a quiet NaN.
+struct diversity_values { double pi, theta_w, tajima_d; };
+diversity_values diversity_values_of(v2m_diversity_bin const &window, u64 n);
+struct divergence_values { double dxy, fst; };
+divergence_values divergence_values_of(v2m_diversity_between_bin const &between, v2m_diversity_bin const &window_a, v2m_diversity_bin const &window_b);
+
+// --output-diversity's lines for one group of n sequences: one per window,
+//   <group><TAB><start><TAB><end><TAB>columns<TAB>called<TAB>diffs<TAB>pairs<TAB>pi<TAB>segregating<TAB>complete<TAB>theta_w<TAB>tajima_d
+// start and end as given (the driver passes 1-based inclusive reference positions), the integers of the window's record (segregating
+// and complete are its counts over all and over complete columns), the doubles printed %.10g as the Newick writer prints lengths, NA
+// where a value does not exist.  header: the line of column names, beginning with '#', first.
+std::string window_diversity_text(std::string const &group, u64 n, v2m_diversity_bin const *windows, u64 const *starts, u64 const *ends, u64 n_windows, bool header);
+
+// --output-divergence's lines for one pair of groups:
+//   <group_a><TAB><group_b><TAB><start><TAB><end><TAB>columns<TAB>called<TAB>diffs<TAB>pairs<TAB>dxy<TAB>fst
+std::string window_divergence_text(std::string const &group_a, std::string const &group_b, v2m_diversity_between_bin const *between, v2m_diversity_bin const *windows_a,
+	v2m_diversity_bin const *windows_b, u64 const *starts, u64 const *ends, u64 n_windows, bool header);
+
+// --diversity-sfs' lines for one group: <group><TAB><n><TAB><minor count><TAB><columns> for every entry of the folded spectrum, then
+// <group><TAB><n><TAB>multiallelic<TAB><count>.
+std::string diversity_sfs_text(std::string const &group, u64 n, u64 const *sfs, u64 multiallelic, bool header);
+
 class output {
 public:
 	output(gpu_context &gpu, char const *pipe_cmd, char const *chromosome_id, bool should_output_reference, bool should_output_unaligned, output_delegate &delegate);
@@ -235,6 +268,28 @@ public:
 	// mutations are kept (16 bytes each) until the last has arrived.  verbose prints the rows, columns, sites, mutations and ranges.
 	void output_tree_parsimony(variant_graph const &graph, char const *newick_path, char const *mutations_path, char const *sites_path, bool verbose = false);
 	void output_tree_parsimony(variant_graph const &graph, std::ostream *newick, std::ostream *mutations, std::ostream *sites, bool verbose = false);
+
+	// --output-diversity, --diversity-sfs, --output-divergence: window_diversity_text, diversity_sfs_text and window_divergence_text
+	// above (each where its stream or path is given) for the rows of the A2M output under the names --output-distances writes, over
+	// the 0-based half-open reference range [ref_begin, ref_end) -- the view in force must be its columns (--region), or whole rows
+	// -- from the first context, which must hold every copy.  The range is cut into bins of `step` positions, the last one perhaps
+	// shorter; bin k begins at the column of position ref_begin + k * step (columns_of_reference_range), so the columns of an
+	// insertion fall to the bin of the reference position before them.  Window j is the bins [j, j + window / step) summed field by
+	// field, for every j with a whole window, or the one short window where the range holds none; start and end are its first and
+	// last reference position, 1-based.  groups: (sequence id, group name) pairs; a sequence not named belongs to no group, an id that
+	// names no row throws, and so do more than 16 groups; empty: one group, `all`, of every row (v2m_window_diversity).  With groups
+	// every group is counted once into a table of v2m_alloc_output (v2m_column_counts_device) and v2m_diversity_of_counts runs per
+	// group and per pair; the tables together may take V2M_DIVERSITY_TABLE_BYTES (environment, read per call; default 16 GiB) at
+	// most, more throws with the figure.  divergence needs at least two groups.
+	struct diversity_params {
+		u64 window{10000}, step{10000};
+		u64 ref_begin{}, ref_end{}, ref_len{};
+		std::vector<std::pair<std::string, std::string>> groups;
+	};
+	void output_diversity(variant_graph const &graph, diversity_params const &params, char const *diversity_path, char const *sfs_path, char const *divergence_path, bool verbose = false);
+	void output_diversity(variant_graph const &graph, diversity_params const &params, std::ostream *diversity, std::ostream *sfs, std::ostream *divergence, bool verbose = false);
+	// the ids output_diversity names the rows by (what a --diversity-groups file may hold)
+	std::vector<std::string> diversity_ids(variant_graph const &graph) { return chain_rows(graph).ids; }
 
 protected:
 	struct row_set {

@@ -34,6 +34,7 @@
 #include "distance_kernels.hpp"
 #include "bootstrap_kernels.hpp"
 #include "parsimony_kernels.hpp"
+#include "diversity_kernels.hpp"
 #include "site_kernels.hpp"
 #include "ld_kernels.hpp"
 #include "nj_kernels.hpp"
@@ -283,6 +284,10 @@ struct v2m_ctx {
 	// its pinned staging, and for the host form a range's leaf bytes, the branch counters and a range's records and mutations (two, in turn)
 	scratch_buf d_fitch_sets, d_fitch_joins, d_fitch_blocks, d_fitch_total, d_fitch_bytes, d_fitch_branches, d_fitch_sites[2], d_fitch_mutations[2];
 	pinned_buf h_fitch_total;
+	// window diversity (v2m_diversity_of_counts, v2m_window_diversity): the bounds, relative to the table; the count of multiallelic
+	// columns with its pinned staging; and for the host form the second group's table, the records and the spectrum
+	scratch_buf d_diversity_bounds, d_diversity_multiallelic, d_diversity_table_b, d_diversity_records, d_diversity_sfs;
+	pinned_buf h_diversity_multiallelic;
 	// variable sites (v2m_variable_sites) and parsimony: the site list (select_rule_sites_emit), the host form's gathered slices (two,
 	// used in turn), the list's pinned staging (fetch_site_columns)
 	scratch_buf d_site_columns, d_site_bytes[2];
@@ -4613,6 +4618,155 @@ int v2m_tree_parsimony(v2m_ctx *ctx, const v2m_row_batch *rows, const v2m_nj_nod
 }
 
 
+// ---- window diversity (diversity_kernels.hpp) ------------------------------------------------------
+
+namespace {
+
+static_assert(sizeof(v2m_diversity_bin) == 64 && sizeof(v2m_diversity_between_bin) == 32 && sizeof(v2m_window_diversity_info) == 40, "the header's sizes");
+static_assert(sizeof(v2m_diversity_bin) == sizeof(v2m::diversity_bin_record) && sizeof(v2m_diversity_between_bin) == sizeof(v2m::diversity_between_record), "the kernels' records");
+static_assert(V2M_DIVERSITY_MAX_ROWS == V2M_PAIR_DISTANCES_MAX_ROWS, "the limit of the pair distances");
+
+// What both forms refuse about the bins and the sizes; `lo` and `hi` bound the columns a bin may hold (`what` names them).
+int check_diversity_bins(v2m_ctx *ctx, u64 const *bounds, u64 n_bins, u64 lo, u64 hi, char const *what, u64 n_a, u64 n_b, u64 L, char const *name)
+{
+	if (!bounds) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "bounds is NULL");
+	for (u64 k(0); k < n_bins; ++k)
+		if (bounds[k] > bounds[k + 1])
+			return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s: bounds[%llu] = %llu descends to bounds[%llu] = %llu", name, (unsigned long long) k, (unsigned long long) bounds[k],
+				(unsigned long long) (k + 1), (unsigned long long) bounds[k + 1]);
+	if (n_bins && (bounds[0] < lo || bounds[n_bins] > hi))
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s: the bins [%llu, %llu) leave %s [%llu, %llu)", name, (unsigned long long) bounds[0], (unsigned long long) bounds[n_bins], what,
+			(unsigned long long) lo, (unsigned long long) hi);
+	if (std::max(n_a, n_b) > V2M_DIVERSITY_MAX_ROWS)
+		return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes at most V2M_DIVERSITY_MAX_ROWS = %u rows a group (got %llu)", name, V2M_DIVERSITY_MAX_ROWS, (unsigned long long) std::max(n_a, n_b));
+	if (L >= (u64(1) << 32)) return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes a view of fewer than 2^32 columns (got %llu)", name, (unsigned long long) L);
+	if (n_bins >= 0xFFFFFFFFull) return fail(ctx, V2M_ERR_UNSUPPORTED, "%s takes fewer than 2^32 - 1 bins (got %llu)", name, (unsigned long long) n_bins);
+	return V2M_OK;
+}
+
+// Queues the reduction of one table (table_b NULL) or two over the n_bins >= 1 bins of `bounds` (host, relative to the tables) into
+// d_bins, and with d_sfs the spectrum of n_a / 2 + 1 entries; the count of multiallelic columns is left in ctx->d_diversity_multiallelic.
+// The upload of the bounds is synchronous; nothing else waits for the host.
+int diversity_run(v2m_ctx *ctx, u32 const *table_a, u32 const *table_b, u64 plane_pitch, u64 n_a, u64 n_b, u64 const *bounds, u64 n_bins, void *d_bins, void *d_sfs,
+	stage_times &times)
+{
+	char const *const who("window diversity");
+	if (int const rc = ensure_named(ctx, ctx->d_diversity_bounds, (n_bins + 1) * sizeof(u64), who, "bounds")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_diversity_multiallelic, 16, who, "the multiallelic count")) return rc;
+	V2M_HIP_TRY(ctx, hipMemcpy(ctx->d_diversity_bounds.p, bounds, (n_bins + 1) * sizeof(u64), hipMemcpyHostToDevice));
+	u64 const *const d_bounds(ctx->d_diversity_bounds.as<u64>());
+	u64 const begin(bounds[0]), end(bounds[n_bins]);
+	u32 const sfs_len(u32(n_a / 2 + 1));
+	u32 const sfs_mode(!d_sfs ? 0u : sfs_len <= u32(v2m::kDiversitySfsLdsBins) ? 1u : 2u);
+	times.begin(stage_times::pairs);
+	hipError_t st(hipMemsetAsync(ctx->d_diversity_multiallelic.p, 0, 16, ctx->stream));
+	if (hipSuccess == st && d_sfs) st = hipMemsetAsync(d_sfs, 0, u64(sfs_len) * sizeof(u64), ctx->stream);
+	unsigned const init_blocks(unsigned((n_bins + 255) / 256));
+	if (table_b) hipLaunchKernelGGL(v2m::diversity_init_kernel<true>, dim3(init_blocks), dim3(256), 0, ctx->stream, d_bounds, u32(n_bins), static_cast<u64 *>(d_bins));
+	else hipLaunchKernelGGL(v2m::diversity_init_kernel<false>, dim3(init_blocks), dim3(256), 0, ctx->stream, d_bounds, u32(n_bins), static_cast<u64 *>(d_bins));
+	if (begin < end) {
+		u64 const first_tile(begin / v2m::kDiversityColumns), tiles((end - 1) / v2m::kDiversityColumns - first_tile + 1);
+		hipLaunchKernelGGL(table_b ? v2m::diversity_bins_kernel<true> : v2m::diversity_bins_kernel<false>, dim3(unsigned(tiles)), dim3(v2m::kDiversityThreads), 0, ctx->stream,
+			table_a, table_b, plane_pitch, d_bounds, u32(n_bins), u32(first_tile), u32(n_a), u32(n_b), static_cast<u64 *>(d_bins), static_cast<u64 *>(d_sfs),
+			ctx->d_diversity_multiallelic.as<u64>(), sfs_mode);
+	}
+	times.end();
+	if (hipSuccess != st || hipSuccess != hipGetLastError()) return fail(ctx, V2M_ERR_HIP, "window diversity: the reduction did not launch");
+	return V2M_OK;
+}
+
+// The count the reduction left, to the host, completed.
+int diversity_fetch_multiallelic(v2m_ctx *ctx, u64 &multiallelic)
+{
+	if (int const rc = ensure_named(ctx, ctx->h_diversity_multiallelic, sizeof(u64), "window diversity", "the multiallelic count")) return rc;
+	V2M_POISON_HOST(ctx->h_diversity_multiallelic.p, sizeof(u64));
+	if (hipSuccess != hipMemcpyAsync(ctx->h_diversity_multiallelic.p, ctx->d_diversity_multiallelic.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream)
+		|| hipSuccess != hipStreamSynchronize(ctx->stream))
+		return fail(ctx, V2M_ERR_HIP, "window diversity: the multiallelic count did not arrive");
+	multiallelic = *ctx->h_diversity_multiallelic.as<u64>();
+	return V2M_OK;
+}
+
+} // namespace
+
+int v2m_diversity_of_counts(v2m_ctx *ctx, const void *d_counts_a, const void *d_counts_b, uint64_t plane_pitch, uint64_t L, uint64_t n_a, uint64_t n_b,
+	const uint64_t *bounds, uint64_t n_bins, void *d_bins, void *d_sfs, v2m_window_diversity_info *info)
+{
+	char const *const name("v2m_diversity_of_counts");
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!d_counts_a) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_counts_a is NULL");
+	if (!d_bins) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_bins is NULL");
+	if (!d_counts_b && n_b) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s: n_b = %llu without a second table", name, (unsigned long long) n_b);
+	if (d_counts_b && d_sfs) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s: the between form has no spectrum: d_sfs must be NULL", name);
+	if ((reinterpret_cast<uintptr_t>(d_counts_a) | reinterpret_cast<uintptr_t>(d_counts_b) | reinterpret_cast<uintptr_t>(d_bins) | reinterpret_cast<uintptr_t>(d_sfs)) & 15)
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_counts_a, d_counts_b, d_bins and d_sfs must be 16-byte aligned");
+	if ((plane_pitch & 3) || plane_pitch < ((L + 3) & ~u64(3)))
+		return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "plane_pitch %llu must be a multiple of 4 and at least %llu", (unsigned long long) plane_pitch, (unsigned long long) ((L + 3) & ~u64(3)));
+	if (int const rc = check_diversity_bins(ctx, bounds, n_bins, 0, L, "the table's columns", n_a, n_b, L, name)) return rc;
+	if (0 == n_bins || 0 == n_a || (d_counts_b && 0 == n_b)) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	stage_times times(ctx);
+	v2m_window_diversity_info out{};
+	out.n_columns = L; out.n_bins = n_bins;
+	int rc(diversity_run(ctx, static_cast<u32 const *>(d_counts_a), static_cast<u32 const *>(d_counts_b), plane_pitch, n_a, n_b, bounds, n_bins, d_bins, d_sfs, times));
+	if (V2M_OK == rc) rc = diversity_fetch_multiallelic(ctx, out.multiallelic);
+	if (V2M_OK == (rc = drain(ctx, rc, false)) && info) { out.bins_ms = times.ms(stage_times::pairs); *info = out; }
+	return rc;
+}
+
+int v2m_window_diversity(v2m_ctx *ctx, const v2m_row_batch *rows_a, const v2m_row_batch *rows_b, const uint64_t *bounds, uint64_t n_bins, void *bins, uint64_t *sfs,
+	v2m_window_diversity_info *info)
+{
+	char const *const name("v2m_window_diversity");
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (!rows_a) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "rows_a is NULL");
+	if (!bins) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "bins is NULL");
+	if (rows_b && sfs) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "%s: the between form has no spectrum: sfs must be NULL", name);
+	if (int const rc = check_batch(ctx, rows_a, 0)) return rc;
+	if (rows_b) if (int const rc = check_batch(ctx, rows_b, 0)) return rc;
+	u64 const L(ctx->view().length()), view_begin(ctx->view().begin), n_a(rows_a->n_rows), n_b(rows_b ? rows_b->n_rows : 0);
+	if (int const rc = check_diversity_bins(ctx, bounds, n_bins, view_begin, ctx->view().end, "the view", n_a, n_b, L, name)) return rc;
+	if (0 == n_bins || 0 == n_a || (rows_b && 0 == n_b)) return V2M_OK;
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	std::vector<u64> relative;
+	try {
+		relative.resize(n_bins + 1);
+	} catch (std::bad_alloc const &) {
+		return fail(ctx, V2M_ERR_OUT_OF_MEMORY, "%s: no host memory for %llu bounds", name, (unsigned long long) (n_bins + 1));
+	}
+	for (u64 k(0); k <= n_bins; ++k) relative[k] = bounds[k] - view_begin;
+	u64 const pitch((L + 3) & ~u64(3)), table_bytes(V2M_COUNT_CLASSES * pitch * 4), record_bytes(n_bins * (rows_b ? sizeof(v2m_diversity_between_bin) : sizeof(v2m_diversity_bin)));
+	u64 const sfs_bytes((n_a / 2 + 1) * sizeof(u64));
+	stage_times times(ctx);
+	v2m_window_diversity_info out{};
+	out.n_columns = L; out.n_bins = n_bins;
+	auto const finish([&](int rc) -> int {
+		if (V2M_OK == (rc = drain(ctx, rc, false)) && info) {
+			out.counts_ms = times.ms(stage_times::counts); out.bins_ms = times.ms(stage_times::pairs);
+			*info = out;
+		}
+		return rc;
+	});
+	V2M_HIP_TRY(ctx, ctx->d_column_table.ensure(table_bytes));
+	if (rows_b) if (int const rc = ensure_named(ctx, ctx->d_diversity_table_b, table_bytes, name, "the second group's counts")) return rc;
+	if (int const rc = ensure_named(ctx, ctx->d_diversity_records, record_bytes, name, "bin records")) return rc;
+	if (sfs) if (int const rc = ensure_named(ctx, ctx->d_diversity_sfs, sfs_bytes, name, "the spectrum")) return rc;
+	u32 *const table_a(ctx->d_column_table.as<u32>()), *const table_b(rows_b ? ctx->d_diversity_table_b.as<u32>() : nullptr);
+	times.begin(stage_times::counts);
+	int rc(column_counts_zero(ctx, table_a, pitch, L));
+	if (V2M_OK == rc) rc = column_counts_accumulate(ctx, rows_a, table_a, pitch);
+	if (V2M_OK == rc && rows_b) rc = column_counts_zero(ctx, table_b, pitch, L);
+	if (V2M_OK == rc && rows_b) rc = column_counts_accumulate(ctx, rows_b, table_b, pitch);
+	times.end();
+	if (V2M_OK != rc) return finish(rc);
+	if (V2M_OK != (rc = diversity_run(ctx, table_a, table_b, pitch, n_a, n_b, relative.data(), n_bins, ctx->d_diversity_records.p, sfs ? ctx->d_diversity_sfs.p : nullptr, times))) return finish(rc);
+	if (hipSuccess != hipMemcpyAsync(bins, ctx->d_diversity_records.p, record_bytes, hipMemcpyDeviceToHost, ctx->stream)
+		|| (sfs && hipSuccess != hipMemcpyAsync(sfs, ctx->d_diversity_sfs.p, sfs_bytes, hipMemcpyDeviceToHost, ctx->stream)))
+		return finish(fail(ctx, V2M_ERR_HIP, "%s: the results did not leave the device", name));
+	return finish(diversity_fetch_multiallelic(ctx, out.multiallelic));
+}
+
+
 // ---- output buffers ------------------------------------------------------------------------------
 
 namespace {
@@ -4700,6 +4854,18 @@ int v2m_free_output(v2m_ctx *ctx, void *d_ptr)
 	if (!d_ptr) return V2M_OK;
 	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
 	V2M_HIP_TRY(ctx, hipFree(d_ptr));
+	return V2M_OK;
+}
+
+int v2m_read_output(v2m_ctx *ctx, const void *d_src, uint64_t bytes, void *dst)
+{
+	if (!ctx) return V2M_ERR_INVALID_ARGUMENT;
+	if (0 == bytes) return V2M_OK;
+	if (!d_src) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "d_src is NULL");
+	if (!dst) return fail(ctx, V2M_ERR_INVALID_ARGUMENT, "dst is NULL");
+	V2M_HIP_TRY(ctx, hipSetDevice(ctx->device));
+	V2M_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	V2M_HIP_TRY(ctx, hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
 	return V2M_OK;
 }
 

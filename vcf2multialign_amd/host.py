@@ -100,6 +100,20 @@ def _load():
 			C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_tree_sites_text.restype = C.c_int64
 		L.v2mh_tree_sites_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_window_diversity_cpu.restype = C.c_int
+		L.v2mh_window_diversity_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, _u64p,
+			C.c_char_p, C.c_size_t]
+		L.v2mh_window_diversity_values.restype = C.c_int
+		L.v2mh_window_diversity_values.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+		L.v2mh_window_divergence_values.restype = C.c_int
+		L.v2mh_window_divergence_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+		L.v2mh_window_diversity_text.restype = C.c_int64
+		L.v2mh_window_diversity_text.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+		L.v2mh_window_divergence_text.restype = C.c_int64
+		L.v2mh_window_divergence_text.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64,
+			C.c_char_p, C.c_size_t]
+		L.v2mh_diversity_sfs_text.restype = C.c_int64
+		L.v2mh_diversity_sfs_text.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
 		L.v2mh_shard_copies.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]
 		L.v2mh_write_cut_positions.restype = C.c_int
 		L.v2mh_write_cut_positions.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -424,6 +438,119 @@ def tree_sites_text(sites, reference_positions, aligned_positions):
 	if size != L.v2mh_tree_sites_text(*args, dst, size, err, len(err)):
 		raise ValueError(err.value.decode())
 	return dst.raw[:size]
+
+
+def window_diversity_cpu(rows, bounds, rows_b=None, length=None, want_sfs=True):
+	"""The host library's plain-loop window diversity (csrc/host/output.cc: window_diversity_cpu; no GPU) from spliced rows: rows[n, pitch]
+	(u8; the first `length` bytes of a row count, all of them by default) and, for the between form, rows_b[n_b, pitch], over the bins of
+	`bounds` (relative to the rows).  Within: (bins, sfs, multiallelic) -- v2m_diversity_bin records, np.uint64[n / 2 + 1] (None and 0 with
+	want_sfs=False).  Between: (bins, None, 0), bins of v2m_diversity_between_bin.  ValueError for bad bounds."""
+	from . import _native as N
+	rows = np.ascontiguousarray(rows, dtype=np.uint8)
+	if rows.ndim != 2:
+		raise ValueError("rows is no matrix of bytes")
+	n, pitch = rows.shape
+	between = rows_b is not None
+	if between:
+		rows_b = np.ascontiguousarray(rows_b, dtype=np.uint8)
+		if rows_b.ndim != 2 or rows_b.shape[1] != pitch:
+			raise ValueError("rows_b is no matrix of bytes of the same pitch")
+	n_b = rows_b.shape[0] if between else 0
+	L_cols = pitch if length is None else int(length)
+	bounds = np.ascontiguousarray(bounds, dtype=np.uint64)
+	n_bins = max(0, len(bounds) - 1)
+	bins = np.zeros(max(1, n_bins), dtype=np.dtype(N.DIVERSITY_BETWEEN_BIN_DTYPE if between else N.DIVERSITY_BIN_DTYPE))
+	sfs = np.zeros(n // 2 + 1, dtype=np.uint64) if (want_sfs and not between) else None
+	multiallelic = C.c_uint64(0)
+	err = C.create_string_buffer(512)
+	if 0 == n_bins:   # (no bin: nothing to walk, as the library's calls return before any work)
+		return bins[:0], sfs, 0
+	if 0 != _load().v2mh_window_diversity_cpu(rows.ctypes.data if rows.size else None, n, rows_b.ctypes.data if between and rows_b.size else None, n_b, L_cols, pitch,
+			bounds.ctypes.data if len(bounds) else None, n_bins, bins.ctypes.data, sfs.ctypes.data if sfs is not None else None, C.byref(multiallelic), err, len(err)):
+		raise ValueError(err.value.decode())
+	return bins[:n_bins], sfs, int(multiallelic.value)
+
+
+def window_diversity_values(windows, n):
+	"""The host library's doubles of include/v2m_hip.h's "window diversity" (csrc/host/output.cc: diversity_values_of): np.float64[len, 3]
+	-- pi, theta_w, tajima_d -- of v2m_diversity_bin records over n sequences; NaN where a value does not exist."""
+	from . import _native as N
+	windows = np.ascontiguousarray(windows, dtype=np.dtype(N.DIVERSITY_BIN_DTYPE))
+	out = np.zeros((len(windows), 3), dtype=np.float64)
+	if len(windows) and 0 != _load().v2mh_window_diversity_values(windows.ctypes.data, len(windows), int(n), out.ctypes.data):
+		raise ValueError("v2mh_window_diversity_values failed")
+	return out
+
+
+def window_divergence_values(between, windows_a, windows_b):
+	"""Likewise np.float64[len, 2] -- dxy, fst -- of v2m_diversity_between_bin records and the two groups' v2m_diversity_bin records."""
+	from . import _native as N
+	between = np.ascontiguousarray(between, dtype=np.dtype(N.DIVERSITY_BETWEEN_BIN_DTYPE))
+	windows_a = np.ascontiguousarray(windows_a, dtype=np.dtype(N.DIVERSITY_BIN_DTYPE))
+	windows_b = np.ascontiguousarray(windows_b, dtype=np.dtype(N.DIVERSITY_BIN_DTYPE))
+	if not len(between) == len(windows_a) == len(windows_b):
+		raise ValueError("the three record lists differ in length")
+	out = np.zeros((len(between), 2), dtype=np.float64)
+	if len(between) and 0 != _load().v2mh_window_divergence_values(between.ctypes.data, windows_a.ctypes.data, windows_b.ctypes.data, len(between), out.ctypes.data):
+		raise ValueError("v2mh_window_divergence_values failed")
+	return out
+
+
+def _handed_over_text(fn, args):
+	err = C.create_string_buffer(512)
+	size = fn(*args, None, 0, err, len(err))
+	if size < 0:
+		raise ValueError(err.value.decode())
+	dst = C.create_string_buffer(max(1, size))
+	if size != fn(*args, dst, size, err, len(err)):
+		raise ValueError(err.value.decode())
+	return dst.raw[:size]
+
+
+def _group_name(group):
+	name = group if isinstance(group, bytes) else str(group).encode()
+	if b"\0" in name:
+		raise ValueError("a group name holds a NUL byte")
+	return name
+
+
+def window_diversity_text(group, n, windows, starts, ends, header=False):
+	"""The host library's formatter of --output-diversity (csrc/host/output.cc: window_diversity_text; no GPU): one line per window of
+	group, start, end, columns, called, diffs, pairs, pi, segregating, complete, theta_w, tajima_d, as bytes."""
+	from . import _native as N
+	windows = np.ascontiguousarray(windows, dtype=np.dtype(N.DIVERSITY_BIN_DTYPE))
+	starts = np.ascontiguousarray(starts, dtype=np.uint64)
+	ends = np.ascontiguousarray(ends, dtype=np.uint64)
+	if not len(windows) == len(starts) == len(ends):
+		raise ValueError("windows, starts and ends differ in length")
+	k = len(windows)
+	return _handed_over_text(_load().v2mh_window_diversity_text, (_group_name(group), int(n), windows.ctypes.data if k else None, starts.ctypes.data if k else None,
+		ends.ctypes.data if k else None, k, 1 if header else 0))
+
+
+def window_divergence_text(group_a, group_b, between, windows_a, windows_b, starts, ends, header=False):
+	"""The host library's formatter of --output-divergence (csrc/host/output.cc: window_divergence_text; no GPU): one line per window of
+	group_a, group_b, start, end, columns, called, diffs, pairs, dxy, fst, as bytes."""
+	from . import _native as N
+	between = np.ascontiguousarray(between, dtype=np.dtype(N.DIVERSITY_BETWEEN_BIN_DTYPE))
+	windows_a = np.ascontiguousarray(windows_a, dtype=np.dtype(N.DIVERSITY_BIN_DTYPE))
+	windows_b = np.ascontiguousarray(windows_b, dtype=np.dtype(N.DIVERSITY_BIN_DTYPE))
+	starts = np.ascontiguousarray(starts, dtype=np.uint64)
+	ends = np.ascontiguousarray(ends, dtype=np.uint64)
+	if not len(between) == len(windows_a) == len(windows_b) == len(starts) == len(ends):
+		raise ValueError("the record lists, starts and ends differ in length")
+	k = len(between)
+	return _handed_over_text(_load().v2mh_window_divergence_text, (_group_name(group_a), _group_name(group_b), between.ctypes.data if k else None,
+		windows_a.ctypes.data if k else None, windows_b.ctypes.data if k else None, starts.ctypes.data if k else None, ends.ctypes.data if k else None, k, 1 if header else 0))
+
+
+def diversity_sfs_text(group, n, sfs, multiallelic, header=False):
+	"""The host library's formatter of --diversity-sfs (csrc/host/output.cc: diversity_sfs_text; no GPU): one line per entry of the folded
+	spectrum of n sequences, `group<TAB>n<TAB>minor count<TAB>columns`, then the multiallelic count, as bytes."""
+	sfs = np.ascontiguousarray(sfs, dtype=np.uint64)
+	if len(sfs) != int(n) // 2 + 1:
+		raise ValueError("a spectrum of %d sequences has %d entries, not %d" % (n, int(n) // 2 + 1, len(sfs)))
+	return _handed_over_text(_load().v2mh_diversity_sfs_text, (_group_name(group), int(n), sfs.ctypes.data, int(multiallelic), 1 if header else 0))
 
 
 def write_cut_positions(path, cut_positions, min_distance, score):

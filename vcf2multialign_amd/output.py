@@ -180,6 +180,117 @@ class Output:
 			sites.write(host.tree_sites_text(site_records, graph.reference_positions, graph.aligned_positions))
 		return info
 
+	def _write_diversity(self, ids, rows, graph, diversity, sfs, divergence, window, step, groups):
+		"""--output-diversity, --diversity-sfs, --output-divergence (each a stream, or None): the texts of host.window_diversity_text,
+		host.diversity_sfs_text and host.window_divergence_text for `rows` named `ids`, over the region's reference range when there is
+		one, as the C++ driver writes them (csrc/host/output.hh: output_diversity).  window, step: --diversity-window, --diversity-step
+		(None: the window); groups: (id, group) pairs or a dict, None for the one group `all`.  With groups every group is counted once
+		into a table of Context.alloc_output and Context.diversity_of_counts runs per group and per pair; the tables together may
+		take V2M_DIVERSITY_TABLE_BYTES (environment; default 16 GiB).  Returns (group names, windows)."""
+		import os
+		import numpy as np
+		from . import _native as N
+		from . import host
+		window = int(window)
+		step = window if step is None else int(step)
+		if window <= 0 or step <= 0 or window % step:
+			raise ValueError("--diversity-step must divide --diversity-window")
+		ref, aln = graph.reference_positions, graph.aligned_positions
+		ref_begin, ref_end = self.region if self.region is not None else (0, int(ref[-1]))
+		if groups is None:
+			names, members = ["all"], [list(range(len(rows)))]
+		else:
+			pairs = list(groups.items()) if isinstance(groups, dict) else list(groups)
+			row_of = {i: r for r, i in reversed(list(enumerate(ids)))}
+			names, members, seen = [], [], set()
+			for i, group in pairs:
+				if i not in row_of:
+					raise ValueError("--diversity-groups: \"%s\" names no output sequence" % i)
+				if i in seen:
+					raise ValueError("--diversity-groups: \"%s\" is named twice" % i)
+				seen.add(i)
+				if group not in names:
+					if len(names) == 16:
+						raise ValueError("--diversity-groups: more than 16 groups")
+					names.append(group)
+					members.append([])
+				members[names.index(group)].append(row_of[i])
+			members = [sorted(m) for m in members]
+		G = len(names)
+		if divergence is not None and G < 2:
+			raise ValueError("--output-divergence needs at least two groups")
+		n_bins = -(-(ref_end - ref_begin) // step)
+		width = window // step
+		bounds = np.array([columns_of_reference_range(ref, aln, ref_begin + k * step, ref_end)[0] for k in range(n_bins)]
+			+ [columns_of_reference_range(ref, aln, ref_begin, ref_end)[1]], dtype=np.uint64)
+		n_windows = n_bins - width + 1 if n_bins >= width else 1
+		starts = np.array([ref_begin + j * step + 1 for j in range(n_windows)], dtype=np.uint64)
+		ends = np.array([min(ref_end, ref_begin + j * step + window) for j in range(n_windows)], dtype=np.uint64)
+
+		def summed(bins):
+			out = np.zeros(n_windows, dtype=bins.dtype)
+			for name in bins.dtype.names:
+				for j in range(n_windows):
+					out[name][j] = bins[name][j:j + width].sum(dtype=np.uint64)
+			return out
+
+		picked = [[rows[r] for r in m] for m in members]
+		if self.region is not None:
+			self.ctx.set_column_window(int(bounds[0]), int(bounds[-1]))
+		held = []
+		try:
+			L = self.ctx.window_length
+			within, spectra, many, between = [], [], [], {}
+			if groups is None:
+				bins, spectrum, info = self.ctx.window_diversity(RowBatch(picked[0]), bounds, info=True)
+				within, spectra, many = [bins], [spectrum], [info["multiallelic"]]
+			else:
+				pitch = (L + 3) & ~3
+				table_bytes = 6 * pitch * 4
+				limit = int(os.environ.get("V2M_DIVERSITY_TABLE_BYTES", 16 << 30))
+				if G * table_bytes > limit:
+					raise ValueError("the counts tables of %d groups over %d columns take %d bytes, more than V2M_DIVERSITY_TABLE_BYTES = %d" % (G, L, G * table_bytes, limit))
+				relative = bounds - bounds[0]
+				tables = []
+				for g in range(G):
+					held.append(self.ctx.alloc_output(max(16, table_bytes), 1))
+					tables.append(held[-1])
+					self.ctx.column_counts_device(RowBatch(picked[g]), tables[g], pitch)
+				most = max(len(m) for m in members)
+				held.append(self.ctx.alloc_output(max(16, n_bins * 64), 1))
+				d_bins = held[-1]
+				held.append(self.ctx.alloc_output((most // 2 + 1) * 8, 1))
+				d_sfs = held[-1]
+				for g in range(G):
+					n = len(members[g])
+					info = self.ctx.diversity_of_counts(tables[g], pitch, L, n, relative, d_bins, d_sfs)
+					within.append(self.ctx.read_output(d_bins, n_bins, N.DIVERSITY_BIN_DTYPE))
+					spectra.append(self.ctx.read_output(d_sfs, n // 2 + 1, np.uint64))
+					many.append(info["multiallelic"])
+				if divergence is not None:
+					for a in range(G):
+						for b in range(a + 1, G):
+							self.ctx.diversity_of_counts(tables[a], pitch, L, len(members[a]), relative, d_bins, None, tables[b], len(members[b]))
+							between[a, b] = self.ctx.read_output(d_bins, n_bins, N.DIVERSITY_BETWEEN_BIN_DTYPE)
+		finally:
+			for ptr in held:
+				self.ctx.free_output(ptr)
+			if self.region is not None:
+				self.ctx.set_column_window(0, self.ctx.aligned_length)
+		windows = [summed(b) for b in within]
+		if diversity is not None:
+			for g in range(G):
+				diversity.write(host.window_diversity_text(names[g], len(members[g]), windows[g], starts, ends, header=g == 0))
+		if sfs is not None:
+			for g in range(G):
+				sfs.write(host.diversity_sfs_text(names[g], len(members[g]), spectra[g], many[g], header=g == 0))
+		if divergence is not None:
+			first = True
+			for (a, b), bins in between.items():
+				divergence.write(host.window_divergence_text(names[a], names[b], summed(bins), windows[a], windows[b], starts, ends, header=first))
+				first = False
+		return names, windows
+
 	def _write_rows(self, stream, ids, rows, graph):
 		if self.region is None:
 			return self._write_bodies(stream, ids, rows)
@@ -236,6 +347,12 @@ class HaplotypeOutput(Output):
 				ids.append(self._chain_name("%s.%d" % (graph.sample_names[sample_idx], 1 + chr_copy_idx)))
 				rows.append(int(graph.ploidy_csum[sample_idx]) + chr_copy_idx)
 		return ids, rows
+
+	def output_diversity(self, graph, diversity=None, sfs=None, divergence=None, window=10000, step=None, groups=None):
+		"""--output-diversity, --diversity-sfs and --output-divergence (each a stream, or None) for the rows of output_distances under
+		its names; window, step and groups as --diversity-window, --diversity-step and --diversity-groups."""
+		ids, rows = self._distance_rows(graph)
+		return self._write_diversity(ids, rows, graph, diversity, sfs, divergence, window, step, groups)
 
 	def output_distances(self, graph, stream, acgt_only=False):
 		"""--output-distances for the rows of output_a2m (REF first, unless omitted), named as one file per sequence would be."""
@@ -333,6 +450,12 @@ class FounderSequenceGreedyOutput(Output):
 			ids.append(self._chain_name(str(1 + col_idx)))
 			rows.append(list(zip(cut_positions[:-1], col)))
 		return ids, rows
+
+	def output_diversity(self, graph, cut_positions, assigned_samples_column_major, diversity=None, sfs=None, divergence=None, window=10000, step=None, groups=None):
+		"""--output-diversity, --diversity-sfs and --output-divergence (each a stream, or None) for the rows of output_distances under
+		its names; window, step and groups as --diversity-window, --diversity-step and --diversity-groups."""
+		ids, rows = self._distance_rows(cut_positions, assigned_samples_column_major)
+		return self._write_diversity(ids, rows, graph, diversity, sfs, divergence, window, step, groups)
 
 	def output_distances(self, graph, cut_positions, assigned_samples_column_major, stream, acgt_only=False):
 		"""--output-distances for the rows of output_a2m (REF first, unless omitted, then the founder rows)."""
